@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the latent-feature-grid sample/decode hot path on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one complete full-volume reconstruction pass of the hot path (BASELINE.json north_star /
@@ -20,9 +20,17 @@ MLP FLOPs per launch / its average launch duration (HIP events on the launch str
 peak of the matrix pipe the build runs on (2.5 PFLOP/s f16 for the default build; the MFMA work actually
 executed -- three f16 products per fp32 product -- is `executed_mfma`); the HBM-side figure on the
 algorithmic gather bytes is `hbm_algorithmic`, the measured HBM traffic per launch `traffic`.
+
+A plain run sets up, warms up, times the steps and prints the line; everything that needs runs of its own is
+behind `--full`:
 `cpu_baseline` times the oracle's op-for-op PyTorch restatement of the reference on the host cores for a
-bounded sample of the same workload (rank 0, N = 1 only).  `extra` (N = 1) puts the other BASELINE
-configs under the same clock: cfg 2 and cfg 5 forward + decode, the cfg-3 train step (default and reduced).
+bounded sample of the same workload (rank 0, N = 1 only), `exact_fp32_build` the same pass in the exact build,
+`extra` (N = 1) puts the other BASELINE configs under the same clock: cfg 2 and cfg 5 forward + decode, the
+cfg-3 train step (default and reduced), and `multi_gpu.other_mode` (N > 1) times the other assembly mode.
+
+`--dump-outputs DIR` writes the volume of the last timed step after the timing: `DIR/volume.npy` (float32,
+the whole (X, Y, Z) volume) when it has at most DUMP_SAMPLES voxels, else `DIR/volume_sample.npy` (float32, the
+voxels at DUMP_SAMPLES flat indices drawn without replacement by numpy PCG64(DUMP_SEED), in ascending order).
 """
 import argparse
 import json
@@ -42,6 +50,8 @@ if ROOT not in sys.path:
 FP32_MFMA_PEAK_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md, dense f32-input MFMA
 F16_MFMA_PEAK_TFLOPS = 2500.0      # same guide, dense BF16/F16 MFMA
 HBM_PEAK_GBS = 8000.0              # same guide, HBM3E spec
+DUMP_SAMPLES = 1 << 22             # --dump-outputs: at most 16 MiB of float32 voxels
+DUMP_SEED = 4242
 
 
 def traffic_bytes(workload, precision):
@@ -174,6 +184,18 @@ def cpu_baseline(model, w, budget_s=20.0, hip_volume=None):
         'sample': '%d tiles of 32^3 (%d samples) of the same lattice; value = grid decoded once (%.3f s, not included), '
                   'value_with_per_tile_decode = the reference\'s behaviour (decode per tile)' % (n_tiles, n_samples, t_decode),
     }
+
+
+def dump_outputs(vol, out_dir):
+    """--dump-outputs: the volume a caller of the timed path receives, whole or as a fixed seeded sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = vol.reshape(-1)
+    if flat.numel() <= DUMP_SAMPLES:
+        np.save(os.path.join(out_dir, 'volume.npy'), vol.float().cpu().numpy())
+        return
+    idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(flat.numel(), DUMP_SAMPLES, replace=False))
+    sample = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    np.save(os.path.join(out_dir, 'volume_sample.npy'), sample)
 
 
 def _event_ms(fn, reps):
@@ -382,10 +404,14 @@ def main():
     ap.add_argument('--precision', default='f16x2', choices=['f16x2', 'fp32', 'f16'],
                     help="layer-GEMM arithmetic: 'f16x2' (default, f16 hi+lo split on the f16 matrix pipe) or 'fp32' (exact f32 MFMA)")
     ap.add_argument('--gather', default='root', choices=['root', 'all'],
-                    help="N > 1: how the volume is assembled for `value` (the other mode is timed beside it)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the other BASELINE configs (cfg 2, cfg 5, cfg-3 train step)')
+                    help="N > 1: how the volume is assembled for `value` (with --full the other mode is timed beside it)")
+    ap.add_argument('--full', action='store_true',
+                    help='also run what needs runs of its own: cpu_baseline, exact_fp32_build, extra, multi_gpu.other_mode')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip cpu_baseline and exact_fp32_build')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip the other BASELINE configs (cfg 2, cfg 5, cfg-3 train step)')
     ap.add_argument('--no-check', action='store_true', help='skip the finite-output check (ablation builds)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the volume of the last one to DIR (see the module docstring)')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -472,6 +498,8 @@ def main():
     value = total_samples * args.steps / elapsed / 1e6
     if vol is not None:
         assert tuple(vol.shape) == tuple(res) and (args.no_check or bool(torch.isfinite(vol).all()))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(vol, args.dump_outputs)
 
     kern_total_ms = float(sum(a.elapsed_time(b) for a, b, _ in ev))
     kern_samples = int(sum(n for _, _, n in ev))
@@ -485,15 +513,16 @@ def main():
                             dtype=torch.float64, device=device)
         allr = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
-        other = 'all' if args.gather == 'root' else 'root'
-        o_steps = max(3, args.steps // 2)
-        o_elapsed, _, _ = timed_loop(other, o_steps, False)
         multi = {'world_size': dist.get_world_size(), 'backend': dist.get_backend(), 'gather': args.gather,
                  'per_rank': {'kernel_ms_per_step': [float(t[0]) for t in allr], 'decode_pack_ms': [float(t[1]) for t in allr],
                               'gather_wait_ms': [float(t[2]) for t in allr]},
-                 'bytes_received_by_root_per_step': 4 * total_samples * (world - 1) // world,
-                 'other_mode': {'gather': other, 'value': total_samples * o_steps / o_elapsed / 1e6,
-                                'ms_per_step': o_elapsed / o_steps * 1e3, 'steps': o_steps}}
+                 'bytes_received_by_root_per_step': 4 * total_samples * (world - 1) // world}
+        if args.full:
+            other = 'all' if args.gather == 'root' else 'root'
+            o_steps = max(3, args.steps // 2)
+            o_elapsed, _, _ = timed_loop(other, o_steps, False)
+            multi['other_mode'] = {'gather': other, 'value': total_samples * o_steps / o_elapsed / 1e6,
+                                   'ms_per_step': o_elapsed / o_steps * 1e3, 'steps': o_steps}
 
     if rank == 0:
         K0 = 3 + 12 + w['C']
@@ -537,7 +566,7 @@ def main():
         }
         if multi is not None:
             out['multi_gpu'] = multi
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(model, w, hip_volume=vol)
             if split:
                 # the same pass with the exact build (v_mfma_f32_32x32x2_f32, bitwise an fp32 fmaf chain): its rate and
@@ -557,7 +586,7 @@ def main():
                 del v32
         else:
             out['cpu_baseline'] = None
-        if world == 1 and not args.no_extra and args.workload == 'headline':
+        if world == 1 and args.full and not args.no_extra and args.workload == 'headline':
             # every other BASELINE config under the same clock (HIP events; sample counts given so value x time can be
             # cross-checked): cfg 2 and cfg 5 forward + decode, the cfg-3 train step in the default and the reduced build
             del vol

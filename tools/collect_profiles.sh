@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
-echo "== default bench run"; python3 bench.py > $O/bench_default_run.log 2>&1; tail -c 400 $O/bench_default_run.log; echo
+echo "== full bench run"; python3 bench.py --full > $O/bench_default_run.log 2>&1; tail -c 400 $O/bench_default_run.log; echo
 # --stats averages over EVERY launch, warm-up included (the first launches of a process run 5-25 % long); the summary beside
 # it is made from the per-dispatch trace with the first WARM launches of each kernel dropped: median, mean, min, max.  That
 # mean is what bench.py's roofline.kernel_ms (HIP events over the timed steps only) has to agree with.
