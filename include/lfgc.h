@@ -59,7 +59,7 @@ const char* lfgc_error_string(int code);
  *                                             contracted axis by axis (224 instead of 512 FMAs per 8 outputs; results equal
  *                                             the dense form up to fp32 rounding) and filter_rev may be NULL
  *   out        device (C, t0,t1,t2)
- * Requires 2*d_a + 2 >= t_a >= 1.  The same `taps` convention applies to every wavelet entry point below. */
+ * Requires 2*d_a + 2 >= t_a >= 1 (4 taps; the *_len_f32 entries below take other lengths).  The same `taps` convention applies to every wavelet entry point below. */
 int lfgc_idwt_level_f32(const float* lll, const float* hf, const float* filter_rev, const float* taps, float* out,
                         int C, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
 
@@ -98,6 +98,32 @@ int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* taps, float* 
 int lfgc_dwt_level_f32(const float* in, const float* filter_fwd, const float* taps, float* out,
                        int C, int n0, int n1, int n2, lfgc_stream_t stream);
 
+/* The same seven entry points for any even filter length L = filter_len in {2, 4, 6, 8} (Haar / db1, db2, db3, db4 and
+ * any other even-length bank: the reference's filter module takes any pywt wavelet, Torch_Wavelet_Transform.py:11-14,
+ * :32-33; its options expose it as --wavelet_filter, Feature_Grid_Training.py:62).  The arithmetic is the reference's
+ * conv_transpose3d / conv3d for an L^3 filter: one level's full output is 2 d_a + L - 2 per axis, so
+ *   1 <= t_a <= 2 d_a + L - 2,  crop offset floor((2 d_a + L - 2 - t_a) / 2)  (_unpad_for_reverse, :69-73),
+ * and the forward DWT pads (2L - 3) // 2 = L - 2 per side plus the odd bit on the high side, with the same pad-slot quirk
+ * (_get_padding_size, :59-63): d_a = (n_a + 2 (L - 2) + odd_a' - L) / 2 + 1.
+ *   filter_rev / filter_fwd  device (8, L,L,L) -- only read for L = 4 with taps == NULL (dense stencil)
+ *   taps                     host float[2 * L] [low taps | high taps], REQUIRED for L != 4 (the reference only ever
+ *                            builds outer products, :39-57); a dense filter of another length returns LFGC_E_UNSUPPORTED
+ * Other lengths return LFGC_E_UNSUPPORTED.  filter_len = 4 is exactly the plain entry point above.  The channel-last pair
+ * takes L = 2 and 4 and returns LFGC_E_UNSUPPORTED for L = 6, 8 (compose the channel-first level with
+ * lfgc_grid_layout_f32).  The drop pair is declared with the drop entry points below. */
+int lfgc_idwt_level_len_f32(const float* lll, const float* hf, const float* filter_rev, const float* taps, int filter_len,
+                            float* out, int C, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
+int lfgc_idwt_level_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
+                                float* d_lll, float* d_hf, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                                lfgc_stream_t stream);
+int lfgc_idwt_level_cl_len_f32(const float* lll, const float* hf, const float* taps, int filter_len, float* out_cl,
+                               int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
+int lfgc_idwt_level_cl_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len, float* d_lll, float* d_hf,
+                                   int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
+                                   lfgc_stream_t stream);
+int lfgc_dwt_level_len_f32(const float* in, const float* filter_fwd, const float* taps, int filter_len, float* out,
+                           int C, int n0, int n1, int n2, lfgc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Pruning ("drop") layers on the wavelet coefficients
  *
@@ -132,6 +158,17 @@ int lfgc_idwt_level_drop_bwd_f32(const float* d_out, const float* filter_rev, co
                                  const float* mul_lll, const float* mul_hf, float* d_lll, float* d_hf,
                                  float* d_mul_lll, float* d_mul_hf, const float* const* penalty_grads,
                                  int C, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
+
+/* lfgc_idwt_level_drop_f32 / lfgc_idwt_level_drop_bwd_f32 for filter length filter_len (see lfgc_idwt_level_len_f32). */
+int lfgc_idwt_level_drop_len_f32(const float* lll, const float* hf, const float* mul_lll, float threshold_lll,
+                                 const float* mul_hf, float threshold_hf, const float* filter_rev, const float* taps,
+                                 int filter_len, float* out, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                                 lfgc_stream_t stream);
+int lfgc_idwt_level_drop_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
+                                     const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                     float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                     const float* const* penalty_grads, int C, int d0, int d1, int d2,
+                                     int t0, int t1, int t2, lfgc_stream_t stream);
 
 /* One drop layer on one tensor outside the decode (the layers' own forward(x)): x, out (C, n), mul (n). */
 int lfgc_drop_apply_f32(const float* x, const float* mul, float threshold, float* out, int C, int64_t n,

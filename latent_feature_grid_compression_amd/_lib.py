@@ -34,7 +34,7 @@ PENALTY_L1, PENALTY_L2, PENALTY_DKL = 0, 1, 2
 PENALTY_MAX_TERMS = 16
 PENALTY_BLOCKS = 1024             # LFGC_PENALTY_SUMS_DOUBLES(n) = n * (1 + PENALTY_BLOCKS)
 _PP = POINTER(c_void_p)
-_TAPS = POINTER(c_float)          # host float[8] (1-D filter bank) or None
+_TAPS = POINTER(c_float)          # host float[2 L] (1-D filter bank of length L) or None
 
 # name -> (restype, argtypes); mirrors include/lfgc.h one to one
 SIGNATURES = {
@@ -49,6 +49,15 @@ SIGNATURES = {
     'lfgc_idwt_level_drop_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, c_void_p, _TAPS, c_void_p] +
                                  [c_int] * 7 + [c_void_p]),
     'lfgc_idwt_level_drop_bwd_f32': (c_int, [c_void_p, c_void_p, _TAPS] + [c_void_p] * 8 + [_PP] + [c_int] * 7 + [c_void_p]),
+    'lfgc_idwt_level_len_f32': (c_int, [c_void_p, c_void_p, c_void_p, _TAPS, c_int, c_void_p] + [c_int] * 7 + [c_void_p]),
+    'lfgc_idwt_level_bwd_len_f32': (c_int, [c_void_p, c_void_p, _TAPS, c_int, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    'lfgc_idwt_level_cl_len_f32': (c_int, [c_void_p, c_void_p, _TAPS, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
+    'lfgc_idwt_level_cl_bwd_len_f32': (c_int, [c_void_p, _TAPS, c_int, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    'lfgc_dwt_level_len_f32': (c_int, [c_void_p, c_void_p, _TAPS, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'lfgc_idwt_level_drop_len_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, c_void_p, _TAPS, c_int,
+                                             c_void_p] + [c_int] * 7 + [c_void_p]),
+    'lfgc_idwt_level_drop_bwd_len_f32': (c_int, [c_void_p, c_void_p, _TAPS, c_int] + [c_void_p] * 8 + [_PP] + [c_int] * 7 +
+                                         [c_void_p]),
     'lfgc_drop_apply_f32': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int64, c_void_p]),
     'lfgc_drop_apply_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'lfgc_sign_variance_update_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),

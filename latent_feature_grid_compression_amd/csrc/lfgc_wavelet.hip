@@ -1,17 +1,21 @@
-// lfgc_wavelet.hip -- 4-tap (db2) separable-bank 3-D wavelet kernels for gfx950.
+// lfgc_wavelet.hip -- separable-bank 3-D wavelet kernels for gfx950, filter length L = 2K in {2, 4, 6, 8}.
 //   lfgc_idwt_level_f32           replaces wavelet_transform/Torch_Wavelet_Transform.py:91-104 (+ crop :69-73)
 //   lfgc_idwt_level_bwd_f32       its adjoint (autograd of the same lines)
 //   lfgc_idwt_level_drop_f32/_bwd the same two with the pruning layers' per-coefficient factors folded in
 //   lfgc_dwt_level_f32            replaces :59-67, :75-89 (init-time encode)
+//   (each with a *_len_f32 twin that takes the filter length; the plain names are the 4-tap (db2) entries)
 //   lfgc_grid_layout_f32          channel-first <-> channel-last conversion of the dense grid (the sampler and the
 //                                 gradient scatter work channel-last, the stencils channel-first)
-// All of them are byte movers with a 64-FMA-per-output stencil (no contraction worth an MFMA).  Both stencils share
+// All of them are byte movers with a (2K)^3-tap stencil per output (no contraction worth an MFMA).  Both stencils share
 // one shape: a workgroup owns 2 z-slices of a run of consecutive cells of the flattened (y,x) plane of ONE channel, copies
 // the input neighbourhood of those cells into LDS as plain contiguous chunks of the source rows (every source value
 // is fetched from memory once per workgroup instead of once per reading thread: the per-thread version was bound by
 // the 64 vector-load instructions each thread issued), then every thread forms its 8 results from LDS with filter
 // taps that are broadcast LDS reads.  Boundary handling is a select on the LDS value, never a branch.
+// The kernels are templates on the half-length K; the K = 2 instances are the original db2 kernels instruction for
+// instruction.  Other lengths take the separable (`taps`) form only: the reference only ever builds outer products.
 #include "lfgc_common.h"
+#include <type_traits>
 
 #ifndef LFGC_WAVELET_ABLATE
 #define LFGC_WAVELET_ABLATE 0          // diagnostics (tools/ablate_wavelet.py): 1 no output stores, 2 no arithmetic, 4 no staging loads
@@ -19,15 +23,16 @@
 
 namespace {
 
+template <int K>
 struct IdwtArgs {
     const float* lll;   // (C, d0,d1,d2)
     const float* hf;    // (C, 7, d0,d1,d2)
-    const float* filt;  // (8,4,4,4)
+    const float* filt;  // (8,4,4,4) (K = 2 dense build only)
     float* out;         // (C, t0,t1,t2)
-    int C, d0, d1, d2, t0, t1, t2, o0, o1, o2;   // o = crop offset floor((2d+2-t)/2)
+    int C, d0, d1, d2, t0, t1, t2, o0, o1, o2;   // o = crop offset floor((2d+2K-2-t)/2)
     int len;            // plane offsets per staged z-plane
     int zchunk;         // sliding-window kernel: output z-slices per workgroup
-    float taps[8];      // SEP build: the 1-D bank the filter is the outer product of: [low | high][tap]
+    float taps[4 * K];  // SEP build: the 1-D bank the filter is the outer product of: [low | high][tap]
     // DROP build only: the pruning layers' per-coefficient factors, shared by all channels
     const float* mul_l; // (d0,d1,d2) or NULL
     const float* mul_h; // (7, d0,d1,d2) or NULL
@@ -46,27 +51,39 @@ __device__ __forceinline__ float drop_value(float x, float m, float thr, bool st
 constexpr int kTileCells = 128;      // analysis: cells of the flattened (y,x) plane per z-slice of a workgroup
 constexpr int kFwdCells = 256;       // synthesis: plane cells per workgroup (one per thread, both z-slices each)
 
-// Synthesis: out_full[o] = sum_{s,t} in[s][i] F_s[t], o = 2 i + t per axis.  Thread = cell jj in [0,d] per axis:
-// it produces the 2x2x2 outputs o = 2 jj + p from the cells i = jj - e (e in {0,1}) with taps t = p + 2 e.
-// LDS: [512 filter taps as [tap][band]] [3 z-planes (jz0 - 1 + zl)][len plane offsets][12 floats: the 8 bands of that
-// cell + pad]; element k is plane offset chunk0 + k, chunk0 = (first cell row - 1) * d2 - 1.  The 48-byte records make
-// both the two ds_write_b128 of the staging and the two ds_read_b128 per neighbour cell conflict-free (stride 4 * 3
-// dwords).  Offsets outside the plane (and z-planes outside the level) are staged as zeros, so only the x range of a
-// neighbour needs a select.
+// Synthesis: out_full[o] = sum_{s,t} in[s][i] F_s[t], o = 2 i + t per axis.  Thread = cell jj in [0,d+K-2] per axis:
+// it produces the 2x2x2 outputs o = 2 jj + p from the cells i = jj - e (e in [0,K)) with taps t = p + 2 e.  Haar
+// (K = 1) has no neighbour cells: each 2x2x2 output block is an 8-to-8 butterfly of one cell's bands.
+// LDS: [512 filter taps as [tap][band] (K = 2 only)] [K+1 z-planes (jz0 - K + 1 + zl)][len plane offsets][12 floats:
+// the 8 bands of that cell + pad]; element k is plane offset chunk0 + k, chunk0 = (first cell row - K + 1) * d2 - K + 1.
+// The 48-byte records make both the two ds_write_b128 of the staging and the two ds_read_b128 per neighbour cell
+// conflict-free (stride 4 * 3 dwords).  Offsets outside the plane (and z-planes outside the level) are staged as zeros,
+// so only the x range of a neighbour needs a select.
 constexpr int kRec = 12;
 
-template <bool DROP, bool SEP>
-__global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
+template <int K> constexpr int filt_floats() { return K == 2 ? 512 : 0; }   // the dense 4-tap filter's LDS slot
+
+// x range of neighbour ex of the cell in column jx (cx = jx - ex in [0, d2)); written so that the bounds that always hold
+// (jx >= 0, jx - (K-1) < d2) are not tested
+template <int K>
+__device__ __forceinline__ bool x_in_level(int jx, int ex, int d2) {
+    return (ex == 0 || jx >= ex) && (ex == K - 1 || jx - ex < d2);
+}
+
+template <bool DROP, bool SEP, int K>
+__global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs<K> a) {
+    static_assert(SEP || K == 2, "dense (non-separable) filters are 4-tap only");
+    constexpr int L = 2 * K;
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     float* s_f = s_dyn;
-    float* s_v = s_dyn + 512;
+    float* s_v = s_dyn + filt_floats<K>();
     if (!SEP)
         for (int i = threadIdx.x; i < 512; i += 256) s_f[(i & 63) * 8 + (i >> 6)] = a.filt[i];
-    const int n0 = a.d0 + 1, n1 = a.d1 + 1, n2 = a.d2 + 1;
+    const int n0 = a.d0 + (K - 1), n1 = a.d1 + (K - 1), n2 = a.d2 + (K - 1);
     const int plane_cells = n1 * n2;
     const int pt = blockIdx.x, zt = blockIdx.y, c = blockIdx.z;     // 3-D grid: no index divisions
     const int f0 = pt * kFwdCells, jz0 = zt * 2;
-    const int chunk0 = (f0 / n2 - 1) * a.d2 - 1;
+    const int chunk0 = (f0 / n2 - (K - 1)) * a.d2 - (K - 1);
     const int len = a.len;
     const int dplane = a.d1 * a.d2;
     const int dvol = dplane * a.d0;                       // < 2^31 / 8 (checked on the host)
@@ -76,10 +93,10 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
     for (int kk = threadIdx.x; kk < len; kk += 256) {
         const int off = chunk0 + kk;
         const bool in_plane = off >= 0 && off < dplane;
-        float r[3][8];
+        float r[K + 1][8];
 #pragma unroll
-        for (int zl = 0; zl < 3; ++zl) {
-            const int iz = jz0 - 1 + zl;
+        for (int zl = 0; zl < K + 1; ++zl) {
+            const int iz = jz0 - (K - 1) + zl;
             const bool ok = in_plane && iz >= 0 && iz < a.d0;
             const int o = ok ? iz * dplane + off : 0;
             r[zl][0] = (LFGC_WAVELET_ABLATE & 4) ? (float)o : lc[o];
@@ -97,7 +114,7 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
             for (int sb = 0; sb < 8; ++sb) r[zl][sb] = ok ? r[zl][sb] : 0.0f;
         }
 #pragma unroll
-        for (int zl = 0; zl < 3; ++zl) {
+        for (int zl = 0; zl < K + 1; ++zl) {
             float* rec = s_v + (zl * len + kk) * kRec;
             *reinterpret_cast<f32x4*>(rec) = f32x4{r[zl][0], r[zl][1], r[zl][2], r[zl][3]};
             *reinterpret_cast<f32x4*>(rec + 4) = f32x4{r[zl][4], r[zl][5], r[zl][6], r[zl][7]};
@@ -105,29 +122,34 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
     }
     __syncthreads();
     // thread = one cell of the (y,x) plane, for BOTH z-slices of the workgroup: the index arithmetic, the x-range
-    // selects' predicates and the middle z-plane's 4 neighbour records are shared by its two output cells
+    // selects' predicates and the shared z-planes' neighbour records are shared by its two output cells
     const int f = f0 + threadIdx.x;
     const bool in_plane = f < plane_cells;
     const int fc = min(f, plane_cells - 1);
     const int jy = fc / n2, jx = fc - jy * n2;
     const int k00 = jy * a.d2 + jx - chunk0;
-    const bool xok0 = jx < a.d2, xok1 = jx >= 1;
-    auto load_plane = [&](int zl, float (&P)[4][8]) {       // P[q = ey*2+ex][band] of z-plane zl
+    bool xok[K];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool xok = (q & 1) ? xok1 : xok0;
-            const float* rec = s_v + (zl * len + k00 - (q >> 1) * a.d2 - (q & 1)) * kRec;
+    for (int ex = 0; ex < K; ++ex) xok[ex] = x_in_level<K>(jx, ex, a.d2);
+    auto load_plane = [&](int zl, float (&P)[K * K][8]) {   // P[q = ey*K+ex][band] of z-plane zl
+#pragma unroll
+        for (int q = 0; q < K * K; ++q) {
+            const bool ok = xok[q % K];
+            const float* rec = s_v + (zl * len + k00 - (q / K) * a.d2 - (q % K)) * kRec;
             const f32x4 lo = *reinterpret_cast<const f32x4*>(rec);
             const f32x4 hi = *reinterpret_cast<const f32x4*>(rec + 4);
-            P[q][0] = xok ? lo.x : 0.0f; P[q][1] = xok ? lo.y : 0.0f; P[q][2] = xok ? lo.z : 0.0f; P[q][3] = xok ? lo.w : 0.0f;
-            P[q][4] = xok ? hi.x : 0.0f; P[q][5] = xok ? hi.y : 0.0f; P[q][6] = xok ? hi.z : 0.0f; P[q][7] = xok ? hi.w : 0.0f;
+            P[q][0] = ok ? lo.x : 0.0f; P[q][1] = ok ? lo.y : 0.0f; P[q][2] = ok ? lo.z : 0.0f; P[q][3] = ok ? lo.w : 0.0f;
+            P[q][4] = ok ? hi.x : 0.0f; P[q][5] = ok ? hi.y : 0.0f; P[q][6] = ok ? hi.z : 0.0f; P[q][7] = ok ? hi.w : 0.0f;
         }
     };
     float* outc = a.out + (long long)c * a.t0 * a.t1 * a.t2;
-    // one output cell jz from its neighbour planes: E0 = plane iz = jz (ez = 0), E1 = plane iz = jz - 1 (ez = 1)
-    auto cell = [&](int jz, const float (&E0)[4][8], const float (&E1)[4][8]) {
+    // K register sets of neighbour records, set zl % K holding z-plane zl
+    float S[K][K * K][8];
+    // one output cell jz = jz0 + h from its neighbour planes: plane iz = jz - ez is staged plane zl = K - 1 + h - ez
+    auto cell = [&](int h) {
+        const int jz = jz0 + h;
         const bool valid = in_plane && jz < n0;
-        auto V = [&](int e, int sb) -> float { return (e >> 2) ? E1[e & 3][sb] : E0[e & 3][sb]; };
+        auto V = [&](int ez, int ey, int ex, int sb) -> float { return S[(K - 1 + h - ez) % K][ey * K + ex][sb]; };
         auto store = [&](int p, float val) {
             const int oz = 2 * jz + (p >> 2) - a.o0, oy = 2 * jy + ((p >> 1) & 1) - a.o1, ox = 2 * jx + (p & 1) - a.o2;
             if (valid && oz >= 0 && oz < a.t0 && oy >= 0 && oy < a.t1 && ox >= 0 && ox < a.t2) {
@@ -139,37 +161,37 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
             for (int p = 0; p < 8; ++p) {
                 float t = 0.0f;
 #pragma unroll
-                for (int s8 = 0; s8 < 8; ++s8) t += V(p, s8);
+                for (int s8 = 0; s8 < 8; ++s8) t += V((p >> 2) % K, ((p >> 1) & 1) % K, (p & 1) % K, s8);
                 store(p, t);
             }
-        } else if (SEP) {
-            // F_s[tz][ty][tx] = T[sz][tz] T[sy][ty] T[sx][tx]: contract x, then y, then z in registers (224 FMAs
+        } else if constexpr (SEP) {
+            // F_s[tz][ty][tx] = T[sz][tz] T[sy][ty] T[sx][tx]: contract x, then y, then z in registers (K = 2: 224 FMAs
             // instead of 512, no filter traffic).  Tap of output parity p and neighbour e along one axis: t = p + 2 e.
-            float X[2][2][2][2][2];                           // [ez][ey][sz][sy][px]
+            float X[K][K][2][2][2];                           // [ez][ey][sz][sy][px]
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int ez = q >> 3, ey = (q >> 2) & 1, sz = (q >> 1) & 1, sy = q & 1;
+            for (int q = 0; q < 4 * K * K; ++q) {
+                const int ez = q / (4 * K), ey = (q / 4) % K, sz = (q >> 1) & 1, sy = q & 1;
 #pragma unroll
                 for (int px = 0; px < 2; ++px) {
                     float t = 0.0f;
 #pragma unroll
-                    for (int ex = 0; ex < 2; ++ex)
+                    for (int ex = 0; ex < K; ++ex)
 #pragma unroll
                         for (int sx = 0; sx < 2; ++sx)
-                            t = __builtin_fmaf(V(ez * 4 + ey * 2 + ex, sz * 4 + sy * 2 + sx), a.taps[sx * 4 + px + 2 * ex], t);
+                            t = __builtin_fmaf(V(ez, ey, ex, sz * 4 + sy * 2 + sx), a.taps[sx * L + px + 2 * ex], t);
                     X[ez][ey][sz][sy][px] = t;
                 }
             }
-            float Y[2][2][2][2];                              // [ez][sz][py][px]
+            float Y[K][2][2][2];                              // [ez][sz][py][px]
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int ez = q >> 3, sz = (q >> 2) & 1, py = (q >> 1) & 1, px = q & 1;
+            for (int q = 0; q < 8 * K; ++q) {
+                const int ez = q / 8, sz = (q >> 2) & 1, py = (q >> 1) & 1, px = q & 1;
                 float t = 0.0f;
 #pragma unroll
-                for (int ey = 0; ey < 2; ++ey)
+                for (int ey = 0; ey < K; ++ey)
 #pragma unroll
                     for (int sy = 0; sy < 2; ++sy)
-                        t = __builtin_fmaf(X[ez][ey][sz][sy][px], a.taps[sy * 4 + py + 2 * ey], t);
+                        t = __builtin_fmaf(X[ez][ey][sz][sy][px], a.taps[sy * L + py + 2 * ey], t);
                 Y[ez][sz][py][px] = t;
             }
 #pragma unroll
@@ -177,10 +199,10 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
                 const int pz = p >> 2, py = (p >> 1) & 1, px = p & 1;
                 float t = 0.0f;
 #pragma unroll
-                for (int ez = 0; ez < 2; ++ez)
+                for (int ez = 0; ez < K; ++ez)
 #pragma unroll
                     for (int sz = 0; sz < 2; ++sz)
-                        t = __builtin_fmaf(Y[ez][sz][py][px], a.taps[sz * 4 + pz + 2 * ez], t);
+                        t = __builtin_fmaf(Y[ez][sz][py][px], a.taps[sz * L + pz + 2 * ez], t);
                 store(p, t);
             }
         } else {
@@ -190,24 +212,24 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
                 float acc = 0.0f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const int tap = ((pz + 2 * (e >> 2)) * 4 + (py + 2 * ((e >> 1) & 1))) * 4 + (px + 2 * (e & 1));
+                    const int ez = e >> 2, ey = (e >> 1) & 1, ex = e & 1;
+                    const int tap = ((pz + 2 * ez) * 4 + (py + 2 * ey)) * 4 + (px + 2 * ex);
                     const f32x4 f0v = *reinterpret_cast<const f32x4*>(s_f + tap * 8);
                     const f32x4 f1v = *reinterpret_cast<const f32x4*>(s_f + tap * 8 + 4);
-                    acc = __builtin_fmaf(V(e, 0), f0v.x, acc); acc = __builtin_fmaf(V(e, 1), f0v.y, acc);
-                    acc = __builtin_fmaf(V(e, 2), f0v.z, acc); acc = __builtin_fmaf(V(e, 3), f0v.w, acc);
-                    acc = __builtin_fmaf(V(e, 4), f1v.x, acc); acc = __builtin_fmaf(V(e, 5), f1v.y, acc);
-                    acc = __builtin_fmaf(V(e, 6), f1v.z, acc); acc = __builtin_fmaf(V(e, 7), f1v.w, acc);
+                    acc = __builtin_fmaf(V(ez, ey, ex, 0), f0v.x, acc); acc = __builtin_fmaf(V(ez, ey, ex, 1), f0v.y, acc);
+                    acc = __builtin_fmaf(V(ez, ey, ex, 2), f0v.z, acc); acc = __builtin_fmaf(V(ez, ey, ex, 3), f0v.w, acc);
+                    acc = __builtin_fmaf(V(ez, ey, ex, 4), f1v.x, acc); acc = __builtin_fmaf(V(ez, ey, ex, 5), f1v.y, acc);
+                    acc = __builtin_fmaf(V(ez, ey, ex, 6), f1v.z, acc); acc = __builtin_fmaf(V(ez, ey, ex, 7), f1v.w, acc);
                 }
                 store(p, acc);      // stored per parity: keeps the filter reads of later parities from being hoisted
             }
         }
     };
-    float PA[4][8], PB[4][8];
-    load_plane(1, PA);
-    load_plane(0, PB);
-    cell(jz0, PA, PB);              // outputs of cell jz0: planes jz0 (ez = 0) and jz0 - 1 (ez = 1)
-    load_plane(2, PB);
-    cell(jz0 + 1, PB, PA);          // cell jz0 + 1: planes jz0 + 1 and jz0
+#pragma unroll
+    for (int zl = K - 1; zl >= 0; --zl) load_plane(zl, S[zl % K]);
+    cell(0);                        // outputs of cell jz0: staged planes K-1 .. 0
+    load_plane(K, S[K % K]);
+    cell(1);                        // cell jz0 + 1: staged planes K .. 1
 }
 
 // Synthesis with a SLIDING WINDOW along z (separable filters): a workgroup keeps its 256 plane cells and walks `zchunk`
@@ -215,8 +237,10 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs a) {
 // tiled kernel above stages 3 planes per 2 slices), into a 2-slot LDS ring with one barrier per step, and the loads of
 // plane jz + 1 are issued right after the barrier so that they fly under the arithmetic of slice jz.  A thread keeps the
 // 4 neighbour records of plane jz in registers: they are the ez = 1 operands of the next step.
+// Written for K = 2 (db2): a Haar level stages every plane once in the tiled kernel already, and the register carry of
+// the K - 1 previous planes does not fit for K >= 3.
 template <bool DROP, int KI>
-__global__ __launch_bounds__(256) void idwt_slide_kernel(const IdwtArgs a) {
+__global__ __launch_bounds__(256) void idwt_slide_kernel(const IdwtArgs<2> a) {
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     float* s_v = s_dyn;                                   // ring[2][len][kRec]: a plane is read from LDS only in its own step
     const int n0 = a.d0 + 1, n1 = a.d1 + 1, n2 = a.d2 + 1;
@@ -356,8 +380,9 @@ __global__ __launch_bounds__(256) void idwt_slide_kernel(const IdwtArgs a) {
 //   band_s[c][i] = sum_t src_full[c][2 i + t] * F_s[t],  src_full[u] = src[u - lo] (0 outside [0, n))
 // DROP (adjoint with the pruning factors):  stored gradient = band_s * m_s,  d_m_s[i] += band_s[c][i] * coef_s[c][i]
 // (float atomics over the channels: whole 256-byte rows per wave instruction, 8..32 adds per address).
-// LDS: [512 taps] [6 chunks (source z-plane 2 iz0 - lo0 + zl) of `len` floats]; chunk element k is plane offset
-// chunk0 + k, chunk0 = (2 * first cell row - lo1) * n2 - lo2.
+// LDS: [512 taps (K = 2 only)] [2K+2 chunks (source z-plane 2 iz0 - lo0 + zl) of `len` floats]; chunk element k is
+// plane offset chunk0 + k, chunk0 = (2 * first cell row - lo1) * n2 - lo2.
+template <int K>
 struct AnalysisArgs {
     const float* src;      // (C, n0,n1,n2)
     const float* filt;
@@ -366,7 +391,7 @@ struct AnalysisArgs {
     long long cstride0, cstrideh;
     int C, n0, n1, n2, lo0, lo1, lo2, d0, d1, d2;
     int len;
-    float taps[8];         // SEP build: [low | high][tap]
+    float taps[4 * K];     // SEP build: [low | high][tap]
     // DROP build only
     const float* lll;      // forward inputs (C, d0,d1,d2), (C, 7, d0,d1,d2): needed for d_mul
     const float* hf;
@@ -382,11 +407,13 @@ struct AnalysisArgs {
 
 __device__ __forceinline__ float sign_of(float v) { return (float)((v > 0.0f) - (v < 0.0f)); }
 
-template <bool DROP, bool SEP>
-__global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs a) {
+template <bool DROP, bool SEP, int K>
+__global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs<K> a) {
+    static_assert(SEP || K == 2, "dense (non-separable) filters are 4-tap only");
+    constexpr int L = 2 * K;
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     float* s_f = s_dyn;
-    float* s_v = s_dyn + 512;
+    float* s_v = s_dyn + filt_floats<K>();
     if (!SEP)
         for (int i = threadIdx.x; i < 512; i += 256) s_f[(i & 63) * 8 + (i >> 6)] = a.filt[i];
     const int plane_cells = a.d1 * a.d2;
@@ -401,16 +428,16 @@ __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs a) {
     for (int kk = threadIdx.x; kk < len; kk += 256) {
         const int off = chunk0 + kk;
         const bool in_plane = off >= 0 && off < nplane;
-        float r[6];
+        float r[L + 2];
 #pragma unroll
-        for (int zl = 0; zl < 6; ++zl) {
+        for (int zl = 0; zl < L + 2; ++zl) {
             const int uz = 2 * iz0 - a.lo0 + zl;
             const bool ok = in_plane && uz >= 0 && uz < a.n0;
             const float x = src[ok ? uz * nplane + off : 0];
             r[zl] = ok ? x : 0.0f;
         }
 #pragma unroll
-        for (int zl = 0; zl < 6; ++zl) s_v[zl * len + kk] = r[zl];
+        for (int zl = 0; zl < L + 2; ++zl) s_v[zl * len + kk] = r[zl];
     }
     __syncthreads();
     const int zl_t = threadIdx.x >> 7;
@@ -425,26 +452,26 @@ __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs a) {
     // every tap of a valid cell lies inside the staged chunk; rows / planes outside the source were staged as zeros,
     // so only the x range needs a select
     const int k0 = (2 * iy - a.lo1) * a.n2 + (2 * ix - a.lo2) - chunk0;
-    bool xok[4];
+    bool xok[L];
 #pragma unroll
-    for (int tx = 0; tx < 4; ++tx) { const int ux = 2 * ix + tx - a.lo2; xok[tx] = ux >= 0 && ux < a.n2; }
-    if (SEP) {
+    for (int tx = 0; tx < L; ++tx) { const int ux = 2 * ix + tx - a.lo2; xok[tx] = ux >= 0 && ux < a.n2; }
+    if constexpr (SEP) {
         // contract x, then y, then z (see idwt_level_kernel): band s = 4 sz + 2 sy + sx
-        float Y[4][2][2];                                 // [tz][sy][sx]
+        float Y[L][2][2];                                 // [tz][sy][sx]
 #pragma unroll
-        for (int tz = 0; tz < 4; ++tz) {
+        for (int tz = 0; tz < L; ++tz) {
             const float* pl = s_v + (2 * zl_t + tz) * len + k0;
-            float X[4][2];                                // [ty][sx]
+            float X[L][2];                                // [ty][sx]
 #pragma unroll
-            for (int ty = 0; ty < 4; ++ty) {
+            for (int ty = 0; ty < L; ++ty) {
                 const float* row = pl + ty * a.n2;
                 float x0 = 0.0f, x1 = 0.0f;
 #pragma unroll
-                for (int tx = 0; tx < 4; ++tx) {
+                for (int tx = 0; tx < L; ++tx) {
                     const float raw = row[tx];                  // always in the chunk: load first, then select (a ternary
                     const float val = xok[tx] ? raw : 0.0f;     // around the load compiles to an exec-masked branch per tap)
                     x0 = __builtin_fmaf(val, a.taps[tx], x0);
-                    x1 = __builtin_fmaf(val, a.taps[4 + tx], x1);
+                    x1 = __builtin_fmaf(val, a.taps[L + tx], x1);
                 }
                 X[ty][0] = x0; X[ty][1] = x1;
             }
@@ -454,7 +481,7 @@ __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs a) {
                 for (int sx = 0; sx < 2; ++sx) {
                     float t = 0.0f;
 #pragma unroll
-                    for (int ty = 0; ty < 4; ++ty) t = __builtin_fmaf(X[ty][sx], a.taps[sy * 4 + ty], t);
+                    for (int ty = 0; ty < L; ++ty) t = __builtin_fmaf(X[ty][sx], a.taps[sy * L + ty], t);
                     Y[tz][sy][sx] = t;
                 }
         }
@@ -462,7 +489,7 @@ __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs a) {
         for (int sb = 0; sb < 8; ++sb) {
             float t = 0.0f;
 #pragma unroll
-            for (int tz = 0; tz < 4; ++tz) t = __builtin_fmaf(Y[tz][(sb >> 1) & 1][sb & 1], a.taps[(sb >> 2) * 4 + tz], t);
+            for (int tz = 0; tz < L; ++tz) t = __builtin_fmaf(Y[tz][(sb >> 1) & 1][sb & 1], a.taps[(sb >> 2) * L + tz], t);
             acc[sb] = t;
         }
     } else {
@@ -568,11 +595,18 @@ __global__ __launch_bounds__(256) void last_to_first_kernel(const float* __restr
     }
 }
 
-inline int check_level(const void* a, const void* b, const void* c, const void* d, int C, int d0, int d1, int d2,
+// filter_len -> K, or 0 for a length without kernels; a dense (non-separable) filter must be 4-tap
+inline int half_len(int filter_len, const float* taps) {
+    if (filter_len != 2 && filter_len != 4 && filter_len != 6 && filter_len != 8) return 0;
+    if (!taps && filter_len != 4) return 0;
+    return filter_len / 2;
+}
+
+inline int check_level(const void* a, const void* b, const void* c, const void* d, int L, int C, int d0, int d1, int d2,
                        int t0, int t1, int t2) {
     if (!a || !b || !c || !d) return LFGC_E_NULL;
     if (C < 1 || d0 < 1 || d1 < 1 || d2 < 1 || t0 < 1 || t1 < 1 || t2 < 1) return LFGC_E_SHAPE;
-    if (t0 > 2 * d0 + 2 || t1 > 2 * d1 + 2 || t2 > 2 * d2 + 2) return LFGC_E_SHAPE;
+    if (t0 > 2 * d0 + L - 2 || t1 > 2 * d1 + L - 2 || t2 > 2 * d2 + L - 2) return LFGC_E_SHAPE;
     return LFGC_OK;
 }
 
@@ -589,19 +623,21 @@ int launch_tiled(K kern, int* lds_limit, const A& a, dim3 blocks, int lds_bytes,
     return LFGC_OK;
 }
 
-int launch_idwt(IdwtArgs a, bool drop, const float* taps, hipStream_t stream) {
-    if (taps) for (int i = 0; i < 8; ++i) a.taps[i] = taps[i];
-    a.o0 = (2 * a.d0 + 2 - a.t0) / 2; a.o1 = (2 * a.d1 + 2 - a.t1) / 2; a.o2 = (2 * a.d2 + 2 - a.t2) / 2;
-    const int n0 = a.d0 + 1, n1 = a.d1 + 1, n2 = a.d2 + 1;
+template <int K>
+int launch_idwt(IdwtArgs<K> a, bool drop, const float* taps, hipStream_t stream) {
+    if (taps) for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
+    a.o0 = (2 * a.d0 + 2 * K - 2 - a.t0) / 2; a.o1 = (2 * a.d1 + 2 * K - 2 - a.t1) / 2; a.o2 = (2 * a.d2 + 2 * K - 2 - a.t2) / 2;
+    const int n0 = a.d0 + K - 1, n1 = a.d1 + K - 1, n2 = a.d2 + K - 1;
     const int span = (kFwdCells + n2 - 2) / n2;             // rows a run of 256 cells can straddle beyond its first
-    a.len = (span + 2) * a.d2 + 2;
+    a.len = (span + K) * a.d2 + 2 * K - 2;
     const long long ptiles = ((long long)n1 * n2 + kFwdCells - 1) / kFwdCells;
     if (ptiles > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
     const dim3 blocks((unsigned)ptiles, (unsigned)((n0 + 1) / 2), (unsigned)a.C);
-    const int lds = (512 + 3 * a.len * kRec) * 4;
+    const int lds = (filt_floats<K>() + (K + 1) * a.len * kRec) * 4;
     if ((long long)a.d0 * a.d1 * a.d2 > 0x7fffffffLL / 8 || (long long)a.t0 * a.t1 * a.t2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
     static int lim[4][LFGC_MAX_DEVICES] = {{0}};       // per (kernel, device)
     const int dev_lim = lfgc_current_device();
+    if constexpr (K == 2) {
     const int ki = (a.len + 255) / 256;
     // Small levels (<= 40 000 output voxels per channel: everything below the last two levels of a 64^3 grid) take the tiled
     // kernel below: one load -> barrier -> stencil -> store round per workgroup instead of a z walk whose every step waits
@@ -622,70 +658,129 @@ int launch_idwt(IdwtArgs a, bool drop, const float* taps, hipStream_t stream) {
         if (ki == 2) return launch_tiled(idwt_slide_kernel<false, 2>, &slim[4][dev_slim], a, sblocks, slds, stream);
         return launch_tiled(idwt_slide_kernel<false, 3>, &slim[5][dev_slim], a, sblocks, slds, stream);
     }
-    if (taps) return drop ? launch_tiled(idwt_level_kernel<true, true>, &lim[3][dev_lim], a, blocks, lds, stream)
-                          : launch_tiled(idwt_level_kernel<false, true>, &lim[2][dev_lim], a, blocks, lds, stream);
-    return drop ? launch_tiled(idwt_level_kernel<true, false>, &lim[1][dev_lim], a, blocks, lds, stream)
-                : launch_tiled(idwt_level_kernel<false, false>, &lim[0][dev_lim], a, blocks, lds, stream);
+    if (!taps) return drop ? launch_tiled(idwt_level_kernel<true, false, K>, &lim[1][dev_lim], a, blocks, lds, stream)
+                           : launch_tiled(idwt_level_kernel<false, false, K>, &lim[0][dev_lim], a, blocks, lds, stream);
+    }
+    return drop ? launch_tiled(idwt_level_kernel<true, true, K>, &lim[3][dev_lim], a, blocks, lds, stream)
+                : launch_tiled(idwt_level_kernel<false, true, K>, &lim[2][dev_lim], a, blocks, lds, stream);
 }
 
-int launch_analysis(AnalysisArgs a, bool drop, const float* taps, hipStream_t stream) {
-    if (taps) for (int i = 0; i < 8; ++i) a.taps[i] = taps[i];
+template <int K>
+int launch_analysis(AnalysisArgs<K> a, bool drop, const float* taps, hipStream_t stream) {
+    if (taps) for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
     const int span = (kTileCells + a.d2 - 2) / a.d2;
-    a.len = (2 * span + 3) * a.n2 + 2 * a.d2 + 2;
+    a.len = (2 * span + 2 * K - 1) * a.n2 + 2 * a.d2 + 2 * K - 2;
     const long long ptiles = ((long long)a.d1 * a.d2 + kTileCells - 1) / kTileCells;
     if (ptiles > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
     const dim3 blocks((unsigned)ptiles, (unsigned)((a.d0 + 1) / 2), (unsigned)a.C);
-    const int lds = (512 + 6 * a.len) * 4;
+    const int lds = (filt_floats<K>() + (2 * K + 2) * a.len) * 4;
     if ((long long)a.n0 * a.n1 * a.n2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
     static int lim[4][LFGC_MAX_DEVICES] = {{0}};       // per (kernel, device)
     const int dev_lim = lfgc_current_device();
-    if (taps) return drop ? launch_tiled(analysis_kernel<true, true>, &lim[3][dev_lim], a, blocks, lds, stream)
-                          : launch_tiled(analysis_kernel<false, true>, &lim[2][dev_lim], a, blocks, lds, stream);
-    return drop ? launch_tiled(analysis_kernel<true, false>, &lim[1][dev_lim], a, blocks, lds, stream)
-                : launch_tiled(analysis_kernel<false, false>, &lim[0][dev_lim], a, blocks, lds, stream);
+    if constexpr (K == 2) {
+        if (!taps) return drop ? launch_tiled(analysis_kernel<true, false, K>, &lim[1][dev_lim], a, blocks, lds, stream)
+                               : launch_tiled(analysis_kernel<false, false, K>, &lim[0][dev_lim], a, blocks, lds, stream);
+    }
+    return drop ? launch_tiled(analysis_kernel<true, true, K>, &lim[3][dev_lim], a, blocks, lds, stream)
+                : launch_tiled(analysis_kernel<false, true, K>, &lim[2][dev_lim], a, blocks, lds, stream);
+}
+
+// Runs f(std::integral_constant<int, K>) for the half-length K of filter_len (half_len() != 0 checked by the caller).
+template <typename F>
+int with_half_len(int K, F&& f) {
+    switch (K) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+    }
+    return LFGC_E_UNSUPPORTED;
+}
+
+template <int K>
+AnalysisArgs<K> adjoint_args(const float* d_out, const float* filter_rev, float* d_lll, float* d_hf,
+                             int C, int d0, int d1, int d2, int t0, int t1, int t2) {
+    AnalysisArgs<K> a = {};
+    a.src = d_out; a.filt = filter_rev; a.band0 = d_lll; a.bandh = d_hf;
+    const long long dvol = (long long)d0 * d1 * d2;
+    a.cstride0 = dvol; a.cstrideh = 7 * dvol;
+    a.C = C; a.n0 = t0; a.n1 = t1; a.n2 = t2;
+    a.lo0 = (2 * d0 + 2 * K - 2 - t0) / 2; a.lo1 = (2 * d1 + 2 * K - 2 - t1) / 2; a.lo2 = (2 * d2 + 2 * K - 2 - t2) / 2;
+    a.d0 = d0; a.d1 = d1; a.d2 = d2;
+    return a;
 }
 
 }  // namespace
 
+extern "C" int lfgc_idwt_level_drop_len_f32(const float* lll, const float* hf, const float* mul_lll, float thr_lll,
+                                            const float* mul_hf, float thr_hf, const float* filter_rev, const float* taps,
+                                            int filter_len, float* out, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                                            lfgc_stream_t stream) {
+    const int K = half_len(filter_len, taps);
+    if (!K) return LFGC_E_UNSUPPORTED;
+    const int rc = check_level(lll, hf, taps ? (const void*)taps : (const void*)filter_rev, out, filter_len, C, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    return with_half_len(K, [&](auto kc) {
+        constexpr int KK = decltype(kc)::value;
+        IdwtArgs<KK> a = {};
+        a.lll = lll; a.hf = hf; a.filt = filter_rev; a.out = out;
+        a.C = C; a.d0 = d0; a.d1 = d1; a.d2 = d2; a.t0 = t0; a.t1 = t1; a.t2 = t2;
+        a.mul_l = mul_lll; a.mul_h = mul_hf; a.thr_l = thr_lll; a.thr_h = thr_hf;
+        return launch_idwt<KK>(a, mul_lll || mul_hf, taps, (hipStream_t)stream);
+    });
+}
+
+extern "C" int lfgc_idwt_level_len_f32(const float* lll, const float* hf, const float* filter_rev, const float* taps,
+                                       int filter_len, float* out, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                                       lfgc_stream_t stream) {
+    return lfgc_idwt_level_drop_len_f32(lll, hf, nullptr, 0.0f, nullptr, 0.0f, filter_rev, taps, filter_len, out,
+                                        C, d0, d1, d2, t0, t1, t2, stream);
+}
+
 extern "C" int lfgc_idwt_level_f32(const float* lll, const float* hf, const float* filter_rev, const float* taps, float* out,
                                    int C, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
-    const int rc = check_level(lll, hf, taps ? (const void*)taps : (const void*)filter_rev, out, C, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    IdwtArgs a = {};
-    a.lll = lll; a.hf = hf; a.filt = filter_rev; a.out = out;
-    a.C = C; a.d0 = d0; a.d1 = d1; a.d2 = d2; a.t0 = t0; a.t1 = t1; a.t2 = t2;
-    return launch_idwt(a, false, taps, (hipStream_t)stream);
+    return lfgc_idwt_level_len_f32(lll, hf, filter_rev, taps, 4, out, C, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_drop_f32(const float* lll, const float* hf, const float* mul_lll, float thr_lll,
                                         const float* mul_hf, float thr_hf, const float* filter_rev, const float* taps, float* out,
                                         int C, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
-    const int rc = check_level(lll, hf, taps ? (const void*)taps : (const void*)filter_rev, out, C, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    IdwtArgs a = {};
-    a.lll = lll; a.hf = hf; a.filt = filter_rev; a.out = out;
-    a.C = C; a.d0 = d0; a.d1 = d1; a.d2 = d2; a.t0 = t0; a.t1 = t1; a.t2 = t2;
-    a.mul_l = mul_lll; a.mul_h = mul_hf; a.thr_l = thr_lll; a.thr_h = thr_hf;
-    return launch_idwt(a, mul_lll || mul_hf, taps, (hipStream_t)stream);
+    return lfgc_idwt_level_drop_len_f32(lll, hf, mul_lll, thr_lll, mul_hf, thr_hf, filter_rev, taps, 4, out,
+                                        C, d0, d1, d2, t0, t1, t2, stream);
 }
 
-static AnalysisArgs adjoint_args(const float* d_out, const float* filter_rev, float* d_lll, float* d_hf,
-                                 int C, int d0, int d1, int d2, int t0, int t1, int t2) {
-    AnalysisArgs a = {};
-    a.src = d_out; a.filt = filter_rev; a.band0 = d_lll; a.bandh = d_hf;
-    const long long dvol = (long long)d0 * d1 * d2;
-    a.cstride0 = dvol; a.cstrideh = 7 * dvol;
-    a.C = C; a.n0 = t0; a.n1 = t1; a.n2 = t2;
-    a.lo0 = (2 * d0 + 2 - t0) / 2; a.lo1 = (2 * d1 + 2 - t1) / 2; a.lo2 = (2 * d2 + 2 - t2) / 2;
-    a.d0 = d0; a.d1 = d1; a.d2 = d2;
-    return a;
+extern "C" int lfgc_idwt_level_drop_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
+                                                const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                                float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                                const float* const* penalty_grads, int C, int d0, int d1, int d2,
+                                                int t0, int t1, int t2, lfgc_stream_t stream) {
+    const int K = half_len(filter_len, taps);
+    if (!K) return LFGC_E_UNSUPPORTED;
+    const int rc = check_level(d_out, taps ? (const void*)taps : (const void*)filter_rev, d_lll, d_hf, filter_len, C, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    if ((d_mul_lll && (!mul_lll || !lll)) || (d_mul_hf && (!mul_hf || !hf))) return LFGC_E_NULL;
+    const float* pg[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (penalty_grads) for (int i = 0; i < 4; ++i) pg[i] = penalty_grads[i];
+    if ((pg[0] && !lll) || (pg[1] && !hf) || (pg[2] && !d_mul_lll) || (pg[3] && !d_mul_hf)) return LFGC_E_NULL;
+    return with_half_len(K, [&](auto kc) {
+        constexpr int KK = decltype(kc)::value;
+        AnalysisArgs<KK> a = adjoint_args<KK>(d_out, filter_rev, d_lll, d_hf, C, d0, d1, d2, t0, t1, t2);
+        a.lll = lll; a.hf = hf; a.mul_l = mul_lll; a.mul_h = mul_hf; a.d_mul_l = d_mul_lll; a.d_mul_h = d_mul_hf;
+        a.g_l2_l = pg[0]; a.g_l2_h = pg[1]; a.g_l1_l = pg[2]; a.g_l1_h = pg[3];
+        return launch_analysis<KK>(a, mul_lll || mul_hf || pg[0] || pg[1], taps, (hipStream_t)stream);
+    });
+}
+
+extern "C" int lfgc_idwt_level_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
+                                           float* d_lll, float* d_hf, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                                           lfgc_stream_t stream) {
+    return lfgc_idwt_level_drop_bwd_len_f32(d_out, filter_rev, taps, filter_len, nullptr, nullptr, nullptr, nullptr, d_lll, d_hf,
+                                            nullptr, nullptr, nullptr, C, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_bwd_f32(const float* d_out, const float* filter_rev, const float* taps, float* d_lll, float* d_hf,
                                        int C, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
-    const int rc = check_level(d_out, taps ? (const void*)taps : (const void*)filter_rev, d_lll, d_hf, C, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    return launch_analysis(adjoint_args(d_out, filter_rev, d_lll, d_hf, C, d0, d1, d2, t0, t1, t2), false, taps, (hipStream_t)stream);
+    return lfgc_idwt_level_bwd_len_f32(d_out, filter_rev, taps, 4, d_lll, d_hf, C, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_drop_bwd_f32(const float* d_out, const float* filter_rev, const float* taps, const float* lll, const float* hf,
@@ -693,33 +788,37 @@ extern "C" int lfgc_idwt_level_drop_bwd_f32(const float* d_out, const float* fil
                                             float* d_mul_lll, float* d_mul_hf, const float* const* penalty_grads,
                                             int C, int d0, int d1, int d2,
                                             int t0, int t1, int t2, lfgc_stream_t stream) {
-    const int rc = check_level(d_out, taps ? (const void*)taps : (const void*)filter_rev, d_lll, d_hf, C, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    if ((d_mul_lll && (!mul_lll || !lll)) || (d_mul_hf && (!mul_hf || !hf))) return LFGC_E_NULL;
-    const float* pg[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (penalty_grads) for (int i = 0; i < 4; ++i) pg[i] = penalty_grads[i];
-    if ((pg[0] && !lll) || (pg[1] && !hf) || (pg[2] && !d_mul_lll) || (pg[3] && !d_mul_hf)) return LFGC_E_NULL;
-    AnalysisArgs a = adjoint_args(d_out, filter_rev, d_lll, d_hf, C, d0, d1, d2, t0, t1, t2);
-    a.lll = lll; a.hf = hf; a.mul_l = mul_lll; a.mul_h = mul_hf; a.d_mul_l = d_mul_lll; a.d_mul_h = d_mul_hf;
-    a.g_l2_l = pg[0]; a.g_l2_h = pg[1]; a.g_l1_l = pg[2]; a.g_l1_h = pg[3];
-    return launch_analysis(a, mul_lll || mul_hf || pg[0] || pg[1], taps, (hipStream_t)stream);
+    return lfgc_idwt_level_drop_bwd_len_f32(d_out, filter_rev, taps, 4, lll, hf, mul_lll, mul_hf, d_lll, d_hf, d_mul_lll,
+                                            d_mul_hf, penalty_grads, C, d0, d1, d2, t0, t1, t2, stream);
+}
+
+extern "C" int lfgc_dwt_level_len_f32(const float* in, const float* filter_fwd, const float* taps, int filter_len, float* out,
+                                      int C, int n0, int n1, int n2, lfgc_stream_t stream) {
+    if (!in || (!filter_fwd && !taps) || !out) return LFGC_E_NULL;
+    const int K = half_len(filter_len, taps);
+    if (!K) return LFGC_E_UNSUPPORTED;
+    if (C < 1 || n0 < 1 || n1 < 1 || n2 < 1) return LFGC_E_SHAPE;
+    // _get_padding_size (Torch_Wavelet_Transform.py:59-63): (2L-3)//2 = L-2 on both sides, plus the odd bit on the high
+    // side; F.pad slots are (last axis lo, hi, ..., first axis lo, hi) while is_odd is indexed first axis first -> the
+    // odd bit of axis a pads axis 2-a.
+    const int lo = filter_len - 2;
+    const int hi0 = lo + (n2 & 1), hi1 = lo + (n1 & 1), hi2 = lo + (n0 & 1);
+    return with_half_len(K, [&](auto kc) {
+        constexpr int KK = decltype(kc)::value;
+        AnalysisArgs<KK> a = {};
+        a.src = in; a.filt = filter_fwd;
+        a.d0 = (n0 + lo + hi0 - filter_len) / 2 + 1; a.d1 = (n1 + lo + hi1 - filter_len) / 2 + 1; a.d2 = (n2 + lo + hi2 - filter_len) / 2 + 1;
+        const long long dvol = (long long)a.d0 * a.d1 * a.d2;
+        a.band0 = out; a.bandh = out + dvol;
+        a.cstride0 = 8 * dvol; a.cstrideh = 8 * dvol;
+        a.C = C; a.n0 = n0; a.n1 = n1; a.n2 = n2; a.lo0 = lo; a.lo1 = lo; a.lo2 = lo;
+        return launch_analysis<KK>(a, false, taps, (hipStream_t)stream);
+    });
 }
 
 extern "C" int lfgc_dwt_level_f32(const float* in, const float* filter_fwd, const float* taps, float* out,
                                   int C, int n0, int n1, int n2, lfgc_stream_t stream) {
-    if (!in || (!filter_fwd && !taps) || !out) return LFGC_E_NULL;
-    if (C < 1 || n0 < 1 || n1 < 1 || n2 < 1) return LFGC_E_SHAPE;
-    // _get_padding_size (Torch_Wavelet_Transform.py:59-63): F.pad slots are (last axis lo, hi, ..., first axis
-    // lo, hi) while is_odd is indexed first axis first -> the odd bit of axis a pads axis 2-a.
-    const int hi0 = 2 + (n2 & 1), hi1 = 2 + (n1 & 1), hi2 = 2 + (n0 & 1);
-    AnalysisArgs a = {};
-    a.src = in; a.filt = filter_fwd;
-    a.d0 = (n0 + 2 + hi0 - 4) / 2 + 1; a.d1 = (n1 + 2 + hi1 - 4) / 2 + 1; a.d2 = (n2 + 2 + hi2 - 4) / 2 + 1;
-    const long long dvol = (long long)a.d0 * a.d1 * a.d2;
-    a.band0 = out; a.bandh = out + dvol;
-    a.cstride0 = 8 * dvol; a.cstrideh = 8 * dvol;
-    a.C = C; a.n0 = n0; a.n1 = n1; a.n2 = n2; a.lo0 = 2; a.lo1 = 2; a.lo2 = 2;
-    return launch_analysis(a, false, taps, (hipStream_t)stream);
+    return lfgc_dwt_level_len_f32(in, filter_fwd, taps, 4, out, C, n0, n1, n2, stream);
 }
 
 extern "C" int lfgc_grid_layout_f32(const float* src, float* dst, int C, int64_t voxels, int channel_stride,

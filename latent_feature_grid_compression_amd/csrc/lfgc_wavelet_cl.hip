@@ -4,6 +4,9 @@
 // so that decode_volume() needs no layout conversion pass (lfgc_grid_layout_f32) on either direction.  Separable
 // filter banks only (`taps`); the dense-stencil path keeps the channel-first kernels + the conversion.
 //
+// Templates on the half filter length K: K = 2 (db2) and K = 1 (Haar, no neighbour cells and no z carry: each 2x2x2
+// output block is a butterfly of one cell's 8 bands).  Longer filters take the channel-first kernels + the conversion.
+//
 // Both kernels have one shape.  A workgroup owns 32 consecutive cells of the flattened (y,x) plane, a group of CW = 32,
 // 16 or 8 channels (CW / 2 waves), and walks a chunk of z steps.  The coefficient side is channel-first (contiguous along the cells), the
 // grid side channel-last (contiguous along the channels), so the arithmetic runs with the lanes along whichever side is
@@ -82,22 +85,25 @@ __device__ __forceinline__ bool cl_work_item(int ptiles, int ngroups, int nchunk
     return true;
 }
 
+template <int K>
 struct IdwtClArgs {
     const float* lll;   // (C, d0,d1,d2)
     const float* hf;    // (C, 7, d0,d1,d2)
     float* out;         // (t0,t1,t2, cs)
-    int C, cs, d0, d1, d2, t0, t1, t2, o0, o1, o2;   // o = crop offset floor((2d+2-t)/2)
+    int C, cs, d0, d1, d2, t0, t1, t2, o0, o1, o2;   // o = crop offset floor((2d+2K-2-t)/2)
     int zchunk, ptiles, ngroups, nchunks;
-    float taps[8];      // [low | high][tap]
+    float taps[4 * K];  // [low | high][tap]
 };
 
-// Synthesis: out_full[o] = sum_{s,t} in[s][i] F_s[t], o = 2 i + t per axis; cell j = (jz,jy,jx) in [0,d] per axis
-// produces the 2x2x2 outputs o = 2 j + p from the coefficient cells i = j - e (e in {0,1}) with taps t = p + 2 e.
+// Synthesis: out_full[o] = sum_{s,t} in[s][i] F_s[t], o = 2 i + t per axis; cell j = (jz,jy,jx) in [0,d+K-2] per axis
+// produces the 2x2x2 outputs o = 2 j + p from the coefficient cells i = j - e (e in [0,K)) with taps t = p + 2 e.
 // Plane iz of the coefficients is contracted over x and y once (Y[sz][py][px]); its e_z = 0 part completes cell slice
-// jz = iz (added to the carry of plane iz - 1), its e_z = 1 part is the carry for slice iz + 1.
+// jz = iz (added to the carry of the earlier planes), its e_z = e part is carried to slice iz + e.
 // Arithmetic role: 32 cells x 2 channels per wave: channel = c0 + 2 wave + lane / 32.
-template <int CW, int CELLS, bool NT>
-__global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs a) {
+template <int CW, int CELLS, bool NT, int K>
+__global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs<K> a) {
+    constexpr int L = 2 * K;
+    constexpr int KC = K > 1 ? K - 1 : 1;             // z-carry slots (8 floats each)
     constexpr int CPL = 64 / CELLS;                   // channels per wave in the arithmetic role
     constexpr int CPW = ClShape<CW>::CPW, VOX = ClShape<CW>::VOX;
     constexpr int TILE = 8 * CELLS * VOX;
@@ -106,7 +112,7 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs a)
     if (!cl_work_item(a.ptiles, a.ngroups, a.nchunks, &pt, &cg, &zc)) return;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n0 = a.d0 + 1, n1 = a.d1 + 1, n2 = a.d2 + 1;
+    const int n0 = a.d0 + (K - 1), n1 = a.d1 + (K - 1), n2 = a.d2 + (K - 1);
     const int plane_cells = n1 * n2;
     const int f0 = pt * CELLS;
     const int c0 = cg * CW;
@@ -114,19 +120,19 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs a)
     const int dplane = a.d1 * a.d2;
     const int dvol = dplane * a.d0;                   // C * 7 * dvol * 4 < 2^30 (host check)
 
-    // arithmetic role: byte offsets of the 4 neighbour cells (jy - ey, jx - ex) inside a coefficient plane, plus the
+    // arithmetic role: byte offsets of the K*K neighbour cells (jy - ey, jx - ex) inside a coefficient plane, plus the
     // lane's channel parity; everything else of the address is wave-uniform
     const int cell = lane & (CELLS - 1), chalf = lane / CELLS;
     const int cw = CPL * w + chalf;                      // channel within the group
-    unsigned offl[4];                                  // low band; the detail bands' offset is offl + hshift (7 bands per channel)
+    unsigned offl[K * K];                              // low band; the detail bands' offset is offl + hshift (7 bands per channel)
     unsigned hshift;
     {
         const int f = f0 + cell;
         const int fc = min(f, plane_cells - 1);
         const int jy = fc / n2, jx = fc - jy * n2;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int cy = jy - (q >> 1), cx = jx - (q & 1);
+        for (int q = 0; q < K * K; ++q) {
+            const int cy = jy - q / K, cx = jx - q % K;
             const bool ok = f < plane_cells && c0 + cw < a.C && cy >= 0 && cy < a.d1 && cx >= 0 && cx < a.d2;
             offl[q] = ok ? 4u * (unsigned)(chalf * dvol + cy * a.d2 + cx) : kOutside;
         }
@@ -155,24 +161,24 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs a)
     const int slice = a.t1 * a.t2 * a.cs;
     const cl_srd rout = cl_make_srd(a.out, (unsigned)(a.t0 * slice * 4));
 
-    float R[32];                                       // [neighbour q][band]
-    float carry[8];
+    float R[8 * K * K];                                // [neighbour q][band]
+    float carry[8 * KC];                               // [slice iz + 1 + e][parity]
 #pragma unroll
-    for (int p = 0; p < 8; ++p) carry[p] = 0.0f;
+    for (int p = 0; p < 8 * KC; ++p) carry[p] = 0.0f;
 
-    auto issue = [&](int iz) {                         // coefficient plane iz: 4 neighbour cells x 8 bands of this lane's channel
+    auto issue = [&](int iz) {                         // coefficient plane iz: K*K neighbour cells x 8 bands of this lane's channel
         const unsigned sl = 4u * (unsigned)((c0 + CPL * w) * dvol + iz * dplane);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) cl_load(R[q * 8], rl, offl[q], sl);
+        for (int q = 0; q < K * K; ++q) cl_load(R[q * 8], rl, offl[q], sl);
 #pragma unroll
         for (int sb = 1; sb < 8; ++sb) {
             const unsigned sh = 4u * (unsigned)(((c0 + CPL * w) * 7 + sb - 1) * dvol + iz * dplane);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) cl_load(R[q * 8 + sb], rh, offl[q] + hshift, sh);
+            for (int q = 0; q < K * K; ++q) cl_load(R[q * 8 + sb], rh, offl[q] + hshift, sh);
         }
     };
 
-    int iz = jz_begin - 1;
+    int iz = jz_begin - (K - 1);
     if (wave_live && iz >= 0) issue(iz);
     int buf = 0;
 #pragma unroll 1
@@ -184,18 +190,18 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs a)
         if (wave_live) {
             float outv[8];
             if (plane_ok) {
-                float X[2][2][2][2];                              // [ey][sz][sy][px]
+                float X[K][2][2][2];                              // [ey][sz][sy][px]
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
+                for (int q = 0; q < 4 * K; ++q) {
                     const int ey = q >> 2, sz = (q >> 1) & 1, sy = q & 1;
 #pragma unroll
                     for (int px = 0; px < 2; ++px) {
                         float t = 0.0f;
 #pragma unroll
-                        for (int ex = 0; ex < 2; ++ex)
+                        for (int ex = 0; ex < K; ++ex)
 #pragma unroll
                             for (int sx = 0; sx < 2; ++sx)
-                                t = __builtin_fmaf(R[(ey * 2 + ex) * 8 + sz * 4 + sy * 2 + sx], a.taps[sx * 4 + px + 2 * ex], t);
+                                t = __builtin_fmaf(R[(ey * K + ex) * 8 + sz * 4 + sy * 2 + sx], a.taps[sx * L + px + 2 * ex], t);
                         X[ey][sz][sy][px] = t;
                     }
                 }
@@ -206,29 +212,37 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs a)
                     const int sz = q >> 2, py = (q >> 1) & 1, px = q & 1;
                     float t = 0.0f;
 #pragma unroll
-                    for (int ey = 0; ey < 2; ++ey)
+                    for (int ey = 0; ey < K; ++ey)
 #pragma unroll
                         for (int sy = 0; sy < 2; ++sy)
-                            t = __builtin_fmaf(X[ey][sz][sy][px], a.taps[sy * 4 + py + 2 * ey], t);
+                            t = __builtin_fmaf(X[ey][sz][sy][px], a.taps[sy * L + py + 2 * ey], t);
                     Y[sz][py][px] = t;
                 }
 #pragma unroll
                 for (int p = 0; p < 8; ++p) {
                     const int pz = p >> 2, py = (p >> 1) & 1, px = p & 1;
-                    float t = carry[p];                           // plane iz - 1 (e_z = 1)
-                    float n = 0.0f;
+                    float t = K > 1 ? carry[p] : 0.0f;            // planes iz - e (e_z = e >= 1)
+                    float n[KC];                                  // slices iz + e, e = 1 .. K-1
+#pragma unroll
+                    for (int e = 1; e < K; ++e) n[e - 1] = e < K - 1 ? carry[e * 8 + p] : 0.0f;
 #pragma unroll
                     for (int sz = 0; sz < 2; ++sz) {
-                        t = __builtin_fmaf(Y[sz][py][px], a.taps[sz * 4 + pz], t);
-                        n = __builtin_fmaf(Y[sz][py][px], a.taps[sz * 4 + pz + 2], n);
+                        t = __builtin_fmaf(Y[sz][py][px], a.taps[sz * L + pz], t);
+#pragma unroll
+                        for (int e = 1; e < K; ++e) n[e - 1] = __builtin_fmaf(Y[sz][py][px], a.taps[sz * L + pz + 2 * e], n[e - 1]);
                     }
                     outv[p] = t;
-                    carry[p] = n;
+#pragma unroll
+                    for (int e = 1; e < K; ++e) carry[(e - 1) * 8 + p] = n[e - 1];
                 }
             } else {
                 if (next_ok) issue(iz + 1);
 #pragma unroll
-                for (int p = 0; p < 8; ++p) { outv[p] = carry[p]; carry[p] = 0.0f; }
+                for (int p = 0; p < 8; ++p) {
+                    outv[p] = K > 1 ? carry[p] : 0.0f;
+#pragma unroll
+                    for (int e = 1; e < K; ++e) carry[(e - 1) * 8 + p] = e < K - 1 ? carry[e * 8 + p] : 0.0f;
+                }
             }
             if (emit) {
 #pragma unroll
@@ -255,20 +269,23 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs a)
     }
 }
 
+template <int K>
 struct AnalysisClArgs {
     const float* src;      // (n0,n1,n2, cs)
     float* band0;          // band 0 of channel c at band0 + c * dvol
     float* bandh;          // band s >= 1 of channel c at bandh + (c * 7 + s - 1) * dvol
     int C, cs, n0, n1, n2, lo0, lo1, lo2, d0, d1, d2;
     int zchunk, ptiles, ngroups, nchunks;
-    float taps[8];
+    float taps[4 * K];
 };
 
-// Adjoint: band_s[c][i] = sum_t src[2 i + t - lo][c] F_s[t].  Step iz reads the source planes 2 iz - lo0 + {2, 3},
-// contracts each over x and y (P[sy][sx]) and combines them with the two planes carried from step iz - 1.
+// Adjoint: band_s[c][i] = sum_t src[2 i + t - lo][c] F_s[t].  Step iz reads the source planes 2 iz - lo0 + L-2 + {0, 1},
+// contracts each over x and y (P[sy][sx]) and combines them with the L - 2 planes carried from the earlier steps.
 // Arithmetic role: lanes = CW channels x CPW cells; cell = wave * CPW + lane / CW.
-template <int CW, int NG>          // NG: cell groups of 32 per workgroup (the channel-first runs it writes are 128 NG bytes)
-__global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClArgs a) {
+template <int CW, int NG, int K>   // NG: cell groups of 32 per workgroup (the channel-first runs it writes are 128 NG bytes)
+__global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClArgs<K> a) {
+    constexpr int L = 2 * K;
+    constexpr int CT = L > 2 ? L - 2 : 1;             // carried source planes
     constexpr int CPW = ClShape<CW>::CPW, CELLS = kCells * NG, CHS = 8 * CELLS + 1;
     constexpr int TILE = CW * CHS;
     extern __shared__ __attribute__((aligned(16))) float s_tile[];      // [2][TILE]: [channel][band][cell] + 1
@@ -285,7 +302,7 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
 
     // arithmetic role: lanes = CW channels x CPW cells; cell of group g = 32 g + wave * CPW + lane / CW
     const int ch = lane & (CW - 1), cslot = w * CPW + lane / CW;
-    unsigned ro[NG][4], co[NG][4]; // byte offsets of row ty / column tx (+ channel) inside a source plane; kOutside when outside
+    unsigned ro[NG][L], co[NG][L]; // byte offsets of row ty / column tx (+ channel) inside a source plane; kOutside when outside
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const int f = f0 + g * kCells + cslot;
@@ -293,7 +310,7 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
         const int fc = min(f, plane_cells - 1);
         const int iy = fc / a.d2, ix = fc - iy * a.d2;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        for (int t = 0; t < L; ++t) {
             const int uy = 2 * iy + t - a.lo1, ux = 2 * ix + t - a.lo2;
             ro[g][t] = (live && uy >= 0 && uy < a.n1) ? 4u * (unsigned)(uy * a.n2 * a.cs) : kOutside;
             co[g][t] = (ux >= 0 && ux < a.n2) ? 4u * (unsigned)(ux * a.cs + c0 + ch) : kOutside;
@@ -315,24 +332,24 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
     const cl_srd rb0 = cl_make_srd(a.band0, (unsigned)(a.C * dvol * 4));
     const cl_srd rbh = cl_make_srd(a.bandh, (unsigned)(a.C * 7 * dvol * 4));
 
-    float R[32];                   // [plane k][ty*4+tx] of the cell group in flight
-    float carry[NG][2][4];         // [group][plane tz = 0, 1 of the next step][sy*2+sx]
+    float R[2 * L * L];            // [plane k][ty*L+tx] of the cell group in flight
+    float carry[NG][CT][4];        // [group][plane tz = 0 .. L-3 of the next step][sy*2+sx]
 #pragma unroll
-    for (int i = 0; i < 8 * NG; ++i) carry[i >> 3][(i >> 2) & 1][i & 3] = 0.0f;
+    for (int i = 0; i < 4 * CT * NG; ++i) carry[i / (4 * CT)][(i >> 2) % CT][i & 3] = 0.0f;
 
-    auto plane_in = [&](int iz, int k) { const int uz = 2 * iz - a.lo0 + 2 + k; return uz >= 0 && uz < a.n0; };
-    auto issue = [&](int iz, int g) {                  // source planes 2 iz - lo0 + {2,3} (outside the level: not read, P = 0)
+    auto plane_in = [&](int iz, int k) { const int uz = 2 * iz - a.lo0 + L - 2 + k; return uz >= 0 && uz < a.n0; };
+    auto issue = [&](int iz, int g) {                  // source planes 2 iz - lo0 + L-2 + {0,1} (outside the level: not read, P = 0)
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             if (plane_in(iz, k)) {
-                const unsigned sp = 4u * (unsigned)((2 * iz - a.lo0 + 2 + k) * nplane);
+                const unsigned sp = 4u * (unsigned)((2 * iz - a.lo0 + L - 2 + k) * nplane);
 #pragma unroll
-                for (int t = 0; t < 16; ++t) cl_load(R[k * 16 + t], rs, ro[g][t >> 2] + co[g][t & 3], sp);
+                for (int t = 0; t < L * L; ++t) cl_load(R[k * L * L + t], rs, ro[g][t / L] + co[g][t % L], sp);
             }
         }
     };
 
-    int iz = iz_begin - 1;
+    int iz = iz_begin - (K - 1);
     issue(iz, 0);
     int buf = 0;
 #pragma unroll 1
@@ -345,14 +362,14 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 if (plane_in(iz, k)) {
-                    float X[4][2];
+                    float X[L][2];
 #pragma unroll
-                    for (int ty = 0; ty < 4; ++ty) {
+                    for (int ty = 0; ty < L; ++ty) {
                         float x0 = 0.0f, x1 = 0.0f;
 #pragma unroll
-                        for (int tx = 0; tx < 4; ++tx) {
-                            x0 = __builtin_fmaf(R[k * 16 + ty * 4 + tx], a.taps[tx], x0);
-                            x1 = __builtin_fmaf(R[k * 16 + ty * 4 + tx], a.taps[4 + tx], x1);
+                        for (int tx = 0; tx < L; ++tx) {
+                            x0 = __builtin_fmaf(R[k * L * L + ty * L + tx], a.taps[tx], x0);
+                            x1 = __builtin_fmaf(R[k * L * L + ty * L + tx], a.taps[L + tx], x1);
                         }
                         X[ty][0] = x0; X[ty][1] = x1;
                     }
@@ -360,7 +377,7 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
                     for (int s4 = 0; s4 < 4; ++s4) {
                         float t = 0.0f;
 #pragma unroll
-                        for (int ty = 0; ty < 4; ++ty) t = __builtin_fmaf(X[ty][s4 & 1], a.taps[(s4 >> 1) * 4 + ty], t);
+                        for (int ty = 0; ty < L; ++ty) t = __builtin_fmaf(X[ty][s4 & 1], a.taps[(s4 >> 1) * L + ty], t);
                         P[k][s4] = t;
                     }
                 } else {
@@ -375,15 +392,20 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
 #pragma unroll
                 for (int sb = 0; sb < 8; ++sb) {
                     const int s4 = sb & 3, sz = sb >> 2;
-                    float t = carry[g][0][s4] * a.taps[sz * 4 + 0];
-                    t = __builtin_fmaf(carry[g][1][s4], a.taps[sz * 4 + 1], t);
-                    t = __builtin_fmaf(P[0][s4], a.taps[sz * 4 + 2], t);
-                    t = __builtin_fmaf(P[1][s4], a.taps[sz * 4 + 3], t);
+                    // source plane tz of this step: carried for tz < L-2, new (P) for the last two
+                    auto plane = [&](int tz) { return tz < L - 2 ? carry[g][tz < CT ? tz : 0][s4] : P[tz >= L - 2 ? tz - (L - 2) : 0][s4]; };
+                    float t = plane(0) * a.taps[sz * L + 0];
+#pragma unroll
+                    for (int tz = 1; tz < L; ++tz) t = __builtin_fmaf(plane(tz), a.taps[sz * L + tz], t);
                     tile[ch * CHS + sb * CELLS + g * kCells + cslot] = t;
                 }
             }
 #pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) { carry[g][0][s4] = P[0][s4]; carry[g][1][s4] = P[1][s4]; }
+            for (int s4 = 0; s4 < 4; ++s4) {
+#pragma unroll
+                for (int tz = 0; tz + 2 < L - 2; ++tz) carry[g][tz][s4] = carry[g][tz + 2][s4];
+                if (L > 2) { carry[g][L > 2 ? L - 4 : 0][s4] = P[0][s4]; carry[g][L > 2 ? L - 3 : 0][s4] = P[1][s4]; }
+            }
         }
         if (emit) {
             __syncthreads();
@@ -442,70 +464,64 @@ int launch_cl(K kern, int threads, const A& a, int lds_bytes, hipStream_t stream
     return LFGC_OK;
 }
 
-int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, const float* taps, int C, int cs,
+int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, const float* taps, int L, int C, int cs,
              int d0, int d1, int d2, int t0, int t1, int t2) {
     if (!p0 || !p1 || !p2 || !p3) return LFGC_E_NULL;
     if (!taps) return LFGC_E_UNSUPPORTED;              // dense stencil: channel-first kernels + lfgc_grid_layout_f32
+    if (L != 2 && L != 4) return LFGC_E_UNSUPPORTED;   // 6- and 8-tap: channel-first kernels + lfgc_grid_layout_f32
     if (C < 1 || d0 < 1 || d1 < 1 || d2 < 1 || t0 < 1 || t1 < 1 || t2 < 1) return LFGC_E_SHAPE;
-    if (t0 > 2 * d0 + 2 || t1 > 2 * d1 + 2 || t2 > 2 * d2 + 2) return LFGC_E_SHAPE;
+    if (t0 > 2 * d0 + L - 2 || t1 > 2 * d1 + L - 2 || t2 > 2 * d2 + L - 2) return LFGC_E_SHAPE;
     if (cs != lfgc_roundup(C, 8)) return LFGC_E_SHAPE;
     // buffer descriptors with kOutside as the out-of-range marker: every array below 2^30 bytes
     if ((long long)t0 * t1 * t2 * cs * 4 >= (1LL << 30) || (long long)d0 * d1 * d2 * 7 * C * 4 >= (1LL << 30)) return LFGC_E_UNSUPPORTED;
     return LFGC_OK;
 }
 
-}  // namespace
-
-extern "C" int lfgc_idwt_level_cl_f32(const float* lll, const float* hf, const float* taps, float* out_cl,
-                                      int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
-                                      lfgc_stream_t stream) {
-    const int rc = check_cl(lll, hf, out_cl, out_cl, taps, C, channel_stride, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    IdwtClArgs a = {};
+template <int K>
+int idwt_cl(const float* lll, const float* hf, const float* taps, float* out_cl, int C, int channel_stride,
+            int d0, int d1, int d2, int t0, int t1, int t2, hipStream_t st) {
+    IdwtClArgs<K> a = {};
     a.lll = lll; a.hf = hf; a.out = out_cl;
     a.C = C; a.cs = channel_stride; a.d0 = d0; a.d1 = d1; a.d2 = d2; a.t0 = t0; a.t1 = t1; a.t2 = t2;
-    a.o0 = (2 * d0 + 2 - t0) / 2; a.o1 = (2 * d1 + 2 - t1) / 2; a.o2 = (2 * d2 + 2 - t2) / 2;
-    for (int i = 0; i < 8; ++i) a.taps[i] = taps[i];
+    a.o0 = (2 * d0 + 2 * K - 2 - t0) / 2; a.o1 = (2 * d1 + 2 * K - 2 - t1) / 2; a.o2 = (2 * d2 + 2 * K - 2 - t2) / 2;
+    for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
     // 32 channels on a large plane: one workgroup of 16 waves writes whole 128-byte lines (d = 65: 197 vs 203 us); on a
     // small one two 8-wave groups balance better (d = 33: 26.5 vs 28.7 us).  24 channels: three groups of 8.
-    const long long ptiles = ((long long)(d1 + 1) * (d2 + 1) + kCells - 1) / kCells;
+    const long long ptiles = ((long long)(d1 + K - 1) * (d2 + K - 1) + kCells - 1) / kCells;
     int cw = channel_stride == 32 ? (ptiles >= 96 ? 32 : 16) : channel_stride == 16 ? 16 : 8;
     if (const char* e = getenv("LFGC_CL_CW")) { const int v = atoi(e); if ((v == 8 || v == 16 || v == 32) && channel_stride % v == 0) cw = v; }   // diagnostics
     a.ngroups = channel_stride / cw;
     if (ptiles * a.ngroups > 0x0fffffffLL) return LFGC_E_UNSUPPORTED;
     a.ptiles = (int)ptiles;
     const int lds = 2 * 8 * kCells * (cw + 1) * 4;
-    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0 + 1, cw == 32 ? 1 : cw == 16 ? 2 : 4);    // 96 VGPRs: 4 waves per SIMD
-    a.nchunks = (d0 + 1 + a.zchunk - 1) / a.zchunk;
-    hipStream_t st = (hipStream_t)stream;
+    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0 + K - 1, cw == 32 ? 1 : cw == 16 ? 2 : 4);    // 96 VGPRs: 4 waves per SIMD
+    a.nchunks = (d0 + K - 1 + a.zchunk - 1) / a.zchunk;
     bool nt = cw == 32 && (long long)t0 * t1 * t2 * channel_stride * 4 > (48LL << 20); // see cl_store
     if (const char* e = getenv("LFGC_CL_NT")) nt = e[0] == '1';                         // diagnostics
     if (cw == 32) {
         static bool raised[LFGC_MAX_DEVICES] = {false};     // 67.6 KB of LDS: above the 64 KB default limit
         const int dev = lfgc_current_device();
         if (!raised[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, true, K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, false, K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             if (e != hipSuccess) return (int)e;
             raised[dev] = true;
         }
-        return nt ? launch_cl(idwt_cl_kernel<32, kCells, true>, 1024, a, lds, st) : launch_cl(idwt_cl_kernel<32, kCells, false>, 1024, a, lds, st);
+        return nt ? launch_cl(idwt_cl_kernel<32, kCells, true, K>, 1024, a, lds, st) : launch_cl(idwt_cl_kernel<32, kCells, false, K>, 1024, a, lds, st);
     }
-    if (cw == 16) return nt ? launch_cl(idwt_cl_kernel<16, kCells, true>, 512, a, lds, st) : launch_cl(idwt_cl_kernel<16, kCells, false>, 512, a, lds, st);
-    return nt ? launch_cl(idwt_cl_kernel<8, kCells, true>, 256, a, lds, st) : launch_cl(idwt_cl_kernel<8, kCells, false>, 256, a, lds, st);
+    if (cw == 16) return nt ? launch_cl(idwt_cl_kernel<16, kCells, true, K>, 512, a, lds, st) : launch_cl(idwt_cl_kernel<16, kCells, false, K>, 512, a, lds, st);
+    return nt ? launch_cl(idwt_cl_kernel<8, kCells, true, K>, 256, a, lds, st) : launch_cl(idwt_cl_kernel<8, kCells, false, K>, 256, a, lds, st);
 }
 
-extern "C" int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf,
-                                          int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
-                                          lfgc_stream_t stream) {
-    const int rc = check_cl(d_out_cl, d_lll, d_hf, d_hf, taps, C, channel_stride, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    AnalysisClArgs a = {};
+template <int K>
+int idwt_cl_bwd(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf, int C, int channel_stride,
+                int d0, int d1, int d2, int t0, int t1, int t2, hipStream_t st) {
+    AnalysisClArgs<K> a = {};
     a.src = d_out_cl; a.band0 = d_lll; a.bandh = d_hf;
     a.C = C; a.cs = channel_stride; a.n0 = t0; a.n1 = t1; a.n2 = t2;
-    a.lo0 = (2 * d0 + 2 - t0) / 2; a.lo1 = (2 * d1 + 2 - t1) / 2; a.lo2 = (2 * d2 + 2 - t2) / 2;
+    a.lo0 = (2 * d0 + 2 * K - 2 - t0) / 2; a.lo1 = (2 * d1 + 2 * K - 2 - t1) / 2; a.lo2 = (2 * d2 + 2 * K - 2 - t2) / 2;
     a.d0 = d0; a.d1 = d1; a.d2 = d2;
-    for (int i = 0; i < 8; ++i) a.taps[i] = taps[i];
+    for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
     const int cw = channel_stride % 16 == 0 ? 16 : 8;
     // cells per workgroup: 64 on a large plane (256-byte runs per (channel, band): one whole line + two shared ones per
     // store instead of two shared ones: 188 -> 176 us at d = 65; 128 cells: no further gain), 32 on a small one (d = 33:
@@ -518,17 +534,48 @@ extern "C" int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* ta
     a.ptiles = (int)ptiles;
     a.zchunk = pick_zchunk(ptiles * a.ngroups, d0, (cw == 16 ? (ng == 2 ? 2 : 3) : (ng == 2 ? 4 : 6)));   // LDS 33 KB x ng per 16 channels; <= 6 waves per SIMD
     a.nchunks = (d0 + a.zchunk - 1) / a.zchunk;
-    hipStream_t st = (hipStream_t)stream;
     const int lds = 2 * cw * (8 * kCells * ng + 1) * 4;
     if (ng == 2 && cw == 16) {
         static bool raised[LFGC_MAX_DEVICES] = {false};     // 65.7 KB of LDS: above the 64 KB default limit
         const int dev = lfgc_current_device();
         if (!raised[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(analysis_cl_kernel<16, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(analysis_cl_kernel<16, 2, K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             if (e != hipSuccess) return (int)e;
             raised[dev] = true;
         }
     }
-    if (ng == 2) return cw == 16 ? launch_cl(analysis_cl_kernel<16, 2>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 2>, 256, a, lds, st);
-    return cw == 16 ? launch_cl(analysis_cl_kernel<16, 1>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 1>, 256, a, lds, st);
+    if (ng == 2) return cw == 16 ? launch_cl(analysis_cl_kernel<16, 2, K>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 2, K>, 256, a, lds, st);
+    return cw == 16 ? launch_cl(analysis_cl_kernel<16, 1, K>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 1, K>, 256, a, lds, st);
+}
+
+}  // namespace
+
+extern "C" int lfgc_idwt_level_cl_len_f32(const float* lll, const float* hf, const float* taps, int filter_len, float* out_cl,
+                                          int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
+                                          lfgc_stream_t stream) {
+    const int rc = check_cl(lll, hf, out_cl, out_cl, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    return filter_len == 2 ? idwt_cl<1>(lll, hf, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
+                           : idwt_cl<2>(lll, hf, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+}
+
+extern "C" int lfgc_idwt_level_cl_f32(const float* lll, const float* hf, const float* taps, float* out_cl,
+                                      int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
+                                      lfgc_stream_t stream) {
+    return lfgc_idwt_level_cl_len_f32(lll, hf, taps, 4, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
+}
+
+extern "C" int lfgc_idwt_level_cl_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len, float* d_lll, float* d_hf,
+                                              int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
+                                              lfgc_stream_t stream) {
+    const int rc = check_cl(d_out_cl, d_lll, d_hf, d_hf, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    return filter_len == 2 ? idwt_cl_bwd<1>(d_out_cl, taps, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
+                           : idwt_cl_bwd<2>(d_out_cl, taps, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+}
+
+extern "C" int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf,
+                                          int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
+                                          lfgc_stream_t stream) {
+    return lfgc_idwt_level_cl_bwd_len_f32(d_out_cl, taps, 4, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
 }

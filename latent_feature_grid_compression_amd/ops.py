@@ -81,21 +81,32 @@ def grid_channel_stride(C: int) -> int:
 
 # ---- wavelet levels ------------------------------------------------------------------------------------
 
-_TAPS_CACHE = {}      # id(filter tensor) -> (weakref, version, ctypes float[8] or None)
+_TAPS_CACHE = {}      # id(filter tensor) -> (weakref, version, ctypes float[2L] or None)
+FILTER_LENGTHS = (2, 4, 6, 8)      # even filter lengths the HIP kernels take (include/lfgc.h: lfgc_idwt_level_len_f32)
+
+
+def filter_length(filt: torch.Tensor) -> int:
+    """L of an (8, L,L,L) wavelet filter buffer."""
+    L = int(filt.shape[-1])
+    if L not in FILTER_LENGTHS:
+        raise NotImplementedError('the HIP wavelet kernels take filter lengths %s, got %d' % (FILTER_LENGTHS, L))
+    return L
 
 
 def _outer_bank(a: np.ndarray) -> np.ndarray:
-    """(2,4) fp32 taps -> (8,4,4,4) fp32 the way the reference forms it: a[sz][tz] * (a[sy][ty] * a[sx][tx]), s = 4sz+2sy+sx
+    """(2,L) fp32 taps -> (8,L,L,L) fp32 the way the reference forms it: a[sz][tz] * (a[sy][ty] * a[sx][tx]), s = 4sz+2sy+sx
     (wavelet_transform/Torch_Wavelet_Transform.py:44-53)."""
     a = a.astype(np.float32)
+    L = a.shape[-1]
     yx = (a[:, None, :, None] * a[None, :, None, :]).astype(np.float32)               # [sy][sx][ty][tx]
     out = (a[:, None, None, :, None, None] * yx[None, :, :, None, :, :]).astype(np.float32)   # [sz][sy][sx][tz][ty][tx]
-    return out.reshape(8, 4, 4, 4)
+    return out.reshape(8, L, L, L)
 
 
 def _factor_bank(f3d: np.ndarray) -> Optional[np.ndarray]:
-    """1-D bank (2,4) whose outer product IS the given (8,4,4,4) filter, or None if the filter is not separable."""
-    f3d = f3d.astype(np.float32).reshape(8, 4, 4, 4)
+    """1-D bank (2,L) whose outer product IS the given (8,L,L,L) filter, or None if the filter is not separable."""
+    L = f3d.shape[-1]
+    f3d = f3d.astype(np.float32).reshape(8, L, L, L)
     c = float(f3d[0, 0, 0, 0])
     if c == 0.0 or not np.isfinite(f3d).all():
         return None
@@ -119,13 +130,13 @@ def _factor_bank(f3d: np.ndarray) -> Optional[np.ndarray]:
 
 
 def filter_taps(filt: torch.Tensor):
-    """ctypes float[8] = the 1-D bank of a wavelet filter buffer (or None: not separable -> dense stencil).  Costs
-    one 2 KB device-to-host copy the first time a buffer is seen; cached per tensor object and in-place version."""
+    """ctypes float[2L] = the 1-D bank of a wavelet filter buffer (or None: not separable -> dense stencil, 4 taps only).
+    Costs one device-to-host copy of the buffer the first time it is seen; cached per tensor object and in-place version."""
     ent = _TAPS_CACHE.get(id(filt))
     if ent is not None and ent[0]() is filt and ent[1] == filt._version:
         return ent[2]
     bank = _factor_bank(filt.detach().float().cpu().numpy())
-    taps = None if bank is None else (ctypes.c_float * 8)(*[float(v) for v in bank.reshape(-1)])
+    taps = None if bank is None else (ctypes.c_float * bank.size)(*[float(v) for v in bank.reshape(-1)])
     if len(_TAPS_CACHE) > 256:
         for k in [k for k, e in _TAPS_CACHE.items() if e[0]() is None]:
             del _TAPS_CACHE[k]
@@ -144,8 +155,14 @@ def idwt_level(lll: torch.Tensor, hf: torch.Tensor, filter_rev: torch.Tensor, ta
         raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
     t = [int(v) for v in target]
     out = torch.empty((C, t[0], t[1], t[2]), dtype=torch.float32, device=lll.device)
-    check(_lib.load().lfgc_idwt_level_f32(lll.data_ptr(), hf.data_ptr(), filter_rev.data_ptr(), taps, out.data_ptr(),
-                                          C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_f32')
+    L = filter_length(filter_rev)
+    if L == 4:
+        check(_lib.load().lfgc_idwt_level_f32(lll.data_ptr(), hf.data_ptr(), filter_rev.data_ptr(), taps, out.data_ptr(),
+                                              C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_f32')
+    else:
+        check(_lib.load().lfgc_idwt_level_len_f32(lll.data_ptr(), hf.data_ptr(), filter_rev.data_ptr(), taps, L,
+                                                  out.data_ptr(), C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)),
+              'lfgc_idwt_level_len_f32')
     return out
 
 
@@ -159,8 +176,15 @@ def idwt_level_bwd(d_out: torch.Tensor, filter_rev: torch.Tensor, d: Sequence[in
     d = [int(v) for v in d]
     d_lll = torch.empty((C, d[0], d[1], d[2]), dtype=torch.float32, device=d_out.device)
     d_hf = torch.empty((C, 7, d[0], d[1], d[2]), dtype=torch.float32, device=d_out.device)
-    check(_lib.load().lfgc_idwt_level_bwd_f32(d_out.data_ptr(), filter_rev.data_ptr(), taps, d_lll.data_ptr(), d_hf.data_ptr(),
-                                              C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)), 'lfgc_idwt_level_bwd_f32')
+    L = filter_length(filter_rev)
+    if L == 4:
+        check(_lib.load().lfgc_idwt_level_bwd_f32(d_out.data_ptr(), filter_rev.data_ptr(), taps, d_lll.data_ptr(),
+                                                  d_hf.data_ptr(), C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
+              'lfgc_idwt_level_bwd_f32')
+    else:
+        check(_lib.load().lfgc_idwt_level_bwd_len_f32(d_out.data_ptr(), filter_rev.data_ptr(), taps, L, d_lll.data_ptr(),
+                                                      d_hf.data_ptr(), C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
+              'lfgc_idwt_level_bwd_len_f32')
     return d_lll, d_hf
 
 
@@ -189,10 +213,11 @@ def to_channel_first(grid_cl: torch.Tensor, C: int) -> torch.Tensor:
     return out
 
 
-def dwt_out_shape(n: Sequence[int]) -> List[int]:
+def dwt_out_shape(n: Sequence[int], L: int = 4) -> List[int]:
     n = [int(v) for v in n]
-    hi = [2 + (n[2] & 1), 2 + (n[1] & 1), 2 + (n[0] & 1)]     # reference pad-slot quirk, see lfgc.h
-    return [(n[a] + 2 + hi[a] - 4) // 2 + 1 for a in range(3)]
+    lo = (2 * L - 3) // 2
+    hi = [lo + (n[2] & 1), lo + (n[1] & 1), lo + (n[0] & 1)]     # reference pad-slot quirk, see lfgc.h
+    return [(n[a] + lo + hi[a] - L) // 2 + 1 for a in range(3)]
 
 
 @_on_device
@@ -202,20 +227,25 @@ def dwt_level(data: torch.Tensor, filter_fwd: torch.Tensor) -> torch.Tensor:
     taps = filter_taps(filter_fwd)
     data, filter_fwd = _f32c(data), _f32c(filter_fwd)
     C, n0, n1, n2 = data.shape
-    d = dwt_out_shape((n0, n1, n2))
+    L = filter_length(filter_fwd)
+    d = dwt_out_shape((n0, n1, n2), L)
     out = torch.empty((C, 8, d[0], d[1], d[2]), dtype=torch.float32, device=data.device)
-    check(_lib.load().lfgc_dwt_level_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, out.data_ptr(), C, n0, n1, n2,
-                                         _stream(data)), 'lfgc_dwt_level_f32')
+    if L == 4:
+        check(_lib.load().lfgc_dwt_level_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, out.data_ptr(), C, n0, n1, n2,
+                                             _stream(data)), 'lfgc_dwt_level_f32')
+    else:
+        check(_lib.load().lfgc_dwt_level_len_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, L, out.data_ptr(), C, n0, n1,
+                                                 n2, _stream(data)), 'lfgc_dwt_level_len_f32')
     return out
 
 
 _E_UNSUPPORTED = -3
 
 
-def _cl_level_ok(C: int, d: Sequence[int], t: Sequence[int], taps) -> bool:
-    """Shapes the channel-last last-level kernels take (lfgc.h: lfgc_idwt_level_cl_f32): separable bank, C <= 32,
-    arrays below 2^30 bytes.  Anything else composes the channel-first level with the layout conversion."""
-    if taps is None or C > 32 or os.environ.get('LFGC_CL_LEVEL', '1') == '0':
+def _cl_level_ok(C: int, d: Sequence[int], t: Sequence[int], taps, L: int = 4) -> bool:
+    """Shapes the channel-last last-level kernels take (lfgc.h: lfgc_idwt_level_cl_f32): separable bank of 2 or 4 taps,
+    C <= 32, arrays below 2^30 bytes.  Anything else composes the channel-first level with the layout conversion."""
+    if taps is None or L not in (2, 4) or C > 32 or os.environ.get('LFGC_CL_LEVEL', '1') == '0':
         return False
     cs = grid_channel_stride(C)
     return t[0] * t[1] * t[2] * cs * 4 < (1 << 30) and d[0] * d[1] * d[2] * 7 * C * 4 < (1 << 30)
@@ -229,15 +259,20 @@ def idwt_level_cl(lll: torch.Tensor, hf: torch.Tensor, filter_rev: torch.Tensor,
     taps = filter_taps(filter_rev)
     C, d0, d1, d2 = lll.shape
     t = [int(v) for v in target]
-    if not _cl_level_ok(C, (d0, d1, d2), t, taps):
+    L = filter_length(filter_rev)
+    if not _cl_level_ok(C, (d0, d1, d2), t, taps, L):
         return to_channel_last(idwt_level(lll, hf, filter_rev, target))
     lll, hf = _f32c(lll), _f32c(hf)
     if tuple(hf.shape) != (C, 7, d0, d1, d2):
         raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
     cs = grid_channel_stride(C)
     out = torch.empty((t[0], t[1], t[2], cs), dtype=torch.float32, device=lll.device)
-    check(_lib.load().lfgc_idwt_level_cl_f32(lll.data_ptr(), hf.data_ptr(), taps, out.data_ptr(), C, cs, d0, d1, d2,
-                                             t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_f32')
+    if L == 4:
+        check(_lib.load().lfgc_idwt_level_cl_f32(lll.data_ptr(), hf.data_ptr(), taps, out.data_ptr(), C, cs, d0, d1, d2,
+                                                 t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_f32')
+    else:
+        check(_lib.load().lfgc_idwt_level_cl_len_f32(lll.data_ptr(), hf.data_ptr(), taps, L, out.data_ptr(), C, cs, d0, d1,
+                                                     d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_len_f32')
     return out
 
 
@@ -249,14 +284,20 @@ def idwt_level_cl_bwd(d_out_cl: torch.Tensor, C: int, filter_rev: torch.Tensor,
     taps = filter_taps(filter_rev)
     d = [int(v) for v in d]
     t0, t1, t2, cs = d_out_cl.shape
-    if not _cl_level_ok(C, d, (t0, t1, t2), taps):
+    L = filter_length(filter_rev)
+    if not _cl_level_ok(C, d, (t0, t1, t2), taps, L):
         return idwt_level_bwd(to_channel_first(d_out_cl, C), filter_rev, d)
     d_out_cl = _f32c(d_out_cl)
     d_lll = torch.empty((C, d[0], d[1], d[2]), dtype=torch.float32, device=d_out_cl.device)
     d_hf = torch.empty((C, 7, d[0], d[1], d[2]), dtype=torch.float32, device=d_out_cl.device)
-    check(_lib.load().lfgc_idwt_level_cl_bwd_f32(d_out_cl.data_ptr(), taps, d_lll.data_ptr(), d_hf.data_ptr(), C, cs,
-                                                 d[0], d[1], d[2], t0, t1, t2, _stream(d_out_cl)),
-          'lfgc_idwt_level_cl_bwd_f32')
+    if L == 4:
+        check(_lib.load().lfgc_idwt_level_cl_bwd_f32(d_out_cl.data_ptr(), taps, d_lll.data_ptr(), d_hf.data_ptr(), C, cs,
+                                                     d[0], d[1], d[2], t0, t1, t2, _stream(d_out_cl)),
+              'lfgc_idwt_level_cl_bwd_f32')
+    else:
+        check(_lib.load().lfgc_idwt_level_cl_bwd_len_f32(d_out_cl.data_ptr(), taps, L, d_lll.data_ptr(), d_hf.data_ptr(),
+                                                         C, cs, d[0], d[1], d[2], t0, t1, t2, _stream(d_out_cl)),
+              'lfgc_idwt_level_cl_bwd_len_f32')
     return d_lll, d_hf
 
 
@@ -335,10 +376,17 @@ def idwt_level_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> 
             raise ValueError('detail drop factor %s does not match %s' % (tuple(mul_h.shape), (7, d0, d1, d2)))
     t = [int(v) for v in target]
     out = torch.empty((C, t[0], t[1], t[2]), dtype=torch.float32, device=lll.device)
-    check(_lib.load().lfgc_idwt_level_drop_f32(
-        lll.data_ptr(), hf.data_ptr(), mul_l.data_ptr() if mul_l is not None else None, _thr(thr_l),
-        mul_h.data_ptr() if mul_h is not None else None, _thr(thr_h), filter_rev.data_ptr(), taps, out.data_ptr(),
-        C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_f32')
+    ml = mul_l.data_ptr() if mul_l is not None else None
+    mh = mul_h.data_ptr() if mul_h is not None else None
+    L = filter_length(filter_rev)
+    if L == 4:
+        check(_lib.load().lfgc_idwt_level_drop_f32(
+            lll.data_ptr(), hf.data_ptr(), ml, _thr(thr_l), mh, _thr(thr_h), filter_rev.data_ptr(), taps, out.data_ptr(),
+            C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_f32')
+    else:
+        check(_lib.load().lfgc_idwt_level_drop_len_f32(
+            lll.data_ptr(), hf.data_ptr(), ml, _thr(thr_l), mh, _thr(thr_h), filter_rev.data_ptr(), taps, L,
+            out.data_ptr(), C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_len_f32')
     return out
 
 
@@ -362,10 +410,17 @@ def idwt_level_drop_bwd(d_out, filter_rev, lll, hf, mul_l, mul_h, want_dml, want
         torch.zeros((7, d[0], d[1], d[2]), dtype=torch.float32, device=dev) if want_dmh else None)
     ptr = lambda t: t.data_ptr() if t is not None else None
     pen, _keep = (None, None) if penalty_ptrs is None else _lib.ptr_array([int(v) for v in penalty_ptrs])
-    check(_lib.load().lfgc_idwt_level_drop_bwd_f32(
-        d_out.data_ptr(), filter_rev.data_ptr(), taps, ptr(lll), ptr(hf), ptr(mul_l), ptr(mul_h), d_lll.data_ptr(),
-        d_hf.data_ptr(), ptr(d_ml), ptr(d_mh), pen, C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-        'lfgc_idwt_level_drop_bwd_f32')
+    L = filter_length(filter_rev)
+    if L == 4:
+        check(_lib.load().lfgc_idwt_level_drop_bwd_f32(
+            d_out.data_ptr(), filter_rev.data_ptr(), taps, ptr(lll), ptr(hf), ptr(mul_l), ptr(mul_h), d_lll.data_ptr(),
+            d_hf.data_ptr(), ptr(d_ml), ptr(d_mh), pen, C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
+            'lfgc_idwt_level_drop_bwd_f32')
+    else:
+        check(_lib.load().lfgc_idwt_level_drop_bwd_len_f32(
+            d_out.data_ptr(), filter_rev.data_ptr(), taps, L, ptr(lll), ptr(hf), ptr(mul_l), ptr(mul_h), d_lll.data_ptr(),
+            d_hf.data_ptr(), ptr(d_ml), ptr(d_mh), pen, C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
+            'lfgc_idwt_level_drop_bwd_len_f32')
     return d_lll, d_hf, d_ml, d_mh
 
 

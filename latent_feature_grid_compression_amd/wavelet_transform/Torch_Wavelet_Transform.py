@@ -20,8 +20,16 @@ from torch.nn import functional as F
 
 from .. import ops
 
-# PyWavelets' db2 filter bank (dec_lo, dec_hi, rec_lo, rec_hi); pywt is used when importable, this table
-# otherwise (the reference only ever uses 'db2': experiment-config-files/*.txt, model/model_utils.py:312).
+# PyWavelets' filter banks (dec_lo, dec_hi, rec_lo, rec_hi) of the built-in wavelets; pywt is used for any other name
+# when importable.  db2 is the reference's default (experiment-config-files/*.txt, model/model_utils.py:312); Haar is the
+# basis its thesis reports for the fv-SRN experiments (--wavelet_filter, Feature_Grid_Training.py:62).
+_HAAR_S = 0.7071067811865476
+_HAAR = (
+    (_HAAR_S, _HAAR_S),
+    (-_HAAR_S, _HAAR_S),
+    (_HAAR_S, _HAAR_S),
+    (_HAAR_S, -_HAAR_S),
+)
 _DB2 = (
     (-0.12940952255126037, 0.2241438680420134, 0.8365163037378079, 0.48296291314453416),
     (-0.48296291314453416, 0.8365163037378079, -0.2241438680420134, -0.12940952255126037),
@@ -30,16 +38,22 @@ _DB2 = (
 )
 
 
+_BUILTIN = {'db2': _DB2, 'haar': _HAAR, 'db1': _HAAR}
+MAX_FILTER_LENGTH = 8       # longest filter the HIP kernels take (include/lfgc.h: lfgc_idwt_level_len_f32)
+
+
 def _filter_bank(wavelet) -> Sequence[Sequence[float]]:
+    """(dec_lo, dec_hi, rec_lo, rec_hi) of a wavelet name or of any object with a ``filter_bank`` (a pywt.Wavelet, as
+    the reference's _as_wavelet accepts, Torch_Wavelet_Transform.py:11-14)."""
     if hasattr(wavelet, 'filter_bank'):
         return wavelet.filter_bank
     name = str(wavelet)
-    if name == 'db2':
-        return _DB2
+    if name in _BUILTIN:
+        return _BUILTIN[name]
     try:
         import pywt
     except ImportError as exc:
-        raise ValueError("wavelet %r needs PyWavelets; only 'db2' is built in" % name) from exc
+        raise ValueError('wavelet %r needs PyWavelets; built in: %s' % (name, ', '.join(sorted(_BUILTIN)))) from exc
     return pywt.Wavelet(name).filter_bank
 
 
@@ -59,9 +73,14 @@ class _WaveletFilterNd(nn.Module):
             raise NotImplementedError("only zero ('constant') padding is implemented, as used by the reference")
         self.dim = dim
         self.padding = padding
-        self._register_filters(_filter_bank(wavelet), dim)
-        if self.filter_length != 4:
-            raise NotImplementedError('the HIP wavelet kernels are written for 4-tap filters (db2)')
+        bank = _filter_bank(wavelet)
+        # the reference asserts an even length after building the filters (Torch_Wavelet_Transform.py:33)
+        if len(bank[0]) % 2 != 0:
+            raise NotImplementedError('[ERROR] Implementation does not support uneven filter length')
+        if len(bank[0]) > MAX_FILTER_LENGTH or len(bank[0]) < 2:
+            raise NotImplementedError('the HIP wavelet kernels take filters of 2 to %d taps, got %d'
+                                      % (MAX_FILTER_LENGTH, len(bank[0])))
+        self._register_filters(bank, dim)
 
     @property
     def filter_length(self) -> int:

@@ -17,6 +17,23 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
 
+def build_model_wavelet(w, seed, device, wavelet):
+    """bench.build_model with another wavelet basis (same seeded grid and weights)."""
+    from latent_feature_grid_compression_amd.model.Feature_Grid_Model import Feature_Grid_Model
+    from latent_feature_grid_compression_amd.model.Feature_Embedding import FourierEmbedding
+    from latent_feature_grid_compression_amd.wavelet_transform.Torch_Wavelet_Transform import WaveletFilter3d
+    rng = np.random.Generator(np.random.PCG64(seed))
+    grid = torch.from_numpy(rng.random((w['C'], w['G'], w['G'], w['G']), dtype=np.float32)).to(device)
+    model = Feature_Grid_Model(FourierEmbedding(2, 3), grid, None, WaveletFilter3d(wavelet).to(device),
+                               hidden_channel=w['H'], num_layer=w['L'], num_levels=w.get('levels'))
+    with torch.no_grad():
+        for lin in list(model.net_layers) + [model.final_layer]:
+            bound = 1.0 / np.sqrt(lin.in_features)
+            lin.weight.copy_(torch.from_numpy(rng.uniform(-bound, bound, tuple(lin.weight.shape)).astype(np.float32)))
+            lin.bias.copy_(torch.from_numpy(rng.uniform(-bound, bound, tuple(lin.bias.shape)).astype(np.float32)))
+    return model.to(device)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=50)
@@ -31,12 +48,14 @@ def main():
                     help='pruning layers on the coefficients + their loss (the reference CLI default is smallify)')
     ap.add_argument('--unfused-drop', action='store_true',
                     help='comparison: apply the drop factors and penalties with torch ops instead of the fused HIP kernels')
+    ap.add_argument('--wavelet', default='db2', help="wavelet basis of the model (db2, haar, ...); db2 is bench.py's")
     args = ap.parse_args()
     from latent_feature_grid_compression_amd.data.Interpolation import trilinear_f_interpolation, trilinear_mse_loss
     from latent_feature_grid_compression_amd.data.IndexDataset import IndexDataset
     dev = torch.device('cuda:0')
     w = bench.WORKLOADS['headline']
-    model = bench.build_model(w, seed=2003, device=dev).train()
+    model = bench.build_model(w, seed=2003, device=dev).train() if args.wavelet == 'db2' else \
+        build_model_wavelet(w, 2003, dev, args.wavelet).train()
     model.precision = args.precision
     drop_loss = None
     if args.drop_type:
