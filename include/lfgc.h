@@ -358,6 +358,52 @@ int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions
                       float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
                       void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
 
+/* Read-only launch-plan queries: which kernel build and launch shape lfgc_forward_f32 / lfgc_backward_f32 pick for these
+ * arguments on the current device.  The launchers consume the very structs these entries fill (one selection function
+ * each, csrc/lfgc_capi_forward.hip and csrc/lfgc_backward.hip), so a query cannot drift from a launch.  Nothing is
+ * enqueued and no device pointer is read; the diagnostics environment knobs (LFGC_NO_ZRUN, LFGC_FWD_WAVES, LFGC_FWD_X2,
+ * LFGC_WGRAD_NO_SPLIT) are honoured exactly as by the launch.  For tests and tools that must know which compiled
+ * instantiation a shape reaches. */
+typedef struct lfgc_forward_launch {
+    int32_t resident;        /* 1: every layer block staged in LDS once; 0: streamed through a 2-deep ring     */
+    int32_t waves;           /* waves per workgroup of the chosen build: 4 or 8                                 */
+    int32_t coord_table;     /* lattice mode: per-axis coordinate tables held in LDS                           */
+    int32_t zrun;            /* lattice mode, f16 builds: z-run tiles + column sampler                         */
+    int32_t nzc;             /* z cells a z-run tile's column holds (2 when zrun == 0)                          */
+    int32_t tiles_per_row;   /* z-run: ceil(res2 / 32), else 1                                                   */
+    int32_t x2;              /* z-run: the two-tiles-per-wave kernel (LFGC_FWD_X2)                              */
+    int32_t lds_bytes;       /* dynamic LDS of the launch                                                        */
+    int64_t nbatches;        /* passes of one workgroup-sized batch of tiles                                     */
+    int64_t ntiles;          /* z-run: tiles of the slab, else 0                                                 */
+    int64_t grid;            /* workgroups launched                                                              */
+} lfgc_forward_launch;
+
+typedef struct lfgc_forward_plan_info {
+    int32_t CH;              /* grid channels rounded up to 8: 8, 16, 24 or 32                                  */
+    int32_t MT;              /* 32-row tiles of the hidden width (96 -> 128): 1, 2 or 4                         */
+    int32_t has_redo;        /* 1: an f16 build with a status word -- `redo` describes the predicated launch    */
+    int32_t reserved;
+    lfgc_forward_launch first;   /* the launch of the build `precision` names                                   */
+    lfgc_forward_launch redo;    /* the exact-fp32 range fallback behind it (zeroed when has_redo == 0)          */
+} lfgc_forward_plan_info;
+
+/* positions as for lfgc_forward_f32 (pos is only tested against NULL); has_stash / has_status: whether the launch would be
+ * given a stash buffer / a status word.  Returns the LFGC_E_* the launch would return for the same shape arguments. */
+int lfgc_forward_plan(const lfgc_mlp_desc* desc, const lfgc_positions* positions, int D, int H, int W, int precision,
+                      int has_stash, int has_status, lfgc_forward_plan_info* out);
+
+typedef struct lfgc_backward_plan_info {
+    int32_t CH, MT;          /* as above                                                                         */
+    int32_t waves;           /* waves per workgroup of the data kernel: 4 or 8                                  */
+    int32_t nslabs;          /* partial slabs (tile groups) of the weight-gradient kernel                       */
+    int32_t roles;           /* workgroups per tile group: 1, or L when the slab split is on                    */
+    int32_t lds_bytes;       /* dynamic LDS of the data kernel                                                   */
+    int64_t nbatches;        /* passes of the data kernel                                                        */
+    int64_t grid;            /* workgroups of the data kernel (the weight-gradient kernel launches nslabs * roles) */
+} lfgc_backward_plan_info;
+
+int lfgc_backward_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out);
+
 /* The reduced-precision pair under the names SURVEY section 8(b) gives it (BASELINE config 3, "bf16 train step"; the
  * reference itself has no reduced-precision path): exactly lfgc_forward_f32 / lfgc_backward_f32 with precision =
  * LFGC_PRECISION_F16 -- layer GEMMs as single 16-bit products on the matrix pipe, fp32 accumulation, fp32 inputs, outputs

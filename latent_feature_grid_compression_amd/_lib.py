@@ -26,6 +26,22 @@ class Positions(Structure):
                 ('x_begin', c_int32), ('x_end', c_int32), ('tile', c_int32)]
 
 
+class ForwardLaunch(Structure):
+    _fields_ = [('resident', c_int32), ('waves', c_int32), ('coord_table', c_int32), ('zrun', c_int32), ('nzc', c_int32),
+                ('tiles_per_row', c_int32), ('x2', c_int32), ('lds_bytes', c_int32),
+                ('nbatches', c_int64), ('ntiles', c_int64), ('grid', c_int64)]
+
+
+class ForwardPlanInfo(Structure):
+    _fields_ = [('CH', c_int32), ('MT', c_int32), ('has_redo', c_int32), ('reserved', c_int32),
+                ('first', ForwardLaunch), ('redo', ForwardLaunch)]
+
+
+class BackwardPlanInfo(Structure):
+    _fields_ = [('CH', c_int32), ('MT', c_int32), ('waves', c_int32), ('nslabs', c_int32), ('roles', c_int32),
+                ('lds_bytes', c_int32), ('nbatches', c_int64), ('grid', c_int64)]
+
+
 class PenaltyTerm(Structure):
     _fields_ = [('a', c_void_p), ('b', c_void_p), ('n', c_int64), ('kind', c_int32)]
 
@@ -83,6 +99,9 @@ SIGNATURES = {
     'lfgc_backward_f32': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, _PP, _PP, c_void_p,
                                   c_void_p, c_int64, c_void_p]),
+    'lfgc_forward_plan': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_int, c_int, c_int, c_int, c_int, c_int,
+                                  POINTER(ForwardPlanInfo)]),
+    'lfgc_backward_plan': (c_int, [POINTER(MlpDesc), c_int64, c_int, POINTER(BackwardPlanInfo)]),
     'lfgc_forward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'lfgc_backward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,

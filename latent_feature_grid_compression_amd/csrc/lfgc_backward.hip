@@ -45,7 +45,37 @@ Carve carve(const LfgcPlan& p, long long n) {
     c.dfeat_floats = c.ntiles * 32 * p.CH;              // feature gradients for the deferred scatter (small batches)
     return c;
 }
+
+// The host-side selection of lfgc_backward_f32 for n > 0 samples: lfgc_backward_f32 launches what this returns and
+// lfgc_backward_plan reports it.
+lfgc_backward_plan_info bwd_select(const LfgcPlan& p, const Carve& c, long long n) {
+    lfgc_backward_plan_info b;
+    b.CH = p.CH; b.MT = p.MT;
+    b.nslabs = c.nslabs; b.roles = c.roles;
+    const int cus = lfgc_num_cus();       // per device
+    // data kernel: one workgroup per CU, 8 waves once every CU gets a 256-sample batch, else 4 (tiles beyond the
+    // last whole 128-sample group are never touched: the stash covers whole 256-sample groups, lfgc_stash_bytes)
+    b.waves = ((n + 255) / 256 >= cus) ? 8 : 4;
+    b.nbatches = c.nbatches * (8 / b.waves);            // same tile range as the forward wrote
+    const int tb0 = p.K0R * p.ST, tb1 = p.HP * p.ST, sc = b.waves * 32 * (p.CH + 4 + 16);
+    int slot = tb0 > tb1 ? tb0 : tb1;
+    if (sc > slot) slot = sc;
+    b.lds_bytes = (p.HP + 4 + 8 + 2 * slot) * 4;
+    b.grid = cus;
+    if (b.grid > b.nbatches) b.grid = b.nbatches;
+    return b;
+}
 }  // namespace
+
+extern "C" int lfgc_backward_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out) {
+    if (!desc || !out) return LFGC_E_NULL;
+    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
+    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
+    if (n_samples < 0) return LFGC_E_SHAPE;
+    const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
+    *out = bwd_select(p, carve(p, n_samples), n_samples);
+    return LFGC_OK;
+}
 
 extern "C" int64_t lfgc_backward_workspace_bytes(const lfgc_mlp_desc* desc, int64_t n_samples) {
     if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
@@ -103,13 +133,11 @@ extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions
 
     LfgcWgradArgs w;
     w.stash = stash; w.dstash = dstash; w.d_out = d_out; w.n = n; w.ntiles = c.ntiles; w.L = p.L;
-    w.slabs = slabs; w.slab_floats = lfgc_slab_floats(p); w.roles = c.roles;
+    w.slabs = slabs; w.slab_floats = lfgc_slab_floats(p);
     w.dscale = precision == LFGC_PRECISION_F32 ? nullptr : dscale;     // f16 builds: f16-split contraction (lfgc_backward.h)
 
-    const int cus = lfgc_num_cus();       // per device
-    // data kernel: one workgroup per CU, 8 waves once every CU gets a 256-sample batch, else 4 (tiles beyond the
-    // last whole 128-sample group are never touched: the stash covers whole 256-sample groups, lfgc_stash_bytes)
-    const int waves = ((n + 255) / 256 >= cus) ? 8 : 4;
+    const lfgc_backward_plan_info b = bwd_select(p, c, n);
+    w.roles = b.roles;
     // Feature-gradient scatter: inside the data kernel.  LFGC_SCATTER=deferred (diagnostics) moves the float atomics into
     // a kernel of their own at full occupancy: measured at the cfg-3 train step, the data kernel drops from 78 to 54 us and
     // the scatter kernel takes 29 us -- 8.4 M device-scope float adds on cold lines cost that much either way (the
@@ -118,26 +146,20 @@ extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions
         const char* env = getenv("LFGC_SCATTER");
         a.dfeat = (env && env[0] == 'd') ? dfeat : nullptr;
     }
-    a.nbatches = c.nbatches * (8 / waves);              // same tile range as the forward wrote
-    const int tb0 = p.K0R * p.ST, tb1 = p.HP * p.ST, sc = waves * 32 * (p.CH + 4 + 16);
-    int slot = tb0 > tb1 ? tb0 : tb1;
-    if (sc > slot) slot = sc;
-    const int lds_bytes = (p.HP + 4 + 8 + 2 * slot) * 4;
-    long long grid_data = cus;
-    if (grid_data > a.nbatches) grid_data = a.nbatches;
+    a.nbatches = b.nbatches;
 
     int rc;
     switch (p.CH) {
-        case 8: rc = lfgc_bwd_dispatch_ch8(p.MT, a, w, waves, precision, lds_bytes, (int)grid_data, c.nslabs * c.roles, st); break;
-        case 16: rc = lfgc_bwd_dispatch_ch16(p.MT, a, w, waves, precision, lds_bytes, (int)grid_data, c.nslabs * c.roles, st); break;
-        case 24: rc = lfgc_bwd_dispatch_ch24(p.MT, a, w, waves, precision, lds_bytes, (int)grid_data, c.nslabs * c.roles, st); break;
-        case 32: rc = lfgc_bwd_dispatch_ch32(p.MT, a, w, waves, precision, lds_bytes, (int)grid_data, c.nslabs * c.roles, st); break;
+        case 8: rc = lfgc_bwd_dispatch_ch8(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
+        case 16: rc = lfgc_bwd_dispatch_ch16(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
+        case 24: rc = lfgc_bwd_dispatch_ch24(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
+        case 32: rc = lfgc_bwd_dispatch_ch32(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
         default: return LFGC_E_UNSUPPORTED;
     }
     if (rc != LFGC_OK) return rc;
 
     LfgcReduceArgs r;
-    r.slabs = slabs; r.nslabs = c.nslabs; r.slab_floats = w.slab_floats; r.plan = p;
+    r.slabs = slabs; r.nslabs = b.nslabs; r.slab_floats = w.slab_floats; r.plan = p;
     for (int l = 0; l <= p.L; ++l) { r.dw[l] = d_weights[l]; r.db[l] = d_biases[l]; }
     for (int i = 0; i < 64; ++i) r.col_of_src[i] = 0;
     for (int cl = 0; cl < p.K0P; ++cl) {

@@ -52,75 +52,140 @@ int lfgc_fill_positions(const lfgc_positions* ps, LfgcFwdArgs* a, long long* n_o
     return LFGC_OK;
 }
 
+namespace {
+// Shape checks the launch and the plan query share (everything lfgc_forward_f32 refuses that is not a pointer).
+int fwd_check_shape(const lfgc_mlp_desc* desc, int D, int H, int W, int precision) {
+    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
+    if (D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
+    if ((long long)D * H * W * lfgc_roundup(desc->grid_channels, 8) >= (1LL << 30)) return LFGC_E_UNSUPPORTED;   // 32-bit byte offsets
+    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
+    return LFGC_OK;
+}
+
+int fwd_env_waves(int resident, int waves) {            // diagnostics: LFGC_FWD_WAVES=4|8, streamed nets only
+    if (const char* e = getenv("LFGC_FWD_WAVES")) { if (!resident && (e[0] == '4' || e[0] == '8')) return e[0] - '0'; }
+    return waves;
+}
+
+// One launch of the exact-fp32 build (h16 = false) or of an f16 build before its z-run decision (h16 = true).
+lfgc_forward_launch fwd_base_launch(const LfgcPlan& p, const LfgcFwdArgs& a, long long n, bool h16, bool env_waves) {
+    lfgc_forward_launch l;
+    // LDS: [Wf | bf] + every layer block (resident: 4-wave workgroups, two per CU) or a 2-deep ring of the
+    // largest block (streamed: 8-wave workgroups, one per CU).  The stash is laid out per 32-sample tile in
+    // whole 128-sample groups either way (lfgc_stash_bytes), so both builds write the same format.
+    const int all_blocks = h16 ? p.blkh0 + (p.L - 1) * p.blkh1 : p.off_final;
+    const int max_block = h16 ? (p.blkh0 > p.blkh1 ? p.blkh0 : p.blkh1) : (p.blk0 > p.blk1 ? p.blk0 : p.blk1);
+    const int fixed = p.HP + 4 + (h16 ? 16 + LFGC_MAX_LAYERS * p.HP : 0);   // [Wf | bf] (+ per-layer scales + resident biases)
+    l.resident = ((fixed + all_blocks) * 4 <= 80 * 1024) ? 1 : 0;
+    l.lds_bytes = (fixed + (l.resident ? all_blocks : 2 * max_block)) * 4;
+    l.coord_table = 0;
+    if (!a.pos) {                                       // per-axis coordinate tables behind the weight region
+        const long long tbl = 4LL * ((long long)a.res0 + a.res1 + a.res2);
+        const long long cap = l.resident ? 80 * 1024 : 160 * 1024;
+        if (l.lds_bytes + tbl <= cap) { l.coord_table = 1; l.lds_bytes += (int)tbl; }
+    }
+    // streamed nets: 8-wave workgroups once every CU gets at least one 256-sample batch, else 4-wave ones
+    l.waves = (!l.resident && (n + 255) / 256 >= num_cus()) ? 8 : 4;
+    if (env_waves) l.waves = fwd_env_waves(l.resident, l.waves);
+    // always whole 256-sample groups of tiles, so the stash covers the same tile range whichever build runs
+    l.nbatches = (n + 255) / 256 * (8 / l.waves);
+    l.zrun = 0; l.nzc = 2; l.tiles_per_row = 1; l.ntiles = 0; l.x2 = 0;
+    l.grid = 0;
+    return l;
+}
+
+void fwd_set_grid(lfgc_forward_launch* l) {
+    l->grid = (l->resident ? 2LL : 1LL) * num_cus();
+    if (l->grid > l->nbatches) l->grid = l->nbatches;
+}
+
+// The host-side selection of lfgc_forward_f32: fills the position part of *a (lfgc_fill_positions), *n and *out.
+// lfgc_forward_f32 launches what *out says and lfgc_forward_plan reports it.
+int fwd_select(const lfgc_mlp_desc* desc, const lfgc_positions* positions, int D, int precision, bool has_stash,
+               bool has_status, const LfgcPlan& p, LfgcFwdArgs* a, long long* n_out, lfgc_forward_plan_info* out) {
+    long long n = 0;
+    const int rc = lfgc_fill_positions(positions, a, &n);
+    if (rc != LFGC_OK) return rc;
+    *n_out = n;
+    const bool h16 = precision != LFGC_PRECISION_F32;
+    out->CH = p.CH; out->MT = p.MT; out->reserved = 0;
+    out->has_redo = (h16 && has_status) ? 1 : 0;
+    lfgc_forward_launch l = fwd_base_launch(p, *a, n, h16, true);
+    // Lattice mode on the f16 builds: z-run tiles + column sampler (lfgc_forward.h) when the column a 32-voxel run touches
+    // is short (volume at least ~3x finer than the grid along z: every BASELINE full-volume shape) and fits the LDS left.
+    if (h16 && !a->pos && l.coord_table && !has_stash && !getenv("LFGC_NO_ZRUN")) {
+        const int nzc = (int)(31.0 * (double)D / (double)(a->res2 - 1) + 1e-3) + 3;
+        const long long rows = (long long)(positions->x_end - positions->x_begin) * a->res1;
+        const int tpr = (a->res2 + LFGC_TILE_SAMPLES - 1) / LFGC_TILE_SAMPLES;
+        const long long ntiles = rows * tpr;
+        const long long tbl4 = 4LL * (((long long)a->res0 + a->res1 + a->res2 + 3) & ~3LL) - 4LL * ((long long)a->res0 + a->res1 + a->res2);
+        const long long cap = l.resident ? 80 * 1024 : 160 * 1024;
+        const long long col = 4LL * 8 * nzc * (p.CH + 4);            // 8 waves x nzc padded rows (LfgcColumnSampler::CS)
+        if (nzc <= 12 && ntiles < (1LL << 31) && l.lds_bytes + tbl4 + col <= cap) {
+            l.zrun = 1; l.nzc = nzc; l.tiles_per_row = tpr; l.ntiles = ntiles;
+            l.lds_bytes += (int)(tbl4 + col);
+            l.waves = fwd_env_waves(l.resident, (!l.resident && (ntiles + 7) / 8 >= num_cus()) ? 8 : 4);
+            l.nbatches = (ntiles + l.waves - 1) / l.waves;
+            // experimental (LFGC_FWD_X2=1): two tiles per wave, one wave per SIMD (lfgc_forward16x2.h; 32 channels x 128 wide)
+            if (!l.resident && p.CH == 32 && p.MT == 4 && (ntiles + 7) / 8 >= num_cus() && getenv("LFGC_FWD_X2")) {
+                l.x2 = 1; l.waves = 4; l.nbatches = (ntiles + 7) / 8;
+            }
+        }
+    }
+    fwd_set_grid(&l);
+    out->first = l;
+    if (out->has_redo) {
+        // Range fallback: the same pass on the exact-fp32 build; residency, workgroup shape and grid are its own.
+        out->redo = fwd_base_launch(p, *a, n, false, false);
+        fwd_set_grid(&out->redo);
+    } else {
+        out->redo = lfgc_forward_launch{};
+    }
+    return LFGC_OK;
+}
+
+void fwd_apply_launch(const lfgc_forward_launch& l, LfgcFwdArgs* a) {
+    a->resident = l.resident; a->waves = l.waves; a->coord_table = l.coord_table; a->nbatches = l.nbatches;
+    a->zrun = l.zrun; a->nzc = l.nzc; a->tiles_per_row = l.tiles_per_row; a->ntiles = l.ntiles; a->x2 = l.x2;
+}
+}  // namespace
+
+extern "C" int lfgc_forward_plan(const lfgc_mlp_desc* desc, const lfgc_positions* positions, int D, int H, int W, int precision,
+                                 int has_stash, int has_status, lfgc_forward_plan_info* out) {
+    if (!desc || !positions || !out) return LFGC_E_NULL;
+    const int rc = fwd_check_shape(desc, D, H, W, precision);
+    if (rc != LFGC_OK) return rc;
+    const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
+    LfgcFwdArgs a;
+    long long n = 0;
+    return fwd_select(desc, positions, D, precision, has_stash != 0, has_status != 0, p, &a, &n, out);
+}
+
 extern "C" int lfgc_forward_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions,
                                 const float* grid_cl, int D, int H, int W,
                                 const float* packed, int precision, int clamp, float* out, float* stash,
                                 int32_t* status, lfgc_stream_t stream) {
     if (!desc || !positions || !grid_cl || !packed || !out) return LFGC_E_NULL;
-    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
-    if (D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
-    if ((long long)D * H * W * lfgc_roundup(desc->grid_channels, 8) >= (1LL << 30)) return LFGC_E_UNSUPPORTED;   // 32-bit byte offsets
-    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
+    const int rcs = fwd_check_shape(desc, D, H, W, precision);
+    if (rcs != LFGC_OK) return rcs;
     if ((((uintptr_t)grid_cl) | ((uintptr_t)packed)) & 15) return LFGC_E_ALIGN;
     const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
     LfgcFwdArgs a;
     long long n = 0;
-    const int rc = lfgc_fill_positions(positions, &a, &n);
+    lfgc_forward_plan_info plan;
+    const int rc = fwd_select(desc, positions, D, precision, stash != nullptr, status != nullptr, p, &a, &n, &plan);
     if (rc != LFGC_OK) return rc;
     if (n == 0) return LFGC_OK;
     a.n = n;
     a.grid = grid_cl; a.D = D; a.H = H; a.W = W; a.Cs = p.CH;
     a.packed = packed; a.L = p.L; a.clamp = clamp; a.out = out; a.stash = stash;
-    // LDS: [Wf | bf] + every layer block (resident: 4-wave workgroups, two per CU) or a 2-deep ring of the
-    // largest block (streamed: 8-wave workgroups, one per CU).  The stash is laid out per 32-sample tile in
-    // whole 128-sample groups either way (lfgc_stash_bytes), so both builds write the same format.
     const bool h16 = precision != LFGC_PRECISION_F32;
     a.single = precision == LFGC_PRECISION_F16 ? 1 : 0;
     a.status = nullptr; a.redo_if = nullptr; a.stamps = nullptr;
 #ifdef LFGC_STAMPS
     a.stamps = g_stamps;
 #endif
-    const int all_blocks = h16 ? p.blkh0 + (p.L - 1) * p.blkh1 : p.off_final;
-    const int max_block = h16 ? (p.blkh0 > p.blkh1 ? p.blkh0 : p.blkh1) : (p.blk0 > p.blk1 ? p.blk0 : p.blk1);
-    const int fixed = p.HP + 4 + (h16 ? 16 + LFGC_MAX_LAYERS * p.HP : 0);   // [Wf | bf] (+ per-layer scales + resident biases)
-    a.resident = ((fixed + all_blocks) * 4 <= 80 * 1024) ? 1 : 0;
-    int lds_bytes = (fixed + (a.resident ? all_blocks : 2 * max_block)) * 4;
-    a.coord_table = 0;
-    if (!a.pos) {                                       // per-axis coordinate tables behind the weight region
-        const long long tbl = 4LL * ((long long)a.res0 + a.res1 + a.res2);
-        const long long cap = a.resident ? 80 * 1024 : 160 * 1024;
-        if (lds_bytes + tbl <= cap) { a.coord_table = 1; lds_bytes += (int)tbl; }
-    }
-    // streamed nets: 8-wave workgroups once every CU gets at least one 256-sample batch, else 4-wave ones
-    a.waves = (!a.resident && (n + 255) / 256 >= num_cus()) ? 8 : 4;
-    if (const char* e = getenv("LFGC_FWD_WAVES")) { if (!a.resident && (e[0] == '4' || e[0] == '8')) a.waves = e[0] - '0'; }   // diagnostics
-    // always whole 256-sample groups of tiles, so the stash covers the same tile range whichever build runs
-    a.nbatches = (n + 255) / 256 * (8 / a.waves);
-    // Lattice mode on the f16 builds: z-run tiles + column sampler (lfgc_forward.h) when the column a 32-voxel run touches
-    // is short (volume at least ~3x finer than the grid along z: every BASELINE full-volume shape) and fits the LDS left.
-    a.zrun = 0; a.nzc = 2; a.tiles_per_row = 1; a.ntiles = 0; a.x2 = 0;
-    if (h16 && !a.pos && a.coord_table && !stash && !getenv("LFGC_NO_ZRUN")) {
-        const int nzc = (int)(31.0 * (double)D / (double)(a.res2 - 1) + 1e-3) + 3;
-        const long long rows = (long long)(positions->x_end - positions->x_begin) * a.res1;
-        const int tpr = (a.res2 + LFGC_TILE_SAMPLES - 1) / LFGC_TILE_SAMPLES;
-        const long long ntiles = rows * tpr;
-        const long long tbl4 = 4LL * (((long long)a.res0 + a.res1 + a.res2 + 3) & ~3LL) - 4LL * ((long long)a.res0 + a.res1 + a.res2);
-        const long long cap = a.resident ? 80 * 1024 : 160 * 1024;
-        const long long col = 4LL * 8 * nzc * (p.CH + 4);            // 8 waves x nzc padded rows (LfgcColumnSampler::CS)
-        if (nzc <= 12 && ntiles < (1LL << 31) && lds_bytes + tbl4 + col <= cap) {
-            a.zrun = 1; a.nzc = nzc; a.tiles_per_row = tpr; a.ntiles = ntiles;
-            lds_bytes += (int)(tbl4 + col);
-            a.waves = (!a.resident && (ntiles + 7) / 8 >= num_cus()) ? 8 : 4;
-            if (const char* e = getenv("LFGC_FWD_WAVES")) { if (!a.resident && (e[0] == '4' || e[0] == '8')) a.waves = e[0] - '0'; }
-            a.nbatches = (ntiles + a.waves - 1) / a.waves;
-            // experimental (LFGC_FWD_X2=1): two tiles per wave, one wave per SIMD (lfgc_forward16x2.h; 32 channels x 128 wide)
-            if (!a.resident && p.CH == 32 && p.MT == 4 && (ntiles + 7) / 8 >= num_cus() && getenv("LFGC_FWD_X2")) {
-                a.x2 = 1; a.waves = 4; a.nbatches = (ntiles + 7) / 8;
-            }
-        }
-    }
-    long long grid = (a.resident ? 2LL : 1LL) * num_cus();
-    if (grid > a.nbatches) grid = a.nbatches;
+    fwd_apply_launch(plan.first, &a);
     hipStream_t st = (hipStream_t)stream;
     if (h16) {
         if (status) {
@@ -134,36 +199,25 @@ extern "C" int lfgc_forward_f32(const lfgc_mlp_desc* desc, const lfgc_positions*
         }
         int rc16;
         switch (p.CH) {
-            case 8: rc16 = lfgc_fwd16_dispatch_ch8(p.MT, a, lds_bytes, (int)grid, st); break;
-            case 16: rc16 = lfgc_fwd16_dispatch_ch16(p.MT, a, lds_bytes, (int)grid, st); break;
-            case 24: rc16 = lfgc_fwd16_dispatch_ch24(p.MT, a, lds_bytes, (int)grid, st); break;
-            case 32: rc16 = lfgc_fwd16_dispatch_ch32(p.MT, a, lds_bytes, (int)grid, st); break;
+            case 8: rc16 = lfgc_fwd16_dispatch_ch8(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
+            case 16: rc16 = lfgc_fwd16_dispatch_ch16(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
+            case 24: rc16 = lfgc_fwd16_dispatch_ch24(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
+            case 32: rc16 = lfgc_fwd16_dispatch_ch32(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
             default: return LFGC_E_UNSUPPORTED;
         }
-        if (rc16 != LFGC_OK || !status) return rc16;
+        if (rc16 != LFGC_OK || !plan.has_redo) return rc16;
         // Range fallback: the same pass on the exact-fp32 build, enqueued behind the fast one; its workgroups return
         // at once unless the fast kernel has set *status (a sample left the f16 range: diverged or very wide model).
         // No host synchronisation, graph-capturable; costs one empty launch when nothing overflowed.
-        a.status = nullptr; a.redo_if = status; a.single = 0; a.zrun = 0; a.x2 = 0;
-        const int all32 = p.off_final, max32 = p.blk0 > p.blk1 ? p.blk0 : p.blk1, fixed32 = p.HP + 4;
-        a.resident = ((fixed32 + all32) * 4 <= 80 * 1024) ? 1 : 0;
-        lds_bytes = (fixed32 + (a.resident ? all32 : 2 * max32)) * 4;
-        a.coord_table = 0;
-        if (!a.pos) {
-            const long long tbl = 4LL * ((long long)a.res0 + a.res1 + a.res2);
-            const long long cap = a.resident ? 80 * 1024 : 160 * 1024;
-            if (lds_bytes + tbl <= cap) { a.coord_table = 1; lds_bytes += (int)tbl; }
-        }
-        a.waves = (!a.resident && (n + 255) / 256 >= num_cus()) ? 8 : 4;
-        a.nbatches = (n + 255) / 256 * (8 / a.waves);
-        grid = (a.resident ? 2LL : 1LL) * num_cus();
-        if (grid > a.nbatches) grid = a.nbatches;
+        a.status = nullptr; a.redo_if = status; a.single = 0;
+        fwd_apply_launch(plan.redo, &a);
     }
+    const lfgc_forward_launch& l32 = h16 ? plan.redo : plan.first;
     switch (p.CH) {
-        case 8: return lfgc_fwd_dispatch_ch8(p.MT, a, lds_bytes, (int)grid, st);
-        case 16: return lfgc_fwd_dispatch_ch16(p.MT, a, lds_bytes, (int)grid, st);
-        case 24: return lfgc_fwd_dispatch_ch24(p.MT, a, lds_bytes, (int)grid, st);
-        case 32: return lfgc_fwd_dispatch_ch32(p.MT, a, lds_bytes, (int)grid, st);
+        case 8: return lfgc_fwd_dispatch_ch8(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
+        case 16: return lfgc_fwd_dispatch_ch16(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
+        case 24: return lfgc_fwd_dispatch_ch24(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
+        case 32: return lfgc_fwd_dispatch_ch32(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
         default: return LFGC_E_UNSUPPORTED;
     }
 }

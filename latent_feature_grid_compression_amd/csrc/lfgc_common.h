@@ -284,22 +284,21 @@ template <int NWAVES>
 __device__ __forceinline__ void lfgc_dma_piece(const LfgcDmaPlan& d, int pi) {
     int base = (d.wave + pi * NWAVES) << 6;              // wave-uniform
     base = base < d.nvec - 64 ? base : d.nvec - 64;
-    const unsigned long long ga = (unsigned long long)(size_t)(d.src + 4 * base);
-    // (wave-uniform by construction; readfirstlane makes it so for the register allocator where it cannot prove it)
-    const unsigned long long sp = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ga) |
-                                  ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ga >> 32)) << 32);
-    const unsigned lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(d.dst + 4 * base));   // low half of the flat address = LDS offset
-    // Written out: the builtin is given a 64-bit per-lane address, and hipcc then keeps one VGPR pair per piece alive
-    // across the whole batch loop (spilled, and reloaded behind an s_waitcnt vmcnt(0) in the middle of the MFMA stream).
-    // This form takes the block address from SGPRs and one 32-bit lane offset that never changes.  M0 is not named as a
-    // clobber (hipcc reserves it); nothing else in the kernels that use this sets M0 except the builtin form of the same
-    // instruction, which writes M0 itself right before each use.
+    // The compiler's own form of the instruction, NOT a hand-assembled "s_mov_b32 m0 / global_load_lds_dwordx4 v, s[..]":
+    // the backward data kernel (the only user) went wrong with the hand-assembled form wherever layer 0 is a single
+    // 32-row tile under a net two or four tiles wide (CH <= 16, MT >= 2, f16 builds): dX0 -- d_grid and d_pos -- came out
+    // 5e-5 to 5e-4 off with 8-wave workgroups and 0.5 to 0.7 off with 4-wave workgroups walking a second batch, while a
+    // build with this form is at fp32 rounding in all of them (tests/test_kernel_matrix_gpu.py).
+    // hipcc sees this load, its LDS destination and its M0 write; it could see none of them inside the asm string.
+    // Register cost, measured with -Rpass-analysis=kernel-resource-usage over the CH = 32 instantiations: at most +12
+    // VGPRs, no scratch, the same occupancy.
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(d.src + 4 * base + (d.lane16 >> 2)),
+                                     (__attribute__((address_space(3))) void*)(d.dst + 4 * base), 16, 0, 0);
+}
+
 #ifndef LFGC_DMA_POLICY
 #define LFGC_DMA_POLICY ""
 #endif
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" LFGC_DMA_POLICY :: "s"(lds_addr), "v"(d.lane16), "s"(sp) : "memory");
-}
-
 // Piece PI (a compile-time index) of a block of NVEC vectors (compile-time too).  Where every wave's piece PI lies wholly
 // inside the block -- all but the last one or two -- its addresses are the wave's block bases (lfgc_dma_plan_block) plus
 // constants: 3 scalar instructions and the load, against 10 for the clamped form.  A lone instruction stream gets one

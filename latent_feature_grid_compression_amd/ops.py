@@ -6,6 +6,7 @@ import ctypes
 import functools
 import os
 import weakref
+from types import SimpleNamespace
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -738,6 +739,37 @@ def forward_raw(desc: MlpDesc, grid_cl: torch.Tensor, packed: torch.Tensor, pos:
     if return_status:
         return out, stash, status
     return out, stash
+
+
+def _launch_dict(l: _lib.ForwardLaunch) -> dict:
+    return {name: int(getattr(l, name)) for name, _t in _lib.ForwardLaunch._fields_}
+
+
+@_on_device
+def forward_plan(desc: MlpDesc, grid_cl: torch.Tensor, pos: Optional[torch.Tensor] = None, lattice=None,
+                 want_stash: bool = False, precision: str = 'f16x2', range_fallback: bool = True) -> SimpleNamespace:
+    """lfgc_forward_plan: the launch forward_raw would make for the same arguments on grid_cl's device, nothing enqueued.
+    Fields: CH, MT, resident, waves, nbatches, grid, coord_table, zrun, nzc, tiles_per_row, x2, ntiles, lds_bytes (of the
+    build `precision` names) and redo = the same fields of the exact-fp32 range-fallback launch, or None without one."""
+    _require_hip(grid_cl, pos)
+    ps, _n = _positions_struct(pos, lattice)
+    D, H, W, _cs = grid_cl.shape
+    has_status = range_fallback and precision != 'fp32'
+    info = _lib.ForwardPlanInfo()
+    check(_lib.load().lfgc_forward_plan(ctypes.byref(desc), ctypes.byref(ps), D, H, W, _lib.PRECISION[precision],
+                                        int(want_stash), int(has_status), ctypes.byref(info)), 'lfgc_forward_plan')
+    return SimpleNamespace(CH=int(info.CH), MT=int(info.MT), **_launch_dict(info.first),
+                           redo=SimpleNamespace(**_launch_dict(info.redo)) if info.has_redo else None)
+
+
+def backward_plan(desc: MlpDesc, n: int, precision: str = 'f16x2', device=None) -> SimpleNamespace:
+    """lfgc_backward_plan: the launch backward_raw would make for n samples on `device` (default: the current one).
+    Fields: CH, MT, waves, nbatches, grid, nslabs, roles, lds_bytes."""
+    info = _lib.BackwardPlanInfo()
+    with torch.cuda.device(device):
+        check(_lib.load().lfgc_backward_plan(ctypes.byref(desc), int(n), _lib.PRECISION[precision], ctypes.byref(info)),
+              'lfgc_backward_plan')
+    return SimpleNamespace(**{name: int(getattr(info, name)) for name, _t in _lib.BackwardPlanInfo._fields_})
 
 
 @_on_device

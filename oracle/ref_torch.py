@@ -331,12 +331,14 @@ def deviation_statistics(prediction: torch.Tensor, ground_truth: torch.Tensor):
 # ---- synthetic model construction shared by tests / smoke / bench (seeded, box-independent) -------
 
 def synth_model(C: int, G: int, H: int, L: int, n_freqs: int = 2, seed: int = 0, num_levels=None,
-                d_in: int = 3, d_out: int = 1):
+                d_in: int = 3, d_out: int = 1, grid_shape=None):
     """Random-init parameters shaped like model_utils.setup_model builds them (model/model_utils.py:
     27-28 grid U(0,1); nn.Linear default init U(+-1/sqrt(fan_in))) from a numpy PCG64 stream so the
-    build container and the GPU box agree bit-for-bit.  Returns a dict of fp32 CPU tensors."""
+    build container and the GPU box agree bit-for-bit.  Returns a dict of fp32 CPU tensors.
+    grid_shape=(D, H, W) builds a non-cubic (C, D, H, W) grid instead of (C, G, G, G); G is then only recorded."""
     rng = np.random.Generator(np.random.PCG64(seed))
-    grid = torch.from_numpy(rng.random((C, G, G, G), dtype=np.float32))
+    dhw = (G, G, G) if grid_shape is None else tuple(int(v) for v in grid_shape)
+    grid = torch.from_numpy(rng.random((C,) + dhw, dtype=np.float32))
     filter_fwd, filter_rev = build_filters(3)
     coeffs, shape_array = encode_volume(grid, filter_fwd, num_levels=num_levels)
     k0 = d_in + 2 * n_freqs * d_in + C

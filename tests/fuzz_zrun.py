@@ -39,14 +39,18 @@ def main():
                 os.environ['LFGC_NO_ZRUN'] = '1'
             try:
                 with torch.no_grad():
+                    if mode == 'zrun':
+                        plan = ops.forward_plan(m._descriptor(), m._decoded_channel_last(), lattice=(res, xb, xe, 32))
                     y, _ = ops.forward_raw(m._descriptor(), m._decoded_channel_last(), m._packed(), lattice=(res, xb, xe, 32), clamp=True)
                 outs[mode] = y.view(xe - xb, res[1], res[2]).cpu()
             finally:
                 os.environ.pop('LFGC_NO_ZRUN', None)
         e = rel_err(outs['zrun'].numpy(), outs['gather'].numpy())
         short = int(31.0 * G / (res[2] - 1) + 1e-3) + 3 <= 12
-        same = bool(torch.equal(outs['zrun'], outs['gather']))
-        taken += int(not same)
+        same = not plan.zrun                     # the launch plan says which sampler ran (the struct the launcher consumes)
+        taken += int(plan.zrun)
+        if same:
+            assert torch.equal(outs['zrun'], outs['gather'])
         # a few tiles through the position-list entry with the reference-style tile positions
         rds = R.VolumeIndexing(res)
         tiles = [b for b in R.tile_iter(rds.vol_res_touple, 32) if b[0] < xe and b[1] > xb]
@@ -59,7 +63,7 @@ def main():
             x0, x1 = max(b[0], xb), min(b[1], xe)
             e2 = max(e2, rel_err(outs['zrun'][x0 - xb:x1 - xb, b[2]:b[3], b[4]:b[5]].numpy(), yp[x0 - b[0]:x1 - b[0]].numpy()))
         worst = max(worst, e, e2)
-        ok = e <= 3e-6 and e2 <= 3e-6 and np.isfinite(outs['zrun'].numpy()).all() and (same or short)
+        ok = e <= 3e-6 and e2 <= 3e-6 and np.isfinite(outs['zrun'].numpy()).all() and (not plan.zrun or short)
         print('%s case %2d C%-2d G%-2d H%-3d L%d res %-14s slab [%d,%d): zrun vs gather %.1e, vs position list %.1e%s'
               % ('ok  ' if ok else 'FAIL', case, C, G, H, L, res, xb, xe, e, e2, '' if not same else '  (same path)'), flush=True)
         if not ok:

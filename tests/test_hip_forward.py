@@ -47,12 +47,12 @@ def build_from_golden(g, dev):
     return m.to(dev)
 
 
-def build_synth(C, G, H, L, seed, dev, num_levels=None):
+def build_synth(C, G, H, L, seed, dev, num_levels=None, grid_shape=None):
     from latent_feature_grid_compression_amd.model.Feature_Grid_Model import Feature_Grid_Model
     from latent_feature_grid_compression_amd.model.Feature_Embedding import FourierEmbedding
     from latent_feature_grid_compression_amd.wavelet_transform.Torch_Wavelet_Transform import WaveletFilter3d
-    sm = R.synth_model(C, G, H, L, seed=seed, num_levels=num_levels)
-    m = Feature_Grid_Model(FourierEmbedding(2, 3), torch.zeros(C, G, G, G), None, WaveletFilter3d('db2'),
+    sm = R.synth_model(C, G, H, L, seed=seed, num_levels=num_levels, grid_shape=grid_shape)
+    m = Feature_Grid_Model(FourierEmbedding(2, 3), torch.zeros_like(sm['grid']), None, WaveletFilter3d('db2'),
                            hidden_channel=H, num_layer=L, num_levels=num_levels)
     assert np.array_equal(m.shape_array, sm['shape_array'])
     with torch.no_grad():
@@ -468,20 +468,21 @@ def test_lattice_zrun_column_sampler(dev, C, G, H, L, res, slab):
     """Lattice mode takes z-run tiles + the column sampler (csrc/lfgc_forward.h, LfgcColumnSampler) where the column is
     short and the per-sample 8-corner gather otherwise (`LFGC_NO_ZRUN=1` forces the latter).  Both against the oracle on
     the reference's own tile positions (<= 1e-5, north_star), and against each other: the two evaluate the same
-    trilinear sum in a different order, so they agree to fp32 rounding -- and, where the column path is taken, are not
-    bit-identical, which is how the test knows it ran."""
+    trilinear sum in a different order, so they agree to fp32 rounding.  Which sampler ran is what the launch plan says
+    (ops.forward_plan, the struct the launcher consumes): the column sampler exactly where the column is short."""
     from latent_feature_grid_compression_amd import ops
     from latent_feature_grid_compression_amd.data.IndexDataset import IndexDataset
     m, sm = build_synth(C, G, H, L, seed=900 + C + G, dev=dev)
     m.eval()
     ds = IndexDataset(res, 16, build_index_table=False)
     xb, xe = slab if slab else (0, res[0])
-    outs = {}
+    outs, plans = {}, {}
     for mode in ('zrun', 'gather'):
         if mode == 'gather':
             os.environ['LFGC_NO_ZRUN'] = '1'
         try:
             with torch.no_grad():
+                plans[mode] = ops.forward_plan(m._descriptor(), m._decoded_channel_last(), lattice=(res, xb, xe, 32))
                 y, _ = ops.forward_raw(m._descriptor(), m._decoded_channel_last(), m._packed(), lattice=(res, xb, xe, 32), clamp=True)
             outs[mode] = y.view(xe - xb, res[1], res[2]).cpu()
         finally:
@@ -496,8 +497,11 @@ def test_lattice_zrun_column_sampler(dev, C, G, H, L, res, slab):
     for mode, y in outs.items():
         assert rel_err(y.numpy(), ref) <= 1e-5, mode
     assert rel_err(outs['zrun'].numpy(), outs['gather'].numpy()) <= 3e-6
-    short_column = int(31.0 * G / (res[2] - 1) + 1e-3) + 3 <= 12
-    assert torch.equal(outs['zrun'], outs['gather']) != short_column, 'which sampler ran is not what the column length says'
+    nzc = int(31.0 * G / (res[2] - 1) + 1e-3) + 3
+    short_column = nzc <= 12
+    assert plans['zrun'].zrun == int(short_column), 'which sampler ran is not what the column length says'
+    assert plans['zrun'].nzc == (nzc if short_column else 2)
+    assert plans['gather'].zrun == 0 and plans['gather'].nzc == 2
 
 
 def test_two_tiles_per_wave_kernel_is_the_same_function(dev):
