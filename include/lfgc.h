@@ -170,6 +170,25 @@ int lfgc_idwt_level_drop_bwd_len_f32(const float* d_out, const float* filter_rev
                                      const float* const* penalty_grads, int C, int d0, int d1, int d2,
                                      int t0, int t1, int t2, lfgc_stream_t stream);
 
+/* The LAST level with drop layers, in the sampler's channel-last layout: lfgc_idwt_level_drop_len_f32 + lfgc_grid_layout_f32
+ * (and lfgc_grid_layout_f32 + lfgc_idwt_level_drop_bwd_len_f32) in one pass over the data each.  Thresholds, overwritten
+ * and accumulated outputs, pre-zeroed d_mul_* and penalty_grads[4] are those of the channel-first drop pair above, word for
+ * word; layouts, pad channels, crop and limits are those of the channel-last pair (out_cl / d_out_cl (t0,t1,t2,
+ * channel_stride), channel_stride = lfgc_grid_channel_stride(C), separable bank `taps` REQUIRED).  filter_len is 2 or 4.
+ * Decided before anything is launched: LFGC_E_NULL for a missing required pointer (lll / hf included where a d_mul_* or an
+ * L2 penalty needs them); LFGC_E_SHAPE for channel_stride != C rounded up to 8 or t_a out of range; LFGC_E_UNSUPPORTED for
+ * taps == NULL, another filter_len, C > 32 or an array of 2^30 bytes and more (compose the channel-first drop entry with
+ * the layout conversion).  With all four factor and penalty pointers NULL they are exactly the plain channel-last pair. */
+int lfgc_idwt_level_cl_drop_len_f32(const float* lll, const float* hf, const float* mul_lll, float threshold_lll,
+                                    const float* mul_hf, float threshold_hf, const float* taps, int filter_len,
+                                    float* out_cl, int C, int channel_stride, int d0, int d1, int d2,
+                                    int t0, int t1, int t2, lfgc_stream_t stream);
+int lfgc_idwt_level_cl_drop_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len,
+                                        const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                        float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                        const float* const* penalty_grads, int C, int channel_stride,
+                                        int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
+
 /* One drop layer on one tensor outside the decode (the layers' own forward(x)): x, out (C, n), mul (n). */
 int lfgc_drop_apply_f32(const float* x, const float* mul, float threshold, float* out, int C, int64_t n,
                         lfgc_stream_t stream);

@@ -15,6 +15,7 @@
 // The kernels are templates on the half-length K; the K = 2 instances are the original db2 kernels instruction for
 // instruction.  Other lengths take the separable (`taps`) form only: the reference only ever builds outer products.
 #include "lfgc_common.h"
+#include "lfgc_drop_value.h"   // drop_value(), sign_of()
 #include <type_traits>
 
 #ifndef LFGC_WAVELET_ABLATE
@@ -38,15 +39,6 @@ struct IdwtArgs {
     const float* mul_h; // (7, d0,d1,d2) or NULL
     float thr_l, thr_h; // NaN: value = x * m;  else masked straight-through: value = (x*(m>=thr) - x*m) + x*m
 };
-
-// One coefficient through its drop layer (model/Smallify_Dropout.py:57, model/Variational_Dropout_Layer.py:109,
-// model/Straight_Through_Dropout.py:28 and :58 -- the latter op for op, so the value is the reference's bit for bit).
-__device__ __forceinline__ float drop_value(float x, float m, float thr, bool ste) {
-    if (!ste) return __fmul_rn(x, m);
-    const float hard = m >= thr ? 1.0f : 0.0f;
-    const float soft = __fmul_rn(x, m);
-    return __fadd_rn(__fsub_rn(__fmul_rn(x, hard), soft), soft);
-}
 
 constexpr int kTileCells = 128;      // analysis: cells of the flattened (y,x) plane per z-slice of a workgroup
 constexpr int kFwdCells = 256;       // synthesis: plane cells per workgroup (one per thread, both z-slices each)
@@ -404,8 +396,6 @@ struct AnalysisArgs {
     // (Smallify beta: adds g sign(factor) to the factor gradient, once, by the channel-0 workgroups)
     const float* g_l2_l; const float* g_l2_h; const float* g_l1_l; const float* g_l1_h;
 };
-
-__device__ __forceinline__ float sign_of(float v) { return (float)((v > 0.0f) - (v < 0.0f)); }
 
 template <bool DROP, bool SEP, int K>
 __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs<K> a) {

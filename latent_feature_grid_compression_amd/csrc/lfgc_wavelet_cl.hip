@@ -1,8 +1,13 @@
 // lfgc_wavelet_cl.hip -- the LAST wavelet level with the dense grid in the sampler's channel-last layout (gfx950).
 //   lfgc_idwt_level_cl_f32      wavelet_transform/Torch_Wavelet_Transform.py:91-104 (+ crop :69-73) writing (t0,t1,t2,Cs)
 //   lfgc_idwt_level_cl_bwd_f32  its adjoint reading the gradient of that (t0,t1,t2,Cs) grid
-// so that decode_volume() needs no layout conversion pass (lfgc_grid_layout_f32) on either direction.  Separable
-// filter banks only (`taps`); the dense-stencil path keeps the channel-first kernels + the conversion.
+//   lfgc_idwt_level_cl_drop_len_f32 / _bwd_len_f32  the same two with the pruning layers' per-coefficient factors (and
+//                               the penalty gradients) folded in: the DROP builds of both kernels, same contract as the
+//                               channel-first lfgc_idwt_level_drop_len_f32 / _bwd_len_f32 (lfgc_wavelet.hip)
+// so that decode_volume() needs no layout conversion pass (lfgc_grid_layout_f32) on either direction, with or without
+// drop layers.  Separable filter banks only (`taps`); the dense-stencil path keeps the channel-first kernels + the
+// conversion.  The non-DROP instantiations are unchanged by the DROP template parameter (every new field and statement
+// sits behind `if (DROP)`; same instruction streams, same registers, same LDS).
 //
 // Templates on the half filter length K: K = 2 (db2) and K = 1 (Haar, no neighbour cells and no z carry: each 2x2x2
 // output block is a butterfly of one cell's 8 bands).  Longer filters take the channel-first kernels + the conversion.
@@ -21,6 +26,7 @@
 // write the two halves of the same 128-byte lines) and neighbouring tiles (they share coefficient rows / source voxels)
 // run on the same XCD and meet in its L2.
 #include "lfgc_common.h"
+#include "lfgc_drop_value.h"   // drop_value(), sign_of()
 #include <cstdlib>
 
 namespace {
@@ -93,6 +99,10 @@ struct IdwtClArgs {
     int C, cs, d0, d1, d2, t0, t1, t2, o0, o1, o2;   // o = crop offset floor((2d+2K-2-t)/2)
     int zchunk, ptiles, ngroups, nchunks;
     float taps[4 * K];  // [low | high][tap]
+    // DROP build only: the pruning layers' per-coefficient factors, shared by all channels (lfgc_wavelet.hip: IdwtArgs)
+    const float* mul_l; // (d0,d1,d2) or NULL
+    const float* mul_h; // (7, d0,d1,d2) or NULL
+    float thr_l, thr_h; // NaN: value = x * m;  else the masked straight-through rule (drop_value)
 };
 
 // Synthesis: out_full[o] = sum_{s,t} in[s][i] F_s[t], o = 2 i + t per axis; cell j = (jz,jy,jx) in [0,d+K-2] per axis
@@ -100,7 +110,14 @@ struct IdwtClArgs {
 // Plane iz of the coefficients is contracted over x and y once (Y[sz][py][px]); its e_z = 0 part completes cell slice
 // jz = iz (added to the carry of the earlier planes), its e_z = e part is carried to slice iz + e.
 // Arithmetic role: 32 cells x 2 channels per wave: channel = c0 + 2 wave + lane / 32.
-template <int CW, int CELLS, bool NT, int K>
+// DROP: every coefficient passes through its drop layer (drop_value) before the in-plane contraction.  Its factor sits
+// at the same cell of a (d0,d1,d2) / (7,d0,d1,d2) array without the channel, so all CW channels of the workgroup use the
+// same 8 K^2 x 32 factors of a plane: the workgroup fetches them ONCE (1 to 4 per thread, the same neighbour-cell offsets
+// through descriptors of the factor arrays, kOutside neighbours read 0 like their coefficients), a step ahead, into a
+// double-buffered LDS table [neighbour][band][cell] that the arithmetic role reads back with its lanes along the cells.
+// Holding a thread's 8 K^2 factors in registers next to its coefficients instead was built first: 164 VGPRs for K = 2
+// (3 waves per SIMD; 67 spilled in the 16-wave workgroup, which is capped at 128).
+template <int CW, int CELLS, bool NT, int K, bool DROP>
 __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs<K> a) {
     constexpr int L = 2 * K;
     constexpr int KC = K > 1 ? K - 1 : 1;             // z-carry slots (8 floats each)
@@ -161,6 +178,48 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs<K>
     const int slice = a.t1 * a.t2 * a.cs;
     const cl_srd rout = cl_make_srd(a.out, (unsigned)(a.t0 * slice * 4));
 
+    // DROP, factor role: table element e = (q * 8 + band) * CELLS + cell, elements thread + k * (workgroup size).  The
+    // band is part of the lane offset (it differs inside a wave), so each element is asked of both factor arrays with
+    // the one it does not belong to (or that is NULL) marked kOutside: reads 0, and the two results are OR-ed.
+    constexpr int NF = 8 * K * K * CELLS;              // factors of one coefficient plane
+    constexpr int FPT = DROP ? (NF + CW * CELLS - 1) / (CW * CELLS) : 1;
+    float* s_fac = s_tile + 2 * TILE;                  // [2][NF], slot = plane & 1
+    unsigned fol[FPT], foh[FPT];
+    float fv[FPT];
+    cl_srd rml, rmh;
+    if (DROP) {
+        rml = cl_make_srd(a.mul_l, a.mul_l ? (unsigned)(dvol * 4) : 0u);
+        rmh = cl_make_srd(a.mul_h, a.mul_h ? (unsigned)(7 * dvol * 4) : 0u);
+#pragma unroll
+        for (int k = 0; k < FPT; ++k) {
+            const int e = (int)threadIdx.x + k * CW * CELLS;
+            const int q = (e / CELLS) >> 3, sb = (e / CELLS) & 7;
+            const int f = f0 + e % CELLS;
+            const int fc = min(f, plane_cells - 1);
+            const int jy = fc / n2, jx = fc - jy * n2;
+            const int cy = jy - q / K, cx = jx - q % K;
+            const bool ok = e < NF && f < plane_cells && cy >= 0 && cy < a.d1 && cx >= 0 && cx < a.d2;
+            fol[k] = ok && sb == 0 && a.mul_l ? 4u * (unsigned)(cy * a.d2 + cx) : kOutside;
+            foh[k] = ok && sb > 0 && a.mul_h ? 4u * (unsigned)((sb - 1) * dvol + cy * a.d2 + cx) : kOutside;
+        }
+    }
+    auto fac_issue = [&](int pz) {                     // factors of coefficient plane pz -> fv
+#pragma unroll
+        for (int k = 0; k < FPT; ++k) {
+            float l, h;
+            cl_load(l, rml, fol[k], 4u * (unsigned)(pz * dplane));
+            cl_load(h, rmh, foh[k], 4u * (unsigned)(pz * dplane));
+            fv[k] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, l) | __builtin_bit_cast(unsigned, h));
+        }
+    };
+    auto fac_put = [&](int pz) {                       // fv -> table slot of plane pz
+#pragma unroll
+        for (int k = 0; k < FPT; ++k) {
+            const int e = (int)threadIdx.x + k * CW * CELLS;
+            if (e < NF) s_fac[(pz & 1) * NF + e] = fv[k];
+        }
+    };
+
     float R[8 * K * K];                                // [neighbour q][band]
     float carry[8 * KC];                               // [slice iz + 1 + e][parity]
 #pragma unroll
@@ -180,6 +239,12 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs<K>
 
     int iz = jz_begin - (K - 1);
     if (wave_live && iz >= 0) issue(iz);
+    if (DROP) {
+        // The table of plane p is filled during step p - 1, before that step's barrier (DROP: every step has one): its
+        // slot was last read in step p - 2, which every wave left through that step's barrier.  First plane: here.
+        if (iz >= 0) { fac_issue(iz); fac_put(iz); }
+        __syncthreads();
+    }
     int buf = 0;
 #pragma unroll 1
     for (; iz < jz_end; ++iz) {
@@ -187,9 +252,24 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs<K>
         const bool plane_ok = iz >= 0 && iz < a.d0;
         const bool next_ok = iz + 1 < jz_end && iz + 1 < a.d0;
         float* tile = s_tile + buf * TILE;
+        if (DROP && next_ok) fac_issue(iz + 1);                   // every wave, also one without channels
         if (wave_live) {
             float outv[8];
             if (plane_ok) {
+                if (DROP) {
+                    const float* fac = s_fac + (iz & 1) * NF + cell;
+                    if (a.mul_l) {
+#pragma unroll
+                        for (int q = 0; q < K * K; ++q) R[q * 8] = drop_value(R[q * 8], fac[q * 8 * CELLS], a.thr_l, a.thr_l == a.thr_l);
+                    }
+                    if (a.mul_h) {
+#pragma unroll
+                        for (int q = 0; q < K * K; ++q)
+#pragma unroll
+                            for (int sb = 1; sb < 8; ++sb)
+                                R[q * 8 + sb] = drop_value(R[q * 8 + sb], fac[(q * 8 + sb) * CELLS], a.thr_h, a.thr_h == a.thr_h);
+                    }
+                }
                 float X[K][2][2][2];                              // [ey][sz][sy][px]
 #pragma unroll
                 for (int q = 0; q < 4 * K; ++q) {
@@ -249,6 +329,10 @@ __global__ __launch_bounds__(CW * CELLS) void idwt_cl_kernel(const IdwtClArgs<K>
                 for (int p = 0; p < 8; ++p) tile[(p * CELLS + cell) * VOX + cw] = outv[p];
             }
         }
+        if (DROP) {
+            if (next_ok) fac_put(iz + 1);
+            if (!emit) __syncthreads();
+        }
         if (emit) {
             __syncthreads();
             // one barrier per step is enough: the other buffer is written only after the NEXT barrier, which every wave
@@ -277,12 +361,27 @@ struct AnalysisClArgs {
     int C, cs, n0, n1, n2, lo0, lo1, lo2, d0, d1, d2;
     int zchunk, ptiles, ngroups, nchunks;
     float taps[4 * K];
+    // DROP build only (lfgc_wavelet.hip: AnalysisArgs)
+    const float* lll;      // forward inputs (C, d0,d1,d2), (C, 7, d0,d1,d2): needed for d_mul and the L2 penalty
+    const float* hf;
+    const float* mul_l;    // (d0,d1,d2) or NULL
+    const float* mul_h;    // (7, d0,d1,d2) or NULL
+    float* d_mul_l;        // (d0,d1,d2) or NULL, pre-zeroed
+    float* d_mul_h;        // (7, d0,d1,d2) or NULL, pre-zeroed
+    const float* g_l2_l; const float* g_l2_h; const float* g_l1_l; const float* g_l1_h;   // penalty gradients folded in
 };
 
 // Adjoint: band_s[c][i] = sum_t src[2 i + t - lo][c] F_s[t].  Step iz reads the source planes 2 iz - lo0 + L-2 + {0, 1},
 // contracts each over x and y (P[sy][sx]) and combines them with the L - 2 planes carried from the earlier steps.
 // Arithmetic role: lanes = CW channels x CPW cells; cell = wave * CPW + lane / CW.
-template <int CW, int NG, int K>   // NG: cell groups of 32 per workgroup (the channel-first runs it writes are 128 NG bytes)
+// DROP (the contract of analysis_kernel<true, ...>, lfgc_wavelet.hip): stored gradient = band_s m_s (+ 2 g coef_s for an
+// L2 penalty), d_m_s[i] += sum_c band_s[c][i] coef_s[c][i] (+ g sign(m) for an L1 penalty, once per address: channel
+// group 0).  In the store role a lane's store address into d_lll / d_hf is the address of the matching lll / hf value
+// (same layout): coef is loaded there, coalesced, the factor at the same cell without the channel.  The lane puts
+// band coef back into its tile slot; after a second barrier the workgroup sums the CW channels of every (band, cell) in
+// LDS and issues ONE float atomic per (band, cell) -- whole runs of consecutive cells per wave instruction -- instead of
+// one per channel.
+template <int CW, int NG, int K, bool DROP>   // NG: cell groups of 32 per workgroup (the channel-first runs it writes are 128 NG bytes)
 __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClArgs<K> a) {
     constexpr int L = 2 * K;
     constexpr int CT = L > 2 ? L - 2 : 1;             // carried source planes
@@ -321,16 +420,52 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
     // store role: NG == 1: lane = (cell, channel parity), one instruction per band; NG >= 2: lane = cell, one instruction per
     // band, channel and 64 cells
     unsigned so0, soh;
+    unsigned som = 0;              // DROP: the cell inside a factor plane (no channel part)
     if (NG == 1) {
         const int sf = f0 + (lane & 31), half = lane >> 5;
         const bool ok = sf < plane_cells && c0 + 2 * w + half < a.C;
         so0 = ok ? 4u * (unsigned)(half * dvol + sf) : kOutside;
         soh = ok ? 4u * (unsigned)(half * 7 * dvol + sf) : kOutside;
+        if (DROP) som = ok ? 4u * (unsigned)sf : kOutside;
     } else {
         so0 = soh = 4u * (unsigned)(f0 + lane);
+        if (DROP) som = so0;
     }
     const cl_srd rb0 = cl_make_srd(a.band0, (unsigned)(a.C * dvol * 4));
     const cl_srd rbh = cl_make_srd(a.bandh, (unsigned)(a.C * 7 * dvol * 4));
+    // DROP: descriptors of the coefficients and the factors; an operand that is absent (or, coefficients, not needed: no
+    // factor gradient and no L2 penalty) gets an EMPTY one: its loads stay in the instruction stream, read 0.0 and
+    // move no bytes -- the store role below is one branch-free block
+    const bool need_l = DROP && a.lll && (a.d_mul_l || a.g_l2_l), need_h = DROP && a.hf && (a.d_mul_h || a.g_l2_h);
+    const cl_srd rc0 = cl_make_srd(DROP ? a.lll : nullptr, need_l ? (unsigned)(a.C * dvol * 4) : 0u);
+    const cl_srd rch = cl_make_srd(DROP ? a.hf : nullptr, need_h ? (unsigned)(a.C * 7 * dvol * 4) : 0u);
+    const cl_srd rm0 = cl_make_srd(DROP ? a.mul_l : nullptr, DROP && a.mul_l ? (unsigned)(dvol * 4) : 0u);
+    const cl_srd rmh = cl_make_srd(DROP ? a.mul_h : nullptr, DROP && a.mul_h ? (unsigned)(7 * dvol * 4) : 0u);
+    // DROP: which operands exist, as bits [low, detail] of one word, and the penalty scalars by value (scalar registers
+    // are what these builds run out of: a pointer costs two and stays live for its NULL test)
+    enum { kMul = 1, kDMul = 4, kL2 = 16, kL1 = 64 };
+    unsigned has = 0;
+    float g2l = 0.0f, g2h = 0.0f, g1l = 0.0f, g1h = 0.0f;
+    if (DROP) {
+        has = (a.mul_l ? kMul : 0) | (a.mul_h ? 2 * kMul : 0) | (a.d_mul_l ? kDMul : 0) | (a.d_mul_h ? 2 * kDMul : 0) |
+              (a.g_l2_l ? kL2 : 0) | (a.g_l2_h ? 2 * kL2 : 0) | (a.g_l1_l ? kL1 : 0) | (a.g_l1_h ? 2 * kL1 : 0);
+        if (a.g_l2_l) g2l = 2.0f * *a.g_l2_l;
+        if (a.g_l2_h) g2h = 2.0f * *a.g_l2_h;
+        if (a.g_l1_l) g1l = *a.g_l1_l;
+        if (a.g_l1_h) g1h = *a.g_l1_h;
+    }
+    // DROP, store role: band value v of band sb whose store address is (lo, uo) and whose factor is at (mlo, mo) -> the
+    // value to store; the lane's share of the factor gradient goes back into its tile slot (read only where a factor
+    // gradient is wanted).  Selects on wave-uniform bits, no branches: the 8 bands' loads are in flight together.
+    auto fold = [&](int sb, float v, unsigned lo, unsigned uo, unsigned mlo, unsigned mo, float* slot) -> float {
+        const unsigned bit = sb == 0 ? 1u : 2u;
+        float x, m;
+        cl_load(x, sb == 0 ? rc0 : rch, lo, uo);
+        cl_load(m, sb == 0 ? rm0 : rmh, mlo, mo);
+        *slot = v * x;
+        v = (has & bit * kMul) ? v * m : v;
+        return (has & bit * kL2) ? __builtin_fmaf(sb == 0 ? g2l : g2h, x, v) : v;
+    };
 
     float R[2 * L * L];            // [plane k][ty*L+tx] of the cell group in flight
     float carry[NG][CT][4];        // [group][plane tz = 0 .. L-3 of the next step][sy*2+sx]
@@ -411,25 +546,64 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
             __syncthreads();
             // store role: this wave's channels are {2 w, 2 w + 1}; whole 128 NG-byte runs of one (channel, band) per half wave / wave
             const unsigned zoff = (unsigned)(iz * plane_cells);
+            // (tests/test_cl_drop_resources.py compiles this file and holds every instantiation to zero spills)
+            // DROP: the uniform offsets and tile addresses below are formed anew in every step -- kept across the loop (8 bands x
+            // 2 channels each, next to the extra descriptors and pointers) they do not fit the scalar registers and were spilled
+            int dvs = dvol, ws = w;
+            if (DROP) asm volatile("" : "+s"(dvs), "+s"(ws));
 #pragma unroll
             for (int sb = 0; sb < 8; ++sb) {
+                const unsigned mo = 4u * ((unsigned)((sb > 0 ? sb - 1 : 0) * dvs) + zoff);   // DROP: (band, z) of the factor
                 if (NG == 1) {                                    // both channels in one instruction (lane / 32)
-                    const float v = tile[(2 * w + (lane >> 5)) * CHS + sb * CELLS + (lane & 31)];
-                    if (sb == 0) cl_store<false>(v, rb0, so0, 4u * ((unsigned)((c0 + 2 * w) * dvol) + zoff));
-                    else cl_store<false>(v, rbh, soh, 4u * ((unsigned)(((c0 + 2 * w) * 7 + sb - 1) * dvol) + zoff));
+                    float* slot = tile + (2 * ws + (lane >> 5)) * CHS + sb * CELLS + (lane & 31);
+                    float v = *slot;
+                    const unsigned uo = sb == 0 ? 4u * ((unsigned)((c0 + 2 * ws) * dvs) + zoff)
+                                                : 4u * ((unsigned)(((c0 + 2 * ws) * 7 + sb - 1) * dvs) + zoff);
+                    if (DROP) v = fold(sb, v, sb == 0 ? so0 : soh, uo, som, mo, slot);
+                    if (sb == 0) cl_store<false>(v, rb0, so0, uo);
+                    else cl_store<false>(v, rbh, soh, uo);
                 } else {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const int cb = c0 + 2 * w + h;
+                        const int cb = c0 + 2 * ws + h;
                         if (cb >= a.C) continue;
 #pragma unroll
                         for (int part = 0; part < NG / 2; ++part) {                   // 64 cells = 256 contiguous bytes each
-                            const float v = tile[(2 * w + h) * CHS + sb * CELLS + part * 64 + lane];
+                            float* slot = tile + (2 * ws + h) * CHS + sb * CELLS + part * 64 + lane;
+                            float v = *slot;
                             const unsigned lo = (f0 + part * 64 + lane < plane_cells) ? so0 + 256u * part : kOutside;
-                            if (sb == 0) cl_store<false>(v, rb0, lo, 4u * ((unsigned)(cb * dvol) + zoff));
-                            else cl_store<false>(v, rbh, lo, 4u * ((unsigned)((cb * 7 + sb - 1) * dvol) + zoff));
+                            const unsigned uo = sb == 0 ? 4u * ((unsigned)(cb * dvs) + zoff) : 4u * ((unsigned)((cb * 7 + sb - 1) * dvs) + zoff);
+                            if (DROP) v = fold(sb, v, lo, uo, lo, mo, slot);
+                            if (sb == 0) cl_store<false>(v, rb0, lo, uo);
+                            else cl_store<false>(v, rbh, lo, uo);
                         }
                     }
+                }
+            }
+            if (DROP && (has & 3 * kDMul)) {
+                // the tile now holds band coef per channel: sum the CW channels, one atomic per (band, cell).  Channels
+                // beyond C add 0, and that rests on the ARITHMETIC role: it marks their source rows kOutside (`live`), so
+                // their band values are 0.  NG == 1 overwrites such a slot with 0 * 0 (coef read through kOutside); NG >= 2
+                // skips those channels in the store role and the slot keeps that band value 0.
+                // The other buffer is written only after the next step's barrier, as before.
+                __syncthreads();
+#pragma unroll
+                for (int idx = threadIdx.x; idx < 8 * CELLS; idx += 32 * CW) {
+                    const int sb = idx / CELLS, f = f0 + idx % CELLS;
+                    const unsigned bit = sb == 0 ? 1u : 2u;
+                    if (!(has & bit * kDMul) || f >= plane_cells) continue;
+                    float t = tile[idx];
+#pragma unroll
+                    for (int c = 1; c < CW; ++c) t += tile[c * CHS + idx];
+                    const long long o = (long long)(sb > 0 ? sb - 1 : 0) * dvs + (long long)zoff + f;
+                    if ((has & bit * kL1) && cg == 0) {           // the factor again: asked of both arrays like the synthesis does
+                        float ml, mh;
+                        cl_load(ml, rm0, sb == 0 ? 4u * (unsigned)o : kOutside, 0u);
+                        cl_load(mh, rmh, sb > 0 ? 4u * (unsigned)o : kOutside, 0u);
+                        const float m = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, ml) | __builtin_bit_cast(unsigned, mh));
+                        t += (sb == 0 ? g1l : g1h) * sign_of(m);
+                    }
+                    atomicAdd((sb == 0 ? a.d_mul_l : a.d_mul_h) + o, t);
                 }
             }
             buf ^= 1;
@@ -464,6 +638,13 @@ int launch_cl(K kern, int threads, const A& a, int lds_bytes, hipStream_t stream
     return LFGC_OK;
 }
 
+// drop-layer operands of the two directions (all NULL / NaN: the plain level)
+struct ClDropFwd { const float* mul_l; const float* mul_h; float thr_l, thr_h; };
+struct ClDropBwd {
+    const float* lll; const float* hf; const float* mul_l; const float* mul_h; float* d_mul_l; float* d_mul_h;
+    const float* pg[4];    // penalty_grads (include/lfgc.h)
+};
+
 int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, const float* taps, int L, int C, int cs,
              int d0, int d1, int d2, int t0, int t1, int t2) {
     if (!p0 || !p1 || !p2 || !p3) return LFGC_E_NULL;
@@ -477,14 +658,34 @@ int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, con
     return LFGC_OK;
 }
 
+// Launch of the selected synthesis shape; DROP picks the instantiation, everything else is decided by idwt_cl below.
+template <int K, bool DROP>
+int idwt_cl_launch(const IdwtClArgs<K>& a, int cw, bool nt, int lds, hipStream_t st) {
+    if (cw == 32) {
+        static bool raised[LFGC_MAX_DEVICES] = {false};     // 67.6 KB of LDS: above the 64 KB default limit
+        const int dev = lfgc_current_device();
+        if (!raised[dev]) {                                 // once per (kernel, device): launches stay graph-capturable
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, true, K, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, false, K, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            if (e != hipSuccess) return (int)e;
+            raised[dev] = true;
+        }
+        return nt ? launch_cl(idwt_cl_kernel<32, kCells, true, K, DROP>, 1024, a, lds, st) : launch_cl(idwt_cl_kernel<32, kCells, false, K, DROP>, 1024, a, lds, st);
+    }
+    if (cw == 16) return nt ? launch_cl(idwt_cl_kernel<16, kCells, true, K, DROP>, 512, a, lds, st) : launch_cl(idwt_cl_kernel<16, kCells, false, K, DROP>, 512, a, lds, st);
+    return nt ? launch_cl(idwt_cl_kernel<8, kCells, true, K, DROP>, 256, a, lds, st) : launch_cl(idwt_cl_kernel<8, kCells, false, K, DROP>, 256, a, lds, st);
+}
+
 template <int K>
-int idwt_cl(const float* lll, const float* hf, const float* taps, float* out_cl, int C, int channel_stride,
+int idwt_cl(const float* lll, const float* hf, const ClDropFwd& dr, const float* taps, float* out_cl, int C, int channel_stride,
             int d0, int d1, int d2, int t0, int t1, int t2, hipStream_t st) {
     IdwtClArgs<K> a = {};
     a.lll = lll; a.hf = hf; a.out = out_cl;
     a.C = C; a.cs = channel_stride; a.d0 = d0; a.d1 = d1; a.d2 = d2; a.t0 = t0; a.t1 = t1; a.t2 = t2;
     a.o0 = (2 * d0 + 2 * K - 2 - t0) / 2; a.o1 = (2 * d1 + 2 * K - 2 - t1) / 2; a.o2 = (2 * d2 + 2 * K - 2 - t2) / 2;
     for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
+    a.mul_l = dr.mul_l; a.mul_h = dr.mul_h; a.thr_l = dr.thr_l; a.thr_h = dr.thr_h;
+    const bool drop = dr.mul_l || dr.mul_h;
     // 32 channels on a large plane: one workgroup of 16 waves writes whole 128-byte lines (d = 65: 197 vs 203 us); on a
     // small one two 8-wave groups balance better (d = 33: 26.5 vs 28.7 us).  24 channels: three groups of 8.
     const long long ptiles = ((long long)(d1 + K - 1) * (d2 + K - 1) + kCells - 1) / kCells;
@@ -493,28 +694,33 @@ int idwt_cl(const float* lll, const float* hf, const float* taps, float* out_cl,
     a.ngroups = channel_stride / cw;
     if (ptiles * a.ngroups > 0x0fffffffLL) return LFGC_E_UNSUPPORTED;
     a.ptiles = (int)ptiles;
-    const int lds = 2 * 8 * kCells * (cw + 1) * 4;
-    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0 + K - 1, cw == 32 ? 1 : cw == 16 ? 2 : 4);    // 96 VGPRs: 4 waves per SIMD
+    const int lds = 2 * 8 * kCells * (cw + 1) * 4 + (drop ? 2 * 8 * K * K * kCells * 4 : 0);    // DROP: + the factor table
+    // workgroups per CU: 96 VGPRs, 4 waves per SIMD.  DROP: 101 to 110 VGPRs (Haar: 40), still 4 waves per SIMD, and the
+    // 8 KB factor table leaves the LDS count as it is (75.8 KB x 1, 43 KB x 2, 26.4 KB x 4 of 160 KB)
+    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0 + K - 1, cw == 32 ? 1 : cw == 16 ? 2 : 4);
     a.nchunks = (d0 + K - 1 + a.zchunk - 1) / a.zchunk;
     bool nt = cw == 32 && (long long)t0 * t1 * t2 * channel_stride * 4 > (48LL << 20); // see cl_store
     if (const char* e = getenv("LFGC_CL_NT")) nt = e[0] == '1';                         // diagnostics
-    if (cw == 32) {
-        static bool raised[LFGC_MAX_DEVICES] = {false};     // 67.6 KB of LDS: above the 64 KB default limit
+    return drop ? idwt_cl_launch<K, true>(a, cw, nt, lds, st) : idwt_cl_launch<K, false>(a, cw, nt, lds, st);
+}
+
+template <int K, bool DROP>
+int idwt_cl_bwd_launch(const AnalysisClArgs<K>& a, int cw, int ng, int lds, hipStream_t st) {
+    if (ng == 2 && cw == 16) {
+        static bool raised[LFGC_MAX_DEVICES] = {false};     // 65.7 KB of LDS: above the 64 KB default limit
         const int dev = lfgc_current_device();
         if (!raised[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, true, K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, false, K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(analysis_cl_kernel<16, 2, K, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             if (e != hipSuccess) return (int)e;
             raised[dev] = true;
         }
-        return nt ? launch_cl(idwt_cl_kernel<32, kCells, true, K>, 1024, a, lds, st) : launch_cl(idwt_cl_kernel<32, kCells, false, K>, 1024, a, lds, st);
     }
-    if (cw == 16) return nt ? launch_cl(idwt_cl_kernel<16, kCells, true, K>, 512, a, lds, st) : launch_cl(idwt_cl_kernel<16, kCells, false, K>, 512, a, lds, st);
-    return nt ? launch_cl(idwt_cl_kernel<8, kCells, true, K>, 256, a, lds, st) : launch_cl(idwt_cl_kernel<8, kCells, false, K>, 256, a, lds, st);
+    if (ng == 2) return cw == 16 ? launch_cl(analysis_cl_kernel<16, 2, K, DROP>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 2, K, DROP>, 256, a, lds, st);
+    return cw == 16 ? launch_cl(analysis_cl_kernel<16, 1, K, DROP>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 1, K, DROP>, 256, a, lds, st);
 }
 
 template <int K>
-int idwt_cl_bwd(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf, int C, int channel_stride,
+int idwt_cl_bwd(const float* d_out_cl, const float* taps, const ClDropBwd& dr, float* d_lll, float* d_hf, int C, int channel_stride,
                 int d0, int d1, int d2, int t0, int t1, int t2, hipStream_t st) {
     AnalysisClArgs<K> a = {};
     a.src = d_out_cl; a.band0 = d_lll; a.bandh = d_hf;
@@ -522,6 +728,9 @@ int idwt_cl_bwd(const float* d_out_cl, const float* taps, float* d_lll, float* d
     a.lo0 = (2 * d0 + 2 * K - 2 - t0) / 2; a.lo1 = (2 * d1 + 2 * K - 2 - t1) / 2; a.lo2 = (2 * d2 + 2 * K - 2 - t2) / 2;
     a.d0 = d0; a.d1 = d1; a.d2 = d2;
     for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
+    a.lll = dr.lll; a.hf = dr.hf; a.mul_l = dr.mul_l; a.mul_h = dr.mul_h; a.d_mul_l = dr.d_mul_l; a.d_mul_h = dr.d_mul_h;
+    a.g_l2_l = dr.pg[0]; a.g_l2_h = dr.pg[1]; a.g_l1_l = dr.pg[2]; a.g_l1_h = dr.pg[3];
+    const bool drop = dr.mul_l || dr.mul_h || dr.pg[0] || dr.pg[1];
     const int cw = channel_stride % 16 == 0 ? 16 : 8;
     // cells per workgroup: 64 on a large plane (256-byte runs per (channel, band): one whole line + two shared ones per
     // store instead of two shared ones: 188 -> 176 us at d = 65; 128 cells: no further gain), 32 on a small one (d = 33:
@@ -532,31 +741,56 @@ int idwt_cl_bwd(const float* d_out_cl, const float* taps, float* d_lll, float* d
     a.ngroups = channel_stride / cw;
     if (ptiles * a.ngroups > 0x0fffffffLL) return LFGC_E_UNSUPPORTED;
     a.ptiles = (int)ptiles;
-    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0, (cw == 16 ? (ng == 2 ? 2 : 3) : (ng == 2 ? 4 : 6)));   // LDS 33 KB x ng per 16 channels; <= 6 waves per SIMD
+    // LDS 33 KB x ng per 16 channels; <= 6 waves per SIMD.  DROP has the same tile; db2 with 32-cell tiles runs at 90
+    // instead of 76 VGPRs, i.e. 5 waves per SIMD = 20 per CU: two 8-wave or five 4-wave workgroups (64-cell tiles: 109
+    // to 111 VGPRs, 4 waves per SIMD as before; Haar: at most 46)
+    int slots = cw == 16 ? (ng == 2 ? 2 : 3) : (ng == 2 ? 4 : 6);
+    if (drop && K == 2 && ng == 1) slots = cw == 16 ? 2 : 5;
+    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0, slots);
     a.nchunks = (d0 + a.zchunk - 1) / a.zchunk;
     const int lds = 2 * cw * (8 * kCells * ng + 1) * 4;
-    if (ng == 2 && cw == 16) {
-        static bool raised[LFGC_MAX_DEVICES] = {false};     // 65.7 KB of LDS: above the 64 KB default limit
-        const int dev = lfgc_current_device();
-        if (!raised[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(analysis_cl_kernel<16, 2, K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return (int)e;
-            raised[dev] = true;
-        }
-    }
-    if (ng == 2) return cw == 16 ? launch_cl(analysis_cl_kernel<16, 2, K>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 2, K>, 256, a, lds, st);
-    return cw == 16 ? launch_cl(analysis_cl_kernel<16, 1, K>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 1, K>, 256, a, lds, st);
+    return drop ? idwt_cl_bwd_launch<K, true>(a, cw, ng, lds, st) : idwt_cl_bwd_launch<K, false>(a, cw, ng, lds, st);
 }
 
 }  // namespace
+
+extern "C" int lfgc_idwt_level_cl_drop_len_f32(const float* lll, const float* hf, const float* mul_lll, float thr_lll,
+                                               const float* mul_hf, float thr_hf, const float* taps, int filter_len,
+                                               float* out_cl, int C, int channel_stride, int d0, int d1, int d2,
+                                               int t0, int t1, int t2, lfgc_stream_t stream) {
+    const int rc = check_cl(lll, hf, out_cl, out_cl, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    if (C > 32) return LFGC_E_UNSUPPORTED;             // channel-first DROP level + lfgc_grid_layout_f32
+    const ClDropFwd dr = {mul_lll, mul_hf, thr_lll, thr_hf};
+    return filter_len == 2 ? idwt_cl<1>(lll, hf, dr, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
+                           : idwt_cl<2>(lll, hf, dr, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+}
+
+extern "C" int lfgc_idwt_level_cl_drop_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len,
+                                                   const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                                   float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                                   const float* const* penalty_grads, int C, int channel_stride,
+                                                   int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
+    ClDropBwd dr = {lll, hf, mul_lll, mul_hf, d_mul_lll, d_mul_hf, {nullptr, nullptr, nullptr, nullptr}};
+    if (penalty_grads) for (int i = 0; i < 4; ++i) dr.pg[i] = penalty_grads[i];
+    if (!d_out_cl || !d_lll || !d_hf) return LFGC_E_NULL;
+    if ((d_mul_lll && (!mul_lll || !lll)) || (d_mul_hf && (!mul_hf || !hf))) return LFGC_E_NULL;
+    if ((dr.pg[0] && !lll) || (dr.pg[1] && !hf) || (dr.pg[2] && !d_mul_lll) || (dr.pg[3] && !d_mul_hf)) return LFGC_E_NULL;
+    const int rc = check_cl(d_out_cl, d_lll, d_hf, d_hf, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    if (C > 32) return LFGC_E_UNSUPPORTED;
+    return filter_len == 2 ? idwt_cl_bwd<1>(d_out_cl, taps, dr, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
+                           : idwt_cl_bwd<2>(d_out_cl, taps, dr, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+}
 
 extern "C" int lfgc_idwt_level_cl_len_f32(const float* lll, const float* hf, const float* taps, int filter_len, float* out_cl,
                                           int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
                                           lfgc_stream_t stream) {
     const int rc = check_cl(lll, hf, out_cl, out_cl, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
     if (rc != LFGC_OK) return rc;
-    return filter_len == 2 ? idwt_cl<1>(lll, hf, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
-                           : idwt_cl<2>(lll, hf, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+    const ClDropFwd none = {nullptr, nullptr, 0.0f, 0.0f};
+    return filter_len == 2 ? idwt_cl<1>(lll, hf, none, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
+                           : idwt_cl<2>(lll, hf, none, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
 }
 
 extern "C" int lfgc_idwt_level_cl_f32(const float* lll, const float* hf, const float* taps, float* out_cl,
@@ -570,8 +804,9 @@ extern "C" int lfgc_idwt_level_cl_bwd_len_f32(const float* d_out_cl, const float
                                               lfgc_stream_t stream) {
     const int rc = check_cl(d_out_cl, d_lll, d_hf, d_hf, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
     if (rc != LFGC_OK) return rc;
-    return filter_len == 2 ? idwt_cl_bwd<1>(d_out_cl, taps, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
-                           : idwt_cl_bwd<2>(d_out_cl, taps, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+    const ClDropBwd none = {};
+    return filter_len == 2 ? idwt_cl_bwd<1>(d_out_cl, taps, none, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
+                           : idwt_cl_bwd<2>(d_out_cl, taps, none, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
 }
 
 extern "C" int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf,

@@ -426,6 +426,84 @@ def idwt_level_drop_bwd(d_out, filter_rev, lll, hf, mul_l, mul_h, want_dml, want
 
 
 @_on_device
+def idwt_level_cl_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> torch.Tensor:
+    """idwt_level_drop writing the sampler's channel-last grid (t0,t1,t2,Cs), pad channels zero: the last level of a
+    decode with drop layers and the layout conversion in one kernel (falls back to the two-kernel form for shapes the
+    channel-last kernels do not take, see _cl_level_ok)."""
+    _require_hip(lll, hf, filter_rev, mul_l, mul_h)
+    taps = filter_taps(filter_rev)
+    C, d0, d1, d2 = lll.shape
+    t = [int(v) for v in target]
+    L = filter_length(filter_rev)
+    if not _cl_level_ok(C, (d0, d1, d2), t, taps, L):
+        return to_channel_last(idwt_level_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target))
+    lll, hf = _f32c(lll), _f32c(hf)
+    if tuple(hf.shape) != (C, 7, d0, d1, d2):
+        raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
+    if mul_l is not None:
+        mul_l = _f32c(mul_l)
+        if tuple(mul_l.shape) != (d0, d1, d2):
+            raise ValueError('low-band drop factor %s does not match %s' % (tuple(mul_l.shape), (d0, d1, d2)))
+    if mul_h is not None:
+        mul_h = _f32c(mul_h)
+        if tuple(mul_h.shape) != (7, d0, d1, d2):
+            raise ValueError('detail drop factor %s does not match %s' % (tuple(mul_h.shape), (7, d0, d1, d2)))
+    cs = grid_channel_stride(C)
+    out = torch.empty((t[0], t[1], t[2], cs), dtype=torch.float32, device=lll.device)
+    ml = mul_l.data_ptr() if mul_l is not None else None
+    mh = mul_h.data_ptr() if mul_h is not None else None
+    check(_lib.load().lfgc_idwt_level_cl_drop_len_f32(
+        lll.data_ptr(), hf.data_ptr(), ml, _thr(thr_l), mh, _thr(thr_h), taps, L, out.data_ptr(), C, cs, d0, d1, d2,
+        t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_drop_len_f32')
+    return out
+
+
+@_on_device
+def idwt_level_cl_drop_bwd(d_out_cl, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs=None):
+    """Adjoint of idwt_level_cl_drop: d_out_cl (t0,t1,t2,Cs) -> (d_lll, d_hf, d_mul_l or None, d_mul_h or None), the
+    arguments of idwt_level_drop_bwd (falls back to it behind the layout conversion like idwt_level_cl_drop)."""
+    _require_hip(d_out_cl, filter_rev)
+    taps = filter_taps(filter_rev)
+    d = [int(v) for v in d]
+    t0, t1, t2, cs = d_out_cl.shape
+    L = filter_length(filter_rev)
+    if not _cl_level_ok(C, d, (t0, t1, t2), taps, L):
+        return idwt_level_drop_bwd(to_channel_first(d_out_cl, C), filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d,
+                                   penalty_ptrs)
+    d_out_cl = _f32c(d_out_cl)
+    dev = d_out_cl.device
+    if cs != grid_channel_stride(C):
+        raise ValueError('gradient grid %s is not the channel-last grid of %d channels' % (tuple(d_out_cl.shape), C))
+    # the kernels take raw addresses: contiguous fp32 of exactly the level's shapes
+    shapes = {'lll': (C, d[0], d[1], d[2]), 'hf': (C, 7, d[0], d[1], d[2]), 'mul_l': (d[0], d[1], d[2]),
+              'mul_h': (7, d[0], d[1], d[2])}
+    given = {'lll': lll, 'hf': hf, 'mul_l': mul_l, 'mul_h': mul_h}
+    for name, x in given.items():
+        if x is not None:
+            _require_hip(x)
+            if tuple(x.shape) != shapes[name]:
+                raise ValueError('%s %s does not match the level %s' % (name, tuple(x.shape), shapes[name]))
+            given[name] = _f32c(x)
+    lll, hf, mul_l, mul_h = given['lll'], given['hf'], given['mul_l'], given['mul_h']
+    for name, x in (('mul_l', want_dml), ('mul_h', want_dmh)):
+        if torch.is_tensor(x) and (tuple(x.shape) != shapes[name] or x.dtype != torch.float32 or not x.is_contiguous()):
+            raise ValueError('gradient buffer of %s must be contiguous fp32 of shape %s' % (name, shapes[name]))
+    d_lll = torch.empty((C, d[0], d[1], d[2]), dtype=torch.float32, device=dev)
+    d_hf = torch.empty((C, 7, d[0], d[1], d[2]), dtype=torch.float32, device=dev)
+    d_ml = want_dml if torch.is_tensor(want_dml) else (
+        torch.zeros((d[0], d[1], d[2]), dtype=torch.float32, device=dev) if want_dml else None)
+    d_mh = want_dmh if torch.is_tensor(want_dmh) else (
+        torch.zeros((7, d[0], d[1], d[2]), dtype=torch.float32, device=dev) if want_dmh else None)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    pen, _keep = (None, None) if penalty_ptrs is None else _lib.ptr_array([int(v) for v in penalty_ptrs])
+    check(_lib.load().lfgc_idwt_level_cl_drop_bwd_len_f32(
+        d_out_cl.data_ptr(), taps, L, ptr(lll), ptr(hf), ptr(mul_l), ptr(mul_h), d_lll.data_ptr(), d_hf.data_ptr(),
+        ptr(d_ml), ptr(d_mh), pen, C, cs, d[0], d[1], d[2], t0, t1, t2, _stream(d_out_cl)),
+        'lfgc_idwt_level_cl_drop_bwd_len_f32')
+    return d_lll, d_hf, d_ml, d_mh
+
+
+@_on_device
 def drop_apply(x: torch.Tensor, mul: torch.Tensor, thr=None) -> torch.Tensor:
     """x (C, ...) * mul (...) with the value rule of include/lfgc.h (one drop layer outside the decode)."""
     _require_hip(x, mul)
@@ -464,12 +542,17 @@ class DropApplyFn(torch.autograd.Function):
 
 def decode_levels_drop(coeffs, factors, thresholds, shape_array, filter_rev, channel_last: bool) -> torch.Tensor:
     """decode_volume() with drop factors (model/Feature_Grid_Model.py:102-108): factors[i] / thresholds[i] belong
-    to coeffs[i]; None = that tensor passes unchanged."""
+    to coeffs[i]; None = that tensor passes unchanged.  channel_last: the last level writes the sampler's layout directly
+    (a one-level model's last level is also its first: it takes factors[0] as the low band's factor)."""
     if len(coeffs) == 1:
         restored = coeffs[0] if factors[0] is None else drop_apply(coeffs[0], factors[0], thresholds[0])
     else:
         restored, mul_l, thr_l = coeffs[0], factors[0], thresholds[0]
+        n = len(coeffs) - 1
         for k in range(1, len(coeffs)):
+            if channel_last and k == n:
+                return idwt_level_cl_drop(restored, coeffs[k], mul_l, thr_l, factors[k], thresholds[k], filter_rev,
+                                          shape_array[k - 1])
             restored = idwt_level_drop(restored, coeffs[k], mul_l, thr_l, factors[k], thresholds[k], filter_rev,
                                        shape_array[k - 1])
             mul_l, thr_l = None, None
@@ -514,7 +597,8 @@ def _decode_drop_backward(ctx, d_out, d_pen):
     it = iter(saved[n:])
     factors = [next(it) if h else None for h in ctx.has]
     C = ctx.dims[0][0]
-    g = to_channel_first(d_out, C) if ctx.channel_last else d_out
+    # channel_last: the last level's adjoint reads the gradient of the sampler's layout directly
+    g = to_channel_first(d_out, C) if (ctx.channel_last and n == 1) else d_out
     d_coef, d_fac = [None] * n, [None] * n
     # the factor gradients are accumulated with atomics: one zero fill for all of them
     sizes = [int(np.prod(ctx.dims[i][1:])) if ctx.want[i] else 0 for i in range(n)]
@@ -535,9 +619,13 @@ def _decode_drop_backward(ctx, d_out, d_pen):
         pens = None
         if d_pen is not None:
             pens = [l2(0) if first else 0, l2(lvl), l1(0) if first else 0, l1(lvl)]
-        g, d_hf, d_ml, d_mh = idwt_level_drop_bwd(
-            g, ctx.filter_rev, coeffs[0] if (first and (ctx.has[0] or d_pen is not None)) else None, coeffs[lvl], ml,
-            factors[lvl], zeroed[0] if first else False, zeroed[lvl], ctx.dims[lvl][2:], pens)
+        lll = coeffs[0] if (first and (ctx.has[0] or d_pen is not None)) else None
+        if ctx.channel_last and lvl == n - 1:
+            g, d_hf, d_ml, d_mh = idwt_level_cl_drop_bwd(g, C, ctx.filter_rev, lll, coeffs[lvl], ml, factors[lvl],
+                                                         zeroed[0] if first else False, zeroed[lvl], ctx.dims[lvl][2:], pens)
+        else:
+            g, d_hf, d_ml, d_mh = idwt_level_drop_bwd(g, ctx.filter_rev, lll, coeffs[lvl], ml, factors[lvl],
+                                                      zeroed[0] if first else False, zeroed[lvl], ctx.dims[lvl][2:], pens)
         d_coef[lvl], d_fac[lvl] = d_hf, d_mh
         if first:
             d_fac[0] = d_ml
