@@ -819,18 +819,7 @@ static __global__ __launch_bounds__(256) void lfgc_bwd_reduce_kernel(const LfgcR
 
 template <int CH, int MT, int NF, int WAVES, int PREC>
 static int lfgc_launch_bwd_data(const LfgcBwdArgs& a, int lds_bytes, int grid_data, hipStream_t stream) {
-    auto kd = lfgc_bwd_data_kernel<CH, MT, NF, WAVES, PREC>;
-    static int lds_limit_set[LFGC_MAX_DEVICES] = {0};      // per (instantiation, device)
-    const int dev = lfgc_current_device();
-    if (lds_bytes > 64 * 1024 && lds_bytes > lds_limit_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kd),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return (int)e;
-        lds_limit_set[dev] = lds_bytes;
-    }
-    hipLaunchKernelGGL(kd, dim3(grid_data), dim3(WAVES * 64), lds_bytes, stream, a);
-    LFGC_HIP_CHECK_LAUNCH();
-    return LFGC_OK;
+    return lfgc_launch<lfgc_bwd_data_kernel<CH, MT, NF, WAVES, PREC>>(dim3(grid_data), dim3(WAVES * 64), lds_bytes, stream, a);
 }
 
 // waves = waves per workgroup of the data kernel (4 or 8, chosen by the caller together with a.nbatches)
@@ -852,23 +841,10 @@ static int lfgc_launch_bwd(const LfgcBwdArgs& a, const LfgcWgradArgs& w, int wav
                            a.D, a.H, a.W, a.Cs);
         LFGC_HIP_CHECK_LAUNCH();
     }
-    {
-        constexpr int K0R_ = (CH + (3 + 6 * NF + 7) / 8 * 8 + 31) / 32 * 32;
-        constexpr int NT0_ = K0R_ / 32;
-        constexpr int TPW0 = (MT + 4 / NT0_ - 1) / (4 / NT0_), TPW1 = (MT + 4 / MT - 1) / (4 / MT);
-        constexpr int TPWM = TPW0 > TPW1 ? TPW0 : TPW1;
-        const int comb_bytes = 4 * TPWM * 17 * 64 * 4;
-        auto kw = lfgc_bwd_weight_kernel<CH, MT, NF>;
-        static int comb_limit_set[LFGC_MAX_DEVICES] = {0};
-        const int dev = lfgc_current_device();
-        if (comb_bytes > 64 * 1024 && comb_bytes > comb_limit_set[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kw),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, comb_bytes);
-            if (e != hipSuccess) return (int)e;
-            comb_limit_set[dev] = comb_bytes;
-        }
-        hipLaunchKernelGGL(kw, dim3(grid_w), dim3(512), comb_bytes, stream, w);
-    }
-    LFGC_HIP_CHECK_LAUNCH();
-    return LFGC_OK;
+    constexpr int K0R_ = (CH + (3 + 6 * NF + 7) / 8 * 8 + 31) / 32 * 32;
+    constexpr int NT0_ = K0R_ / 32;
+    constexpr int TPW0 = (MT + 4 / NT0_ - 1) / (4 / NT0_), TPW1 = (MT + 4 / MT - 1) / (4 / MT);
+    constexpr int TPWM = TPW0 > TPW1 ? TPW0 : TPW1;
+    const int comb_bytes = 4 * TPWM * 17 * 64 * 4;
+    return lfgc_launch<lfgc_bwd_weight_kernel<CH, MT, NF>>(dim3(grid_w), dim3(512), comb_bytes, stream, w);
 }

@@ -349,3 +349,29 @@ static inline int lfgc_num_cus() {
 }
 
 #define LFGC_HIP_CHECK_LAUNCH() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
+
+// Dynamic LDS above the 64 KB default needs the kernel's limit raised first.  Done once per (kernel, device) and size, so
+// that later launches make no attribute call and stay graph-capturable: `limit` belongs to this instantiation, i.e. to
+// the kernel VALUE it is instantiated on -- there is no table to index wrongly.
+template <auto Kern>
+int lfgc_raise_lds_limit(int lds_bytes) {
+    static int limit[LFGC_MAX_DEVICES] = {0};
+    if (lds_bytes <= 64 * 1024) return LFGC_OK;
+    const int dev = lfgc_current_device();
+    if (lds_bytes > limit[dev]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return (int)e;
+        limit[dev] = lds_bytes;
+    }
+    return LFGC_OK;
+}
+
+// Raise the limit if needed, launch, report the launch error.
+template <auto Kern, class Args>
+int lfgc_launch(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const Args& a) {
+    const int rc = lfgc_raise_lds_limit<Kern>(lds_bytes);
+    if (rc != LFGC_OK) return rc;
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, stream, a);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}

@@ -614,20 +614,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
 
 template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH, bool SPLIT, bool ZRUN>
 static int lfgc_launch_fwd16_cfg(const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream) {
-    auto kern = lfgc_fwd16_kernel<CH, MT, NF, WAVES, STREAM, STASH, SPLIT, ZRUN>;
-    // the >64 KB dynamic-LDS attribute is per device: raised once per (instantiation, device); one-time, so launches
-    // stay graph-capturable
-    static int lds_limit_set[LFGC_MAX_DEVICES] = {0};
-    const int dev = lfgc_current_device();
-    if (lds_bytes > 64 * 1024 && lds_bytes > lds_limit_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return (int)e;
-        lds_limit_set[dev] = lds_bytes;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds_bytes, stream, a);
-    LFGC_HIP_CHECK_LAUNCH();
-    return LFGC_OK;
+    return lfgc_launch<lfgc_fwd16_kernel<CH, MT, NF, WAVES, STREAM, STASH, SPLIT, ZRUN>>(dim3(grid), dim3(WAVES * 64), lds_bytes,
+                                                                                         stream, a);
 }
 
 template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH>

@@ -362,17 +362,6 @@ __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs 
 
 template <int CH, int MT, int NF>
 static int lfgc_launch_fwd16x2(const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream) {
-    auto launch = [&](auto kern) -> int {
-        static int lds_limit_set[2][LFGC_MAX_DEVICES] = {{0}};
-        const int dev = lfgc_current_device(), which = a.single ? 1 : 0;
-        if (lds_bytes > 64 * 1024 && lds_bytes > lds_limit_set[which][dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-            if (e != hipSuccess) return (int)e;
-            lds_limit_set[which][dev] = lds_bytes;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, stream, a);
-        LFGC_HIP_CHECK_LAUNCH();
-        return LFGC_OK;
-    };
-    return a.single ? launch(lfgc_fwd16x2_kernel<CH, MT, NF, false>) : launch(lfgc_fwd16x2_kernel<CH, MT, NF, true>);
+    return a.single ? lfgc_launch<lfgc_fwd16x2_kernel<CH, MT, NF, false>>(dim3(grid), dim3(256), lds_bytes, stream, a)
+                    : lfgc_launch<lfgc_fwd16x2_kernel<CH, MT, NF, true>>(dim3(grid), dim3(256), lds_bytes, stream, a);
 }

@@ -600,17 +600,16 @@ inline int check_level(const void* a, const void* b, const void* c, const void* 
     return LFGC_OK;
 }
 
-template <typename K, typename A>
-int launch_tiled(K kern, int* lds_limit, const A& a, dim3 blocks, int lds_bytes, hipStream_t stream) {
+template <auto Kern, typename A>
+int launch_tiled(const A& a, dim3 blocks, int lds_bytes, hipStream_t stream) {
     if (blocks.y > 65535u || blocks.z > 65535u || lds_bytes > 160 * 1024) return LFGC_E_UNSUPPORTED;
-    if (lds_bytes > 64 * 1024 && lds_bytes > *lds_limit) {      // raised once per kernel: launches stay graph-capturable
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return (int)e;
-        *lds_limit = lds_bytes;
-    }
-    hipLaunchKernelGGL(kern, blocks, dim3(256), lds_bytes, stream, a);
-    LFGC_HIP_CHECK_LAUNCH();
-    return LFGC_OK;
+    return lfgc_launch<Kern>(blocks, dim3(256), lds_bytes, stream, a);
+}
+
+// Runs f(std::bool_constant<drop>): the DROP template argument of the level kernels.
+template <typename F>
+int with_drop(bool drop, F&& f) {
+    return drop ? f(std::true_type()) : f(std::false_type());
 }
 
 template <int K>
@@ -625,8 +624,6 @@ int launch_idwt(IdwtArgs<K> a, bool drop, const float* taps, hipStream_t stream)
     const dim3 blocks((unsigned)ptiles, (unsigned)((n0 + 1) / 2), (unsigned)a.C);
     const int lds = (filt_floats<K>() + (K + 1) * a.len * kRec) * 4;
     if ((long long)a.d0 * a.d1 * a.d2 > 0x7fffffffLL / 8 || (long long)a.t0 * a.t1 * a.t2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    static int lim[4][LFGC_MAX_DEVICES] = {{0}};       // per (kernel, device)
-    const int dev_lim = lfgc_current_device();
     if constexpr (K == 2) {
     const int ki = (a.len + 255) / 256;
     // Small levels (<= 40 000 output voxels per channel: everything below the last two levels of a 64^3 grid) take the tiled
@@ -637,22 +634,16 @@ int launch_idwt(IdwtArgs<K> a, bool drop, const float* taps, hipStream_t stream)
         a.zchunk = n0 < 6 ? n0 : 5;
         const dim3 sblocks((unsigned)ptiles, (unsigned)((n0 + a.zchunk - 1) / a.zchunk), (unsigned)a.C);
         const int slds = 2 * a.len * kRec * 4;
-        static int slim[6][LFGC_MAX_DEVICES] = {{0}};       // per (kernel, device)
-    const int dev_slim = lfgc_current_device();
-        if (drop) {
-            if (ki == 1) return launch_tiled(idwt_slide_kernel<true, 1>, &slim[0][dev_slim], a, sblocks, slds, stream);
-            if (ki == 2) return launch_tiled(idwt_slide_kernel<true, 2>, &slim[1][dev_slim], a, sblocks, slds, stream);
-            return launch_tiled(idwt_slide_kernel<true, 3>, &slim[2][dev_slim], a, sblocks, slds, stream);
-        }
-        if (ki == 1) return launch_tiled(idwt_slide_kernel<false, 1>, &slim[3][dev_slim], a, sblocks, slds, stream);
-        if (ki == 2) return launch_tiled(idwt_slide_kernel<false, 2>, &slim[4][dev_slim], a, sblocks, slds, stream);
-        return launch_tiled(idwt_slide_kernel<false, 3>, &slim[5][dev_slim], a, sblocks, slds, stream);
+        return with_drop(drop, [&](auto dc) {
+            constexpr bool DROP = decltype(dc)::value;
+            if (ki == 1) return launch_tiled<idwt_slide_kernel<DROP, 1>>(a, sblocks, slds, stream);
+            if (ki == 2) return launch_tiled<idwt_slide_kernel<DROP, 2>>(a, sblocks, slds, stream);
+            return launch_tiled<idwt_slide_kernel<DROP, 3>>(a, sblocks, slds, stream);
+        });
     }
-    if (!taps) return drop ? launch_tiled(idwt_level_kernel<true, false, K>, &lim[1][dev_lim], a, blocks, lds, stream)
-                           : launch_tiled(idwt_level_kernel<false, false, K>, &lim[0][dev_lim], a, blocks, lds, stream);
+    if (!taps) return with_drop(drop, [&](auto dc) { return launch_tiled<idwt_level_kernel<decltype(dc)::value, false, K>>(a, blocks, lds, stream); });
     }
-    return drop ? launch_tiled(idwt_level_kernel<true, true, K>, &lim[3][dev_lim], a, blocks, lds, stream)
-                : launch_tiled(idwt_level_kernel<false, true, K>, &lim[2][dev_lim], a, blocks, lds, stream);
+    return with_drop(drop, [&](auto dc) { return launch_tiled<idwt_level_kernel<decltype(dc)::value, true, K>>(a, blocks, lds, stream); });
 }
 
 template <int K>
@@ -665,14 +656,10 @@ int launch_analysis(AnalysisArgs<K> a, bool drop, const float* taps, hipStream_t
     const dim3 blocks((unsigned)ptiles, (unsigned)((a.d0 + 1) / 2), (unsigned)a.C);
     const int lds = (filt_floats<K>() + (2 * K + 2) * a.len) * 4;
     if ((long long)a.n0 * a.n1 * a.n2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    static int lim[4][LFGC_MAX_DEVICES] = {{0}};       // per (kernel, device)
-    const int dev_lim = lfgc_current_device();
     if constexpr (K == 2) {
-        if (!taps) return drop ? launch_tiled(analysis_kernel<true, false, K>, &lim[1][dev_lim], a, blocks, lds, stream)
-                               : launch_tiled(analysis_kernel<false, false, K>, &lim[0][dev_lim], a, blocks, lds, stream);
+        if (!taps) return with_drop(drop, [&](auto dc) { return launch_tiled<analysis_kernel<decltype(dc)::value, false, K>>(a, blocks, lds, stream); });
     }
-    return drop ? launch_tiled(analysis_kernel<true, true, K>, &lim[3][dev_lim], a, blocks, lds, stream)
-                : launch_tiled(analysis_kernel<false, true, K>, &lim[2][dev_lim], a, blocks, lds, stream);
+    return with_drop(drop, [&](auto dc) { return launch_tiled<analysis_kernel<decltype(dc)::value, true, K>>(a, blocks, lds, stream); });
 }
 
 // Runs f(std::integral_constant<int, K>) for the half-length K of filter_len (half_len() != 0 checked by the caller).

@@ -628,14 +628,12 @@ int pick_zchunk(long long columns, int nz, int slots_per_cu) {
     return best;
 }
 
-template <typename K, typename A>
-int launch_cl(K kern, int threads, const A& a, int lds_bytes, hipStream_t stream) {
+template <auto Kern, typename A>
+int launch_cl(int threads, const A& a, int lds_bytes, hipStream_t stream) {
     const long long total = (long long)a.ptiles * a.ngroups * a.nchunks;
     const long long blocks = (total + 7) / 8 * 8;      // cl_work_item: 8 XCD queues of ceil(total / 8)
     if (blocks > 0x7fffffffLL || lds_bytes > 80 * 1024) return LFGC_E_UNSUPPORTED;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), lds_bytes, stream, a);
-    LFGC_HIP_CHECK_LAUNCH();
-    return LFGC_OK;
+    return lfgc_launch<Kern>(dim3((unsigned)blocks), dim3(threads), lds_bytes, stream, a);
 }
 
 // drop-layer operands of the two directions (all NULL / NaN: the plain level)
@@ -662,18 +660,15 @@ int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, con
 template <int K, bool DROP>
 int idwt_cl_launch(const IdwtClArgs<K>& a, int cw, bool nt, int lds, hipStream_t st) {
     if (cw == 32) {
-        static bool raised[LFGC_MAX_DEVICES] = {false};     // 67.6 KB of LDS: above the 64 KB default limit
-        const int dev = lfgc_current_device();
-        if (!raised[dev]) {                                 // once per (kernel, device): launches stay graph-capturable
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, true, K, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(idwt_cl_kernel<32, kCells, false, K, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return (int)e;
-            raised[dev] = true;
-        }
-        return nt ? launch_cl(idwt_cl_kernel<32, kCells, true, K, DROP>, 1024, a, lds, st) : launch_cl(idwt_cl_kernel<32, kCells, false, K, DROP>, 1024, a, lds, st);
+        // 67.6 KB of LDS, above the 64 KB default limit: the first use raises BOTH store-policy builds, so that a first
+        // launch of the other one inside a later graph capture makes no attribute call
+        int rc = lfgc_raise_lds_limit<idwt_cl_kernel<32, kCells, true, K, DROP>>(lds);
+        if (rc == LFGC_OK) rc = lfgc_raise_lds_limit<idwt_cl_kernel<32, kCells, false, K, DROP>>(lds);
+        if (rc != LFGC_OK) return rc;
+        return nt ? launch_cl<idwt_cl_kernel<32, kCells, true, K, DROP>>(1024, a, lds, st) : launch_cl<idwt_cl_kernel<32, kCells, false, K, DROP>>(1024, a, lds, st);
     }
-    if (cw == 16) return nt ? launch_cl(idwt_cl_kernel<16, kCells, true, K, DROP>, 512, a, lds, st) : launch_cl(idwt_cl_kernel<16, kCells, false, K, DROP>, 512, a, lds, st);
-    return nt ? launch_cl(idwt_cl_kernel<8, kCells, true, K, DROP>, 256, a, lds, st) : launch_cl(idwt_cl_kernel<8, kCells, false, K, DROP>, 256, a, lds, st);
+    if (cw == 16) return nt ? launch_cl<idwt_cl_kernel<16, kCells, true, K, DROP>>(512, a, lds, st) : launch_cl<idwt_cl_kernel<16, kCells, false, K, DROP>>(512, a, lds, st);
+    return nt ? launch_cl<idwt_cl_kernel<8, kCells, true, K, DROP>>(256, a, lds, st) : launch_cl<idwt_cl_kernel<8, kCells, false, K, DROP>>(256, a, lds, st);
 }
 
 template <int K>
@@ -706,17 +701,9 @@ int idwt_cl(const float* lll, const float* hf, const ClDropFwd& dr, const float*
 
 template <int K, bool DROP>
 int idwt_cl_bwd_launch(const AnalysisClArgs<K>& a, int cw, int ng, int lds, hipStream_t st) {
-    if (ng == 2 && cw == 16) {
-        static bool raised[LFGC_MAX_DEVICES] = {false};     // 65.7 KB of LDS: above the 64 KB default limit
-        const int dev = lfgc_current_device();
-        if (!raised[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(analysis_cl_kernel<16, 2, K, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return (int)e;
-            raised[dev] = true;
-        }
-    }
-    if (ng == 2) return cw == 16 ? launch_cl(analysis_cl_kernel<16, 2, K, DROP>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 2, K, DROP>, 256, a, lds, st);
-    return cw == 16 ? launch_cl(analysis_cl_kernel<16, 1, K, DROP>, 512, a, lds, st) : launch_cl(analysis_cl_kernel<8, 1, K, DROP>, 256, a, lds, st);
+    if (ng == 2) return cw == 16 ? launch_cl<analysis_cl_kernel<16, 2, K, DROP>>(512, a, lds, st)      // 65.7 KB of LDS
+                                 : launch_cl<analysis_cl_kernel<8, 2, K, DROP>>(256, a, lds, st);
+    return cw == 16 ? launch_cl<analysis_cl_kernel<16, 1, K, DROP>>(512, a, lds, st) : launch_cl<analysis_cl_kernel<8, 1, K, DROP>>(256, a, lds, st);
 }
 
 template <int K>
@@ -752,25 +739,23 @@ int idwt_cl_bwd(const float* d_out_cl, const float* taps, const ClDropBwd& dr, f
     return drop ? idwt_cl_bwd_launch<K, true>(a, cw, ng, lds, st) : idwt_cl_bwd_launch<K, false>(a, cw, ng, lds, st);
 }
 
-}  // namespace
-
-extern "C" int lfgc_idwt_level_cl_drop_len_f32(const float* lll, const float* hf, const float* mul_lll, float thr_lll,
-                                               const float* mul_hf, float thr_hf, const float* taps, int filter_len,
-                                               float* out_cl, int C, int channel_stride, int d0, int d1, int d2,
-                                               int t0, int t1, int t2, lfgc_stream_t stream) {
+// The two entries behind the C ABI: argument checks, then the one dispatch on the filter length.  wide_ok: the plain pair
+// does not refuse C > 32, the drop pair does (open points).
+int idwt_cl_entry(bool wide_ok, const float* lll, const float* hf, const float* mul_lll, float thr_lll, const float* mul_hf,
+                  float thr_hf, const float* taps, int filter_len, float* out_cl, int C, int channel_stride,
+                  int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
     const int rc = check_cl(lll, hf, out_cl, out_cl, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
     if (rc != LFGC_OK) return rc;
-    if (C > 32) return LFGC_E_UNSUPPORTED;             // channel-first DROP level + lfgc_grid_layout_f32
+    if (C > 32 && !wide_ok) return LFGC_E_UNSUPPORTED;             // channel-first DROP level + lfgc_grid_layout_f32
     const ClDropFwd dr = {mul_lll, mul_hf, thr_lll, thr_hf};
     return filter_len == 2 ? idwt_cl<1>(lll, hf, dr, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
                            : idwt_cl<2>(lll, hf, dr, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
 }
 
-extern "C" int lfgc_idwt_level_cl_drop_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len,
-                                                   const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
-                                                   float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
-                                                   const float* const* penalty_grads, int C, int channel_stride,
-                                                   int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
+int idwt_cl_bwd_entry(bool wide_ok, const float* d_out_cl, const float* taps, int filter_len, const float* lll, const float* hf,
+                      const float* mul_lll, const float* mul_hf, float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                      const float* const* penalty_grads, int C, int channel_stride, int d0, int d1, int d2,
+                      int t0, int t1, int t2, lfgc_stream_t stream) {
     ClDropBwd dr = {lll, hf, mul_lll, mul_hf, d_mul_lll, d_mul_hf, {nullptr, nullptr, nullptr, nullptr}};
     if (penalty_grads) for (int i = 0; i < 4; ++i) dr.pg[i] = penalty_grads[i];
     if (!d_out_cl || !d_lll || !d_hf) return LFGC_E_NULL;
@@ -778,19 +763,35 @@ extern "C" int lfgc_idwt_level_cl_drop_bwd_len_f32(const float* d_out_cl, const 
     if ((dr.pg[0] && !lll) || (dr.pg[1] && !hf) || (dr.pg[2] && !d_mul_lll) || (dr.pg[3] && !d_mul_hf)) return LFGC_E_NULL;
     const int rc = check_cl(d_out_cl, d_lll, d_hf, d_hf, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
     if (rc != LFGC_OK) return rc;
-    if (C > 32) return LFGC_E_UNSUPPORTED;
+    if (C > 32 && !wide_ok) return LFGC_E_UNSUPPORTED;
     return filter_len == 2 ? idwt_cl_bwd<1>(d_out_cl, taps, dr, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
                            : idwt_cl_bwd<2>(d_out_cl, taps, dr, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int lfgc_idwt_level_cl_drop_len_f32(const float* lll, const float* hf, const float* mul_lll, float thr_lll,
+                                               const float* mul_hf, float thr_hf, const float* taps, int filter_len,
+                                               float* out_cl, int C, int channel_stride, int d0, int d1, int d2,
+                                               int t0, int t1, int t2, lfgc_stream_t stream) {
+    return idwt_cl_entry(false, lll, hf, mul_lll, thr_lll, mul_hf, thr_hf, taps, filter_len, out_cl, C, channel_stride,
+                         d0, d1, d2, t0, t1, t2, stream);
+}
+
+extern "C" int lfgc_idwt_level_cl_drop_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len,
+                                                   const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                                   float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                                   const float* const* penalty_grads, int C, int channel_stride,
+                                                   int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
+    return idwt_cl_bwd_entry(false, d_out_cl, taps, filter_len, lll, hf, mul_lll, mul_hf, d_lll, d_hf, d_mul_lll, d_mul_hf,
+                             penalty_grads, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_cl_len_f32(const float* lll, const float* hf, const float* taps, int filter_len, float* out_cl,
                                           int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
                                           lfgc_stream_t stream) {
-    const int rc = check_cl(lll, hf, out_cl, out_cl, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    const ClDropFwd none = {nullptr, nullptr, 0.0f, 0.0f};
-    return filter_len == 2 ? idwt_cl<1>(lll, hf, none, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
-                           : idwt_cl<2>(lll, hf, none, taps, out_cl, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+    return idwt_cl_entry(true, lll, hf, nullptr, 0.0f, nullptr, 0.0f, taps, filter_len, out_cl, C, channel_stride,
+                         d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_cl_f32(const float* lll, const float* hf, const float* taps, float* out_cl,
@@ -802,11 +803,8 @@ extern "C" int lfgc_idwt_level_cl_f32(const float* lll, const float* hf, const f
 extern "C" int lfgc_idwt_level_cl_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len, float* d_lll, float* d_hf,
                                               int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
                                               lfgc_stream_t stream) {
-    const int rc = check_cl(d_out_cl, d_lll, d_hf, d_hf, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
-    if (rc != LFGC_OK) return rc;
-    const ClDropBwd none = {};
-    return filter_len == 2 ? idwt_cl_bwd<1>(d_out_cl, taps, none, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
-                           : idwt_cl_bwd<2>(d_out_cl, taps, none, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
+    return idwt_cl_bwd_entry(true, d_out_cl, taps, filter_len, nullptr, nullptr, nullptr, nullptr, d_lll, d_hf, nullptr, nullptr,
+                             nullptr, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf,

@@ -145,48 +145,176 @@ def filter_taps(filt: torch.Tensor):
     return taps
 
 
+_E_UNSUPPORTED = -3
+_NAN = float('nan')
+
+
+def _thr(v) -> float:
+    return _NAN if v is None else float(v)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _cl_level_ok(C: int, d: Sequence[int], t: Sequence[int], taps, L: int = 4) -> bool:
+    """Shapes the channel-last last-level kernels take (lfgc.h: lfgc_idwt_level_cl_f32): separable bank of 2 or 4 taps,
+    C <= 32, arrays below 2^30 bytes.  Anything else composes the channel-first level with the layout conversion."""
+    if taps is None or L not in (2, 4) or C > 32 or os.environ.get('LFGC_CL_LEVEL', '1') == '0':
+        return False
+    cs = grid_channel_stride(C)
+    return t[0] * t[1] * t[2] * cs * 4 < (1 << 30) and d[0] * d[1] * d[2] * 7 * C * 4 < (1 << 30)
+
+
+def _level_shapes(C: int, d: Sequence[int]) -> dict:
+    d = tuple(int(v) for v in d)
+    return {'lll': (C,) + d, 'hf': (C, 7) + d, 'mul_l': d, 'mul_h': (7,) + d}
+
+
+def _synthesis(lll, hf, filter_rev, target, mul_l=None, thr_l=None, mul_h=None, thr_h=None, channel_last=False):
+    """One IDWT level, every variant: lll (C,d0,d1,d2), hf (C,7,d0,d1,d2), optional drop factors mul_l (d0,d1,d2) /
+    mul_h (7,d0,d1,d2) with their thresholds (include/lfgc.h) -> (C,t0,t1,t2), or with channel_last the sampler's
+    (t0,t1,t2,Cs) grid.  The kernels take raw addresses: every tensor becomes contiguous fp32 of exactly the level's
+    shape here.  Shapes the channel-last kernels do not take (_cl_level_ok) run channel-first behind to_channel_last."""
+    _require_hip(lll, hf, filter_rev, mul_l, mul_h)
+    taps = filter_taps(filter_rev)
+    L = filter_length(filter_rev)
+    C, d0, d1, d2 = lll.shape
+    shapes = _level_shapes(C, (d0, d1, d2))
+    if tuple(hf.shape) != shapes['hf']:
+        raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
+    if mul_l is not None and tuple(mul_l.shape) != shapes['mul_l']:
+        raise ValueError('low-band drop factor %s does not match %s' % (tuple(mul_l.shape), shapes['mul_l']))
+    if mul_h is not None and tuple(mul_h.shape) != shapes['mul_h']:
+        raise ValueError('detail drop factor %s does not match %s' % (tuple(mul_h.shape), shapes['mul_h']))
+    lll, hf = _f32c(lll), _f32c(hf)
+    mul_l = _f32c(mul_l) if mul_l is not None else None
+    mul_h = _f32c(mul_h) if mul_h is not None else None
+    t = [int(v) for v in target]
+    if channel_last and _cl_level_ok(C, (d0, d1, d2), t, taps, L):
+        cs = grid_channel_stride(C)
+        out = torch.empty((t[0], t[1], t[2], cs), dtype=torch.float32, device=lll.device)
+        check(_lib.load().lfgc_idwt_level_cl_drop_len_f32(
+            lll.data_ptr(), hf.data_ptr(), _ptr(mul_l), _thr(thr_l), _ptr(mul_h), _thr(thr_h), taps, L, out.data_ptr(),
+            C, cs, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_drop_len_f32')
+        return out
+    filter_rev = _f32c(filter_rev)
+    out = torch.empty((C, t[0], t[1], t[2]), dtype=torch.float32, device=lll.device)
+    check(_lib.load().lfgc_idwt_level_drop_len_f32(
+        lll.data_ptr(), hf.data_ptr(), _ptr(mul_l), _thr(thr_l), _ptr(mul_h), _thr(thr_h), filter_rev.data_ptr(), taps, L,
+        out.data_ptr(), C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_len_f32')
+    return to_channel_last(out) if channel_last else out
+
+
+def _adjoint(d_out, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs, channel_last):
+    """Adjoint of _synthesis -> (d_lll, d_hf, d_mul_l or None, d_mul_h or None).  d_out (C,t0,t1,t2), or with
+    channel_last (t0,t1,t2,Cs) and C given.  lll / hf / mul_l / mul_h: the forward's inputs as far as the factor and
+    penalty gradients need them, else None.  want_dml / want_dmh: False, True (a zero tensor is allocated) or a
+    ZERO-FILLED tensor of the factor's shape to accumulate into.  penalty_ptrs: None or 4 device addresses (0 = none) of
+    the upstream gradients of [sum lll^2, sum hf^2, sum |mul_l|, sum |mul_h|] whose own gradients the kernel folds in
+    (include/lfgc.h)."""
+    _require_hip(d_out, filter_rev, lll, hf, mul_l, mul_h)
+    taps = filter_taps(filter_rev)
+    L = filter_length(filter_rev)
+    d = [int(v) for v in d]
+    if channel_last:
+        t0, t1, t2, cs = d_out.shape
+    else:
+        C, t0, t1, t2 = d_out.shape
+    # the kernels take raw addresses: contiguous fp32 of exactly the level's shapes
+    shapes = _level_shapes(C, d)
+    given = {'lll': lll, 'hf': hf, 'mul_l': mul_l, 'mul_h': mul_h}
+    for name, x in given.items():
+        if x is not None:
+            if tuple(x.shape) != shapes[name]:
+                raise ValueError('%s %s does not match the level %s' % (name, tuple(x.shape), shapes[name]))
+            given[name] = _f32c(x)
+    for name, x in (('mul_l', want_dml), ('mul_h', want_dmh)):
+        if torch.is_tensor(x) and (tuple(x.shape) != shapes[name] or x.dtype != torch.float32 or not x.is_contiguous()):
+            raise ValueError('gradient buffer of %s must be contiguous fp32 of shape %s' % (name, shapes[name]))
+    use_cl = channel_last and _cl_level_ok(C, d, (t0, t1, t2), taps, L)
+    if use_cl and cs != grid_channel_stride(C):
+        raise ValueError('gradient grid %s is not the channel-last grid of %d channels' % (tuple(d_out.shape), C))
+    d_out = _f32c(to_channel_first(d_out, C) if (channel_last and not use_cl) else d_out)
+    dev = d_out.device
+    d_lll = torch.empty(shapes['lll'], dtype=torch.float32, device=dev)
+    d_hf = torch.empty(shapes['hf'], dtype=torch.float32, device=dev)
+    d_ml = want_dml if torch.is_tensor(want_dml) else (
+        torch.zeros(shapes['mul_l'], dtype=torch.float32, device=dev) if want_dml else None)
+    d_mh = want_dmh if torch.is_tensor(want_dmh) else (
+        torch.zeros(shapes['mul_h'], dtype=torch.float32, device=dev) if want_dmh else None)
+    pen, _keep = (None, None) if penalty_ptrs is None else _lib.ptr_array([int(v) for v in penalty_ptrs])
+    operands = (_ptr(given['lll']), _ptr(given['hf']), _ptr(given['mul_l']), _ptr(given['mul_h']), d_lll.data_ptr(),
+                d_hf.data_ptr(), _ptr(d_ml), _ptr(d_mh), pen, C)
+    if use_cl:
+        check(_lib.load().lfgc_idwt_level_cl_drop_bwd_len_f32(
+            d_out.data_ptr(), taps, L, *operands, cs, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
+            'lfgc_idwt_level_cl_drop_bwd_len_f32')
+    else:
+        filter_rev = _f32c(filter_rev)
+        check(_lib.load().lfgc_idwt_level_drop_bwd_len_f32(
+            d_out.data_ptr(), filter_rev.data_ptr(), taps, L, *operands, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
+            'lfgc_idwt_level_drop_bwd_len_f32')
+    return d_lll, d_hf, d_ml, d_mh
+
+
 @_on_device
 def idwt_level(lll: torch.Tensor, hf: torch.Tensor, filter_rev: torch.Tensor, target: Sequence[int]) -> torch.Tensor:
     """lll (C,d0,d1,d2), hf (C,7,d0,d1,d2) -> (C,t0,t1,t2)."""
-    _require_hip(lll, hf, filter_rev)
-    taps = filter_taps(filter_rev)
-    lll, hf, filter_rev = _f32c(lll), _f32c(hf), _f32c(filter_rev)
-    C, d0, d1, d2 = lll.shape
-    if tuple(hf.shape) != (C, 7, d0, d1, d2):
-        raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
-    t = [int(v) for v in target]
-    out = torch.empty((C, t[0], t[1], t[2]), dtype=torch.float32, device=lll.device)
-    L = filter_length(filter_rev)
-    if L == 4:
-        check(_lib.load().lfgc_idwt_level_f32(lll.data_ptr(), hf.data_ptr(), filter_rev.data_ptr(), taps, out.data_ptr(),
-                                              C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_f32')
-    else:
-        check(_lib.load().lfgc_idwt_level_len_f32(lll.data_ptr(), hf.data_ptr(), filter_rev.data_ptr(), taps, L,
-                                                  out.data_ptr(), C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)),
-              'lfgc_idwt_level_len_f32')
-    return out
+    return _synthesis(lll, hf, filter_rev, target)
 
 
 @_on_device
 def idwt_level_bwd(d_out: torch.Tensor, filter_rev: torch.Tensor, d: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
     """d_out (C,t0,t1,t2) -> (d_lll (C,d0,d1,d2), d_hf (C,7,d0,d1,d2))."""
-    _require_hip(d_out, filter_rev)
-    taps = filter_taps(filter_rev)
-    d_out, filter_rev = _f32c(d_out), _f32c(filter_rev)
-    C, t0, t1, t2 = d_out.shape
-    d = [int(v) for v in d]
-    d_lll = torch.empty((C, d[0], d[1], d[2]), dtype=torch.float32, device=d_out.device)
-    d_hf = torch.empty((C, 7, d[0], d[1], d[2]), dtype=torch.float32, device=d_out.device)
-    L = filter_length(filter_rev)
-    if L == 4:
-        check(_lib.load().lfgc_idwt_level_bwd_f32(d_out.data_ptr(), filter_rev.data_ptr(), taps, d_lll.data_ptr(),
-                                                  d_hf.data_ptr(), C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-              'lfgc_idwt_level_bwd_f32')
-    else:
-        check(_lib.load().lfgc_idwt_level_bwd_len_f32(d_out.data_ptr(), filter_rev.data_ptr(), taps, L, d_lll.data_ptr(),
-                                                      d_hf.data_ptr(), C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-              'lfgc_idwt_level_bwd_len_f32')
-    return d_lll, d_hf
+    return _adjoint(d_out, None, filter_rev, None, None, None, None, False, False, d, None, False)[:2]
+
+
+@_on_device
+def idwt_level_cl(lll: torch.Tensor, hf: torch.Tensor, filter_rev: torch.Tensor, target: Sequence[int]) -> torch.Tensor:
+    """lll (C,d0,d1,d2), hf (C,7,d0,d1,d2) -> (t0,t1,t2,Cs) channel-last, pad channels zero: the last level of the
+    decode and the layout conversion in one kernel (falls back to the two-kernel form for shapes it does not take)."""
+    return _synthesis(lll, hf, filter_rev, target, channel_last=True)
+
+
+@_on_device
+def idwt_level_cl_bwd(d_out_cl: torch.Tensor, C: int, filter_rev: torch.Tensor,
+                      d: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """d_out_cl (t0,t1,t2,Cs) -> (d_lll (C,d0,d1,d2), d_hf (C,7,d0,d1,d2)): adjoint of idwt_level_cl."""
+    return _adjoint(d_out_cl, C, filter_rev, None, None, None, None, False, False, d, None, True)[:2]
+
+
+# The pruning ("drop") layers fused into the level (SURVEY.md section 8, row f3)
+
+@_on_device
+def idwt_level_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> torch.Tensor:
+    """One IDWT level with the drop factors of its inputs folded in: mul_l (d0,d1,d2) / mul_h (7,d0,d1,d2) or None;
+    thr None = plain product, a float = masked straight-through rule (see include/lfgc.h)."""
+    return _synthesis(lll, hf, filter_rev, target, mul_l, thr_l, mul_h, thr_h)
+
+
+@_on_device
+def idwt_level_drop_bwd(d_out, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs=None):
+    """Adjoint of idwt_level_drop -> (d_lll, d_hf, d_mul_l or None, d_mul_h or None).  want_dml / want_dmh: False, True
+    (a zero tensor is allocated) or a ZERO-FILLED tensor of the factor's shape to accumulate into.  penalty_ptrs: None or
+    4 device addresses (0 = none) of the upstream gradients of [sum lll^2, sum hf^2, sum |mul_l|, sum |mul_h|] whose own
+    gradients the kernel folds in (include/lfgc.h)."""
+    return _adjoint(d_out, None, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs, False)
+
+
+@_on_device
+def idwt_level_cl_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> torch.Tensor:
+    """idwt_level_drop writing the sampler's channel-last grid (t0,t1,t2,Cs), pad channels zero: the last level of a
+    decode with drop layers and the layout conversion in one kernel (falls back to the two-kernel form for shapes the
+    channel-last kernels do not take, see _cl_level_ok)."""
+    return _synthesis(lll, hf, filter_rev, target, mul_l, thr_l, mul_h, thr_h, channel_last=True)
+
+
+@_on_device
+def idwt_level_cl_drop_bwd(d_out_cl, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs=None):
+    """Adjoint of idwt_level_cl_drop: d_out_cl (t0,t1,t2,Cs) -> (d_lll, d_hf, d_mul_l or None, d_mul_h or None), the
+    arguments of idwt_level_drop_bwd (falls back to it behind the layout conversion like idwt_level_cl_drop)."""
+    return _adjoint(d_out_cl, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs, True)
 
 
 @_on_device
@@ -231,276 +359,9 @@ def dwt_level(data: torch.Tensor, filter_fwd: torch.Tensor) -> torch.Tensor:
     L = filter_length(filter_fwd)
     d = dwt_out_shape((n0, n1, n2), L)
     out = torch.empty((C, 8, d[0], d[1], d[2]), dtype=torch.float32, device=data.device)
-    if L == 4:
-        check(_lib.load().lfgc_dwt_level_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, out.data_ptr(), C, n0, n1, n2,
-                                             _stream(data)), 'lfgc_dwt_level_f32')
-    else:
-        check(_lib.load().lfgc_dwt_level_len_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, L, out.data_ptr(), C, n0, n1,
-                                                 n2, _stream(data)), 'lfgc_dwt_level_len_f32')
+    check(_lib.load().lfgc_dwt_level_len_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, L, out.data_ptr(), C, n0, n1, n2,
+                                             _stream(data)), 'lfgc_dwt_level_len_f32')
     return out
-
-
-_E_UNSUPPORTED = -3
-
-
-def _cl_level_ok(C: int, d: Sequence[int], t: Sequence[int], taps, L: int = 4) -> bool:
-    """Shapes the channel-last last-level kernels take (lfgc.h: lfgc_idwt_level_cl_f32): separable bank of 2 or 4 taps,
-    C <= 32, arrays below 2^30 bytes.  Anything else composes the channel-first level with the layout conversion."""
-    if taps is None or L not in (2, 4) or C > 32 or os.environ.get('LFGC_CL_LEVEL', '1') == '0':
-        return False
-    cs = grid_channel_stride(C)
-    return t[0] * t[1] * t[2] * cs * 4 < (1 << 30) and d[0] * d[1] * d[2] * 7 * C * 4 < (1 << 30)
-
-
-@_on_device
-def idwt_level_cl(lll: torch.Tensor, hf: torch.Tensor, filter_rev: torch.Tensor, target: Sequence[int]) -> torch.Tensor:
-    """lll (C,d0,d1,d2), hf (C,7,d0,d1,d2) -> (t0,t1,t2,Cs) channel-last, pad channels zero: the last level of the
-    decode and the layout conversion in one kernel (falls back to the two-kernel form for shapes it does not take)."""
-    _require_hip(lll, hf, filter_rev)
-    taps = filter_taps(filter_rev)
-    C, d0, d1, d2 = lll.shape
-    t = [int(v) for v in target]
-    L = filter_length(filter_rev)
-    if not _cl_level_ok(C, (d0, d1, d2), t, taps, L):
-        return to_channel_last(idwt_level(lll, hf, filter_rev, target))
-    lll, hf = _f32c(lll), _f32c(hf)
-    if tuple(hf.shape) != (C, 7, d0, d1, d2):
-        raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
-    cs = grid_channel_stride(C)
-    out = torch.empty((t[0], t[1], t[2], cs), dtype=torch.float32, device=lll.device)
-    if L == 4:
-        check(_lib.load().lfgc_idwt_level_cl_f32(lll.data_ptr(), hf.data_ptr(), taps, out.data_ptr(), C, cs, d0, d1, d2,
-                                                 t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_f32')
-    else:
-        check(_lib.load().lfgc_idwt_level_cl_len_f32(lll.data_ptr(), hf.data_ptr(), taps, L, out.data_ptr(), C, cs, d0, d1,
-                                                     d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_len_f32')
-    return out
-
-
-@_on_device
-def idwt_level_cl_bwd(d_out_cl: torch.Tensor, C: int, filter_rev: torch.Tensor,
-                      d: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
-    """d_out_cl (t0,t1,t2,Cs) -> (d_lll (C,d0,d1,d2), d_hf (C,7,d0,d1,d2)): adjoint of idwt_level_cl."""
-    _require_hip(d_out_cl, filter_rev)
-    taps = filter_taps(filter_rev)
-    d = [int(v) for v in d]
-    t0, t1, t2, cs = d_out_cl.shape
-    L = filter_length(filter_rev)
-    if not _cl_level_ok(C, d, (t0, t1, t2), taps, L):
-        return idwt_level_bwd(to_channel_first(d_out_cl, C), filter_rev, d)
-    d_out_cl = _f32c(d_out_cl)
-    d_lll = torch.empty((C, d[0], d[1], d[2]), dtype=torch.float32, device=d_out_cl.device)
-    d_hf = torch.empty((C, 7, d[0], d[1], d[2]), dtype=torch.float32, device=d_out_cl.device)
-    if L == 4:
-        check(_lib.load().lfgc_idwt_level_cl_bwd_f32(d_out_cl.data_ptr(), taps, d_lll.data_ptr(), d_hf.data_ptr(), C, cs,
-                                                     d[0], d[1], d[2], t0, t1, t2, _stream(d_out_cl)),
-              'lfgc_idwt_level_cl_bwd_f32')
-    else:
-        check(_lib.load().lfgc_idwt_level_cl_bwd_len_f32(d_out_cl.data_ptr(), taps, L, d_lll.data_ptr(), d_hf.data_ptr(),
-                                                         C, cs, d[0], d[1], d[2], t0, t1, t2, _stream(d_out_cl)),
-              'lfgc_idwt_level_cl_bwd_len_f32')
-    return d_lll, d_hf
-
-
-def decode_levels(coeffs: Sequence[torch.Tensor], shape_array, filter_rev: torch.Tensor,
-                  channel_last: bool) -> torch.Tensor:
-    """All IDWT levels (model/Feature_Grid_Model.py:102-108, drop layers already applied by the caller);
-    channel_last: the last level writes the sampler's layout directly."""
-    restored = coeffs[0]          # grids smaller than 6 voxels have no wavelet level at all (dwt_max_level = 0)
-    n = len(coeffs) - 1
-    for k, (hf, shape) in enumerate(zip(coeffs[1:], shape_array)):
-        if channel_last and k == n - 1:
-            return idwt_level_cl(restored, hf, filter_rev, shape)
-        restored = idwt_level(restored, hf, filter_rev, shape)
-    return to_channel_last(restored) if channel_last else restored
-
-
-class DecodeVolumeFn(torch.autograd.Function):
-    """decode_volume() as one autograd node: IDWT chain forward, adjoint chain backward."""
-
-    @staticmethod
-    def forward(ctx, filter_rev, shape_array, channel_last, *coeffs):
-        ctx.filter_rev = filter_rev
-        ctx.shape_array = [tuple(int(v) for v in s) for s in shape_array]
-        ctx.channel_last = bool(channel_last)
-        ctx.dims = [tuple(c.shape) for c in coeffs]
-        with torch.no_grad():
-            out = decode_levels([c.detach() for c in coeffs], ctx.shape_array, filter_rev, ctx.channel_last)
-            # zero levels and channel-first: the output would alias the parameter; hand autograd a fresh tensor
-            return out.clone() if out.data_ptr() == coeffs[0].data_ptr() else out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_out):
-        C = ctx.dims[0][0]
-        n_levels = len(ctx.dims) - 1
-        grads = [None] * len(ctx.dims)
-        if ctx.channel_last and n_levels == 0:
-            d_out = to_channel_first(d_out, C)
-        g = d_out
-        for lvl in range(n_levels, 0, -1):
-            if ctx.channel_last and lvl == n_levels:
-                g, d_hf = idwt_level_cl_bwd(g, C, ctx.filter_rev, ctx.dims[lvl][2:])
-            else:
-                g, d_hf = idwt_level_bwd(g, ctx.filter_rev, ctx.dims[lvl][2:])
-            grads[lvl] = d_hf
-        grads[0] = g
-        return (None, None, None) + tuple(grads)
-
-
-# ---- pruning ("drop") layers fused into the decode (SURVEY.md section 8, row f3) --------------------------------
-
-_NAN = float('nan')
-
-
-def _thr(v) -> float:
-    return _NAN if v is None else float(v)
-
-
-@_on_device
-def idwt_level_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> torch.Tensor:
-    """One IDWT level with the drop factors of its inputs folded in: mul_l (d0,d1,d2) / mul_h (7,d0,d1,d2) or None;
-    thr None = plain product, a float = masked straight-through rule (see include/lfgc.h)."""
-    _require_hip(lll, hf, filter_rev, mul_l, mul_h)
-    taps = filter_taps(filter_rev)
-    lll, hf, filter_rev = _f32c(lll), _f32c(hf), _f32c(filter_rev)
-    C, d0, d1, d2 = lll.shape
-    if tuple(hf.shape) != (C, 7, d0, d1, d2):
-        raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
-    if mul_l is not None:
-        mul_l = _f32c(mul_l)
-        if tuple(mul_l.shape) != (d0, d1, d2):
-            raise ValueError('low-band drop factor %s does not match %s' % (tuple(mul_l.shape), (d0, d1, d2)))
-    if mul_h is not None:
-        mul_h = _f32c(mul_h)
-        if tuple(mul_h.shape) != (7, d0, d1, d2):
-            raise ValueError('detail drop factor %s does not match %s' % (tuple(mul_h.shape), (7, d0, d1, d2)))
-    t = [int(v) for v in target]
-    out = torch.empty((C, t[0], t[1], t[2]), dtype=torch.float32, device=lll.device)
-    ml = mul_l.data_ptr() if mul_l is not None else None
-    mh = mul_h.data_ptr() if mul_h is not None else None
-    L = filter_length(filter_rev)
-    if L == 4:
-        check(_lib.load().lfgc_idwt_level_drop_f32(
-            lll.data_ptr(), hf.data_ptr(), ml, _thr(thr_l), mh, _thr(thr_h), filter_rev.data_ptr(), taps, out.data_ptr(),
-            C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_f32')
-    else:
-        check(_lib.load().lfgc_idwt_level_drop_len_f32(
-            lll.data_ptr(), hf.data_ptr(), ml, _thr(thr_l), mh, _thr(thr_h), filter_rev.data_ptr(), taps, L,
-            out.data_ptr(), C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_len_f32')
-    return out
-
-
-@_on_device
-def idwt_level_drop_bwd(d_out, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs=None):
-    """Adjoint of idwt_level_drop -> (d_lll, d_hf, d_mul_l or None, d_mul_h or None).  want_dml / want_dmh: False, True
-    (a zero tensor is allocated) or a ZERO-FILLED tensor of the factor's shape to accumulate into.  penalty_ptrs: None or
-    4 device addresses (0 = none) of the upstream gradients of [sum lll^2, sum hf^2, sum |mul_l|, sum |mul_h|] whose own
-    gradients the kernel folds in (include/lfgc.h)."""
-    _require_hip(d_out, filter_rev)
-    taps = filter_taps(filter_rev)
-    d_out, filter_rev = _f32c(d_out), _f32c(filter_rev)
-    C, t0, t1, t2 = d_out.shape
-    d = [int(v) for v in d]
-    dev = d_out.device
-    d_lll = torch.empty((C, d[0], d[1], d[2]), dtype=torch.float32, device=dev)
-    d_hf = torch.empty((C, 7, d[0], d[1], d[2]), dtype=torch.float32, device=dev)
-    d_ml = want_dml if torch.is_tensor(want_dml) else (
-        torch.zeros((d[0], d[1], d[2]), dtype=torch.float32, device=dev) if want_dml else None)
-    d_mh = want_dmh if torch.is_tensor(want_dmh) else (
-        torch.zeros((7, d[0], d[1], d[2]), dtype=torch.float32, device=dev) if want_dmh else None)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    pen, _keep = (None, None) if penalty_ptrs is None else _lib.ptr_array([int(v) for v in penalty_ptrs])
-    L = filter_length(filter_rev)
-    if L == 4:
-        check(_lib.load().lfgc_idwt_level_drop_bwd_f32(
-            d_out.data_ptr(), filter_rev.data_ptr(), taps, ptr(lll), ptr(hf), ptr(mul_l), ptr(mul_h), d_lll.data_ptr(),
-            d_hf.data_ptr(), ptr(d_ml), ptr(d_mh), pen, C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-            'lfgc_idwt_level_drop_bwd_f32')
-    else:
-        check(_lib.load().lfgc_idwt_level_drop_bwd_len_f32(
-            d_out.data_ptr(), filter_rev.data_ptr(), taps, L, ptr(lll), ptr(hf), ptr(mul_l), ptr(mul_h), d_lll.data_ptr(),
-            d_hf.data_ptr(), ptr(d_ml), ptr(d_mh), pen, C, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-            'lfgc_idwt_level_drop_bwd_len_f32')
-    return d_lll, d_hf, d_ml, d_mh
-
-
-@_on_device
-def idwt_level_cl_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> torch.Tensor:
-    """idwt_level_drop writing the sampler's channel-last grid (t0,t1,t2,Cs), pad channels zero: the last level of a
-    decode with drop layers and the layout conversion in one kernel (falls back to the two-kernel form for shapes the
-    channel-last kernels do not take, see _cl_level_ok)."""
-    _require_hip(lll, hf, filter_rev, mul_l, mul_h)
-    taps = filter_taps(filter_rev)
-    C, d0, d1, d2 = lll.shape
-    t = [int(v) for v in target]
-    L = filter_length(filter_rev)
-    if not _cl_level_ok(C, (d0, d1, d2), t, taps, L):
-        return to_channel_last(idwt_level_drop(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target))
-    lll, hf = _f32c(lll), _f32c(hf)
-    if tuple(hf.shape) != (C, 7, d0, d1, d2):
-        raise ValueError('detail bands %s do not match low band %s' % (tuple(hf.shape), tuple(lll.shape)))
-    if mul_l is not None:
-        mul_l = _f32c(mul_l)
-        if tuple(mul_l.shape) != (d0, d1, d2):
-            raise ValueError('low-band drop factor %s does not match %s' % (tuple(mul_l.shape), (d0, d1, d2)))
-    if mul_h is not None:
-        mul_h = _f32c(mul_h)
-        if tuple(mul_h.shape) != (7, d0, d1, d2):
-            raise ValueError('detail drop factor %s does not match %s' % (tuple(mul_h.shape), (7, d0, d1, d2)))
-    cs = grid_channel_stride(C)
-    out = torch.empty((t[0], t[1], t[2], cs), dtype=torch.float32, device=lll.device)
-    ml = mul_l.data_ptr() if mul_l is not None else None
-    mh = mul_h.data_ptr() if mul_h is not None else None
-    check(_lib.load().lfgc_idwt_level_cl_drop_len_f32(
-        lll.data_ptr(), hf.data_ptr(), ml, _thr(thr_l), mh, _thr(thr_h), taps, L, out.data_ptr(), C, cs, d0, d1, d2,
-        t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_cl_drop_len_f32')
-    return out
-
-
-@_on_device
-def idwt_level_cl_drop_bwd(d_out_cl, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs=None):
-    """Adjoint of idwt_level_cl_drop: d_out_cl (t0,t1,t2,Cs) -> (d_lll, d_hf, d_mul_l or None, d_mul_h or None), the
-    arguments of idwt_level_drop_bwd (falls back to it behind the layout conversion like idwt_level_cl_drop)."""
-    _require_hip(d_out_cl, filter_rev)
-    taps = filter_taps(filter_rev)
-    d = [int(v) for v in d]
-    t0, t1, t2, cs = d_out_cl.shape
-    L = filter_length(filter_rev)
-    if not _cl_level_ok(C, d, (t0, t1, t2), taps, L):
-        return idwt_level_drop_bwd(to_channel_first(d_out_cl, C), filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d,
-                                   penalty_ptrs)
-    d_out_cl = _f32c(d_out_cl)
-    dev = d_out_cl.device
-    if cs != grid_channel_stride(C):
-        raise ValueError('gradient grid %s is not the channel-last grid of %d channels' % (tuple(d_out_cl.shape), C))
-    # the kernels take raw addresses: contiguous fp32 of exactly the level's shapes
-    shapes = {'lll': (C, d[0], d[1], d[2]), 'hf': (C, 7, d[0], d[1], d[2]), 'mul_l': (d[0], d[1], d[2]),
-              'mul_h': (7, d[0], d[1], d[2])}
-    given = {'lll': lll, 'hf': hf, 'mul_l': mul_l, 'mul_h': mul_h}
-    for name, x in given.items():
-        if x is not None:
-            _require_hip(x)
-            if tuple(x.shape) != shapes[name]:
-                raise ValueError('%s %s does not match the level %s' % (name, tuple(x.shape), shapes[name]))
-            given[name] = _f32c(x)
-    lll, hf, mul_l, mul_h = given['lll'], given['hf'], given['mul_l'], given['mul_h']
-    for name, x in (('mul_l', want_dml), ('mul_h', want_dmh)):
-        if torch.is_tensor(x) and (tuple(x.shape) != shapes[name] or x.dtype != torch.float32 or not x.is_contiguous()):
-            raise ValueError('gradient buffer of %s must be contiguous fp32 of shape %s' % (name, shapes[name]))
-    d_lll = torch.empty((C, d[0], d[1], d[2]), dtype=torch.float32, device=dev)
-    d_hf = torch.empty((C, 7, d[0], d[1], d[2]), dtype=torch.float32, device=dev)
-    d_ml = want_dml if torch.is_tensor(want_dml) else (
-        torch.zeros((d[0], d[1], d[2]), dtype=torch.float32, device=dev) if want_dml else None)
-    d_mh = want_dmh if torch.is_tensor(want_dmh) else (
-        torch.zeros((7, d[0], d[1], d[2]), dtype=torch.float32, device=dev) if want_dmh else None)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    pen, _keep = (None, None) if penalty_ptrs is None else _lib.ptr_array([int(v) for v in penalty_ptrs])
-    check(_lib.load().lfgc_idwt_level_cl_drop_bwd_len_f32(
-        d_out_cl.data_ptr(), taps, L, ptr(lll), ptr(hf), ptr(mul_l), ptr(mul_h), d_lll.data_ptr(), d_hf.data_ptr(),
-        ptr(d_ml), ptr(d_mh), pen, C, cs, d[0], d[1], d[2], t0, t1, t2, _stream(d_out_cl)),
-        'lfgc_idwt_level_cl_drop_bwd_len_f32')
-    return d_lll, d_hf, d_ml, d_mh
 
 
 @_on_device
@@ -540,23 +401,63 @@ class DropApplyFn(torch.autograd.Function):
         return d_x, d_m, None
 
 
+@_on_device
 def decode_levels_drop(coeffs, factors, thresholds, shape_array, filter_rev, channel_last: bool) -> torch.Tensor:
     """decode_volume() with drop factors (model/Feature_Grid_Model.py:102-108): factors[i] / thresholds[i] belong
     to coeffs[i]; None = that tensor passes unchanged.  channel_last: the last level writes the sampler's layout directly
     (a one-level model's last level is also its first: it takes factors[0] as the low band's factor)."""
-    if len(coeffs) == 1:
+    n = len(coeffs) - 1            # grids smaller than 6 voxels have no wavelet level at all (dwt_max_level = 0)
+    if n == 0:
         restored = coeffs[0] if factors[0] is None else drop_apply(coeffs[0], factors[0], thresholds[0])
-    else:
-        restored, mul_l, thr_l = coeffs[0], factors[0], thresholds[0]
-        n = len(coeffs) - 1
-        for k in range(1, len(coeffs)):
-            if channel_last and k == n:
-                return idwt_level_cl_drop(restored, coeffs[k], mul_l, thr_l, factors[k], thresholds[k], filter_rev,
-                                          shape_array[k - 1])
-            restored = idwt_level_drop(restored, coeffs[k], mul_l, thr_l, factors[k], thresholds[k], filter_rev,
-                                       shape_array[k - 1])
-            mul_l, thr_l = None, None
-    return to_channel_last(restored) if channel_last else restored
+        return to_channel_last(restored) if channel_last else restored
+    restored, mul_l, thr_l = coeffs[0], factors[0], thresholds[0]
+    for k in range(1, n + 1):
+        restored = _synthesis(restored, coeffs[k], filter_rev, shape_array[k - 1], mul_l, thr_l, factors[k], thresholds[k],
+                              channel_last=channel_last and k == n)
+        mul_l, thr_l = None, None
+    return restored
+
+
+def decode_levels(coeffs: Sequence[torch.Tensor], shape_array, filter_rev: torch.Tensor,
+                  channel_last: bool) -> torch.Tensor:
+    """All IDWT levels (model/Feature_Grid_Model.py:102-108, drop layers already applied by the caller);
+    channel_last: the last level writes the sampler's layout directly."""
+    none = [None] * len(coeffs)
+    return decode_levels_drop(coeffs, none, none, shape_array, filter_rev, channel_last)
+
+
+def _decode_forward(ctx, filter_rev, shape_array, channel_last, thresholds, coeffs, factors, l1_flags):
+    """Context set-up and decode shared by the three decode nodes -> (grid, detached coeffs, detached factors)."""
+    n = len(coeffs)
+    ctx.filter_rev = filter_rev
+    ctx.shape_array = [tuple(int(v) for v in s) for s in shape_array]
+    ctx.channel_last = bool(channel_last)
+    ctx.n = n
+    ctx.dims = [tuple(c.shape) for c in coeffs]
+    ctx.want = [f is not None and f.requires_grad for f in factors]
+    ctx.has = [f is not None for f in factors]
+    ctx.l1_flags = [bool(f) and factors[i] is not None for i, f in enumerate(l1_flags)]
+    det = [c.detach() for c in coeffs]
+    fdet = [f.detach() if f is not None else None for f in factors]
+    ctx.save_for_backward(*det, *[f for f in fdet if f is not None])
+    with torch.no_grad():
+        return decode_levels_drop(det, fdet, list(thresholds), ctx.shape_array, filter_rev, ctx.channel_last), det, fdet
+
+
+class DecodeVolumeFn(torch.autograd.Function):
+    """decode_volume() as one autograd node: IDWT chain forward, adjoint chain backward."""
+
+    @staticmethod
+    def forward(ctx, filter_rev, shape_array, channel_last, *coeffs):
+        none = [None] * len(coeffs)
+        out = _decode_forward(ctx, filter_rev, shape_array, channel_last, none, coeffs, none, none)[0]
+        # zero levels and channel-first: the output would alias the parameter; hand autograd a fresh tensor
+        return out.clone() if out.data_ptr() == coeffs[0].data_ptr() else out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        return (None, None, None) + tuple(_decode_drop_backward(ctx, d_out, None)[0])
 
 
 class DecodeVolumeDropFn(torch.autograd.Function):
@@ -566,20 +467,8 @@ class DecodeVolumeDropFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, filter_rev, shape_array, channel_last, thresholds, n, *tensors):
-        coeffs, factors = tensors[:n], tensors[n:]
-        ctx.filter_rev = filter_rev
-        ctx.shape_array = [tuple(int(v) for v in s) for s in shape_array]
-        ctx.channel_last = bool(channel_last)
-        ctx.n = n
-        ctx.dims = [tuple(c.shape) for c in coeffs]
-        ctx.want = [f is not None and f.requires_grad for f in factors]
-        ctx.has = [f is not None for f in factors]
-        ctx.l1_flags = [False] * n
-        det = [c.detach() for c in coeffs]
-        fdet = [f.detach() if f is not None else None for f in factors]
-        ctx.save_for_backward(*det, *[f for f in fdet if f is not None])
-        with torch.no_grad():
-            return decode_levels_drop(det, fdet, list(thresholds), ctx.shape_array, filter_rev, ctx.channel_last)
+        return _decode_forward(ctx, filter_rev, shape_array, channel_last, thresholds, tensors[:n], tensors[n:],
+                               [False] * n)[0]
 
     @staticmethod
     @once_differentiable
@@ -588,9 +477,10 @@ class DecodeVolumeDropFn(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(d_coef) + tuple(d_fac)
 
 
+@_on_device
 def _decode_drop_backward(ctx, d_out, d_pen):
-    """Shared backward of the two decode-with-factors nodes; d_pen fp32 or None = upstream gradients of the penalty sums
-    (layout of DecodeVolumePenaltyFn) folded into the adjoint kernels."""
+    """Shared backward of the decode nodes; d_pen fp32 or None = upstream gradients of the penalty sums (layout of
+    DecodeVolumePenaltyFn) folded into the adjoint kernels."""
     n = ctx.n
     saved = list(ctx.saved_tensors)
     coeffs = saved[:n]
@@ -620,17 +510,23 @@ def _decode_drop_backward(ctx, d_out, d_pen):
         if d_pen is not None:
             pens = [l2(0) if first else 0, l2(lvl), l1(0) if first else 0, l1(lvl)]
         lll = coeffs[0] if (first and (ctx.has[0] or d_pen is not None)) else None
-        if ctx.channel_last and lvl == n - 1:
-            g, d_hf, d_ml, d_mh = idwt_level_cl_drop_bwd(g, C, ctx.filter_rev, lll, coeffs[lvl], ml, factors[lvl],
-                                                         zeroed[0] if first else False, zeroed[lvl], ctx.dims[lvl][2:], pens)
-        else:
-            g, d_hf, d_ml, d_mh = idwt_level_drop_bwd(g, ctx.filter_rev, lll, coeffs[lvl], ml, factors[lvl],
-                                                      zeroed[0] if first else False, zeroed[lvl], ctx.dims[lvl][2:], pens)
+        g, d_hf, d_ml, d_mh = _adjoint(g, C, ctx.filter_rev, lll, coeffs[lvl], ml, factors[lvl],
+                                       zeroed[0] if first else False, zeroed[lvl], ctx.dims[lvl][2:], pens,
+                                       ctx.channel_last and lvl == n - 1)
         d_coef[lvl], d_fac[lvl] = d_hf, d_mh
         if first:
             d_fac[0] = d_ml
     d_coef[0] = g
     return d_coef, d_fac
+
+
+@_on_device
+def _penalty_sums(kinds, tensors):
+    """All penalty terms in one lfgc_penalty_sums_f32 launch -> fp32 (len(kinds),)."""
+    terms, keep = _penalty_terms(kinds, tensors)
+    sums = torch.empty(len(kinds) * (1 + _lib.PENALTY_BLOCKS), dtype=torch.float64, device=keep[0][0].device)   # results + scratch
+    check(_lib.load().lfgc_penalty_sums_f32(terms, len(kinds), sums.data_ptr(), _stream(sums)), 'lfgc_penalty_sums_f32')
+    return sums[:len(kinds)].float()
 
 
 class DecodeVolumePenaltyFn(torch.autograd.Function):
@@ -641,30 +537,13 @@ class DecodeVolumePenaltyFn(torch.autograd.Function):
     factors that ARE the penalised parameter, e.g. Smallify betas."""
 
     @staticmethod
-    @_on_device
     def forward(ctx, filter_rev, shape_array, channel_last, thresholds, n, l1_flags, *tensors):
-        coeffs, factors = tensors[:n], tensors[n:]
         ctx.set_materialize_grads(False)
-        ctx.filter_rev = filter_rev
-        ctx.shape_array = [tuple(int(v) for v in s) for s in shape_array]
-        ctx.channel_last = bool(channel_last)
-        ctx.n = n
-        ctx.l1_flags = [bool(f) and factors[i] is not None for i, f in enumerate(l1_flags)]
-        ctx.dims = [tuple(c.shape) for c in coeffs]
-        ctx.want = [f is not None and f.requires_grad for f in factors]
-        ctx.has = [f is not None for f in factors]
-        det = [c.detach() for c in coeffs]
-        fdet = [f.detach() if f is not None else None for f in factors]
-        ctx.save_for_backward(*det, *[f for f in fdet if f is not None])
-        with torch.no_grad():
-            grid = decode_levels_drop(det, fdet, list(thresholds), ctx.shape_array, filter_rev, ctx.channel_last)
-            l1_idx = [i for i in range(n) if ctx.l1_flags[i]]
-            kinds = [_lib.PENALTY_L2] * n + [_lib.PENALTY_L1] * len(l1_idx)
-            terms, keep = _penalty_terms(kinds, det + [fdet[i] for i in l1_idx])
-            sums = torch.empty(len(kinds) * (1 + _lib.PENALTY_BLOCKS), dtype=torch.float64, device=grid.device)
-            check(_lib.load().lfgc_penalty_sums_f32(terms, len(kinds), sums.data_ptr(), _stream(sums)), 'lfgc_penalty_sums_f32')
-            pen = sums[:len(kinds)].float()
+        grid, det, fdet = _decode_forward(ctx, filter_rev, shape_array, channel_last, thresholds, tensors[:n],
+                                          tensors[n:], l1_flags)
+        l1_idx = [i for i in range(n) if ctx.l1_flags[i]]
         ctx.l1_pos = {i: j for j, i in enumerate(l1_idx)}
+        pen = _penalty_sums([_lib.PENALTY_L2] * n + [_lib.PENALTY_L1] * len(l1_idx), det + [fdet[i] for i in l1_idx])
         return grid, pen
 
     @staticmethod
@@ -724,16 +603,10 @@ class PenaltyFn(torch.autograd.Function):
     apply(kinds, *tensors) -> fp32 (len(kinds),); a DKL term consumes two tensors (log_thetas, log_var)."""
 
     @staticmethod
-    @_on_device
     def forward(ctx, kinds, *tensors):
-        kinds = [int(k) for k in kinds]
-        terms, keep = _penalty_terms(kinds, tensors)
-        dev = keep[0][0].device
-        sums = torch.empty(len(kinds) * (1 + _lib.PENALTY_BLOCKS), dtype=torch.float64, device=dev)   # results + scratch
-        check(_lib.load().lfgc_penalty_sums_f32(terms, len(kinds), sums.data_ptr(), _stream(sums)), 'lfgc_penalty_sums_f32')
-        ctx.kinds = kinds
+        ctx.kinds = [int(k) for k in kinds]
         ctx.save_for_backward(*[t.detach() for t in tensors])
-        return sums[:len(kinds)].float()
+        return _penalty_sums(ctx.kinds, tensors)
 
     @staticmethod
     @once_differentiable
@@ -1004,15 +877,19 @@ def codec_dequant(packed: torch.Tensor, bits: int, n: int, centres: torch.Tensor
 
 # ---- ground truth / statistics -------------------------------------------------------------------------
 
+def _float3(v):
+    """Host sequence, array or tensor of 3 numbers -> ctypes float[3]."""
+    return (ctypes.c_float * 3)(*[float(x) for x in (v.tolist() if hasattr(v, 'tolist') else v)])
+
+
 @_on_device
 def gt_interp(p: torch.Tensor, f: torch.Tensor, min_bb, max_bb, res) -> torch.Tensor:
     lib = _lib.load()
     _require_hip(p, f)
     p, f = _f32c(p), _f32c(f)
-    arr = lambda v: (ctypes.c_float * 3)(*[float(x) for x in (v.tolist() if hasattr(v, 'tolist') else v)])
     out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
     X, Y, Z = f.shape
-    check(lib.lfgc_gt_interp_f32(p.data_ptr(), f.data_ptr(), arr(min_bb), arr(max_bb), arr(res), p.shape[0], X, Y, Z,
+    check(lib.lfgc_gt_interp_f32(p.data_ptr(), f.data_ptr(), _float3(min_bb), _float3(max_bb), _float3(res), p.shape[0], X, Y, Z,
                                  out.data_ptr(), _stream(p)), 'lfgc_gt_interp_f32')
     return out
 
@@ -1031,12 +908,11 @@ class GtMseLossFn(torch.autograd.Function):
         n = pred_c.numel()
         if p.shape != (n, 3):
             raise ValueError('positions %s do not match %d predictions' % (tuple(p.shape), n))
-        arr = lambda v: (ctypes.c_float * 3)(*[float(x) for x in (v.tolist() if hasattr(v, 'tolist') else v)])
         d_pred = torch.empty_like(pred_c)
         loss = torch.empty((), dtype=torch.float32, device=pred_c.device)
         ws = torch.empty(int(lib.lfgc_gt_mse_workspace_bytes(n)) // 8, dtype=torch.float64, device=pred_c.device)
         X, Y, Z = f.shape
-        check(lib.lfgc_gt_mse_f32(p.data_ptr(), f.data_ptr(), arr(min_bb), arr(max_bb), arr(res), n, X, Y, Z,
+        check(lib.lfgc_gt_mse_f32(p.data_ptr(), f.data_ptr(), _float3(min_bb), _float3(max_bb), _float3(res), n, X, Y, Z,
                                   pred_c.data_ptr(), None, d_pred.data_ptr(), loss.data_ptr(), ws.data_ptr(),
                                   ws.numel() * 8, _stream(pred_c)), 'lfgc_gt_mse_f32')
         ctx.save_for_backward(d_pred)
@@ -1065,9 +941,8 @@ def lattice_positions(flat: torch.Tensor, res, min_idx, max_idx, scales) -> Tupl
     n = flat.numel()
     raw = torch.empty((n, 3), dtype=torch.float32, device=flat.device)
     norm = torch.empty((n, 3), dtype=torch.float32, device=flat.device)
-    f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in (v.tolist() if hasattr(v, 'tolist') else v)])
     r3 = (ctypes.c_int32 * 3)(*[int(x) for x in res])
-    check(_lib.load().lfgc_lattice_positions_f32(flat.data_ptr(), n, r3, f3(min_idx), f3(max_idx), f3(scales),
+    check(_lib.load().lfgc_lattice_positions_f32(flat.data_ptr(), n, r3, _float3(min_idx), _float3(max_idx), _float3(scales),
                                                  raw.data_ptr(), norm.data_ptr(), _stream(flat)), 'lfgc_lattice_positions_f32')
     return raw, norm
 
@@ -1085,10 +960,9 @@ def lattice_sample(state: torch.Tensor, n: int, seed: int, res, min_idx, max_idx
     raw = torch.empty((n, 3), dtype=torch.float32, device=state.device)
     norm = torch.empty((n, 3), dtype=torch.float32, device=state.device)
     flat = torch.empty(n, dtype=torch.int64, device=state.device) if want_flat else None
-    f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in (v.tolist() if hasattr(v, 'tolist') else v)])
     r3 = (ctypes.c_int32 * 3)(*[int(x) for x in res])
-    check(_lib.load().lfgc_lattice_sample_f32(int(seed) & 0xFFFFFFFFFFFFFFFF, state.data_ptr(), n, r3, f3(min_idx), f3(max_idx),
-                                              f3(scales), raw.data_ptr(), norm.data_ptr(),
+    check(_lib.load().lfgc_lattice_sample_f32(int(seed) & 0xFFFFFFFFFFFFFFFF, state.data_ptr(), n, r3, _float3(min_idx), _float3(max_idx),
+                                              _float3(scales), raw.data_ptr(), norm.data_ptr(),
                                               flat.data_ptr() if want_flat else None, _stream(state)),
           'lfgc_lattice_sample_f32')
     return (raw, norm, flat) if want_flat else (raw, norm)

@@ -358,3 +358,80 @@ def test_graph_capture_and_replay(dev, basis):
         assert np.array_equal(got_grid, want_grid), trial
         for p, a in zip(params, got):
             assert rel_err(a, p.grad.cpu().numpy()) <= 2e-5, trial
+
+
+def _strided(x):
+    """The same values with the last two axes stored transposed (not contiguous)."""
+    y = x.transpose(-1, -2).contiguous().transpose(-1, -2)
+    assert not y.is_contiguous() and torch.equal(x, y)
+    return y
+
+
+@pytest.mark.parametrize('thr', [None, 0.5])
+@pytest.mark.parametrize('channel_last', [False, True])
+@pytest.mark.parametrize('basis', ['haar', 'db2'])
+def test_decode_nodes_take_non_contiguous_inputs(dev, basis, channel_last, thr):
+    """DecodeVolumeDropFn and DecodeVolumePenaltyFn on coefficient and factor tensors that are not contiguous against the
+    same values stored contiguously: the kernels take raw addresses, so every level -- channel-first ones included --
+    must lay its operands out itself.  Two levels; with channel_last level 1 is channel-first and level 2 channel-last.
+    Grid, penalty sums (fixed-order fp64 reduction) and coefficient gradients (overwritten) are bit-equal; the factor
+    gradients are float-atomic sums over the channels: 1e-6 of the largest entry, the bound of
+    test_len_entries_bit_equal_plain_4tap for the same quantity.  The contiguous run against oracle autograd: 2e-5."""
+    from latent_feature_grid_compression_amd import ops
+    C, cs = 5, 8
+    dims, targets = [(4, 5, 4), (7, 9, 8)], [(7, 9, 8), (13, 17, 15)]
+    shape_array = [level_target(basis, dd, tt) for dd, tt in zip(dims, targets)]
+    frev = filters(basis)
+    rng = np.random.default_rng(17)
+    coeffs = [torch.from_numpy(rng.standard_normal((C,) + dims[0]).astype(np.float32))]
+    coeffs += [torch.from_numpy(rng.standard_normal((C, 7) + dd).astype(np.float32)) for dd in dims]
+    factors = [torch.from_numpy((rng.uniform(0.05, 1.0, c.shape[1:]) * rng.choice([-1.0, 1.0], c.shape[1:])).astype(np.float32))
+               for c in coeffs]
+    n = len(coeffs)
+    w_cf = torch.from_numpy(rng.standard_normal((C,) + tuple(shape_array[-1])).astype(np.float32))
+    w = w_cf
+    if channel_last:
+        w = torch.zeros(tuple(shape_array[-1]) + (cs,))
+        w[..., :C] = w_cf.permute(1, 2, 3, 0)
+    weights = torch.from_numpy(rng.uniform(0.5, 2.0, 2 * n).astype(np.float32))
+    thresholds = [thr] * n
+
+    def run(penalty, layout):
+        cs_in = [layout(c).to(dev).requires_grad_(True) for c in coeffs]
+        fs_in = [layout(f).to(dev).requires_grad_(True) for f in factors]
+        assert all(x.is_contiguous() == (layout is not _strided) for x in cs_in + fs_in)
+        if penalty:
+            grid, pen = ops.DecodeVolumePenaltyFn.apply(frev.to(dev), shape_array, channel_last, thresholds, n, [True] * n,
+                                                        *cs_in, *fs_in)
+            ((grid * w.to(dev)).sum() + (pen * weights.to(dev)).sum()).backward()
+        else:
+            grid, pen = ops.DecodeVolumeDropFn.apply(frev.to(dev), shape_array, channel_last, thresholds, n, *cs_in, *fs_in), None
+            (grid * w.to(dev)).sum().backward()
+        return (grid.detach().cpu(), None if pen is None else pen.detach().cpu(), [c.grad.cpu() for c in cs_in],
+                [f.grad.cpu() for f in fs_in])
+
+    leaves_c = [c.clone().requires_grad_(True) for c in coeffs]
+    leaves_f = [f.clone().requires_grad_(True) for f in factors]
+    restored = applied(leaves_c[0], leaves_f[0], thr)
+    for k in range(1, n):
+        b = applied(leaves_c[k], leaves_f[k], thr)
+        restored = R.wavelet_decode(torch.cat([restored.unsqueeze(0).unsqueeze(2), b.unsqueeze(0)], dim=2), shape_array[k - 1], frev)[0]
+    pens = torch.stack([D.grid_l2_penalty([c]) for c in leaves_c] + [D.l1_penalty(f) for f in leaves_f])
+    data_loss = (restored * w_cf).sum()
+
+    for penalty in (False, True):
+        loss = data_loss + (pens * weights).sum() if penalty else data_loss
+        want = torch.autograd.grad(loss, leaves_c + leaves_f, retain_graph=True)
+        grid, pen, d_c, d_f = run(penalty, lambda x: x)
+        grid_s, pen_s, d_c_s, d_f_s = run(penalty, _strided)
+        assert torch.equal(grid, grid_s), penalty
+        if penalty:
+            assert torch.equal(pen, pen_s)
+        for i in range(n):
+            assert torch.equal(d_c[i], d_c_s[i]), (penalty, 'coeff', i)
+            err = rel_err(d_f_s[i].numpy(), d_f[i].numpy())
+            print('factor', i, basis, channel_last, thr, penalty, err)
+            assert err <= 1e-6, (penalty, 'factor', i)
+            e_c, e_f = rel_err(d_c[i].numpy(), want[i].numpy()), rel_err(d_f[i].numpy(), want[n + i].numpy())
+            print('oracle', i, basis, channel_last, thr, penalty, e_c, e_f)
+            assert e_c <= 2e-5 and e_f <= 2e-5, (penalty, i)

@@ -362,3 +362,66 @@ def test_every_name_the_reference_imports_from_the_swapped_modules_exists():
         if not hasattr(ours, name):
             missing.append('%s.%s (%s)' % (mod, name, fn))
     assert not missing, missing
+
+
+def test_channel_last_level_entries_agree_on_argument_errors(built_lib):
+    """The argument-error rows of tests/test_cl_drop_host.py (all but the C > 32 ones, where the two pairs differ on
+    purpose) through every channel-last level entry: the plain `_len` pair and the drop pair with NULL factors return the
+    same code, and the 4-tap aliases the code of `_len` with 4.  Every row returns before anything is launched (dummy
+    addresses, no device work)."""
+    from latent_feature_grid_compression_amd import _lib
+    lib = _lib.load()
+    E_NULL, E_SHAPE, E_UNSUPPORTED = -1, -2, -3
+    one, nan = ctypes.c_void_p(16), float('nan')
+    taps8 = (ctypes.c_float * 16)(*[0.5] * 16)
+    ok_shape = (4, 8, 3, 3, 3, 6, 6, 6)
+    rows = []                 # (expected, pointers a b c [forward: lll hf out; adjoint: d_out d_lll d_hf], taps, L, shape)
+    for L in (2, 4):
+        for missing in range(3):              # a required pointer is missing
+            rows.append((E_NULL, [None if i == missing else one for i in range(3)], taps8, L, ok_shape))
+        rows += [(E_SHAPE, [one] * 3, taps8, L, shape) for shape in (
+            (4, 16, 3, 3, 3, 6, 6, 6), (9, 8, 3, 3, 3, 6, 6, 6),           # stride is not C rounded up to 8
+            (4, 8, 3, 3, 3, 2 * 3 + L - 1, 6, 6), (4, 8, 3, 3, 3, 6, 2 * 3 + L - 1, 6), (4, 8, 3, 3, 3, 6, 6, 0))]   # t_a
+        rows.append((E_UNSUPPORTED, [one] * 3, None, L, ok_shape))           # dense stencil
+        rows += [(E_UNSUPPORTED, [one] * 3, taps8, L, shape) for shape in (  # arrays of 2^30 bytes and more
+            (32, 32, 200, 200, 200, 400, 400, 400), (32, 32, 110, 110, 110, 6, 6, 6))]
+    rows += [(E_UNSUPPORTED, [one] * 3, taps8, L, ok_shape) for L in (0, 1, 3, 6, 8)]
+    for want, (a, b, c), taps, L, shape in rows:
+        fwd = (lib.lfgc_idwt_level_cl_len_f32(a, b, taps, L, c, *shape, None),
+               lib.lfgc_idwt_level_cl_drop_len_f32(a, b, None, nan, None, nan, taps, L, c, *shape, None))
+        bwd = (lib.lfgc_idwt_level_cl_bwd_len_f32(a, taps, L, b, c, *shape, None),
+               lib.lfgc_idwt_level_cl_drop_bwd_len_f32(a, taps, L, None, None, None, None, b, c, None, None, None, *shape, None))
+        if L == 4:
+            fwd += (lib.lfgc_idwt_level_cl_f32(a, b, taps, c, *shape, None),)
+            bwd += (lib.lfgc_idwt_level_cl_bwd_f32(a, taps, b, c, *shape, None),)
+        assert set(fwd) == {want} and set(bwd) == {want}, (want, fwd, bwd, L, shape)
+
+
+def test_public_level_and_decode_signatures():
+    """The wrappers that tests, tools and the model call by position keep the signatures they had before the level
+    wrappers were folded into one synthesis and one adjoint function."""
+    import inspect
+    from latent_feature_grid_compression_amd import ops
+    want = {
+        'idwt_level': '(lll: torch.Tensor, hf: torch.Tensor, filter_rev: torch.Tensor, target: Sequence[int]) -> torch.Tensor',
+        'idwt_level_bwd': '(d_out: torch.Tensor, filter_rev: torch.Tensor, d: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]',
+        'idwt_level_cl': '(lll: torch.Tensor, hf: torch.Tensor, filter_rev: torch.Tensor, target: Sequence[int]) -> torch.Tensor',
+        'idwt_level_cl_bwd': '(d_out_cl: torch.Tensor, C: int, filter_rev: torch.Tensor, d: Sequence[int]) '
+                             '-> Tuple[torch.Tensor, torch.Tensor]',
+        'idwt_level_drop': '(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> torch.Tensor',
+        'idwt_level_drop_bwd': '(d_out, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs=None)',
+        'idwt_level_cl_drop': '(lll, hf, mul_l, thr_l, mul_h, thr_h, filter_rev, target) -> torch.Tensor',
+        'idwt_level_cl_drop_bwd': '(d_out_cl, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs=None)',
+        'decode_levels': '(coeffs: Sequence[torch.Tensor], shape_array, filter_rev: torch.Tensor, channel_last: bool) '
+                         '-> torch.Tensor',
+        'decode_levels_drop': '(coeffs, factors, thresholds, shape_array, filter_rev, channel_last: bool) -> torch.Tensor',
+        'dwt_level': '(data: torch.Tensor, filter_fwd: torch.Tensor) -> torch.Tensor',
+        'DecodeVolumeFn.forward': '(ctx, filter_rev, shape_array, channel_last, *coeffs)',
+        'DecodeVolumeDropFn.forward': '(ctx, filter_rev, shape_array, channel_last, thresholds, n, *tensors)',
+        'DecodeVolumePenaltyFn.forward': '(ctx, filter_rev, shape_array, channel_last, thresholds, n, l1_flags, *tensors)',
+    }
+    for name, sig in want.items():
+        obj = ops
+        for part in name.split('.'):
+            obj = getattr(obj, part)
+        assert str(inspect.signature(obj)).replace("'", '') == sig, name      # annotations are kept as strings
