@@ -132,6 +132,31 @@ __device__ __forceinline__ void lfgc_split_scaled(const float* __restrict__ v, f
     }
 }
 
+// Dynamic LDS of lfgc_bwd_data_kernel in floats, in the order the kernel carves it:
+//   s_final [Wf (HP) | bf (4)] | s_inv 8 | s_ring: 2 slots, each a transposed weight image (tblk0 / tblk1) or, once the
+//   layer-0 image is consumed, the scatter staging of all `waves` waves (scatter_wave() each).
+// The host's launch selection sizes the allocation with lfgc_bwd_lds_floats; the kernel takes its slot from the same function.
+constexpr int lfgc_bwd_lds_slot(const LfgcPlan& p, int waves) {
+    const int img = p.tblk0 > p.tblk1 ? p.tblk0 : p.tblk1, sc = waves * p.scatter_wave();
+    return img > sc ? img : sc;
+}
+constexpr int lfgc_bwd_lds_floats(const LfgcPlan& p, int waves) { return p.HP + 4 + 8 + 2 * lfgc_bwd_lds_slot(p, waves); }
+
+// The blob offsets and tile strides lfgc_bwd_data_kernel spells out at run time, repeated for a given L and compared with
+// the plan's (off_img: the exact chain reads the images at off_t, the f16 chains those at off_ht).
+template <int CH, int MT, int NF>
+constexpr bool lfgc_bwd_offsets_are_the_plans(int L) {
+    constexpr LfgcPlan P = LfgcShape<CH, MT, NF>::P;
+    constexpr int HP = P.HP, KS0 = P.KS0, blk0 = P.blk0, blk1 = P.blk1, tblk0 = P.tblk0, tblk1 = P.tblk1, blkh0 = P.blkh0, blkh1 = P.blkh1;
+    const LfgcPlan q = lfgc_make_plan(CH, HP, L, NF);
+    const int off_final = blk0 + (L - 1) * blk1;
+    const int off_t = off_final + HP + 4;
+    const int off_h = off_t + tblk0 + (L - 1) * tblk1;
+    const int off_img16 = off_h + 32 + LFGC_MAX_LAYERS * HP + HP + blkh0 + (L - 1) * blkh1;
+    return off_final == q.off_final && off_t == q.off_t && off_h == q.off_h && off_img16 == q.off_ht &&
+           64LL * (KS0 + L * 16 * MT) == q.stash_tile_floats && 64LL * (L * 16 * MT) == (long long)L * q.stash_layer_floats();
+}
+
 // PREC (the C-ABI precision code) 0: exact f32 MFMA chain.  1: the chain's GEMMs run f16-split like the default forward
 // build (dA carried as f16 hi+lo fragments, transposed weight images pre-split and scaled; fp32 accumulate, scaled
 // back).  2: reduced precision, the hi halves only (one f16 product).
@@ -139,35 +164,31 @@ template <int CH, int MT, int NF, int WAVES, int PREC>
 __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const LfgcBwdArgs a) {
     constexpr bool H16 = PREC != 0;
     constexpr bool SPLIT = PREC == 1;
-    constexpr int E = 3 + 6 * NF;
-    constexpr int EP = (E + 7) / 8 * 8;
-    constexpr int K0P = CH + EP;
-    constexpr int K0R = (K0P + 31) / 32 * 32;
-    constexpr int KS0 = K0P / 2;
-    constexpr int HP = 32 * MT;
-    constexpr int KS1 = HP / 2;
-    constexpr int S0 = K0P + 4, S1 = HP + 4, ST = HP + 4;
-    constexpr int BLK0 = HP * S0 + HP, BLK1 = HP * S1 + HP;
-    constexpr int TB0 = K0R * ST, TB1 = HP * ST;
-    constexpr int CHH = CH / 2, EPH = EP / 2;
+    using SHAPE = LfgcShape<CH, MT, NF>;
+    constexpr LfgcPlan P = SHAPE::P;
+    constexpr int E = P.E, K0R = P.K0R, KS0 = P.KS0, HP = P.HP, KS1 = P.KS1, ST = P.ST;
+    constexpr int blk0 = P.blk0, blk1 = P.blk1, tblk0 = P.tblk0, tblk1 = P.tblk1;
+    constexpr int CHH = P.CHH(), EPH = P.EPH();
     constexpr int TXF = (CHH + 15) / 16;         // M tiles of dX0 that hold grid-feature gradients
     constexpr int TXA = K0R / 32;                // ... all of dX0 (features + scalar inputs)
-    constexpr int SCS = CH + 4;                  // scatter staging row stride (floats)
-    constexpr int SC_WAVE = 32 * (SCS + 16);     // per wave: dfeat rows + 8 weights + 8 offsets per sample
+    constexpr int SCS = P.scatter_row();         // scatter staging row stride (floats)
+    constexpr int SC_WAVE = P.scatter_wave();    // per wave: dfeat rows + 8 weights + 8 offsets per sample
     constexpr int SPI = 64 / CH;                 // samples covered by one atomic wave-instruction
-    constexpr int TBMAX = TB0 > TB1 ? TB0 : TB1;
-    constexpr int SLOT = TBMAX > WAVES * SC_WAVE ? TBMAX : WAVES * SC_WAVE;   // ring slot (floats)
+    constexpr int TBMAX = tblk0 > tblk1 ? tblk0 : tblk1;
+    constexpr int SLOT = lfgc_bwd_lds_slot(P, WAVES);   // ring slot (floats): an image or the scatter staging of every wave
     constexpr int NT = WAVES * 64;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_final = smem;               // Wf (HP) | bf (4)
     float* s_inv = smem + HP + 4;        // 1 / scale per layer (f16-split build), 8 floats
     float* s_ring = s_inv + 8;           // 2 x SLOT: transposed weight images / scatter staging
+    static_assert(lfgc_bwd_lds_floats(P, WAVES) == (HP + 4) + 8 + 2 * SLOT && SLOT >= TBMAX && SLOT >= WAVES * SC_WAVE,
+                  "this carve is not the one the host sizes");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, hh = lane >> 5;
     const int L = a.L;
-    const int off_final = BLK0 + (L - 1) * BLK1;
+    const int off_final = blk0 + (L - 1) * blk1;
     const int off_t = off_final + HP + 4;
     const long long per_tile = 64LL * (KS0 + L * 16 * MT);
     const long long dper_tile = 64LL * (L * 16 * MT);
@@ -176,16 +197,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
         const f32x4* src = reinterpret_cast<const f32x4*>(a.packed + off_final);
         for (int i = tid; i < (HP + 4) / 4; i += NT) reinterpret_cast<f32x4*>(s_final)[i] = src[i];
     }
-    // image sequence per batch: W_{L-1}^T, ..., W_1^T (TB1 each), then W_0^T (TB0)
-    constexpr int K0P16 = (K0P + 15) / 16 * 16;
-    constexpr int HBLK0 = HP * (K0P16 + 4) + HP, HBLK1 = HP * (HP + 4) + HP;
-    const int off_h = off_t + TB0 + (L - 1) * TB1;            // scales, then the f16-split forward blocks (lfgc_common.h)
-    const int off_img = H16 ? off_h + 32 + LFGC_MAX_LAYERS * HP + HP + HBLK0 + (L - 1) * HBLK1 : off_t;
+    // image sequence per batch: W_{L-1}^T, ..., W_1^T (tblk1 each), then W_0^T (tblk0)
+    constexpr int blkh0 = P.blkh0, blkh1 = P.blkh1;
+    const int off_h = off_t + tblk0 + (L - 1) * tblk1;        // scales, then the f16-split forward blocks (lfgc_common.h)
+    const int off_img = H16 ? off_h + 32 + LFGC_MAX_LAYERS * HP + HP + blkh0 + (L - 1) * blkh1 : off_t;
+    static_assert(lfgc_bwd_offsets_are_the_plans<CH, MT, NF>(1) && lfgc_bwd_offsets_are_the_plans<CH, MT, NF>(LFGC_MAX_LAYERS),
+                  "off_final / off_t / off_h / off_img / the tile strides here are not lfgc_make_plan's");
     auto image_src = [&](int l) -> const float* {
-        return l == 0 ? a.packed + off_img : a.packed + off_img + TB0 + (long long)(l - 1) * TB1;
+        return l == 0 ? a.packed + off_img : a.packed + off_img + tblk0 + (long long)(l - 1) * tblk1;
     };
     if (tid < LFGC_MAX_LAYERS) s_inv[tid] = a.packed[off_h + 8 + tid];      // all LDS lives in the one dynamic array
-    lfgc_dma_to_lds(image_src(L - 1), s_ring, (L - 1) == 0 ? TB0 : TB1, wave, lane, WAVES);
+    lfgc_dma_to_lds(image_src(L - 1), s_ring, (L - 1) == 0 ? tblk0 : tblk1, wave, lane, WAVES);
     __syncthreads();
     unsigned step = 0;
 #ifdef LFGC_STAMPS
@@ -198,7 +220,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
 #define LFGC_BWD_DMA_BURST 0         // diagnostics: 1 = every wave issues its pieces back to back after the barrier (round 2)
 #endif
     constexpr int NPW = (H16 && !LFGC_BWD_DMA_BURST) ? ((TBMAX / 4 + 63) / 64 + WAVES - 1) / WAVES : 0;   // pieces per wave and image
-    LfgcDmaPlan dma = {a.packed, s_ring, TB1 / 4, __builtin_amdgcn_readfirstlane(wave), (unsigned)lane * 16u, 0ull, 0u};
+    LfgcDmaPlan dma = {a.packed, s_ring, tblk1 / 4, __builtin_amdgcn_readfirstlane(wave), (unsigned)lane * 16u, 0ull, 0u};
     const long long N = a.n;
     for (long long batch = blockIdx.x; batch < a.nbatches; batch += gridDim.x) {
         asm volatile("" : "+s"(dma.wave));                // (keeps the pieces' address arithmetic inside the loop)
@@ -216,9 +238,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
                 // filled once more for nobody, which keeps the MFMA loops free of branches)
                 dma.src = image_src(ln);
                 dma.dst = s_ring + ((step + 1) & 1) * SLOT;
-                dma.nvec = (ln == 0 ? TB0 : TB1) / 4;
+                dma.nvec = (ln == 0 ? tblk0 : tblk1) / 4;
             } else if (l != 0 || batch + gridDim.x < a.nbatches) {
-                lfgc_dma_to_lds(image_src(ln), s_ring + ((step + 1) & 1) * SLOT, ln == 0 ? TB0 : TB1, wave, lane, WAVES);
+                lfgc_dma_to_lds(image_src(ln), s_ring + ((step + 1) & 1) * SLOT, ln == 0 ? tblk0 : tblk1, wave, lane, WAVES);
             }
             ++step;
             return img;
@@ -245,9 +267,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
         for (int l = L - 1; l >= 1; --l) {
             LFGC_BSTAMP(3);                                   // the MFMAs of the layer before (or the head's dH)
             float dA[16 * MT];
-            lfgc_snake_bwd<MT>(st_tile + 64 * KS0 + (long long)l * (64 * 16 * MT), dH, dA, lane);
+            lfgc_snake_bwd<MT>(st_tile + 64 * KS0 + (long long)l * P.stash_layer_floats(), dH, dA, lane);
 #pragma unroll
-            for (int i = 0; i < 16 * MT; ++i) dst_tile[(long long)l * (64 * 16 * MT) + i * 64 + lane] = dA[i];
+            for (int i = 0; i < 16 * MT; ++i) dst_tile[(long long)l * P.stash_layer_floats() + i * 64 + lane] = dA[i];
             if (H16) {
                 h16x8 Fhi[2 * MT], Flo[2 * MT];
                 float isc;
@@ -346,6 +368,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
         float* s_df = s_ring + ((step - 1) & 1) * SLOT + wave * SC_WAVE;   // [32][SCS]
         float* s_cw = s_df + 32 * SCS;                    // [32][8] corner weights
         int* s_co = reinterpret_cast<int*>(s_cw + 32 * 8);   // [32][8] corner row offsets (floats)
+        static_assert(32 * SCS + 32 * 8 + 32 * 8 == SC_WAVE, "a wave's staging is exactly its share of the slot");
 #pragma unroll
         for (int c4 = 0; c4 < CHH / 4; ++c4) {
             f32x4 v;
@@ -521,10 +544,10 @@ struct LfgcWgradArgs {
 
 // Slab layout (floats): per hidden layer l: dW [HP][NC_l] (NC_0 = K0R in packed column order, else HP) | db [HP];
 // then final layer: dWf [HP] | dbf [4].
-__host__ __device__ inline int lfgc_slab_layer_off(const LfgcPlan& p, int l) {
-    return l == 0 ? 0 : (p.HP * p.K0R + p.HP) + (l - 1) * (p.HP * p.HP + p.HP);
+__host__ __device__ constexpr int lfgc_slab_layer_off(const LfgcPlan& p, int l) {
+    return l == 0 ? 0 : p.slab_blk0() + (l - 1) * p.slab_blk1();
 }
-__host__ __device__ inline int lfgc_slab_floats(const LfgcPlan& p) { return lfgc_slab_layer_off(p, p.L) + p.HP + 4; }
+__host__ __device__ constexpr int lfgc_slab_floats(const LfgcPlan& p) { return lfgc_slab_layer_off(p, p.L) + p.HP + 4; }
 
 // The 16 samples a lane contributes to a tile's contraction: [8 kh, 8 kh + 8) and [16 + 8 kh, 16 + 8 kh + 8) of stash row
 // `base` (= row start + lane-half offset): exactly the k values lane half kh feeds to the two 16-deep k-steps of
@@ -690,12 +713,9 @@ __device__ __forceinline__ void lfgc_wgrad_layer(const LfgcWgradArgs& a, int l, 
 template <int CH, int MT, int NF>
 __global__ __launch_bounds__(512, 2) void lfgc_bwd_weight_kernel(const LfgcWgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float s_comb[];
-    constexpr int E = 3 + 6 * NF;
-    constexpr int EP = (E + 7) / 8 * 8;
-    constexpr int K0P = CH + EP;
-    constexpr int K0R = (K0P + 31) / 32 * 32;
-    constexpr int KS0 = K0P / 2;
-    constexpr int HP = 32 * MT;
+    using SHAPE = LfgcShape<CH, MT, NF>;
+    constexpr LfgcPlan P = SHAPE::P;
+    constexpr int K0P = P.K0P, K0R = P.K0R, KS0 = P.KS0, HP = P.HP;
     constexpr int NT0 = K0R / 32;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int L = a.L;
@@ -704,23 +724,30 @@ __global__ __launch_bounds__(512, 2) void lfgc_bwd_weight_kernel(const LfgcWgrad
     const int R = a.roles;
     const int role = (int)blockIdx.x % R, grp = (int)blockIdx.x / R, ngrp = (int)gridDim.x / R;    // workgroup-uniform
     float* slab = a.slabs + (long long)grp * a.slab_floats;
+    // the slab offsets below, written out in l, are lfgc_slab_layer_off's
+    constexpr int slab_blk0 = P.slab_blk0(), slab_blk1 = P.slab_blk1();
+    constexpr auto slab_off_of = [](int l) { return slab_blk0 + (l - 1) * slab_blk1; };
+    static_assert(slab_off_of(1) == lfgc_slab_layer_off(SHAPE::PL, 1) &&
+                  slab_off_of(LFGC_MAX_LAYERS) == lfgc_slab_layer_off(SHAPE::PL, LFGC_MAX_LAYERS), "slab layout");
+    constexpr auto stash_tile_of = [](int L) { return 64 * (KS0 + L * 16 * MT); };
+    LFGC_ASSERT_PLAN_OFFSET(SHAPE, stash_tile_of, stash_tile_floats);
 
     if (R == 1 || role == 0) lfgc_wgrad_layer<MT, NT0, true, KS0>(a, 0, slab, K0R, K0P, per_tile, dper_tile, lane, wave, s_comb, grp, ngrp);
     for (int l = 1; l < L; ++l) {
         if (R != 1 && role != l) continue;
-        float* slab_l = slab + (HP * K0R + HP) + (long long)(l - 1) * (HP * HP + HP);
+        float* slab_l = slab + slab_blk0 + (long long)(l - 1) * slab_blk1;
         lfgc_wgrad_layer<MT, MT, false, KS0>(a, l, slab_l, HP, K0P, per_tile, dper_tile, lane, wave, s_comb, grp, ngrp);
     }
 
     // final Linear: dWf[k] = sum_n dy_n H_L[n,k], dbf = sum_n dy_n.  Wave w owns column tile w.
     if (R == 1 || role == L - 1) {
-        float* slab_f = slab + (HP * K0R + HP) + (long long)(L - 1) * (HP * HP + HP);
+        float* slab_f = slab + slab_blk0 + (long long)(L - 1) * slab_blk1;
         const int i = lane & 31, kk = lane >> 5;
         const int half = wave >> 2, w4 = wave & 3;
         float wsum = 0.0f, bsum = 0.0f;
         if (w4 < MT) {
             const int r = (i & 3) + 4 * (i >> 3), hb = (i >> 2) & 1;
-            const long long boff = 64LL * KS0 + (long long)(L - 1) * (64 * 16 * MT) + (long long)(w4 * 16 + r) * 64 + hb * 32;
+            const long long boff = 64LL * KS0 + (long long)(L - 1) * P.stash_layer_floats() + (long long)(w4 * 16 + r) * 64 + hb * 32;
             for (long long t = grp + (long long)half * ngrp; t < a.ntiles; t += 2LL * ngrp) {
                 float Bv[16];
                 lfgc_load16(a.stash + t * per_tile + boff, kk, Bv);
@@ -841,8 +868,7 @@ static int lfgc_launch_bwd(const LfgcBwdArgs& a, const LfgcWgradArgs& w, int wav
                            a.D, a.H, a.W, a.Cs);
         LFGC_HIP_CHECK_LAUNCH();
     }
-    constexpr int K0R_ = (CH + (3 + 6 * NF + 7) / 8 * 8 + 31) / 32 * 32;
-    constexpr int NT0_ = K0R_ / 32;
+    constexpr int NT0_ = LfgcShape<CH, MT, NF>::P.K0R / 32;
     constexpr int TPW0 = (MT + 4 / NT0_ - 1) / (4 / NT0_), TPW1 = (MT + 4 / MT - 1) / (4 / MT);
     constexpr int TPWM = TPW0 > TPW1 ? TPW0 : TPW1;
     const int comb_bytes = 4 * TPWM * 17 * 64 * 4;

@@ -2,10 +2,9 @@
 #include <cstdlib>
 #include "lfgc_backward.h"
 
-int lfgc_bwd_dispatch_ch8(int, const LfgcBwdArgs&, const LfgcWgradArgs&, int, int, int, int, int, hipStream_t);
-int lfgc_bwd_dispatch_ch16(int, const LfgcBwdArgs&, const LfgcWgradArgs&, int, int, int, int, int, hipStream_t);
-int lfgc_bwd_dispatch_ch24(int, const LfgcBwdArgs&, const LfgcWgradArgs&, int, int, int, int, int, hipStream_t);
-int lfgc_bwd_dispatch_ch32(int, const LfgcBwdArgs&, const LfgcWgradArgs&, int, int, int, int, int, hipStream_t);
+typedef int LfgcBwdDispatch(int MT, const LfgcBwdArgs& a, const LfgcWgradArgs& w, int waves, int precision, int lds_bytes,
+                            int grid_data, int grid_w, hipStream_t stream);
+LfgcBwdDispatch lfgc_bwd_dispatch_ch8, lfgc_bwd_dispatch_ch16, lfgc_bwd_dispatch_ch24, lfgc_bwd_dispatch_ch32;
 
 #ifdef LFGC_STAMPS
 static unsigned long long* g_bwd_stamps = nullptr;
@@ -18,6 +17,8 @@ namespace {
 #define LFGC_MAX_SLABS 256
 #endif
 const int kMaxSlabs = LFGC_MAX_SLABS;   // workgroups of the weight-gradient kernel (one partial slab each)
+// The per-channel instantiation files' entries, by CH / 8 - 1 (CH = 8, 16, 24, 32: lfgc_mlp_supported).
+LfgcBwdDispatch* const kBwd[4] = {lfgc_bwd_dispatch_ch8, lfgc_bwd_dispatch_ch16, lfgc_bwd_dispatch_ch24, lfgc_bwd_dispatch_ch32};
 
 struct Carve {
     long long ntiles, nbatches;
@@ -39,7 +40,7 @@ Carve carve(const LfgcPlan& p, long long n) {
         c.roles = p.L;
         c.nslabs = kMaxSlabs / p.L;
     }
-    c.dstash_floats = c.ntiles * 64LL * (p.L * 16 * p.MT);
+    c.dstash_floats = c.ntiles * (long long)p.L * p.stash_layer_floats();
     c.slab_floats_total = (long long)c.nslabs * lfgc_slab_floats(p);
     c.dscale_floats = (c.ntiles * p.L + 3) / 4 * 4;     // one power-of-two scale per (tile, layer), f16 builds
     c.dfeat_floats = c.ntiles * 32 * p.CH;              // feature gradients for the deferred scatter (small batches)
@@ -57,10 +58,7 @@ lfgc_backward_plan_info bwd_select(const LfgcPlan& p, const Carve& c, long long 
     // last whole 128-sample group are never touched: the stash covers whole 256-sample groups, lfgc_stash_bytes)
     b.waves = ((n + 255) / 256 >= cus) ? 8 : 4;
     b.nbatches = c.nbatches * (8 / b.waves);            // same tile range as the forward wrote
-    const int tb0 = p.K0R * p.ST, tb1 = p.HP * p.ST, sc = b.waves * 32 * (p.CH + 4 + 16);
-    int slot = tb0 > tb1 ? tb0 : tb1;
-    if (sc > slot) slot = sc;
-    b.lds_bytes = (p.HP + 4 + 8 + 2 * slot) * 4;
+    b.lds_bytes = 4 * lfgc_bwd_lds_floats(p, b.waves);
     b.grid = cus;
     if (b.grid > b.nbatches) b.grid = b.nbatches;
     return b;
@@ -148,14 +146,7 @@ extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions
     }
     a.nbatches = b.nbatches;
 
-    int rc;
-    switch (p.CH) {
-        case 8: rc = lfgc_bwd_dispatch_ch8(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
-        case 16: rc = lfgc_bwd_dispatch_ch16(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
-        case 24: rc = lfgc_bwd_dispatch_ch24(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
-        case 32: rc = lfgc_bwd_dispatch_ch32(p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st); break;
-        default: return LFGC_E_UNSUPPORTED;
-    }
+    const int rc = kBwd[p.CH / 8 - 1](p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st);
     if (rc != LFGC_OK) return rc;
 
     LfgcReduceArgs r;

@@ -1,17 +1,15 @@
 // lfgc_capi_forward.hip -- C-ABI entry for the fused forward: argument checks, plan, dispatch.
 #include <stdlib.h>
-#include "lfgc_forward.h"
+#include "lfgc_forward16.h"      // the LDS layouts of both kernel families (lfgc_fwd_lds_floats, lfgc_fwd16_lds_floats)
 
-int lfgc_fwd_dispatch_ch8(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
-int lfgc_fwd_dispatch_ch16(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
-int lfgc_fwd_dispatch_ch24(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
-int lfgc_fwd_dispatch_ch32(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
-int lfgc_fwd16_dispatch_ch8(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
-int lfgc_fwd16_dispatch_ch16(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
-int lfgc_fwd16_dispatch_ch24(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
-int lfgc_fwd16_dispatch_ch32(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
+typedef int LfgcFwdDispatch(int MT, const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream);
+LfgcFwdDispatch lfgc_fwd_dispatch_ch8, lfgc_fwd_dispatch_ch16, lfgc_fwd_dispatch_ch24, lfgc_fwd_dispatch_ch32;
+LfgcFwdDispatch lfgc_fwd16_dispatch_ch8, lfgc_fwd16_dispatch_ch16, lfgc_fwd16_dispatch_ch24, lfgc_fwd16_dispatch_ch32;
 
 namespace {
+// The per-channel instantiation files' entries, by CH / 8 - 1 (CH = 8, 16, 24, 32: lfgc_mlp_supported).
+LfgcFwdDispatch* const kFwd[4] = {lfgc_fwd_dispatch_ch8, lfgc_fwd_dispatch_ch16, lfgc_fwd_dispatch_ch24, lfgc_fwd_dispatch_ch32};
+LfgcFwdDispatch* const kFwd16[4] = {lfgc_fwd16_dispatch_ch8, lfgc_fwd16_dispatch_ch16, lfgc_fwd16_dispatch_ch24, lfgc_fwd16_dispatch_ch32};
 int num_cus() { return lfgc_num_cus(); }
 #ifdef LFGC_STAMPS
 unsigned long long* g_stamps = nullptr;
@@ -67,22 +65,25 @@ int fwd_env_waves(int resident, int waves) {            // diagnostics: LFGC_FWD
     return waves;
 }
 
+long long fwd_lds_bytes(const LfgcPlan& p, bool h16, bool resident, long long table_floats, int nzc) {
+    return 4 * (h16 ? lfgc_fwd16_lds_floats(p, resident, table_floats, nzc) : lfgc_fwd_lds_floats(p, resident, table_floats));
+}
+long long fwd_table_floats(const LfgcFwdArgs& a) { return (long long)a.res0 + a.res1 + a.res2; }
+int fwd_lds_cap(int resident) { return resident ? LFGC_LDS_BYTES_RESIDENT : LFGC_LDS_BYTES_STREAMED; }
+
 // One launch of the exact-fp32 build (h16 = false) or of an f16 build before its z-run decision (h16 = true).
 lfgc_forward_launch fwd_base_launch(const LfgcPlan& p, const LfgcFwdArgs& a, long long n, bool h16, bool env_waves) {
     lfgc_forward_launch l;
-    // LDS: [Wf | bf] + every layer block (resident: 4-wave workgroups, two per CU) or a 2-deep ring of the
-    // largest block (streamed: 8-wave workgroups, one per CU).  The stash is laid out per 32-sample tile in
-    // whole 128-sample groups either way (lfgc_stash_bytes), so both builds write the same format.
-    const int all_blocks = h16 ? p.blkh0 + (p.L - 1) * p.blkh1 : p.off_final;
-    const int max_block = h16 ? (p.blkh0 > p.blkh1 ? p.blkh0 : p.blkh1) : (p.blk0 > p.blk1 ? p.blk0 : p.blk1);
-    const int fixed = p.HP + 4 + (h16 ? 16 + LFGC_MAX_LAYERS * p.HP : 0);   // [Wf | bf] (+ per-layer scales + resident biases)
-    l.resident = ((fixed + all_blocks) * 4 <= 80 * 1024) ? 1 : 0;
-    l.lds_bytes = (fixed + (l.resident ? all_blocks : 2 * max_block)) * 4;
+    // LDS as the kernels carve it (lfgc_fwd_lds_floats, lfgc_fwd16_lds_floats): every layer block when that fits
+    // (resident: 4-wave workgroups, two per CU), else a 2-deep ring of the largest block (streamed: 8-wave workgroups, one per
+    // CU).  The stash is laid out per 32-sample tile in whole 128-sample groups either way (lfgc_stash_bytes), so both
+    // builds write the same format.
+    l.resident = fwd_lds_bytes(p, h16, true, 0, 0) <= LFGC_LDS_BYTES_RESIDENT ? 1 : 0;
+    l.lds_bytes = (int)fwd_lds_bytes(p, h16, l.resident, 0, 0);
     l.coord_table = 0;
-    if (!a.pos) {                                       // per-axis coordinate tables behind the weight region
-        const long long tbl = 4LL * ((long long)a.res0 + a.res1 + a.res2);
-        const long long cap = l.resident ? 80 * 1024 : 160 * 1024;
-        if (l.lds_bytes + tbl <= cap) { l.coord_table = 1; l.lds_bytes += (int)tbl; }
+    if (!a.pos) {                                       // per-axis coordinate tables behind the weight region, if they fit
+        const long long with_tables = fwd_lds_bytes(p, h16, l.resident, fwd_table_floats(a), 0);
+        if (with_tables <= fwd_lds_cap(l.resident)) { l.coord_table = 1; l.lds_bytes = (int)with_tables; }
     }
     // streamed nets: 8-wave workgroups once every CU gets at least one 256-sample batch, else 4-wave ones
     l.waves = (!l.resident && (n + 255) / 256 >= num_cus()) ? 8 : 4;
@@ -118,12 +119,10 @@ int fwd_select(const lfgc_mlp_desc* desc, const lfgc_positions* positions, int D
         const long long rows = (long long)(positions->x_end - positions->x_begin) * a->res1;
         const int tpr = (a->res2 + LFGC_TILE_SAMPLES - 1) / LFGC_TILE_SAMPLES;
         const long long ntiles = rows * tpr;
-        const long long tbl4 = 4LL * (((long long)a->res0 + a->res1 + a->res2 + 3) & ~3LL) - 4LL * ((long long)a->res0 + a->res1 + a->res2);
-        const long long cap = l.resident ? 80 * 1024 : 160 * 1024;
-        const long long col = 4LL * 8 * nzc * (p.CH + 4);            // 8 waves x nzc padded rows (LfgcColumnSampler::CS)
-        if (nzc <= 12 && ntiles < (1LL << 31) && l.lds_bytes + tbl4 + col <= cap) {
+        const long long with_columns = fwd_lds_bytes(p, true, l.resident, fwd_table_floats(*a), nzc);
+        if (nzc <= LFGC_NZC_MAX && ntiles < (1LL << 31) && with_columns <= fwd_lds_cap(l.resident)) {
             l.zrun = 1; l.nzc = nzc; l.tiles_per_row = tpr; l.ntiles = ntiles;
-            l.lds_bytes += (int)(tbl4 + col);
+            l.lds_bytes = (int)with_columns;
             l.waves = fwd_env_waves(l.resident, (!l.resident && (ntiles + 7) / 8 >= num_cus()) ? 8 : 4);
             l.nbatches = (ntiles + l.waves - 1) / l.waves;
             // experimental (LFGC_FWD_X2=1): two tiles per wave, one wave per SIMD (lfgc_forward16x2.h; 32 channels x 128 wide)
@@ -197,14 +196,7 @@ extern "C" int lfgc_forward_f32(const lfgc_mlp_desc* desc, const lfgc_positions*
             LFGC_HIP_CHECK_LAUNCH();
             a.status = status;
         }
-        int rc16;
-        switch (p.CH) {
-            case 8: rc16 = lfgc_fwd16_dispatch_ch8(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
-            case 16: rc16 = lfgc_fwd16_dispatch_ch16(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
-            case 24: rc16 = lfgc_fwd16_dispatch_ch24(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
-            case 32: rc16 = lfgc_fwd16_dispatch_ch32(p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st); break;
-            default: return LFGC_E_UNSUPPORTED;
-        }
+        const int rc16 = kFwd16[p.CH / 8 - 1](p.MT, a, plan.first.lds_bytes, (int)plan.first.grid, st);
         if (rc16 != LFGC_OK || !plan.has_redo) return rc16;
         // Range fallback: the same pass on the exact-fp32 build, enqueued behind the fast one; its workgroups return
         // at once unless the fast kernel has set *status (a sample left the f16 range: diverged or very wide model).
@@ -213,13 +205,7 @@ extern "C" int lfgc_forward_f32(const lfgc_mlp_desc* desc, const lfgc_positions*
         fwd_apply_launch(plan.redo, &a);
     }
     const lfgc_forward_launch& l32 = h16 ? plan.redo : plan.first;
-    switch (p.CH) {
-        case 8: return lfgc_fwd_dispatch_ch8(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
-        case 16: return lfgc_fwd_dispatch_ch16(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
-        case 24: return lfgc_fwd_dispatch_ch24(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
-        case 32: return lfgc_fwd_dispatch_ch32(p.MT, a, l32.lds_bytes, (int)l32.grid, st);
-        default: return LFGC_E_UNSUPPORTED;
-    }
+    return kFwd[p.CH / 8 - 1](p.MT, a, l32.lds_bytes, (int)l32.grid, st);
 }
 
 extern "C" int lfgc_forward_bf16(const lfgc_mlp_desc* desc, const lfgc_positions* positions, const float* grid_cl, int D, int H,

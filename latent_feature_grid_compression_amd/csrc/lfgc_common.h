@@ -21,38 +21,65 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define LFGC_TILE_SAMPLES 32          // samples per wave tile (N dimension of v_mfma_f32_32x32x2_f32)
 
 // ------------------------------------------------------------------------------------------------
-// Packed-parameter plan.  Everything is derived from the descriptor; host and device agree through
-// these constexpr-able formulas.
+// The plan: every shape, stride, blob offset and tile size the packing kernel, the fused kernels and their host
+// planners share, derived from the descriptor in ONE constexpr function.  The host calls lfgc_make_plan at run time;
+// a kernel takes its compile-time constants from LfgcShape<CH, MT, NF>::P (below) and static_asserts the offsets it
+// must spell out in L against the same function, so the two sides cannot disagree in a library that builds.
 //   CH   grid channels padded to 8            MT   hidden width in 32-row MFMA tiles
 //   E    scalar inputs 3 + 6*NF               EP   E padded to 8
-//   K0P  padded layer-0 fan-in = CH + EP      KS0  layer-0 k-steps = K0P/2 (one MFMA = 2 k values)
+//   K0P  padded layer-0 fan-in = CH + EP      KS0  layer-0 k-steps = K0P/2 (one fp32 MFMA = 2 k values)
 //   HP   padded hidden = 32*MT                KS1  hidden k-steps = HP/2
-// Row strides carry +4 floats so that the 16 lanes of a ds_read_b128 group (distinct rows, same
+//   K0R  K0P rounded to 32 (whole MFMA row tiles of the transposed layer-0 image)
+//   K0P16 K0P rounded to 16 (whole 16-wide k-steps of the f16 MFMA)
+// Row strides (S0, S1, ST, SH0, SH1) carry +4 floats so that the 16 lanes of a ds_read_b128 group (distinct rows, same
 // column) fall on 16 distinct 16-byte bank slots (stride = 4 * odd).
-// Blob (floats):  [layer0: W (HP x S0) | bias HP] [layer l=1..L-1: W (HP x S1) | bias HP]
-//                 [final: Wf HP | bf 4]
-//                 [transposed copies for backward: layer0^T (K0R x ST, K0R = K0P rounded to 32), layer l^T (HP x ST)]
+// Blob (floats), in this order:
+//   0          exact forward blocks   [layer 0: W (HP x S0) | bias HP] [layer l = 1..L-1: W (HP x S1) | bias HP]
+//   off_final  head                   [Wf HP | bf 4]
+//   off_t      transposed fp32 images for the exact backward chain: layer 0^T (K0R x ST), layer l^T (HP x ST)
+//   off_h      32 scales: scale[8] | 1/scale[8] of the f16-split transposed images (true W), then scale[8] | 1/scale[8] of
+//              the f16-split forward images (W / pi [/ LFGC_ACT_SCALE], lfgc_forward16.h)
+//   off_hbias  hidden-layer biases divided by pi, un-scaled, LFGC_MAX_LAYERS x HP (the f16 forward adds them in its
+//              epilogue and keeps them LDS-resident)
+//   off_hwf    head weights divided by LFGC_ACT_SCALE, HP (the last hidden layer hands its activations over scaled like
+//              every other)
+//   off_hblk   f16-split forward blocks [layer 0: HP x SH0 | bias HP] [layer l: HP x SH1 | bias HP]: a row holds, per
+//              16-column k-step, [lane half 0: 8 hi halfs | 8 lo halfs][lane half 1: 8 hi | 8 lo] (64 B), i.e. 4 bytes per
+//              weight like the fp32 blocks, same +16 B row padding, followed by the scaled fp32 bias
+//   off_ht     f16-split TRANSPOSED images for the f16 backward data chain (same sizes as tblk0 / tblk1)
+//   total_floats
+// LfgcPlan travels by value inside kernel arguments (pack, reduce): its data members are fixed.  Values derived from them
+// that more than one place needs are the member functions below.
 // ------------------------------------------------------------------------------------------------
 struct LfgcPlan {
     int C, CH, H, HP, MT, L, NF, E, EP, K0P, K0R, KS0, KS1, S0, S1, ST;
-    int blk0, blk1;          // floats per forward layer block (weights + bias)
+    int blk0, blk1;          // floats per exact forward layer block (weights + bias)
     int off_final;           // float offset of [Wf | bf]
-    int fwd_floats;          // floats of the forward part
-    int tblk0, tblk1;        // floats per transposed block
+    int fwd_floats;          // floats of the exact forward part
+    int tblk0, tblk1;        // floats per transposed image
     int off_t;               // float offset of the transposed part
     int total_floats;
-    int stash_tile_floats;   // floats saved per 32-sample tile: 64 * (KS0 + L*16*MT)
-    // f16-split forward section (lfgc_forward16.h): per-layer power-of-two scales, then layer blocks whose rows
-    // hold, per 16-column k-step, [lane half 0: 8 hi halfs | 8 lo halfs][lane half 1: 8 hi | 8 lo] (64 B), i.e.
-    // 4 bytes per weight like the fp32 blocks, same +16 B row padding, followed by the scaled fp32 bias.
-    int K0P16, SH0, SH1, blkh0, blkh1, off_h, off_hbias, off_hwf, off_hblk;
-    int off_ht;              // f16-split TRANSPOSED images for the backward data chain (same sizes as tblk0 / tblk1)
+    int stash_tile_floats;   // floats saved per 32-sample tile: 64 * KS0 + L * stash_layer_floats()
+    int K0P16, SH0, SH1, blkh0, blkh1, off_h, off_hbias, off_hwf, off_hblk;   // f16-split section (above)
+    int off_ht;
+
+    constexpr int CHH() const { return CH / 2; }                 // grid channels gathered per lane (one lane half)
+    constexpr int EPH() const { return EP / 2; }                 // scalar inputs carried per lane
+    constexpr int KS16_0() const { return K0P16 / 16; }          // 16-wide k-steps of layer 0 (f16 MFMA)
+    constexpr int KS16_1() const { return HP / 16; }             // ... of a hidden layer
+    constexpr int stash_layer_floats() const { return 64 * 16 * MT; }   // one layer's pre-activations of a 32-sample tile
+    constexpr int hblk_floats() const { return off_ht - off_hblk; }     // all f16-split forward blocks
+    constexpr int slab_blk0() const { return HP * K0R + HP; }    // weight-gradient slab: dW_0 [HP][K0R] | db_0 [HP]
+    constexpr int slab_blk1() const { return HP * HP + HP; }     // ... dW_l [HP][HP] | db_l [HP]
+    constexpr int col_row() const { return CH + 4; }             // LDS row of one column cell (LfgcColumnSampler)
+    constexpr int scatter_row() const { return CH + 4; }         // backward scatter staging: row of one sample's d feat
+    constexpr int scatter_wave() const { return 32 * (scatter_row() + 16); }   // per wave: 32 rows + 8 weights + 8 offsets each
 };
 
-__host__ __device__ inline int lfgc_roundup(int v, int m) { return (v + m - 1) / m * m; }
+__host__ __device__ constexpr int lfgc_roundup(int v, int m) { return (v + m - 1) / m * m; }
 
-__host__ __device__ inline LfgcPlan lfgc_make_plan(int C, int H, int L, int NF) {
-    LfgcPlan p;
+__host__ __device__ constexpr LfgcPlan lfgc_make_plan(int C, int H, int L, int NF) {
+    LfgcPlan p{};
     p.C = C; p.H = H; p.L = L; p.NF = NF;
     p.CH = lfgc_roundup(C, 8);
     p.HP = lfgc_roundup(H, 32);
@@ -70,7 +97,7 @@ __host__ __device__ inline LfgcPlan lfgc_make_plan(int C, int H, int L, int NF) 
     p.blk1 = p.HP * p.S1 + p.HP;
     p.off_final = p.blk0 + (L - 1) * p.blk1;
     p.fwd_floats = p.off_final + p.HP + 4;
-    p.K0R = lfgc_roundup(p.K0P, 32);     // layer-0 transposed image: rows padded to whole 32-row MFMA tiles
+    p.K0R = lfgc_roundup(p.K0P, 32);
     p.tblk0 = p.K0R * p.ST;
     p.tblk1 = p.HP * p.ST;
     p.off_t = p.fwd_floats;
@@ -79,19 +106,36 @@ __host__ __device__ inline LfgcPlan lfgc_make_plan(int C, int H, int L, int NF) 
     p.SH1 = p.HP + 4;
     p.blkh0 = p.HP * p.SH0 + p.HP;
     p.blkh1 = p.HP * p.SH1 + p.HP;
-    // 32 floats: scale[8] | 1/scale[8] of the transposed images (true W), then scale[8] | 1/scale[8] of the forward
-    // images (W / pi [/ LFGC_ACT_SCALE], lfgc_forward16.h); then the hidden-layer biases divided by pi, un-scaled,
-    // LFGC_MAX_LAYERS x HP (the f16-split forward adds them in its epilogue and keeps them LDS-resident); then the head's
-    // weights divided by LFGC_ACT_SCALE (the last hidden layer hands its activations over scaled like every other)
     p.off_h = p.off_t + p.tblk0 + (L - 1) * p.tblk1;
     p.off_hbias = p.off_h + 32;
-    p.off_hwf = p.off_hbias + LFGC_MAX_LAYERS * p.HP;        // head weights divided by LFGC_ACT_SCALE: HP floats
+    p.off_hwf = p.off_hbias + LFGC_MAX_LAYERS * p.HP;
     p.off_hblk = p.off_hwf + p.HP;
     p.off_ht = p.off_hblk + p.blkh0 + (L - 1) * p.blkh1;
     p.total_floats = p.off_ht + p.tblk0 + (L - 1) * p.tblk1;
-    p.stash_tile_floats = 64 * (p.KS0 + L * 16 * p.MT);
+    p.stash_tile_floats = 64 * p.KS0 + L * p.stash_layer_floats();
     return p;
 }
+
+// The plan of one compiled instantiation.  P is the shape at L = 1: everything a kernel uses as a compile-time constant
+// is independent of L.  Offsets that grow with L stay runtime expressions written out in the kernels (their register
+// allocation follows the expression tree); PL = the same shape at the largest L pins them: each is affine in L, so
+// agreeing with the plan at L = 1 and at L = LFGC_MAX_LAYERS is agreeing everywhere.
+template <int CH, int MT, int NF>
+struct LfgcShape {
+    static constexpr LfgcPlan P = lfgc_make_plan(CH, 32 * MT, 1, NF);
+    static constexpr LfgcPlan PL = lfgc_make_plan(CH, 32 * MT, LFGC_MAX_LAYERS, NF);
+    static_assert(P.CH == CH && P.MT == MT && P.HP == 32 * MT, "not a compiled shape: CH a multiple of 8, MT in {1, 2, 4}");
+    static_assert(P.S0 % 8 == 4 && P.S1 % 8 == 4 && P.ST % 8 == 4 && P.SH0 % 8 == 4 && P.SH1 % 8 == 4,
+                  "row strides are 4 * odd floats: the kernels' ds_read_b128 groups rely on it (and on 16-byte rows)");
+};
+// `of_L` is a constexpr callable repeating a kernel's runtime expression for a given L; `field` the plan's name for it.
+#define LFGC_ASSERT_PLAN_OFFSET(SHAPE, of_L, field)                                                    \
+    static_assert(of_L(1) == SHAPE::P.field && of_L(LFGC_MAX_LAYERS) == SHAPE::PL.field,               \
+                  "this kernel's " #field " is not lfgc_make_plan's")
+
+// Dynamic LDS a workgroup may ask for: resident builds run two workgroups per CU, streamed builds one.
+constexpr int LFGC_LDS_BYTES_RESIDENT = 80 * 1024;
+constexpr int LFGC_LDS_BYTES_STREAMED = 160 * 1024;
 
 // Original nn.Linear column of layer 0 that packed column `cl` (0..K0P) holds, or -1 for padding.
 // Packed order: k-step s = cl/8*4 + cl%4, lane half hh = (cl/4)&1.  Steps s < CH/2 carry grid

@@ -85,10 +85,8 @@ __device__ __forceinline__ float lfgc_lattice_coord(int v, int res, int tile, fl
 // (E[0 .. EP/2) = entries [hh EP/2, (hh+1) EP/2)).
 template <int NF>
 __device__ __forceinline__ void lfgc_embed_inputs(float p0, float p1, float p2, int hh, float* __restrict__ E) {
-    constexpr int EE = 3 + 6 * NF;
-    constexpr int EP = (EE + 7) / 8 * 8;
-    constexpr int EPH = EP / 2;
-    constexpr int E_ = EE;
+    constexpr LfgcPlan P = LfgcShape<8, 1, NF>::P;      // the scalar inputs depend on NF alone
+    constexpr int EP = P.EP, EPH = P.EPH(), E_ = P.E;
 
         // ---- scalar inputs [p | sin f_k p | cos f_k p]: a lane keeps only its half of the list ---------------------
         if constexpr (NF == 2) {
@@ -160,10 +158,8 @@ __device__ __forceinline__ void lfgc_embed_inputs(float p0, float p1, float p2, 
 // not short-circuit branches.
 template <int CH, int NF>
 struct LfgcSampler {
-    static constexpr int E = 3 + 6 * NF;
-    static constexpr int EP = (E + 7) / 8 * 8;
-    static constexpr int CHH = CH / 2;
-    static constexpr int EPH = EP / 2;
+    static constexpr LfgcPlan P = LfgcShape<CH, 1, NF>::P;      // the input side does not depend on the hidden width
+    static constexpr int CHH = P.CHH(), EPH = P.EPH();
     float p0, p1, p2;
     float w[8];
     f32x4 v[8][CHH / 4];
@@ -271,19 +267,18 @@ struct LfgcSampler {
 // instead of once per sample: the texture-address path, which the 8 waves of a workgroup used to fill for 4 k cycles per
 // batch (32 x 8 x 1 KiB through 64 B / clock), is nearly idle.  Lanes whose cell index lies past the column redo one of
 // its cells (same value to the same LDS address): no lane predicate, no branch.
+constexpr int LFGC_NZC_MAX = 12;                    // longest column (z cells) the host selects this path for
 template <int CH, int NF>
 struct LfgcColumnSampler {
-    static constexpr int E = 3 + 6 * NF;
-    static constexpr int EP = (E + 7) / 8 * 8;
-    static constexpr int CHH = CH / 2;
-    static constexpr int EPH = EP / 2;
+    static constexpr LfgcPlan P = LfgcShape<CH, 1, NF>::P;
+    static constexpr int CHH = P.CHH(), EPH = P.EPH();
     static constexpr int LPC = CH / 4;              // lanes per cell: one 4-channel quad each
     static constexpr int CPP = 64 / LPC;            // cells per pass of the wave
-    static constexpr int NZC_MAX = 12;              // longest column the host selects this path for
+    static constexpr int NZC_MAX = LFGC_NZC_MAX;
     static constexpr int NPASS = (NZC_MAX + CPP - 1) / CPP;
     // LDS row of one column cell: CH floats + 4 of padding -- with 128-byte rows, rows r and r + 2 start on the same bank
     // and the read-back (16 lanes of a ds_read_b128 group spread over 4-5 neighbouring rows) conflicted 2-3 ways
-    static constexpr int CS = CH + 4;
+    static constexpr int CS = P.col_row();
     float p0, p1, p2;
     float wz0, wz1;
     int zrel;                                       // (z cell of the sample) - zc_lo, in [0, nzc - 2]
@@ -369,7 +364,7 @@ struct LfgcColumnSampler {
 
 template <int CH, int NF>
 __device__ __forceinline__ void lfgc_sample_inputs(const LfgcFwdArgs& a, long long nc, long long N, const float* s_coord,
-                                               int hh, float (&B0)[CH / 2 + ((3 + 6 * NF + 7) / 8 * 8) / 2]) {
+                                               int hh, float (&B0)[LfgcShape<CH, 1, NF>::P.KS0]) {
     LfgcSampler<CH, NF> sm;
     sm.issue(a, nc, N, s_coord, hh);
     sm.finish(hh, B0);
@@ -433,6 +428,17 @@ __device__ __forceinline__ void lfgc_layer_fwd(const float* __restrict__ s_blk, 
     }
 }
 
+// Dynamic LDS of lfgc_fwd_kernel in floats, in the order the kernel carves it:
+//   s_final [Wf (HP) | bf (4)] | s_w: every layer block (resident) or a ring of 2 slots of the larger block (streamed)
+//   | s_coord: the per-axis coordinate tables, `table_floats` = res0 + res1 + res2 (lattice mode, where they fit; else 0).
+// The host's launch selection sizes the allocation with these functions and the kernel static_asserts its pointers
+// against them.
+constexpr int lfgc_fwd_lds_head(const LfgcPlan& p) { return p.HP + 4; }
+constexpr int lfgc_fwd_lds_ring_slot(const LfgcPlan& p) { return p.blk0 > p.blk1 ? p.blk0 : p.blk1; }
+constexpr long long lfgc_fwd_lds_floats(const LfgcPlan& p, bool resident, long long table_floats) {
+    return lfgc_fwd_lds_head(p) + (resident ? p.off_final : 2 * lfgc_fwd_lds_ring_slot(p)) + table_floats;
+}
+
 // STREAM = false: WAVES = 4, two workgroups per CU, layer blocks staged once ("resident" nets that fit 80 KB of LDS).
 // STREAM = true : one workgroup per CU, the layer blocks stream through a 2-deep LDS ring by LDS-DMA: the block of
 //            layer t+1 is in flight while layer t computes, one barrier per layer, no exposed staging.  WAVES = 8
@@ -440,31 +446,28 @@ __device__ __forceinline__ void lfgc_layer_fwd(const float* __restrict__ s_blk, 
 //            32 768-sample call (one reference tile / train step) still spreads over all 256 CUs.
 template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH>
 __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd_kernel(const LfgcFwdArgs a) {
-    constexpr int E = 3 + 6 * NF;
-    constexpr int EP = (E + 7) / 8 * 8;
-    constexpr int K0P = CH + EP;
-    constexpr int KS0 = K0P / 2;
-    constexpr int HP = 32 * MT;
-    constexpr int KS1 = HP / 2;
-    constexpr int S0 = K0P + 4;
-    constexpr int S1 = HP + 4;
-    constexpr int BLK0 = HP * S0 + HP;
-    constexpr int BLK1 = HP * S1 + HP;
-    constexpr int BLKMAX = BLK0 > BLK1 ? BLK0 : BLK1;
-    constexpr int CHH = CH / 2;          // channels gathered per lane
-    constexpr int EPH = EP / 2;          // scalar inputs carried per lane
+    using SHAPE = LfgcShape<CH, MT, NF>;
+    constexpr LfgcPlan P = SHAPE::P;
+    constexpr int HP = P.HP, KS0 = P.KS0, KS1 = P.KS1, S0 = P.S0, S1 = P.S1, blk0 = P.blk0, blk1 = P.blk1;
+    constexpr int BLKMAX = lfgc_fwd_lds_ring_slot(P);
     constexpr int NT = WAVES * 64;
 
     // range fallback of the f16 builds: nothing to redo (uniform).  Device-scope load: the word is written by the kernel
-    // enqueued just before this one (and cleared by a memset before that), possibly through another XCD's L2
+    // enqueued just before this one (and cleared by lfgc_clear_word_kernel before that), possibly through another XCD's L2
     if (a.redo_if && __hip_atomic_load(a.redo_if, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_final = smem;               // Wf (HP) | bf (4)
-    float* s_w = smem + HP + 4;          // resident: every layer block; streamed: ring of 2 x BLKMAX
+    constexpr int HEAD = lfgc_fwd_lds_head(P);
+    float* s_w = smem + HEAD;            // resident: every layer block; streamed: ring of 2 x BLKMAX
     // lattice mode: coordinate of every voxel index per axis, built once per workgroup (the per-sample form
     // costs two fp64 divisions per axis); placed behind the weight region
-    float* s_coord = s_w + (STREAM ? 2 * BLKMAX : (BLK0 + (a.L - 1) * BLK1));
+    float* s_coord = s_w + (STREAM ? 2 * BLKMAX : (blk0 + (a.L - 1) * blk1));
+    static_assert(HEAD == HP + 4, "s_final is [Wf (HP) | bf (4)]");
+    static_assert(lfgc_fwd_lds_floats(P, false, 0) == HEAD + 2 * BLKMAX, "streamed: s_coord follows the ring");
+    constexpr auto resident_floats_of = [](int L) { return HEAD + (blk0 + (L - 1) * blk1); };
+    static_assert(resident_floats_of(1) == lfgc_fwd_lds_floats(SHAPE::P, true, 0) &&
+                  resident_floats_of(LFGC_MAX_LAYERS) == lfgc_fwd_lds_floats(SHAPE::PL, true, 0), "resident: s_coord follows the blocks");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -472,7 +475,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd_kernel(const LfgcFwdAr
     const int j = lane & 31;
     const int hh = lane >> 5;
     const int L = a.L;
-    const int off_final = BLK0 + (L - 1) * BLK1;
+    const int off_final = blk0 + (L - 1) * blk1;
+    constexpr auto off_final_of = [](int L) { return blk0 + (L - 1) * blk1; };
+    LFGC_ASSERT_PLAN_OFFSET(SHAPE, off_final_of, off_final);
+    constexpr auto stash_tile_of = [](int L) { return 64 * (KS0 + L * 16 * MT); };
+    LFGC_ASSERT_PLAN_OFFSET(SHAPE, stash_tile_of, stash_tile_floats);
 
     {   // final layer (+ every layer block when resident): staged once per workgroup
         const f32x4* src = reinterpret_cast<const f32x4*>(a.packed + off_final);
@@ -481,7 +488,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd_kernel(const LfgcFwdAr
             const f32x4* srcw = reinterpret_cast<const f32x4*>(a.packed);
             for (int i = tid; i < off_final / 4; i += NT) reinterpret_cast<f32x4*>(s_w)[i] = srcw[i];
         } else {
-            lfgc_dma_to_lds(a.packed, s_w, BLK0, wave, lane, WAVES);      // layer 0 of the first batch -> slot 0
+            lfgc_dma_to_lds(a.packed, s_w, blk0, wave, lane, WAVES);      // layer 0 of the first batch -> slot 0
         }
     }
     if (!a.pos && a.coord_table) {
@@ -521,14 +528,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd_kernel(const LfgcFwdAr
         // streamed: this layer's block was put in flight one step ago: wait for my pieces, then for everyone's;
         // the same barrier says every wave is done with the other ring slot -> prefetch the next block into it
         auto acquire = [&](int l) -> const float* {
-            if (!STREAM) return s_w + (l == 0 ? 0 : BLK0 + (l - 1) * BLK1);
+            if (!STREAM) return s_w + (l == 0 ? 0 : blk0 + (l - 1) * blk1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             const float* blk = s_w + (step & 1) * BLKMAX;
             const int ln = (l + 1 == L) ? 0 : l + 1;
             if (ln != 0 || batch + gridDim.x < a.nbatches) {
-                const float* src = a.packed + (ln == 0 ? 0 : BLK0 + (long long)(ln - 1) * BLK1);
-                lfgc_dma_to_lds(src, s_w + ((step + 1) & 1) * BLKMAX, ln == 0 ? BLK0 : BLK1, wave, lane, WAVES);
+                const float* src = a.packed + (ln == 0 ? 0 : blk0 + (long long)(ln - 1) * blk1);
+                lfgc_dma_to_lds(src, s_w + ((step + 1) & 1) * BLKMAX, ln == 0 ? blk0 : blk1, wave, lane, WAVES);
             }
             ++step;
             return blk;
@@ -544,15 +551,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd_kernel(const LfgcFwdAr
             int l = 1;
             for (; l + 1 < L; l += 2) {
                 const float* blk = acquire(l);
-                lfgc_layer_fwd<KS1, MT, S1, STASH>(blk, Bn, Bm, STASH ? stash_tile + (long long)l * (64 * 16 * MT) : nullptr,
+                lfgc_layer_fwd<KS1, MT, S1, STASH>(blk, Bn, Bm, STASH ? stash_tile + (long long)l * P.stash_layer_floats() : nullptr,
                                                    j, hh, lane);
                 blk = acquire(l + 1);
-                lfgc_layer_fwd<KS1, MT, S1, STASH>(blk, Bm, Bn, STASH ? stash_tile + (long long)(l + 1) * (64 * 16 * MT) : nullptr,
+                lfgc_layer_fwd<KS1, MT, S1, STASH>(blk, Bm, Bn, STASH ? stash_tile + (long long)(l + 1) * P.stash_layer_floats() : nullptr,
                                                    j, hh, lane);
             }
             if (l < L) {
                 const float* blk = acquire(l);
-                lfgc_layer_fwd<KS1, MT, S1, STASH>(blk, Bn, Bm, STASH ? stash_tile + (long long)l * (64 * 16 * MT) : nullptr,
+                lfgc_layer_fwd<KS1, MT, S1, STASH>(blk, Bn, Bm, STASH ? stash_tile + (long long)l * P.stash_layer_floats() : nullptr,
                                                    j, hh, lane);
 #pragma unroll
                 for (int s = 0; s < KS1; ++s) Bn[s] = Bm[s];

@@ -352,38 +352,62 @@ __device__ __forceinline__ void lfgc_layer_fwd16(const float* __restrict__ s_blk
 #define LFGC_STAMP(k) do { } while (0)
 #endif
 
+// Dynamic LDS of the f16 kernels (lfgc_fwd16_kernel and lfgc_fwd16x2_kernel) in floats, in the order they carve it:
+//   s_final [Wf (HP) | bf (4)] | s_scale 16 | s_bias LFGC_MAX_LAYERS x HP | s_w: every f16-split block (resident) or a ring
+//   of 2 slots of the larger block (streamed) | s_coord: the coordinate tables, `table_floats` = res0 + res1 + res2
+//   | z-run launches (nzc > 0) only: the tables rounded up to 4 floats, then 8 columns per workgroup -- 8 waves x 1 tile or
+//   4 waves x 2 tiles -- of nzc rows of col_row() floats (LfgcColumnSampler).
+// The host's launch selection sizes the allocation with these functions; the kernels static_assert their carve against them.
+constexpr int LFGC_ZRUN_COLUMNS = 8;     // columns a z-run workgroup holds: one per wave (<= 8 waves), or two for each of 4 waves
+constexpr int lfgc_fwd16_lds_head(const LfgcPlan& p) { return p.HP + 4 + 16 + LFGC_MAX_LAYERS * p.HP; }
+constexpr int lfgc_fwd16_lds_ring_slot(const LfgcPlan& p) { return p.blkh0 > p.blkh1 ? p.blkh0 : p.blkh1; }
+constexpr long long lfgc_fwd16_lds_floats(const LfgcPlan& p, bool resident, long long table_floats, int nzc) {
+    const long long weights = lfgc_fwd16_lds_head(p) + (resident ? p.hblk_floats() : 2 * lfgc_fwd16_lds_ring_slot(p));
+    return nzc > 0 ? weights + ((table_floats + 3) & ~3LL) + (long long)LFGC_ZRUN_COLUMNS * nzc * p.col_row() : weights + table_floats;
+}
+// The blob offsets both f16 kernels spell out at run time (off_final, off_h, the reads at off_h + 16 / + 32 / + 32 +
+// LFGC_MAX_LAYERS * HP, hblk) and their stash tile stride, repeated here for a given L and compared with the plan's.
+template <int CH, int MT, int NF>
+constexpr bool lfgc_fwd16_offsets_are_the_plans(int L) {
+    constexpr LfgcPlan P = LfgcShape<CH, MT, NF>::P;
+    constexpr int HP = P.HP, KS0 = P.KS0, blk0 = P.blk0, blk1 = P.blk1, tblk0 = P.tblk0, tblk1 = P.tblk1;
+    const LfgcPlan q = lfgc_make_plan(CH, HP, L, NF);
+    const int off_final = blk0 + (L - 1) * blk1;
+    const int off_h = off_final + HP + 4 + tblk0 + (L - 1) * tblk1;
+    return off_final == q.off_final && off_h == q.off_h && off_h + 32 == q.off_hbias &&
+           off_h + 32 + LFGC_MAX_LAYERS * HP == q.off_hwf && off_h + 32 + LFGC_MAX_LAYERS * HP + HP == q.off_hblk &&
+           64 * (KS0 + L * 16 * MT) == q.stash_tile_floats;
+}
+
 // ZRUN (lattice mode only, never with STASH): z-run tiles and the column sampler (LfgcColumnSampler, lfgc_forward.h).
 template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH, bool SPLIT, bool ZRUN>
 __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwdArgs a) {
-    constexpr int E = 3 + 6 * NF;
-    constexpr int EP = (E + 7) / 8 * 8;
-    constexpr int K0P = CH + EP;
-    constexpr int KS0 = K0P / 2;                 // fp32 inputs per lane (stash layout of the exact build)
-    constexpr int K0P16 = (K0P + 15) / 16 * 16;
-    constexpr int KS16_0 = K0P16 / 16;           // 16-wide k-steps of layer 0
-    constexpr int HP = 32 * MT;
-    constexpr int KS16_1 = HP / 16;
-    constexpr int S0 = K0P16 + 4;
-    constexpr int S1 = HP + 4;
-    constexpr int BLK0 = HP * S0 + HP;
-    constexpr int BLK1 = HP * S1 + HP;
-    constexpr int BLKMAX = BLK0 > BLK1 ? BLK0 : BLK1;
+    using SHAPE = LfgcShape<CH, MT, NF>;
+    constexpr LfgcPlan P = SHAPE::P;
+    constexpr int HP = P.HP, KS0 = P.KS0;        // KS0: fp32 inputs per lane (stash layout of the exact build)
+    constexpr int KS16_0 = P.KS16_0(), KS16_1 = P.KS16_1(), SH0 = P.SH0, SH1 = P.SH1, blkh0 = P.blkh0, blkh1 = P.blkh1;
+    constexpr int BLKMAX = lfgc_fwd16_lds_ring_slot(P);
     constexpr int NT = WAVES * 64;
     // 1-KiB DMA pieces per wave for a hidden layer's block (streamed under the layer before it) and for layer 0's (under
     // the last layer of the batch before)
-    constexpr int NP1 = STREAM ? ((BLK1 / 4 + 63) / 64 + WAVES - 1) / WAVES : 0;
-    constexpr int NP0 = STREAM ? ((BLK0 / 4 + 63) / 64 + WAVES - 1) / WAVES : 0;
-    // offsets inside the packed blob (lfgc_common.h)
-    constexpr int F_BLK0 = HP * (K0P + 4) + HP, F_BLK1 = HP * (HP + 4) + HP;
-    constexpr int K0R = (K0P + 31) / 32 * 32;
+    constexpr int NP1 = STREAM ? ((blkh1 / 4 + 63) / 64 + WAVES - 1) / WAVES : 0;
+    constexpr int NP0 = STREAM ? ((blkh0 / 4 + 63) / 64 + WAVES - 1) / WAVES : 0;
+    constexpr int blk0 = P.blk0, blk1 = P.blk1, tblk0 = P.tblk0, tblk1 = P.tblk1;     // for the offsets inside the packed blob (lfgc_common.h)
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_final = smem;               // Wf (HP) | bf (4)
     float* s_scale = smem + HP + 4;      // scale[8] | 1/scale[8]
     float* s_bias = s_scale + 16;        // b/pi of every hidden layer: LFGC_MAX_LAYERS x HP
     float* s_w = s_bias + LFGC_MAX_LAYERS * HP;   // resident: every layer block; streamed: ring of 2 x BLKMAX
-    float* s_coord = s_w + (STREAM ? 2 * BLKMAX : (BLK0 + (a.L - 1) * BLK1));
-    float* s_col = s_coord + ((a.res0 + a.res1 + a.res2 + 3) & ~3) + (threadIdx.x >> 6) * (a.nzc * (CH + 4));   // ZRUN: this wave's column (rows of LfgcColumnSampler::CS floats)
+    float* s_coord = s_w + (STREAM ? 2 * BLKMAX : (blkh0 + (a.L - 1) * blkh1));
+    float* s_col = s_coord + ((a.res0 + a.res1 + a.res2 + 3) & ~3) + (threadIdx.x >> 6) * (a.nzc * P.col_row());   // ZRUN: this wave's column (rows of LfgcColumnSampler::CS floats)
+    static_assert(WAVES <= LFGC_ZRUN_COLUMNS, "one column per wave");
+    constexpr int HEAD = lfgc_fwd16_lds_head(P);
+    static_assert(HEAD == (HP + 4) + 16 + LFGC_MAX_LAYERS * HP, "s_final | s_scale | s_bias as carved above");
+    static_assert(lfgc_fwd16_lds_floats(P, false, 0, 0) == HEAD + 2 * BLKMAX, "streamed: s_coord follows the ring");
+    constexpr auto resident_floats_of = [](int L) { return HEAD + (blkh0 + (L - 1) * blkh1); };
+    static_assert(resident_floats_of(1) == lfgc_fwd16_lds_floats(SHAPE::P, true, 0, 0) &&
+                  resident_floats_of(LFGC_MAX_LAYERS) == lfgc_fwd16_lds_floats(SHAPE::PL, true, 0, 0), "resident: s_coord follows the blocks");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -392,9 +416,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
     const int j = lane & 31;
     const int hh = lane >> 5;
     const int L = a.L;
-    const int off_final = F_BLK0 + (L - 1) * F_BLK1;
-    const int off_h = off_final + HP + 4 + K0R * (HP + 4) + (L - 1) * HP * (HP + 4);
+    const int off_final = blk0 + (L - 1) * blk1;
+    const int off_h = off_final + HP + 4 + tblk0 + (L - 1) * tblk1;
     const float* hblk = a.packed + off_h + 32 + LFGC_MAX_LAYERS * HP + HP;
+    static_assert(lfgc_fwd16_offsets_are_the_plans<CH, MT, NF>(1) && lfgc_fwd16_offsets_are_the_plans<CH, MT, NF>(LFGC_MAX_LAYERS),
+                  "off_final / off_h / hblk / the stash tile below are not lfgc_make_plan's");
     {
         // head: weights divided by LFGC_ACT_SCALE (the last hidden layer's activations arrive scaled), bias as it is
         for (int i = tid; i < HP; i += NT) s_final[i] = a.packed[off_h + 32 + LFGC_MAX_LAYERS * HP + i];
@@ -403,12 +429,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
         for (int i = tid; i < L * HP; i += NT) s_bias[i] = a.packed[off_h + 32 + i];
         if (!STREAM) {
             const f32x4* srcw = reinterpret_cast<const f32x4*>(hblk);
-            for (int i = tid; i < (BLK0 + (L - 1) * BLK1) / 4; i += NT) reinterpret_cast<f32x4*>(s_w)[i] = srcw[i];
+            for (int i = tid; i < (blkh0 + (L - 1) * blkh1) / 4; i += NT) reinterpret_cast<f32x4*>(s_w)[i] = srcw[i];
         } else {
-            lfgc_dma_to_lds(hblk, s_w, BLK0, wave, lane, WAVES);
+            lfgc_dma_to_lds(hblk, s_w, blkh0, wave, lane, WAVES);
 #if LFGC_ABLATE & 8             // diagnostics: both ring slots hold layer 1's block for good (finite data, wrong results)
-            lfgc_dma_to_lds(hblk + BLK0, s_w, BLK1, wave, lane, WAVES);
-            lfgc_dma_to_lds(hblk + BLK0, s_w + BLKMAX, BLK1, wave, lane, WAVES);
+            lfgc_dma_to_lds(hblk + blkh0, s_w, blkh1, wave, lane, WAVES);
+            lfgc_dma_to_lds(hblk + blkh0, s_w + BLKMAX, blkh1, wave, lane, WAVES);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
         }
@@ -478,12 +504,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
         }
 #endif
 
-        LfgcDmaPlan dma = {hblk, s_w, BLK0 / 4, wave_s, (unsigned)lane * 16u, 0ull, 0u};
+        LfgcDmaPlan dma = {hblk, s_w, blkh0 / 4, wave_s, (unsigned)lane * 16u, 0ull, 0u};
         // opaque per batch: otherwise the address arithmetic of every piece of every block is hoisted out of this loop
         // into ~60 SGPRs that do not exist (spilled to VGPR lanes, v_readlane in the gaps)
         asm volatile("" : "+s"(dma.wave));
         auto acquire = [&](int l) -> const float* {
-            if (!STREAM) return s_w + (l == 0 ? 0 : BLK0 + (l - 1) * BLK1);
+            if (!STREAM) return s_w + (l == 0 ? 0 : blkh0 + (l - 1) * blkh1);
             LFGC_STAMP(2 + 2 * (l < 6 ? l : 6));           // the layer before this acquire (or the input phase for l = 0 -> slot 1 below)
 #if LFGC_ABLATE & 8                                        // diagnostics: no weight streaming, no barriers (wrong results)
             return s_w + (l & 1) * BLKMAX;
@@ -505,15 +531,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
             // (after the last batch the slot is filled once more for nobody: an unconditional stream keeps the gaps
             // free of branches)
             const int ln = (l + 1 == L) ? 0 : l + 1;
-            dma.src = hblk + (ln == 0 ? 0 : BLK0 + (long long)(ln - 1) * BLK1);
+            dma.src = hblk + (ln == 0 ? 0 : blkh0 + (long long)(ln - 1) * blkh1);
             dma.dst = s_w + ((step + 1) & 1) * BLKMAX;
-            dma.nvec = (ln == 0 ? BLK0 : BLK1) / 4;
+            dma.nvec = (ln == 0 ? blkh0 : blkh1) / 4;
             lfgc_dma_plan_block(dma);
             ++step;
             return blk;
         };
         float* stash_tile = STASH ? a.stash + tile_idx * (long long)(64 * (KS0 + L * 16 * MT)) + 64 * KS0 : nullptr;
-        auto stash_of = [&](int l) -> float* { return STASH ? stash_tile + (long long)l * (64 * 16 * MT) : nullptr; };
+        auto stash_of = [&](int l) -> float* { return STASH ? stash_tile + (long long)l * P.stash_layer_floats() : nullptr; };
 
         float ydot = 0.0f, tmax = 0.0f;
         u32x4 Ahi[2 * MT], Alo[2 * MT], Bhi[2 * MT], Blo[2 * MT];
@@ -555,10 +581,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
             const float* blk = acquire(0);
 #endif
             if (L == 1)
-                lfgc_layer_fwd16<KS16_0, MT, S0, STASH, true, SPLIT, false, NP0, BLK0 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
+                lfgc_layer_fwd16<KS16_0, MT, SH0, STASH, true, SPLIT, false, NP0, blkh0 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
                                                                             s_final, ydot, tmax, stash_of(0), j, hh, lane, dma);
             else
-                lfgc_layer_fwd16<KS16_0, MT, S0, STASH, false, SPLIT, false, NP1, BLK1 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
+                lfgc_layer_fwd16<KS16_0, MT, SH0, STASH, false, SPLIT, false, NP1, blkh1 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
                                                                              s_final, ydot, tmax, stash_of(0), j, hh, lane, dma);
         }
         // hidden layers 1 .. L-2 in ping-pong pairs, then the last one with the head folded in
@@ -566,23 +592,23 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
             int l = 1;
             for (; l + 2 < L; l += 2) {
                 const float* blk = acquire(l);
-                lfgc_layer_fwd16<KS16_1, MT, S1, STASH, false, SPLIT, true, NP1, BLK1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
+                lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
                                                                             s_final, ydot, tmax, stash_of(l), j, hh, lane, dma);
                 blk = acquire(l + 1);
-                lfgc_layer_fwd16<KS16_1, MT, S1, STASH, false, SPLIT, true, NP1, BLK1 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[9 + l], s_bias + (l + 1) * HP, Ahi, Alo, ca,
+                lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[9 + l], s_bias + (l + 1) * HP, Ahi, Alo, ca,
                                                                             s_final, ydot, tmax, stash_of(l + 1), j, hh, lane, dma);
             }
             if (l + 1 < L) {       // one more non-final layer: A -> B, final consumes B
                 const float* blk = acquire(l);
-                lfgc_layer_fwd16<KS16_1, MT, S1, STASH, false, SPLIT, true, NP1, BLK1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
+                lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
                                                                             s_final, ydot, tmax, stash_of(l), j, hh, lane, dma);
                 ++l;
                 blk = acquire(l);
-                lfgc_layer_fwd16<KS16_1, MT, S1, STASH, true, SPLIT, true, NP0, BLK0 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[8 + l], s_bias + l * HP, Ahi, Alo, ca,
+                lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, true, SPLIT, true, NP0, blkh0 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[8 + l], s_bias + l * HP, Ahi, Alo, ca,
                                                                            s_final, ydot, tmax, stash_of(l), j, hh, lane, dma);
             } else if (l < L) {    // final layer consumes A
                 const float* blk = acquire(l);
-                lfgc_layer_fwd16<KS16_1, MT, S1, STASH, true, SPLIT, true, NP0, BLK0 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
+                lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, true, SPLIT, true, NP0, blkh0 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
                                                                            s_final, ydot, tmax, stash_of(l), j, hh, lane, dma);
             }
         }

@@ -163,24 +163,15 @@ __device__ __forceinline__ void lfgc_layer_fwd16x2(const float* __restrict__ s_b
 template <int CH, int MT, int NF, bool SPLIT>
 __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs a) {
     constexpr int WAVES = 4;
-    constexpr int E = 3 + 6 * NF;
-    constexpr int EP = (E + 7) / 8 * 8;
-    constexpr int K0P = CH + EP;
-    constexpr int KS0 = K0P / 2;
-    constexpr int K0P16 = (K0P + 15) / 16 * 16;
-    constexpr int KS16_0 = K0P16 / 16;
-    constexpr int HP = 32 * MT;
-    constexpr int KS16_1 = HP / 16;
-    constexpr int S0 = K0P16 + 4;
-    constexpr int S1 = HP + 4;
-    constexpr int BLK0 = HP * S0 + HP;
-    constexpr int BLK1 = HP * S1 + HP;
-    constexpr int BLKMAX = BLK0 > BLK1 ? BLK0 : BLK1;
+    using SHAPE = LfgcShape<CH, MT, NF>;
+    constexpr LfgcPlan P = SHAPE::P;
+    constexpr int HP = P.HP, KS0 = P.KS0;
+    constexpr int KS16_0 = P.KS16_0(), KS16_1 = P.KS16_1(), SH0 = P.SH0, SH1 = P.SH1, blkh0 = P.blkh0, blkh1 = P.blkh1;
+    constexpr int BLKMAX = lfgc_fwd16_lds_ring_slot(P);
     constexpr int NT = WAVES * 64;
-    constexpr int NP1 = ((BLK1 / 4 + 63) / 64 + WAVES - 1) / WAVES;
-    constexpr int NP0 = ((BLK0 / 4 + 63) / 64 + WAVES - 1) / WAVES;
-    constexpr int F_BLK0 = HP * (K0P + 4) + HP, F_BLK1 = HP * (HP + 4) + HP;
-    constexpr int K0R = (K0P + 31) / 32 * 32;
+    constexpr int NP1 = ((blkh1 / 4 + 63) / 64 + WAVES - 1) / WAVES;
+    constexpr int NP0 = ((blkh0 / 4 + 63) / 64 + WAVES - 1) / WAVES;
+    constexpr int blk0 = P.blk0, blk1 = P.blk1, tblk0 = P.tblk0, tblk1 = P.tblk1;     // for the offsets inside the packed blob (lfgc_common.h)
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_final = smem;
@@ -189,6 +180,10 @@ __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs 
     float* s_w = s_bias + LFGC_MAX_LAYERS * HP;
     float* s_coord = s_w + 2 * BLKMAX;
     float* s_colbase = s_coord + ((a.res0 + a.res1 + a.res2 + 3) & ~3);
+    constexpr int HEAD = lfgc_fwd16_lds_head(P);
+    static_assert(HEAD == (HP + 4) + 16 + LFGC_MAX_LAYERS * HP, "s_final | s_scale | s_bias as carved above");
+    static_assert(lfgc_fwd16_lds_floats(P, false, 0, 0) == HEAD + 2 * BLKMAX, "s_coord follows the ring");
+    static_assert(2 * WAVES == LFGC_ZRUN_COLUMNS, "two columns per wave");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -197,16 +192,18 @@ __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs 
     const int j = lane & 31;
     const int hh = lane >> 5;
     const int L = a.L;
-    const int off_final = F_BLK0 + (L - 1) * F_BLK1;
-    const int off_h = off_final + HP + 4 + K0R * (HP + 4) + (L - 1) * HP * (HP + 4);
+    const int off_final = blk0 + (L - 1) * blk1;
+    const int off_h = off_final + HP + 4 + tblk0 + (L - 1) * tblk1;
     const float* hblk = a.packed + off_h + 32 + LFGC_MAX_LAYERS * HP + HP;
-    float* s_col[2] = {s_colbase + (2 * wave) * (a.nzc * (CH + 4)), s_colbase + (2 * wave + 1) * (a.nzc * (CH + 4))};
+    static_assert(lfgc_fwd16_offsets_are_the_plans<CH, MT, NF>(1) && lfgc_fwd16_offsets_are_the_plans<CH, MT, NF>(LFGC_MAX_LAYERS),
+                  "off_final / off_h / hblk below are not lfgc_make_plan's");
+    float* s_col[2] = {s_colbase + (2 * wave) * (a.nzc * P.col_row()), s_colbase + (2 * wave + 1) * (a.nzc * P.col_row())};
 
     for (int i = tid; i < HP; i += NT) s_final[i] = a.packed[off_h + 32 + LFGC_MAX_LAYERS * HP + i];
     if (tid < 4) s_final[HP + tid] = a.packed[off_final + HP + tid];
     if (tid < 16) s_scale[tid] = a.packed[off_h + 16 + tid];
     for (int i = tid; i < L * HP; i += NT) s_bias[i] = a.packed[off_h + 32 + i];
-    lfgc_dma_to_lds(hblk, s_w, BLK0, wave, lane, WAVES);
+    lfgc_dma_to_lds(hblk, s_w, blkh0, wave, lane, WAVES);
     {
         const int r01 = a.res0 + a.res1, r012 = r01 + a.res2;
         for (int i = tid; i < r012; i += NT) {
@@ -260,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs 
             zx[t] += dzx + c2;
         }
 
-        LfgcDmaPlan dma = {hblk, s_w, BLK0 / 4, wave_s, (unsigned)lane * 16u, 0ull, 0u};
+        LfgcDmaPlan dma = {hblk, s_w, blkh0 / 4, wave_s, (unsigned)lane * 16u, 0ull, 0u};
         asm volatile("" : "+s"(dma.wave));
         auto acquire = [&](int l) -> const float* {
             LFGC_STAMP(2 + 2 * (l < 6 ? l : 6));
@@ -272,9 +269,9 @@ __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs 
             LFGC_STAMP(3 + 2 * (l < 5 ? l : 5));
             const float* blk = s_w + (step & 1) * BLKMAX;
             const int ln = (l + 1 == L) ? 0 : l + 1;
-            dma.src = hblk + (ln == 0 ? 0 : BLK0 + (long long)(ln - 1) * BLK1);
+            dma.src = hblk + (ln == 0 ? 0 : blkh0 + (long long)(ln - 1) * blkh1);
             dma.dst = s_w + ((step + 1) & 1) * BLKMAX;
-            dma.nvec = (ln == 0 ? BLK0 : BLK1) / 4;
+            dma.nvec = (ln == 0 ? blkh0 : blkh1) / 4;
             lfgc_dma_plan_block(dma);
             ++step;
             return blk;
@@ -306,33 +303,33 @@ __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs 
                 }
             }
             if (L == 1)
-                lfgc_layer_fwd16x2<KS16_0, MT, S0, true, SPLIT, false, NP0, BLK0 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
+                lfgc_layer_fwd16x2<KS16_0, MT, SH0, true, SPLIT, false, NP0, blkh0 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
                                                                                  s_final, ydot, tmax, j, hh, dma);
             else
-                lfgc_layer_fwd16x2<KS16_0, MT, S0, false, SPLIT, false, NP1, BLK1 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
+                lfgc_layer_fwd16x2<KS16_0, MT, SH0, false, SPLIT, false, NP1, blkh1 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
                                                                                   s_final, ydot, tmax, j, hh, dma);
         }
         {
             int l = 1;
             for (; l + 2 < L; l += 2) {
                 const float* blk = acquire(l);
-                lfgc_layer_fwd16x2<KS16_1, MT, S1, false, SPLIT, true, NP1, BLK1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
+                lfgc_layer_fwd16x2<KS16_1, MT, SH1, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
                                                                                  s_final, ydot, tmax, j, hh, dma);
                 blk = acquire(l + 1);
-                lfgc_layer_fwd16x2<KS16_1, MT, S1, false, SPLIT, true, NP1, BLK1 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[9 + l], s_bias + (l + 1) * HP, Ahi, Alo, ca,
+                lfgc_layer_fwd16x2<KS16_1, MT, SH1, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[9 + l], s_bias + (l + 1) * HP, Ahi, Alo, ca,
                                                                                  s_final, ydot, tmax, j, hh, dma);
             }
             if (l + 1 < L) {
                 const float* blk = acquire(l);
-                lfgc_layer_fwd16x2<KS16_1, MT, S1, false, SPLIT, true, NP1, BLK1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
+                lfgc_layer_fwd16x2<KS16_1, MT, SH1, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
                                                                                  s_final, ydot, tmax, j, hh, dma);
                 ++l;
                 blk = acquire(l);
-                lfgc_layer_fwd16x2<KS16_1, MT, S1, true, SPLIT, true, NP0, BLK0 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[8 + l], s_bias + l * HP, Ahi, Alo, ca,
+                lfgc_layer_fwd16x2<KS16_1, MT, SH1, true, SPLIT, true, NP0, blkh0 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[8 + l], s_bias + l * HP, Ahi, Alo, ca,
                                                                                 s_final, ydot, tmax, j, hh, dma);
             } else if (l < L) {
                 const float* blk = acquire(l);
-                lfgc_layer_fwd16x2<KS16_1, MT, S1, true, SPLIT, true, NP0, BLK0 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
+                lfgc_layer_fwd16x2<KS16_1, MT, SH1, true, SPLIT, true, NP0, blkh0 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[8 + l], s_bias + l * HP, Bhi, Blo, cb,
                                                                                 s_final, ydot, tmax, j, hh, dma);
             }
         }
