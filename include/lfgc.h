@@ -265,6 +265,40 @@ int64_t lfgc_codec_kmeans_workspace_bytes(int k);
 int lfgc_codec_kmeans1d_f32(const float* x, int64_t n, int k, float* centres, uint8_t* labels, int iterations,
                             void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
 
+/* The same codebook construction for k up to 65 536 (label widths 9 to 16), over the values SORTED ascending by the caller.
+ * The Lloyd iteration is the one above, step for step: `centres` holds the sorted initial centres and is overwritten
+ * (stays sorted); the midpoints are fp32 `0.5f * (c[j] + c[j+1])`; a value's label is the number of midpoints < it (so of
+ * equal centres the first one takes the values); cluster sums are fp64; centre = (float)(sum / count); an empty cluster
+ * keeps its centre; `iterations` steps, no convergence test.  ONE difference, which the k <= 256 entry keeps as it is:
+ * between neighbouring floats c[j] < c[j+1] the rounded midpoint can be c[j+1] itself, which would label the value c[j+1]
+ * with j; here such a midpoint is the float below c[j+1] instead, so every centre owns its own value and a codebook with
+ * one centre per distinct value (k >= n: any small tensor at 16 bits) reproduces the values exactly and stays put.  In sorted order cluster j is the contiguous range of values
+ * in (midpoint j-1, midpoint j], found by binary search, and its sum is taken piecewise (partial head, whole 1 024-value
+ * blocks summed once before the loop, partial tail) in a fixed order: no atomics, deterministic -- two calls give
+ * identical bits -- and within fp64 summation-order rounding of the unsorted form.  Replaces kmeans_quantization
+ * (model_utils.py:73-76) where the writer asks for more than 8 bits.  Workspace from the caller
+ * (lfgc_codec_kmeans_sorted_workspace_bytes; 0 for arguments the entry refuses), nothing allocated, no synchronisation. */
+#define LFGC_CODEC_KMEANS_MAX_K 65536
+int64_t lfgc_codec_kmeans_sorted_workspace_bytes(int64_t n, int k);
+int lfgc_codec_kmeans1d_sorted_f32(const float* x_sorted, int64_t n, int k, float* centres, int iterations,
+                                   void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+/* labels[i] (uint16) = number of midpoints of the sorted `centres` (k <= 65 536) that are < x[i], the midpoints being those
+ * of lfgc_codec_kmeans1d_sorted_f32 above; for values in any order. */
+int lfgc_codec_labels_u16_f32(const float* x, int64_t n, int k, const float* centres, uint16_t* labels,
+                              lfgc_stream_t stream);
+
+/* Labels -> byte stream of the quantised blocks (ints_to_bits_to_bytes, model_utils.py:79-90): label i, masked to its low
+ * `bits` bits, at stream bits [bits*i, bits*(i+1)), MSB first.  labels: uint8 (label_bytes 1, bits <= 8) or uint16
+ * (label_bytes 2); 1 <= bits <= 16; packed_bytes >= (n*bits + 7) / 8, of which exactly that many are written.
+ * TAIL: when n*bits is no multiple of 8 the leftover bits are LEFT-aligned in the last byte (plain continuation of the
+ * stream, zero bits on the right).  The reference's helper right-aligns them, but its reader (and lfgc_codec_dequant_f32)
+ * slices the stream MSB-first and repairs only the LAST label from the uint32 that follows the stream; at 1, 2, 3 and 5 bits
+ * the last byte holds whole labels before the last one, which a right-aligned tail makes that reader mis-decode.  The
+ * reference's writer only ever emits 8 bits (no tail), so there are no reference bytes to match -- only the reader's rule,
+ * which the left-aligned tail satisfies at every width.  The file writer still appends the uint32. */
+int lfgc_codec_pack_labels(const void* labels, int label_bytes, int64_t n, int bits, uint8_t* packed, int64_t packed_bytes,
+                           lfgc_stream_t stream);
+
 /* out[i] = centres[label_i], label_i = bits [bits*i, bits*(i+1)) of `packed`, MSB first, 1 <= bits <= 16
  * (read_in_data_quantized, model_utils.py:255-275). */
 int lfgc_codec_dequant_f32(const uint8_t* packed, int64_t packed_bytes, int bits, int64_t n, const float* centres,

@@ -90,7 +90,11 @@ SIGNATURES = {
     'lfgc_codec_ward_init_host': (c_int, [POINTER(c_float), c_int64, c_int, POINTER(c_float)]),
     'lfgc_codec_kmeans_workspace_bytes': (c_int64, [c_int]),
     'lfgc_codec_kmeans1d_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
-    'lfgc_codec_dequant_f32': (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    'lfgc_codec_kmeans_sorted_workspace_bytes': (c_int64, [c_int64, c_int]),
+    'lfgc_codec_kmeans1d_sorted_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    'lfgc_codec_labels_u16_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    'lfgc_codec_pack_labels': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    'lfgc_codec_dequant_f32':(c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     'lfgc_mlp_supported': (c_int, [POINTER(MlpDesc)]),
     'lfgc_grid_channel_stride': (c_int, [c_int]),
     'lfgc_packed_bytes': (c_int64, [POINTER(MlpDesc)]),

@@ -4,6 +4,8 @@
 //   lfgc_codec_mask_f32        bit mask of the non-zero coefficients, MSB first (:204-208, binary_writing :89-107)
 //   lfgc_codec_compact_f32     order-preserving removal of the zeros (:210-212)
 //   lfgc_codec_kmeans1d_f32    2^bits-entry codebook of a 1-D value set by Lloyd iterations + labels (:65-70, :176-186)
+//   lfgc_codec_kmeans1d_sorted_f32 / lfgc_codec_labels_u16_f32   the same for up to 2^16 entries, over sorted values
+//   lfgc_codec_pack_labels     labels -> `bits`-wide MSB-first byte stream (ints_to_bits_to_bytes :79-90, tail left-aligned)
 //   lfgc_codec_dequant_f32     labels (`bits` wide, MSB first) -> codebook values (read_in_data_quantized :255-275)
 //   lfgc_codec_expand_f32      re-insertion of the zeros by the mask (:297-306)
 // Byte / index work, bound by HBM: every kernel streams its input once with coalesced rows; prefix sums are
@@ -175,6 +177,137 @@ __global__ __launch_bounds__(kBlock) void kmeans_label_kernel(const float* __res
         labels[i] = (unsigned char)nearest_centre(s_mid, k, x[i]);
 }
 
+// ---- 1-D k-means over SORTED values, up to 65 536 centres ------------------------------------------------------------------
+// The same Lloyd iteration as above (fp32 midpoints, label = number of midpoints < v, fp64 sums), but in sorted order a
+// cluster is the contiguous range [bound[j], bound[j+1]): no histogram, no atomics, no LDS.
+constexpr int kSumBlock = 1024;                 // sorted values per precomputed fp64 block sum
+
+// Midpoint of two sorted centres.  Between neighbouring floats a < b the sum rounds, and half the time 0.5f * (a + b) is b
+// itself: b would then be labelled a, and a codebook with one centre per value (more centres than values: every small
+// tensor at 16 bits) would not reproduce them.  Such a midpoint is moved one float down, so a centre always owns its value.
+__device__ __forceinline__ float wide_midpoint(float c0, float c1) {
+    const float mid = 0.5f * (c0 + c1);
+    return (mid < c1 || !(c0 < c1)) ? mid : nextafterf(c1, c0);
+}
+
+__device__ __forceinline__ double wave_sum(double s) {               // fixed-shape butterfly: every lane gets the total
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+
+// wave w of the grid: bsum[w] = fp64 sum of xs[w * 1024, min(n, (w + 1) * 1024))
+__global__ __launch_bounds__(kBlock) void sorted_block_sums_kernel(const float* __restrict__ xs, long long n, long long nblocks,
+                                                                   double* __restrict__ bsum) {
+    const long long w = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (w >= nblocks) return;
+    const int lane = threadIdx.x & 63;
+    const long long base = w * kSumBlock;
+    double s = 0.0;
+#pragma unroll
+    for (int t = 0; t < kSumBlock / 64; ++t) {
+        const long long i = base + t * 64 + lane;
+        if (i < n) s += (double)xs[i];
+    }
+    s = wave_sum(s);
+    if (lane == 0) bsum[w] = s;
+}
+
+// thread j (0..k): bound[j] = first sorted index of cluster j; bound[0] = 0, bound[k] = n, otherwise the number of values
+// <= midpoint j-1 (a value's label is the number of midpoints < it, so cluster j-1 ends where the values exceed it)
+__global__ __launch_bounds__(kBlock) void sorted_bounds_kernel(const float* __restrict__ xs, long long n, int k,
+                                                               const float* __restrict__ centres, long long* __restrict__ bound) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j > k) return;
+    long long lo = 0, hi = n;
+    if (j == k) lo = n;
+    else if (j == 0) hi = 0;
+    else {
+        const float mid = wide_midpoint(centres[j - 1], centres[j]);
+        while (lo < hi) {                                        // first index whose value is > mid
+            const long long m = lo + ((hi - lo) >> 1);
+            if (xs[m] <= mid) lo = m + 1; else hi = m;
+        }
+    }
+    bound[j] = lo;
+}
+
+// wave j: centre j = mean of xs[bound[j], bound[j+1]): head piece up to the next multiple of 1024, whole blocks from bsum,
+// tail piece -- lanes stride over each, then one butterfly.  No prefix-sum differences (cancellation).
+__global__ __launch_bounds__(kBlock) void sorted_update_kernel(const float* __restrict__ xs, int k, const long long* __restrict__ bound,
+                                                               const double* __restrict__ bsum, float* __restrict__ centres) {
+    const int j = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (j >= k) return;
+    const int lane = threadIdx.x & 63;
+    const long long lo = bound[j], hi = bound[j + 1];
+    if (hi <= lo) return;                                        // an empty cluster keeps its centre
+    const long long b_lo = (lo + kSumBlock - 1) / kSumBlock;     // first whole block
+    const long long b_hi = hi / kSumBlock;                       // one past the last whole block
+    double s = 0.0;
+    if (b_lo >= b_hi) {                                          // no whole block inside: the range itself
+        for (long long i = lo + lane; i < hi; i += 64) s += (double)xs[i];
+    } else {
+        for (long long i = lo + lane; i < b_lo * kSumBlock; i += 64) s += (double)xs[i];
+        for (long long b = b_lo + lane; b < b_hi; b += 64) s += bsum[b];
+        for (long long i = b_hi * kSumBlock + lane; i < hi; i += 64) s += (double)xs[i];
+    }
+    s = wave_sum(s);
+    if (lane == 0) centres[j] = (float)(s / (double)(hi - lo));
+}
+
+// labels of UNSORTED values against up to 65 536 centres.  LDS holds every (1 << shift)-th midpoint: coarse[t] = midpoint
+// ((t + 1) << shift) - 1; t = number of coarse entries < v puts the label in [t << shift, (t << shift) + (1 << shift) - 1],
+// searched over the centres themselves (L2).  shift = 0: the table is all midpoints and the second search is empty.
+__global__ __launch_bounds__(kBlock) void label_u16_kernel(const float* __restrict__ x, long long n, int k, int shift,
+                                                           const float* __restrict__ centres, unsigned short* __restrict__ labels) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    float* s_coarse = reinterpret_cast<float*>(s_raw);
+    const int nc = (k - 1) >> shift;
+    for (int t = threadIdx.x; t < nc; t += kBlock) {
+        const int m = ((t + 1) << shift) - 1;                    // <= k - 2
+        s_coarse[t] = wide_midpoint(centres[m], centres[m + 1]);
+    }
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+        const float v = x[i];
+        int lo = 0, hi = nc;
+        while (lo < hi) {
+            const int m = (lo + hi) >> 1;
+            if (s_coarse[m] < v) lo = m + 1; else hi = m;
+        }
+        lo <<= shift;
+        hi = lo + (1 << shift) - 1;
+        if (hi > k - 1) hi = k - 1;
+        while (lo < hi) {                                        // midpoints lo .. hi-1 exist: hi <= k - 1
+            const int m = (lo + hi) >> 1;
+            if (wide_midpoint(centres[m], centres[m + 1]) < v) lo = m + 1; else hi = m;
+        }
+        labels[i] = (unsigned short)lo;
+    }
+}
+
+// ---- label packing -----------------------------------------------------------------------------------------------------------
+// thread = one output byte b = stream bits [8b, 8b+8); label i occupies bits [i*bits, (i+1)*bits), MSB first.  At most 8
+// labels overlap a byte; bits past n*bits stay zero (left-aligned tail).  Every offset is 64-bit.
+template <typename L>
+__global__ __launch_bounds__(kBlock) void pack_labels_kernel(const L* __restrict__ labels, long long n, int bits,
+                                                             unsigned char* __restrict__ packed, long long nbytes) {
+    const long long b = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (b >= nbytes) return;
+    const long long bit0 = b * 8;
+    const long long first = bit0 / bits;
+    long long last = (bit0 + 7) / bits;
+    if (last > n - 1) last = n - 1;
+    const unsigned mask = (1u << bits) - 1u;
+    unsigned out = 0;
+    for (long long i = first; i <= last; ++i) {
+        const unsigned lab = (unsigned)labels[i] & mask;
+        const int shift = (int)((i + 1) * bits - (bit0 + 8));   // label bits below the byte's last bit: -7 .. 15
+        out |= shift >= 0 ? lab >> shift : lab << -shift;
+    }
+    packed[b] = (unsigned char)out;
+}
+
 // ---- dequantisation -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void dequant_kernel(const unsigned char* __restrict__ packed, long long packed_bytes,
                                                          int bits, long long n, const float* __restrict__ centres,
@@ -280,6 +413,69 @@ extern "C" int lfgc_codec_kmeans1d_f32(const float* x, int64_t n, int k, float* 
                            x, (long long)n, k, centres, labels);
         LFGC_HIP_CHECK_LAUNCH();
     }
+    return LFGC_OK;
+}
+
+extern "C" int64_t lfgc_codec_kmeans_sorted_workspace_bytes(int64_t n, int k) {
+    if (n < 1 || k < 1 || k > LFGC_CODEC_KMEANS_MAX_K) return 0;
+    const int64_t nblocks = (n + kSumBlock - 1) / kSumBlock;
+    return nblocks * 8 + ((int64_t)k + 1) * 8 + 64;
+}
+
+extern "C" int lfgc_codec_kmeans1d_sorted_f32(const float* x_sorted, int64_t n, int k, float* centres, int iterations,
+                                              void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
+    if (!x_sorted || !centres || !workspace) return LFGC_E_NULL;
+    if (n < 1 || k < 1 || k > LFGC_CODEC_KMEANS_MAX_K || iterations < 0) return LFGC_E_SHAPE;
+    if (workspace_bytes < lfgc_codec_kmeans_sorted_workspace_bytes(n, k)) return LFGC_E_WORKSPACE;
+    const long long nblocks = (n + kSumBlock - 1) / kSumBlock;
+    const long long sum_grid = (nblocks + kBlock / 64 - 1) / (kBlock / 64);
+    if (sum_grid > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
+    double* bsum = reinterpret_cast<double*>(workspace);
+    long long* bound = reinterpret_cast<long long*>(bsum + nblocks);
+    if (iterations > 0) {
+        hipLaunchKernelGGL(sorted_block_sums_kernel, dim3((unsigned)sum_grid), dim3(kBlock), 0, (hipStream_t)stream,
+                           x_sorted, (long long)n, nblocks, bsum);
+        LFGC_HIP_CHECK_LAUNCH();
+    }
+    for (int it = 0; it < iterations; ++it) {
+        hipLaunchKernelGGL(sorted_bounds_kernel, dim3((unsigned)(k / kBlock + 1)), dim3(kBlock), 0, (hipStream_t)stream,
+                           x_sorted, (long long)n, k, centres, bound);
+        LFGC_HIP_CHECK_LAUNCH();
+        hipLaunchKernelGGL(sorted_update_kernel, dim3((unsigned)((k + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
+                           (hipStream_t)stream, x_sorted, k, bound, bsum, centres);
+        LFGC_HIP_CHECK_LAUNCH();
+    }
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_codec_labels_u16_f32(const float* x, int64_t n, int k, const float* centres, uint16_t* labels,
+                                         lfgc_stream_t stream) {
+    if (!x || !centres || !labels) return LFGC_E_NULL;
+    if (n < 1 || k < 1 || k > LFGC_CODEC_KMEANS_MAX_K) return LFGC_E_SHAPE;
+    const int shift = k <= 8192 ? 0 : 8;                         // all midpoints in LDS (<= 32 KB), or every 256th (<= 1 KB)
+    hipLaunchKernelGGL(label_u16_kernel, dim3(blocks_cap(n, kBlock * 4, 4096)), dim3(kBlock), ((k - 1) >> shift) * 4,
+                       (hipStream_t)stream, x, (long long)n, k, shift, centres, labels);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_codec_pack_labels(const void* labels, int label_bytes, int64_t n, int bits, uint8_t* packed,
+                                      int64_t packed_bytes, lfgc_stream_t stream) {
+    if (!labels || !packed) return LFGC_E_NULL;
+    if (n < 1 || bits < 1 || bits > 16 || (label_bytes != 1 && label_bytes != 2) || (bits > 8 && label_bytes != 2))
+        return LFGC_E_SHAPE;
+    if (n > INT64_MAX / 16) return LFGC_E_SHAPE;
+    const long long nbytes = (n * bits + 7) / 8;
+    if (packed_bytes < nbytes) return LFGC_E_SHAPE;
+    const long long grid = (nbytes + kBlock - 1) / kBlock;
+    if (grid > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
+    if (label_bytes == 1)
+        hipLaunchKernelGGL(pack_labels_kernel<unsigned char>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream,
+                           reinterpret_cast<const unsigned char*>(labels), (long long)n, bits, packed, nbytes);
+    else
+        hipLaunchKernelGGL(pack_labels_kernel<unsigned short>, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream,
+                           reinterpret_cast<const unsigned short*>(labels), (long long)n, bits, packed, nbytes);
+    LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }
 

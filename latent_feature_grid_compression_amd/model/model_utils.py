@@ -71,13 +71,20 @@ def get_net_weights_biases(net):
 
 
 def kmeans_quantization(w, q):
-    """(labels, centres) as Python lists like the reference helper (:65-70); the clustering runs on the GPU."""
+    """(labels, centres) as Python lists like the reference helper (:73-76), ``q`` up to 65 536; the clustering runs on the
+    GPU."""
     t = torch.as_tensor(np.asarray(w, dtype=np.float32).reshape(-1))
     centres, labels = ops.codec_kmeans(t.cuda(), int(q))
-    return labels.cpu().tolist(), centres.cpu().tolist()
+    return labels.cpu().numpy().tolist(), centres.cpu().tolist()
 
 
-_BIT_PRECISION = 8        # the reference hard-codes 8 (:141); the reader below accepts any width the header names
+_BIT_PRECISION = 8        # the writer's default width: the only one the reference's own writer emits (:141)
+
+
+def _check_bit_precision(bit_precision) -> int:
+    if isinstance(bit_precision, bool) or not isinstance(bit_precision, (int, np.integer)) or not 1 <= bit_precision <= 16:
+        raise ValueError('bit_precision must be an integer from 1 to 16, got %r' % (bit_precision,))
+    return int(bit_precision)
 
 
 def _device_flat(t: torch.Tensor) -> torch.Tensor:
@@ -91,21 +98,30 @@ def _f32_bytes(t) -> bytes:
     return np.ascontiguousarray(t.detach().cpu().numpy().reshape(-1).astype('<f4')).tobytes()
 
 
-def _quantised_block(values: torch.Tensor) -> bytes:
-    """[2^8 fp32 centres][one label byte per value] (reference write_tensor_quantized :170-182)."""
-    centres, labels = ops.codec_kmeans(values, 1 << _BIT_PRECISION)
-    return _f32_bytes(centres) + labels.cpu().numpy().tobytes()
+def _quantised_block(values: torch.Tensor, bits: int) -> bytes:
+    """[2^bits fp32 centres][labels, `bits` each, MSB first][bits % 8: the last label as uint32] (reference
+    write_tensor_quantized :170-182).  At 8 bits the uint8 label array is the stream; at any other width
+    lfgc_codec_pack_labels packs it, a partial last byte LEFT-aligned (include/lfgc.h) -- what the readers slice."""
+    centres, labels = ops.codec_kmeans(values, 1 << bits)
+    if bits == 8:
+        return _f32_bytes(centres) + labels.cpu().numpy().tobytes()
+    block = _f32_bytes(centres) + ops.codec_pack_labels(labels, bits).cpu().numpy().tobytes()
+    if bits % 8 != 0:
+        block += struct.pack('<I', int(labels[-1:].cpu().numpy()[0]))
+    return block
 
 
-def store_model_parameters(model, filename):
+def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION):
     """Write ``filename`` (header, first / final layer in fp32, hidden layers and the non-zero wavelet coefficients as
-    8-bit codebook indices) and ``filename + "_mask.bnr"`` (bit mask of the non-zero coefficients): reference :120-223."""
+    ``bit_precision``-bit codebook indices, 1 to 16) and ``filename + "_mask.bnr"`` (bit mask of the non-zero
+    coefficients): reference :120-223, whose ``bit_precision = 8`` (:141) is the default here."""
+    bits = _check_bit_precision(bit_precision)
     if len(model.shape_array) == 0:
         raise ValueError('a model without wavelet levels has no grid_size to put in the header (reference :131)')
     grids = [_device_flat(g) for g in model.feature_grid]
     nonzero = [ops.codec_compact(g) for g in grids]
     header = struct.pack('9B', model.num_layer, model.hidden_width, model.input_channel, model.d_in, model.output_channel,
-                         _BIT_PRECISION, int(model.shape_array[-1][0]), len(grids), int(model.feature_grid[0].shape[0]))
+                         bits, int(model.shape_array[-1][0]), len(grids), int(model.feature_grid[0].shape[0]))
     weights, biases = get_net_weights_biases(model)
     with open(filename, 'wb') as f:
         f.write(header)
@@ -116,7 +132,7 @@ def store_model_parameters(model, filename):
         f.write(_f32_bytes(weights[0]))
         f.write(_f32_bytes(biases[0]))
         for w, b in zip(weights[1:-1], biases[1:-1]):
-            f.write(_quantised_block(_device_flat(w)))
+            f.write(_quantised_block(_device_flat(w), bits))
             f.write(_f32_bytes(b))
         f.write(_f32_bytes(weights[-1]))
         f.write(_f32_bytes(biases[-1]))
@@ -124,16 +140,17 @@ def store_model_parameters(model, filename):
             if nz.numel() == 0:
                 raise ValueError('a coefficient tensor without any non-zero entry cannot be quantised (the reference '
                                  'fails in KMeans here as well)')
-            f.write(_quantised_block(nz))
+            f.write(_quantised_block(nz, bits))
     mask = ops.codec_mask(torch.cat(grids))           # one bit stream over all tensors, like the reference's mask_string
     with open(filename + '_mask.bnr', 'wb') as f:
         f.write(mask.cpu().numpy().tobytes())
 
 
-def restore_model(filename):
+def restore_model(filename, wavelet_filter='db2'):
     """Rebuild the model a parameter file + mask file describe (reference :226-332).  Like the reference the network is
-    re-created with 'fourier' embedding (2 frequencies), db2 and no drop layers; unlike it the model is returned on the GPU
-    (it cannot run anywhere else)."""
+    re-created with 'fourier' embedding (2 frequencies) and no drop layers; unlike it the model is returned on the GPU
+    (it cannot run anywhere else).  The format has no field for the wavelet basis: ``wavelet_filter`` (passed on to
+    ``setup_model``) names the one the stored model was built with, db2 like the reference by default."""
     with open(filename, 'rb') as f:
         raw = f.read()
     with open(filename + '_mask.bnr', 'rb') as f:
@@ -200,8 +217,14 @@ def restore_model(filename):
 
     model = setup_model(input_channel=input_channel, hidden_channel=layer_width, out_channel=output_dim,
                         num_layer=n_layers, embedding_type='fourier', n_embedding_freq=2, drop_type='',
-                        drop_momentum=0.025, drop_threshold=0.75, wavelet_filter='db2', grid_features=feature_size,
-                        grid_size=grid_size, checkpoint_path='').to(dev)
+                        drop_momentum=0.025, drop_threshold=0.75, wavelet_filter=wavelet_filter,
+                        grid_features=feature_size, grid_size=grid_size, checkpoint_path='').to(dev)
+    built = [p.numel() for name, p in model.named_parameters() if re.match(r'.*grid.*', name, re.I)]
+    stored = [nz + z for nz, z in zip(grid_sizes, zeros)]
+    if built != stored:
+        raise ValueError('%s holds %d coefficient tensors of %s elements, a %r model of this shape has %d of %s: name the '
+                         'stored model\'s basis with wavelet_filter=' % (filename, len(stored), stored, wavelet_filter,
+                                                                        len(built), built))
     wdx = bdx = gdx = 0
     for name, p in model.named_parameters():        # same name tests, same order as the reference (:316-328)
         if re.match(r'.*grid.*', name, re.I):
