@@ -189,6 +189,29 @@ int lfgc_idwt_level_cl_drop_bwd_len_f32(const float* d_out_cl, const float* taps
                                         const float* const* penalty_grads, int C, int channel_stride,
                                         int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
 
+/* The two drop adjoints with bitwise repeatable factor gradients: every address of a factor-gradient array gets exactly
+ * ONE add.  slice_stride (floats) > 0: d_mul_lll / d_mul_hf are ZERO-FILLED scratch of S slices, slice s at d_mul_* + s *
+ * slice_stride; the channel-first entry writes channel c into slice c (S = C), the channel-last entry writes its channel
+ * group into one slice each (S = channel_stride / 16 where that divides, else channel_stride / 8).  The L1 penalty term
+ * goes to slice 0.  lfgc_sum_slices_f32 then folds the slices in the order 0 .. S-1 into the factor gradient.
+ * slice_stride must hold the larger factor wanted (7 d0 d1 d2 with d_mul_hf, else d0 d1 d2), else LFGC_E_SHAPE.
+ * slice_stride == 0 IS the plain entry (float atomics over the channels); every other argument, check and return code
+ * is the plain entry's. */
+int lfgc_idwt_level_drop_bwd_det_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
+                                         const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                         float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                         int64_t slice_stride, const float* const* penalty_grads, int C,
+                                         int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
+int lfgc_idwt_level_cl_drop_bwd_det_len_f32(const float* d_out_cl, const float* taps, int filter_len,
+                                            const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                            float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                            int64_t slice_stride, const float* const* penalty_grads, int C,
+                                            int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
+                                            lfgc_stream_t stream);
+/* out[i] = ((slices[i] + slices[stride + i]) + slices[2 stride + i]) + ... over nslices slices, i < n <= stride: fixed
+ * order, no atomics.  out may be slice 0 itself. */
+int lfgc_sum_slices_f32(const float* slices, int nslices, int64_t stride, int64_t n, float* out, lfgc_stream_t stream);
+
 /* One drop layer on one tensor outside the decode (the layers' own forward(x)): x, out (C, n), mul (n). */
 int lfgc_drop_apply_f32(const float* x, const float* mul, float threshold, float* out, int C, int64_t n,
                         lfgc_stream_t stream);
@@ -410,6 +433,28 @@ int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions
                       const float* packed, int precision, const float* stash, const float* d_out,
                       float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
                       void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+
+/* lfgc_backward_f32 with an ORDER-INDEPENDENT grid gradient: same arguments, same weight / bias / position gradients.
+ * The feature gradients are scattered in 64-bit fixed point with integer atomics (one power-of-two quantum per call, taken
+ * from max |feature gradient|; each contribution is rounded once, by at most half a quantum, which lies 2^-(61 - ceil(log2
+ * (8 N))) below that maximum), so d_grid_cl is bitwise independent of the order of the samples and of the launch geometry.
+ *   d_grid_cl   OVERWRITTEN, every element (no zero fill needed).  All zero if every feature gradient is zero.  If ANY
+ *               feature gradient of the N samples is non-finite the WHOLE array is NaN (lfgc_backward_f32 poisons only
+ *               the addresses that sample touches): a non-finite gradient never comes out finite.
+ *   workspace   lfgc_backward_det_workspace_bytes(desc, N, D, H, W) bytes: lfgc_backward_f32's scratch + an int64
+ *               accumulator of D H W Cs elements + the maximum word
+ * N == 0 returns like lfgc_backward_f32 (zero weight / bias gradients, d_grid_cl untouched). */
+int64_t lfgc_backward_det_workspace_bytes(const lfgc_mlp_desc* desc, int64_t n_samples, int D, int H, int W);
+int lfgc_backward_det_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions,
+                          const float* grid_cl, int D, int H, int W,
+                          const float* packed, int precision, const float* stash, const float* d_out,
+                          float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
+                          void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+/* Host only: log2 of the quantum lfgc_backward_det_f32 uses for n_samples samples whose largest |feature gradient| has the
+ * fp32 bit pattern max_bits: E - B with 2^E >= max (E minimal) and B = 61 - ceil(log2(8 n_samples)), so that the 8
+ * n_samples contributions that can meet at one address sum to at most 2^61.  0 where no quantum is used (max_bits 0 or
+ * non-finite, n_samples < 1). */
+int lfgc_det_quantum_exp(uint32_t max_bits, int64_t n_samples);
 
 /* Read-only launch-plan queries: which kernel build and launch shape lfgc_forward_f32 / lfgc_backward_f32 pick for these
  * arguments on the current device.  The launchers consume the very structs these entries fill (one selection function

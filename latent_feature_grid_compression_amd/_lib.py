@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('LFGC_LIB_PATH') or os.path.join(PKG_DIR, 'liblfgc.so')   # override: diagnostics builds only
@@ -77,6 +77,11 @@ SIGNATURES = {
     'lfgc_idwt_level_cl_drop_len_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, _TAPS, c_int, c_void_p] +
                                         [c_int] * 8 + [c_void_p]),
     'lfgc_idwt_level_cl_drop_bwd_len_f32': (c_int, [c_void_p, _TAPS, c_int] + [c_void_p] * 8 + [_PP] + [c_int] * 8 + [c_void_p]),
+    'lfgc_idwt_level_drop_bwd_det_len_f32': (c_int, [c_void_p, c_void_p, _TAPS, c_int] + [c_void_p] * 8 + [c_int64, _PP] +
+                                             [c_int] * 7 + [c_void_p]),
+    'lfgc_idwt_level_cl_drop_bwd_det_len_f32': (c_int, [c_void_p, _TAPS, c_int] + [c_void_p] * 8 + [c_int64, _PP] + [c_int] * 8 +
+                                                [c_void_p]),
+    'lfgc_sum_slices_f32': (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     'lfgc_drop_apply_f32': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int64, c_void_p]),
     'lfgc_drop_apply_bwd_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'lfgc_sign_variance_update_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
@@ -106,6 +111,11 @@ SIGNATURES = {
     'lfgc_backward_f32': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, _PP, _PP, c_void_p,
                                   c_void_p, c_int64, c_void_p]),
+    'lfgc_backward_det_workspace_bytes': (c_int64, [POINTER(MlpDesc), c_int64, c_int, c_int, c_int]),
+    'lfgc_backward_det_f32': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, _PP, _PP, c_void_p,
+                                      c_void_p, c_int64, c_void_p]),
+    'lfgc_det_quantum_exp': (c_int, [c_uint32, c_int64]),
     'lfgc_forward_plan': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_int, c_int, c_int, c_int, c_int, c_int,
                                   POINTER(ForwardPlanInfo)]),
     'lfgc_backward_plan': (c_int, [POINTER(MlpDesc), c_int64, c_int, POINTER(BackwardPlanInfo)]),

@@ -525,6 +525,127 @@ __global__ __launch_bounds__(256) void lfgc_bwd_scatter_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// order-independent scatter (lfgc_backward_det_f32): 64-bit fixed point, integer atomics
+// ---------------------------------------------------------------------------------------------------------
+// d_grid[i] = q * sum round(v w / q) with ONE power-of-two quantum q per call: integer addition is associative, so the
+// sum depends on neither the order of the samples nor the launch geometry.  Steps, all on the call's stream:
+//   lfgc_det_zero_kernel     acc = 0, max word = 0 (a kernel, not a memset node: DESIGN.md 3.1)
+//   lfgc_det_max_kernel      max word = max bits of |dfeat| over the n valid rows (unsigned atomicMax: order-independent;
+//                            a non-finite value is any bits >= 0x7f800000 and wins the maximum)
+//   lfgc_bwd_scatter_det_kernel   lfgc_bwd_scatter_kernel op for op up to the fp32 product v w, which is scaled exactly in
+//                            double by 1 / q, rounded to nearest and added with a 64-bit integer atomic
+//   lfgc_det_finish_kernel   d_grid[i] = (float)(acc[i] q) for EVERY element (zeros included: d_grid needs no zero fill);
+//                            max == 0: all zero; non-finite max: all NaN
+struct LfgcDetScatter {
+    long long* acc;            // (D,H,W,Cs) int64 fixed-point accumulator (workspace)
+    unsigned* maxw;            // max bits of |dfeat| (workspace)
+};
+
+constexpr unsigned kLfgcDetNonFinite = 0x7f800000u;
+
+// Exponent of the quantum, q = 2^(E - B): 2^E >= max (E minimal) and B = 61 - ceil(log2(8 n)).  Corner weights are <= 1
+// and at most 8 n contributions meet at one address, so |sum| <= 8 n 2^B <= 2^61: a quarter of the int64 range.
+// max_bits = 0, non-finite bits or n < 1 have no quantum: 0.
+__host__ __device__ inline int lfgc_det_qexp(unsigned max_bits, long long n) {
+    if (max_bits == 0u || max_bits >= kLfgcDetNonFinite || n < 1) return 0;
+    const int e = (int)(max_bits >> 23);
+    const unsigned mant = max_bits & 0x7fffffu;
+    int E;
+    if (e == 0) E = (mant == 1u ? 0 : 32 - __builtin_clz(mant - 1u)) - 149;        // subnormal: mant 2^-149
+    else E = e - 127 + (mant != 0u);
+    const unsigned long long m = 8ull * (unsigned long long)n;                     // >= 8
+    const int B = 61 - (64 - __builtin_clzll(m - 1ull));
+    return E - B;
+}
+
+// 2^k as a double for |k| <= 1022 (lfgc_det_qexp is within [-207, 102])
+__device__ __forceinline__ double lfgc_det_pow2(int k) {
+    return __longlong_as_double((long long)(1023 + k) << 52);
+}
+
+static __global__ __launch_bounds__(256) void lfgc_det_zero_kernel(long long* __restrict__ acc, long long cells,
+                                                                 unsigned* __restrict__ maxw) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;            // cells is a multiple of 8
+    if (i < cells) *reinterpret_cast<u32x4*>(acc + i) = u32x4{0u, 0u, 0u, 0u};
+    if (blockIdx.x == 0 && threadIdx.x == 0) *maxw = 0u;
+}
+
+static __global__ __launch_bounds__(256) void lfgc_det_max_kernel(const float* __restrict__ dfeat, long long count,
+                                                                unsigned* __restrict__ maxw) {
+    unsigned m = 0u;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        const unsigned b = __float_as_uint(dfeat[i]) & 0x7fffffffu;
+        m = b > m ? b : m;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)m, off);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(maxw, m);
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void lfgc_bwd_scatter_det_kernel(const float* __restrict__ pos, const float* __restrict__ dfeat,
+                                                                  long long* __restrict__ acc, const unsigned* __restrict__ maxw,
+                                                                  long long n, int D, int H, int W, int Cs) {
+    constexpr int SPI = 64 / CH;                          // samples per wave-instruction
+    const int lane = threadIdx.x & 63;
+    const long long gw = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int sp = lane / CH, c = lane % CH;
+    const unsigned mb = *maxw;
+    if (sp >= SPI || mb == 0u || mb >= kLfgcDetNonFinite) return;      // nothing to add / the finish pass writes NaN
+    const double inv_q = lfgc_det_pow2(-lfgc_det_qexp(mb, n));
+#pragma unroll 1
+    for (int i = 0; i < 8 / SPI + (8 % SPI != 0); ++i) {
+        const long long smp = gw * 8 + i * SPI + sp;
+        if (i * SPI + sp >= 8 || smp >= n) continue;
+        const float p0 = pos[3 * smp], p1 = pos[3 * smp + 1], p2 = pos[3 * smp + 2];
+        const float ix = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p0, 1.0f), (float)W), 1.0f), 0.5f);
+        const float iy = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p1, 1.0f), (float)H), 1.0f), 0.5f);
+        const float iz = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p2, 1.0f), (float)D), 1.0f), 0.5f);
+        const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
+        const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)W);
+        const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)H);
+        const int z0 = (int)fminf(fmaxf(fz0, -2.0f), (float)D);
+        float wx[2], wy[2], wz[2];
+        wx[1] = __fsub_rn(ix, fx0); wx[0] = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
+        wy[1] = __fsub_rn(iy, fy0); wy[0] = __fsub_rn(__fadd_rn(fy0, 1.0f), iy);
+        wz[1] = __fsub_rn(iz, fz0); wz[0] = __fsub_rn(__fadd_rn(fz0, 1.0f), iz);
+        const float v = dfeat[smp * CH + c];
+#pragma unroll
+        for (int corner = 0; corner < 8; ++corner) {
+            const int dz = corner >> 2, dy = (corner >> 1) & 1, dx = corner & 1;
+            const int xi = x0 + dx, yi = y0 + dy, zi = z0 + dz;
+            const bool ok = (unsigned)xi < (unsigned)W && (unsigned)yi < (unsigned)H && (unsigned)zi < (unsigned)D;
+            const float w = __fmul_rn(__fmul_rn(wx[dx], wy[dy]), wz[dz]);
+            if (ok && w != 0.0f) {
+                const long long k = __double2ll_rn((double)__fmul_rn(v, w) * inv_q);    // |k| <= 2^B: |v| <= max, w <= 1
+                atomicAdd(reinterpret_cast<unsigned long long*>(acc + ((long long)(zi * H + yi) * W + xi) * Cs + c),
+                          (unsigned long long)k);
+            }
+        }
+    }
+}
+
+static __global__ __launch_bounds__(256) void lfgc_det_finish_kernel(const long long* __restrict__ acc,
+                                                                   const unsigned* __restrict__ maxw, long long n,
+                                                                   float* __restrict__ d_grid, long long cells) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;            // cells is a multiple of 8
+    if (i >= cells) return;
+    const unsigned mb = *maxw;
+    f32x4 o;
+    if (mb >= kLfgcDetNonFinite) {
+        o.x = o.y = o.z = o.w = __uint_as_float(0x7fc00000u);
+    } else {
+        const double q = lfgc_det_pow2(lfgc_det_qexp(mb, n));                      // max == 0: acc is all zero
+        o.x = (float)((double)acc[i] * q); o.y = (float)((double)acc[i + 1] * q);
+        o.z = (float)((double)acc[i + 2] * q); o.w = (float)((double)acc[i + 3] * q);
+    }
+    *reinterpret_cast<f32x4*>(d_grid + i) = o;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // weight gradients
 // ---------------------------------------------------------------------------------------------------------
 struct LfgcWgradArgs {
@@ -852,7 +973,7 @@ static int lfgc_launch_bwd_data(const LfgcBwdArgs& a, int lds_bytes, int grid_da
 // waves = waves per workgroup of the data kernel (4 or 8, chosen by the caller together with a.nbatches)
 template <int CH, int MT, int NF>
 static int lfgc_launch_bwd(const LfgcBwdArgs& a, const LfgcWgradArgs& w, int waves, int h16, int lds_bytes, int grid_data,
-                           int grid_w, hipStream_t stream) {
+                           int grid_w, hipStream_t stream, const LfgcDetScatter* det) {
     int rc;
     // h16 = the C-ABI precision code: 0 exact f32 MFMA chain, 1 f16 hi/lo split, 2 single f16 product
     if (h16 == 1) rc = waves == 8 ? lfgc_launch_bwd_data<CH, MT, NF, 8, 1>(a, lds_bytes, grid_data, stream)
@@ -864,8 +985,17 @@ static int lfgc_launch_bwd(const LfgcBwdArgs& a, const LfgcWgradArgs& w, int wav
     if (rc != LFGC_OK) return rc;
     if (a.dfeat) {                                        // deferred scatter of the feature gradients
         const long long blocks = (a.n + 31) / 32;         // 4 waves x 8 samples
-        hipLaunchKernelGGL(lfgc_bwd_scatter_kernel<CH>, dim3((unsigned)blocks), dim3(256), 0, stream, a.pos, a.dfeat, a.d_grid, a.n,
-                           a.D, a.H, a.W, a.Cs);
+        if (det) {                                        // fixed point, integer atomics (the caller zeroes and finishes)
+            const long long count = a.n * CH, mblocks = (count + 255) / 256;
+            hipLaunchKernelGGL(lfgc_det_max_kernel, dim3((unsigned)(mblocks < 2048 ? mblocks : 2048)), dim3(256), 0, stream,
+                               a.dfeat, count, det->maxw);
+            LFGC_HIP_CHECK_LAUNCH();
+            hipLaunchKernelGGL(lfgc_bwd_scatter_det_kernel<CH>, dim3((unsigned)blocks), dim3(256), 0, stream, a.pos, a.dfeat,
+                               det->acc, det->maxw, a.n, a.D, a.H, a.W, a.Cs);
+        } else {
+            hipLaunchKernelGGL(lfgc_bwd_scatter_kernel<CH>, dim3((unsigned)blocks), dim3(256), 0, stream, a.pos, a.dfeat, a.d_grid,
+                               a.n, a.D, a.H, a.W, a.Cs);
+        }
         LFGC_HIP_CHECK_LAUNCH();
     }
     constexpr int NT0_ = LfgcShape<CH, MT, NF>::P.K0R / 32;

@@ -3,7 +3,7 @@
 #include "lfgc_backward.h"
 
 typedef int LfgcBwdDispatch(int MT, const LfgcBwdArgs& a, const LfgcWgradArgs& w, int waves, int precision, int lds_bytes,
-                            int grid_data, int grid_w, hipStream_t stream);
+                            int grid_data, int grid_w, hipStream_t stream, const LfgcDetScatter* det);
 LfgcBwdDispatch lfgc_bwd_dispatch_ch8, lfgc_bwd_dispatch_ch16, lfgc_bwd_dispatch_ch24, lfgc_bwd_dispatch_ch32;
 
 #ifdef LFGC_STAMPS
@@ -63,6 +63,12 @@ lfgc_backward_plan_info bwd_select(const LfgcPlan& p, const Carve& c, long long 
     if (b.grid > b.nbatches) b.grid = b.nbatches;
     return b;
 }
+
+long long carve_floats(const Carve& c) { return c.dstash_floats + c.slab_floats_total + c.dscale_floats + c.dfeat_floats; }
+
+// lfgc_backward_det_f32's tail behind carve_floats(), 16-byte aligned: int64 accumulator (D,H,W,Cs) | max word (16 bytes)
+long long det_offset_bytes(const Carve& c) { return (carve_floats(c) * 4 + 15) / 16 * 16; }
+long long det_cells(const LfgcPlan& p, int D, int H, int W) { return (long long)D * H * W * p.CH; }
 }  // namespace
 
 extern "C" int lfgc_backward_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out) {
@@ -80,14 +86,24 @@ extern "C" int64_t lfgc_backward_workspace_bytes(const lfgc_mlp_desc* desc, int6
     if (n_samples < 0) return LFGC_E_SHAPE;
     const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
     const Carve c = carve(p, n_samples);
-    return (c.dstash_floats + c.slab_floats_total + c.dscale_floats + c.dfeat_floats) * 4;
+    return carve_floats(c) * 4;
 }
 
-extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions,
-                                 const float* grid_cl, int D, int H, int W,
-                                 const float* packed, int precision, const float* stash, const float* d_out,
-                                 float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
-                                 void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
+extern "C" int64_t lfgc_backward_det_workspace_bytes(const lfgc_mlp_desc* desc, int64_t n_samples, int D, int H, int W) {
+    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
+    if (n_samples < 0 || D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
+    const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
+    return det_offset_bytes(carve(p, n_samples)) + det_cells(p, D, H, W) * 8 + 16;
+}
+
+extern "C" int lfgc_det_quantum_exp(uint32_t max_bits, int64_t n_samples) { return lfgc_det_qexp(max_bits, n_samples); }
+
+// det: lfgc_backward_det_f32 (the deferred feature-gradient path + the fixed-point scatter of lfgc_backward.h)
+static int backward_impl(bool det, const lfgc_mlp_desc* desc, const lfgc_positions* positions,
+                         const float* grid_cl, int D, int H, int W,
+                         const float* packed, int precision, const float* stash, const float* d_out,
+                         float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
+                         void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
     if (!desc || !positions || !grid_cl || !packed || !stash || !d_out || !d_grid_cl || !d_weights || !d_biases)
         return LFGC_E_NULL;
     if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
@@ -113,7 +129,9 @@ extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions
         return LFGC_OK;
     }
     const Carve c = carve(p, n);
-    if (!workspace || workspace_bytes < (c.dstash_floats + c.slab_floats_total + c.dscale_floats + c.dfeat_floats) * 4) return LFGC_E_WORKSPACE;
+    const long long cells = det_cells(p, D, H, W);
+    const long long need = det ? det_offset_bytes(c) + cells * 8 + 16 : carve_floats(c) * 4;
+    if (!workspace || workspace_bytes < need) return LFGC_E_WORKSPACE;
     float* dstash = reinterpret_cast<float*>(workspace);
     float* slabs = dstash + c.dstash_floats;
     float* dscale = slabs + c.slab_floats_total;
@@ -142,12 +160,26 @@ extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions
     // in-kernel phase stamps' 40 % "scatter" share is their latency, not an occupancy problem), so the step does not move.
     {
         const char* env = getenv("LFGC_SCATTER");
-        a.dfeat = (env && env[0] == 'd') ? dfeat : nullptr;
+        a.dfeat = (det || (env && env[0] == 'd')) ? dfeat : nullptr;
     }
     a.nbatches = b.nbatches;
+    LfgcDetScatter ds;
+    ds.acc = reinterpret_cast<long long*>(reinterpret_cast<char*>(workspace) + det_offset_bytes(c));
+    ds.maxw = reinterpret_cast<unsigned*>(ds.acc + cells);
+    if (det) {
+        if ((cells / 2 + 255) / 256 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
+        hipLaunchKernelGGL(lfgc_det_zero_kernel, dim3((unsigned)((cells / 2 + 255) / 256)), dim3(256), 0, st, ds.acc, cells, ds.maxw);
+        LFGC_HIP_CHECK_LAUNCH();
+    }
 
-    const int rc = kBwd[p.CH / 8 - 1](p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st);
+    const int rc = kBwd[p.CH / 8 - 1](p.MT, a, w, b.waves, precision, b.lds_bytes, (int)b.grid, b.nslabs * b.roles, st,
+                                      det ? &ds : nullptr);
     if (rc != LFGC_OK) return rc;
+    if (det) {
+        hipLaunchKernelGGL(lfgc_det_finish_kernel, dim3((unsigned)((cells / 4 + 255) / 256)), dim3(256), 0, st, ds.acc, ds.maxw, n,
+                           d_grid_cl, cells);
+        LFGC_HIP_CHECK_LAUNCH();
+    }
 
     LfgcReduceArgs r;
     r.slabs = slabs; r.nslabs = b.nslabs; r.slab_floats = w.slab_floats; r.plan = p;
@@ -163,6 +195,24 @@ extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions
     hipLaunchKernelGGL(lfgc_bwd_reduce_kernel, dim3(g), dim3(256), 0, st, r);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
+}
+
+extern "C" int lfgc_backward_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions,
+                                 const float* grid_cl, int D, int H, int W,
+                                 const float* packed, int precision, const float* stash, const float* d_out,
+                                 float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
+                                 void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
+    return backward_impl(false, desc, positions, grid_cl, D, H, W, packed, precision, stash, d_out, d_grid_cl, d_weights, d_biases,
+                         d_pos, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lfgc_backward_det_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions,
+                                     const float* grid_cl, int D, int H, int W,
+                                     const float* packed, int precision, const float* stash, const float* d_out,
+                                     float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
+                                     void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
+    return backward_impl(true, desc, positions, grid_cl, D, H, W, packed, precision, stash, d_out, d_grid_cl, d_weights, d_biases,
+                         d_pos, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lfgc_backward_bf16(const lfgc_mlp_desc* desc, const lfgc_positions* positions, const float* grid_cl, int D, int H,

@@ -42,6 +42,17 @@ __global__ __launch_bounds__(256) void drop_apply_bwd_kernel(const float* __rest
     if (d_mul) d_mul[i] = acc;
 }
 
+// out[i] = slices[0][i] + slices[1][i] + ... in that order (slice s at slices + s * stride): the fold of the factor-gradient
+// slices the deterministic drop adjoints write (one writer per address), bitwise repeatable
+__global__ __launch_bounds__(256) void sum_slices_kernel(const float* __restrict__ slices, int nslices, long long stride,
+                                                         long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float acc = slices[i];
+    for (int s = 1; s < nslices; ++s) acc = __fadd_rn(acc, slices[(long long)s * stride + i]);
+    out[i] = acc;
+}
+
 // phi = sign(beta) - EMA;  EMA += mom * phi;  EMAVar = (1 - mom) * (EMAVar + mom * phi^2)      -- the reference's fp32
 // operation order (Smallify_Dropout.py:108-112), so the state is bit-identical to its CPU tensors.
 __global__ __launch_bounds__(256) void sign_variance_kernel(const float* __restrict__ betas, float* __restrict__ ema,
@@ -198,6 +209,15 @@ extern "C" int lfgc_drop_apply_bwd_f32(const float* d_out, const float* x, const
     if (C < 1 || n < 1) return LFGC_E_SHAPE;
     hipLaunchKernelGGL(drop_apply_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        d_out, x, mul, d_x, d_mul, C, (long long)n);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_sum_slices_f32(const float* slices, int nslices, int64_t stride, int64_t n, float* out, lfgc_stream_t stream) {
+    if (!slices || !out) return LFGC_E_NULL;
+    if (nslices < 1 || n < 1 || stride < n || (n + 255) / 256 > 0x7fffffffLL) return LFGC_E_SHAPE;
+    hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       slices, nslices, (long long)stride, (long long)n, out);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }

@@ -391,6 +391,9 @@ struct AnalysisArgs {
     const float* mul_h;    // (7, d0,d1,d2) or NULL
     float* d_mul_l;        // (d0,d1,d2) or NULL, pre-zeroed
     float* d_mul_h;        // (7, d0,d1,d2) or NULL, pre-zeroed
+    long long dmul_cstride;   // 0: every channel adds into the one d_mul_l / d_mul_h array (float atomics over the channels);
+                              // else channel c adds into its own slice d_mul_* + c * dmul_cstride: one add onto zero per
+                              // address, exact in any order (lfgc_sum_slices_f32 folds the slices in channel order)
     // penalty gradients folded in (device scalars or NULL): upstream gradient of  sum coef^2  of the low / detail tensor
     // (adds 2 g coef to its gradient) and of  sum |factor|  of a factor that is itself the penalised parameter
     // (Smallify beta: adds g sign(factor) to the factor gradient, once, by the channel-0 workgroups)
@@ -511,7 +514,7 @@ __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs<K> a) 
                 const float x = (a.d_mul_l || a.g_l2_l) ? a.lll[(long long)c * dvol + sp] : 0.0f;
                 if (a.mul_l) {
                     const float m = a.mul_l[sp];
-                    if (a.d_mul_l) atomicAdd(a.d_mul_l + sp, acc[0] * x + ((a.g_l1_l && c == 0) ? *a.g_l1_l * sign_of(m) : 0.0f));
+                    if (a.d_mul_l) atomicAdd(a.d_mul_l + c * a.dmul_cstride + sp, acc[0] * x + ((a.g_l1_l && c == 0) ? *a.g_l1_l * sign_of(m) : 0.0f));
                     acc[0] *= m;
                 }
                 if (a.g_l2_l) acc[0] = __builtin_fmaf(2.0f * *a.g_l2_l, x, acc[0]);
@@ -525,7 +528,7 @@ __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs<K> a) 
                     const float x = (a.d_mul_h || a.g_l2_h) ? a.hf[(long long)c * 7 * dvol + o] : 0.0f;
                     if (a.mul_h) {
                         const float m = a.mul_h[o];
-                        if (a.d_mul_h) atomicAdd(a.d_mul_h + o, acc[s] * x + g1 * sign_of(m));
+                        if (a.d_mul_h) atomicAdd(a.d_mul_h + c * a.dmul_cstride + o, acc[s] * x + g1 * sign_of(m));
                         acc[s] *= m;
                     }
                     acc[s] = __builtin_fmaf(g2, x, acc[s]);
@@ -726,11 +729,11 @@ extern "C" int lfgc_idwt_level_drop_f32(const float* lll, const float* hf, const
                                         C, d0, d1, d2, t0, t1, t2, stream);
 }
 
-extern "C" int lfgc_idwt_level_drop_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
-                                                const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
-                                                float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
-                                                const float* const* penalty_grads, int C, int d0, int d1, int d2,
-                                                int t0, int t1, int t2, lfgc_stream_t stream) {
+extern "C" int lfgc_idwt_level_drop_bwd_det_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
+                                                    const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                                    float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                                    int64_t slice_stride, const float* const* penalty_grads, int C,
+                                                    int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
     const int K = half_len(filter_len, taps);
     if (!K) return LFGC_E_UNSUPPORTED;
     const int rc = check_level(d_out, taps ? (const void*)taps : (const void*)filter_rev, d_lll, d_hf, filter_len, C, d0, d1, d2, t0, t1, t2);
@@ -739,13 +742,25 @@ extern "C" int lfgc_idwt_level_drop_bwd_len_f32(const float* d_out, const float*
     const float* pg[4] = {nullptr, nullptr, nullptr, nullptr};
     if (penalty_grads) for (int i = 0; i < 4; ++i) pg[i] = penalty_grads[i];
     if ((pg[0] && !lll) || (pg[1] && !hf) || (pg[2] && !d_mul_lll) || (pg[3] && !d_mul_hf)) return LFGC_E_NULL;
+    // slices of one factor each at least: the detail factor is the larger one
+    if (slice_stride < 0 || (slice_stride > 0 && slice_stride < (d_mul_hf ? 7 : 1) * (int64_t)d0 * d1 * d2)) return LFGC_E_SHAPE;
     return with_half_len(K, [&](auto kc) {
         constexpr int KK = decltype(kc)::value;
         AnalysisArgs<KK> a = adjoint_args<KK>(d_out, filter_rev, d_lll, d_hf, C, d0, d1, d2, t0, t1, t2);
+        a.dmul_cstride = slice_stride;
         a.lll = lll; a.hf = hf; a.mul_l = mul_lll; a.mul_h = mul_hf; a.d_mul_l = d_mul_lll; a.d_mul_h = d_mul_hf;
         a.g_l2_l = pg[0]; a.g_l2_h = pg[1]; a.g_l1_l = pg[2]; a.g_l1_h = pg[3];
         return launch_analysis<KK>(a, mul_lll || mul_hf || pg[0] || pg[1], taps, (hipStream_t)stream);
     });
+}
+
+extern "C" int lfgc_idwt_level_drop_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
+                                                const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                                float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                                const float* const* penalty_grads, int C, int d0, int d1, int d2,
+                                                int t0, int t1, int t2, lfgc_stream_t stream) {
+    return lfgc_idwt_level_drop_bwd_det_len_f32(d_out, filter_rev, taps, filter_len, lll, hf, mul_lll, mul_hf, d_lll, d_hf,
+                                                d_mul_lll, d_mul_hf, 0, penalty_grads, C, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,

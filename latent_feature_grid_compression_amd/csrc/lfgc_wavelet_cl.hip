@@ -369,6 +369,8 @@ struct AnalysisClArgs {
     float* d_mul_l;        // (d0,d1,d2) or NULL, pre-zeroed
     float* d_mul_h;        // (7, d0,d1,d2) or NULL, pre-zeroed
     const float* g_l2_l; const float* g_l2_h; const float* g_l1_l; const float* g_l1_h;   // penalty gradients folded in
+    int dmul_gstride;      // 0: every channel group adds into the one d_mul_* array; else group cg adds into its own slice
+                           // d_mul_* + cg * dmul_gstride (floats): one add onto zero per address, exact in any order
 };
 
 // Adjoint: band_s[c][i] = sum_t src[2 i + t - lo][c] F_s[t].  Step iz reads the source planes 2 iz - lo0 + L-2 + {0, 1},
@@ -603,7 +605,7 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
                         const float m = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, ml) | __builtin_bit_cast(unsigned, mh));
                         t += (sb == 0 ? g1l : g1h) * sign_of(m);
                     }
-                    atomicAdd((sb == 0 ? a.d_mul_l : a.d_mul_h) + o, t);
+                    atomicAdd((sb == 0 ? a.d_mul_l : a.d_mul_h) + (long long)cg * a.dmul_gstride + o, t);
                 }
             }
             buf ^= 1;
@@ -641,6 +643,7 @@ struct ClDropFwd { const float* mul_l; const float* mul_h; float thr_l, thr_h; }
 struct ClDropBwd {
     const float* lll; const float* hf; const float* mul_l; const float* mul_h; float* d_mul_l; float* d_mul_h;
     const float* pg[4];    // penalty_grads (include/lfgc.h)
+    int gstride;           // AnalysisClArgs::dmul_gstride
 };
 
 int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, const float* taps, int L, int C, int cs,
@@ -717,6 +720,7 @@ int idwt_cl_bwd(const float* d_out_cl, const float* taps, const ClDropBwd& dr, f
     for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
     a.lll = dr.lll; a.hf = dr.hf; a.mul_l = dr.mul_l; a.mul_h = dr.mul_h; a.d_mul_l = dr.d_mul_l; a.d_mul_h = dr.d_mul_h;
     a.g_l2_l = dr.pg[0]; a.g_l2_h = dr.pg[1]; a.g_l1_l = dr.pg[2]; a.g_l1_h = dr.pg[3];
+    a.dmul_gstride = dr.gstride;
     const bool drop = dr.mul_l || dr.mul_h || dr.pg[0] || dr.pg[1];
     const int cw = channel_stride % 16 == 0 ? 16 : 8;
     // cells per workgroup: 64 on a large plane (256-byte runs per (channel, band): one whole line + two shared ones per
@@ -754,9 +758,9 @@ int idwt_cl_entry(bool wide_ok, const float* lll, const float* hf, const float* 
 
 int idwt_cl_bwd_entry(bool wide_ok, const float* d_out_cl, const float* taps, int filter_len, const float* lll, const float* hf,
                       const float* mul_lll, const float* mul_hf, float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
-                      const float* const* penalty_grads, int C, int channel_stride, int d0, int d1, int d2,
+                      int64_t slice_stride, const float* const* penalty_grads, int C, int channel_stride, int d0, int d1, int d2,
                       int t0, int t1, int t2, lfgc_stream_t stream) {
-    ClDropBwd dr = {lll, hf, mul_lll, mul_hf, d_mul_lll, d_mul_hf, {nullptr, nullptr, nullptr, nullptr}};
+    ClDropBwd dr = {lll, hf, mul_lll, mul_hf, d_mul_lll, d_mul_hf, {nullptr, nullptr, nullptr, nullptr}, (int)slice_stride};
     if (penalty_grads) for (int i = 0; i < 4; ++i) dr.pg[i] = penalty_grads[i];
     if (!d_out_cl || !d_lll || !d_hf) return LFGC_E_NULL;
     if ((d_mul_lll && (!mul_lll || !lll)) || (d_mul_hf && (!mul_hf || !hf))) return LFGC_E_NULL;
@@ -764,6 +768,9 @@ int idwt_cl_bwd_entry(bool wide_ok, const float* d_out_cl, const float* taps, in
     const int rc = check_cl(d_out_cl, d_lll, d_hf, d_hf, taps, filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
     if (rc != LFGC_OK) return rc;
     if (C > 32 && !wide_ok) return LFGC_E_UNSUPPORTED;
+    // slices of one factor each at least (the detail factor is the larger one); 4 of them stay below 2^30 floats
+    if (slice_stride < 0 || slice_stride >= (1LL << 28) ||
+        (slice_stride > 0 && slice_stride < (d_mul_hf ? 7 : 1) * (int64_t)d0 * d1 * d2)) return LFGC_E_SHAPE;
     return filter_len == 2 ? idwt_cl_bwd<1>(d_out_cl, taps, dr, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream)
                            : idwt_cl_bwd<2>(d_out_cl, taps, dr, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, (hipStream_t)stream);
 }
@@ -778,13 +785,23 @@ extern "C" int lfgc_idwt_level_cl_drop_len_f32(const float* lll, const float* hf
                          d0, d1, d2, t0, t1, t2, stream);
 }
 
+extern "C" int lfgc_idwt_level_cl_drop_bwd_det_len_f32(const float* d_out_cl, const float* taps, int filter_len,
+                                                       const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
+                                                       float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
+                                                       int64_t slice_stride, const float* const* penalty_grads, int C,
+                                                       int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
+                                                       lfgc_stream_t stream) {
+    return idwt_cl_bwd_entry(false, d_out_cl, taps, filter_len, lll, hf, mul_lll, mul_hf, d_lll, d_hf, d_mul_lll, d_mul_hf,
+                             slice_stride, penalty_grads, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
+}
+
 extern "C" int lfgc_idwt_level_cl_drop_bwd_len_f32(const float* d_out_cl, const float* taps, int filter_len,
                                                    const float* lll, const float* hf, const float* mul_lll, const float* mul_hf,
                                                    float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
                                                    const float* const* penalty_grads, int C, int channel_stride,
                                                    int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
-    return idwt_cl_bwd_entry(false, d_out_cl, taps, filter_len, lll, hf, mul_lll, mul_hf, d_lll, d_hf, d_mul_lll, d_mul_hf,
-                             penalty_grads, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
+    return lfgc_idwt_level_cl_drop_bwd_det_len_f32(d_out_cl, taps, filter_len, lll, hf, mul_lll, mul_hf, d_lll, d_hf, d_mul_lll,
+                                                   d_mul_hf, 0, penalty_grads, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_cl_len_f32(const float* lll, const float* hf, const float* taps, int filter_len, float* out_cl,
@@ -804,7 +821,7 @@ extern "C" int lfgc_idwt_level_cl_bwd_len_f32(const float* d_out_cl, const float
                                               int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
                                               lfgc_stream_t stream) {
     return idwt_cl_bwd_entry(true, d_out_cl, taps, filter_len, nullptr, nullptr, nullptr, nullptr, d_lll, d_hf, nullptr, nullptr,
-                             nullptr, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
+                             0, nullptr, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
 }
 
 extern "C" int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf,

@@ -67,6 +67,10 @@ class Feature_Grid_Model(nn.Module):
         # so the result is reference-equivalent for any finite parameters: include/lfgc.h, lfgc_forward_f32 `status`)
         # or 'fp32' (exact f32 MFMA throughout)
         self.precision = 'f16x2'
+        # bitwise repeatable gradients (fixed-point grid-gradient scatter, one writer per drop-factor gradient address):
+        # None follows torch.are_deterministic_algorithms_enabled(), True / False force the mode.  Promised for the same
+        # build, shapes, precision and device
+        self.deterministic = None
         self._grid_cache = None      # (key, channel-last dense grid) while parameters are unchanged (eval)
         self._pack_cache = None      # (key, packed MLP blob)
         self._penalty_cache = None   # penalty sums taken inside the last differentiable fused decode
@@ -200,6 +204,11 @@ class Feature_Grid_Model(nn.Module):
         return grid
 
     def forward(self, input):
+        # the mode is resolved once per forward; the autograd nodes built below keep it in their ctx for the backward
+        with ops.deterministic_mode(self.deterministic):
+            return self._forward(input)
+
+    def _forward(self, input):
         grid_cl = self._decoded_channel_last()
 
         orig_shape = input.shape
@@ -243,7 +252,8 @@ class Feature_Grid_Model(nn.Module):
 
     def decode_volume(self) -> torch.Tensor:
         """Dense grid (C,G,G,G), channel-first like the reference's decode_volume()."""
-        return self._decode(channel_last=False)
+        with ops.deterministic_mode(self.deterministic):
+            return self._decode(channel_last=False)
 
     # ---- pruning bookkeeping (reference :110-140): pure tensor logic on the drop layers' own methods ------
     def save_dropvalues_on_grid(self, device):

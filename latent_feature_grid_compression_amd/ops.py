@@ -2,9 +2,11 @@
 arithmetic happens in liblfgc.so) and the two autograd Functions of the hot path."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import functools
 import os
+import threading
 import weakref
 from types import SimpleNamespace
 from typing import List, Optional, Sequence, Tuple
@@ -59,6 +61,32 @@ def _on_device(fn):
         with torch.cuda.device(dev):
             return fn(*args, **kwargs)
     return wrapped
+
+
+# ---- deterministic mode ----------------------------------------------------------------------------------
+# Bitwise repeatable gradients: the grid gradient is scattered in 64-bit fixed point and the drop
+# factors' gradients get one writer per address.  The autograd nodes below read the mode once, in their forward, and keep it
+# in their ctx for the backward; their apply() signatures do not carry it.
+
+_MODE = threading.local()
+
+
+def deterministic_enabled() -> bool:
+    """The mode the autograd nodes built right now will run their backward in: the innermost deterministic_mode() of this
+    thread, else torch.are_deterministic_algorithms_enabled()."""
+    forced = getattr(_MODE, 'forced', None)
+    return torch.are_deterministic_algorithms_enabled() if forced is None else forced
+
+
+@contextlib.contextmanager
+def deterministic_mode(flag: Optional[bool]):
+    """Force the mode on (True) or off (False) for the nodes built inside; None follows the torch global."""
+    before = getattr(_MODE, 'forced', None)
+    _MODE.forced = None if flag is None else bool(flag)
+    try:
+        yield
+    finally:
+        _MODE.forced = before
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -206,13 +234,16 @@ def _synthesis(lll, hf, filter_rev, target, mul_l=None, thr_l=None, mul_h=None, 
     return to_channel_last(out) if channel_last else out
 
 
-def _adjoint(d_out, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs, channel_last):
+def _adjoint(d_out, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d, penalty_ptrs, channel_last,
+             deterministic=False):
     """Adjoint of _synthesis -> (d_lll, d_hf, d_mul_l or None, d_mul_h or None).  d_out (C,t0,t1,t2), or with
     channel_last (t0,t1,t2,Cs) and C given.  lll / hf / mul_l / mul_h: the forward's inputs as far as the factor and
     penalty gradients need them, else None.  want_dml / want_dmh: False, True (a zero tensor is allocated) or a
     ZERO-FILLED tensor of the factor's shape to accumulate into.  penalty_ptrs: None or 4 device addresses (0 = none) of
     the upstream gradients of [sum lll^2, sum hf^2, sum |mul_l|, sum |mul_h|] whose own gradients the kernel folds in
-    (include/lfgc.h)."""
+    (include/lfgc.h).  deterministic: every address of a factor gradient gets one writer -- the kernels write S slices
+    (channel-first: one per channel; channel-last: one per channel group) of a zero-filled S x factor scratch, which
+    lfgc_sum_slices_f32 folds in slice order (S == 1 is that already)."""
     _require_hip(d_out, filter_rev, lll, hf, mul_l, mul_h)
     taps = filter_taps(filter_rev)
     L = filter_length(filter_rev)
@@ -244,17 +275,29 @@ def _adjoint(d_out, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d,
     d_mh = want_dmh if torch.is_tensor(want_dmh) else (
         torch.zeros(shapes['mul_h'], dtype=torch.float32, device=dev) if want_dmh else None)
     pen, _keep = (None, None) if penalty_ptrs is None else _lib.ptr_array([int(v) for v in penalty_ptrs])
+    # slices of the deterministic mode: the channel-last adjoint runs channel groups of 16 where they divide the stride
+    nslices = (cs // 16 if cs % 16 == 0 else cs // 8) if use_cl else C
+    stride, sl, sh = 0, d_ml, d_mh
+    if deterministic and nslices > 1 and (d_ml is not None or d_mh is not None):
+        stride = int(np.prod(shapes['mul_h' if d_mh is not None else 'mul_l']))
+        sl = torch.zeros((nslices, stride), dtype=torch.float32, device=dev) if d_ml is not None else None
+        sh = torch.zeros((nslices, stride), dtype=torch.float32, device=dev) if d_mh is not None else None
     operands = (_ptr(given['lll']), _ptr(given['hf']), _ptr(given['mul_l']), _ptr(given['mul_h']), d_lll.data_ptr(),
-                d_hf.data_ptr(), _ptr(d_ml), _ptr(d_mh), pen, C)
+                d_hf.data_ptr(), _ptr(sl), _ptr(sh), stride, pen, C)
     if use_cl:
-        check(_lib.load().lfgc_idwt_level_cl_drop_bwd_len_f32(
+        check(_lib.load().lfgc_idwt_level_cl_drop_bwd_det_len_f32(
             d_out.data_ptr(), taps, L, *operands, cs, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-            'lfgc_idwt_level_cl_drop_bwd_len_f32')
+            'lfgc_idwt_level_cl_drop_bwd_det_len_f32')
     else:
         filter_rev = _f32c(filter_rev)
-        check(_lib.load().lfgc_idwt_level_drop_bwd_len_f32(
+        check(_lib.load().lfgc_idwt_level_drop_bwd_det_len_f32(
             d_out.data_ptr(), filter_rev.data_ptr(), taps, L, *operands, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-            'lfgc_idwt_level_drop_bwd_len_f32')
+            'lfgc_idwt_level_drop_bwd_det_len_f32')
+    if stride:
+        for slices, out in ((sl, d_ml), (sh, d_mh)):
+            if out is not None:
+                check(_lib.load().lfgc_sum_slices_f32(slices.data_ptr(), nslices, stride, out.numel(), out.data_ptr(),
+                                                      _stream(d_out)), 'lfgc_sum_slices_f32')
     return d_lll, d_hf, d_ml, d_mh
 
 
@@ -437,6 +480,7 @@ def _decode_forward(ctx, filter_rev, shape_array, channel_last, thresholds, coef
     ctx.want = [f is not None and f.requires_grad for f in factors]
     ctx.has = [f is not None for f in factors]
     ctx.l1_flags = [bool(f) and factors[i] is not None for i, f in enumerate(l1_flags)]
+    ctx.deterministic = deterministic_enabled()
     det = [c.detach() for c in coeffs]
     fdet = [f.detach() if f is not None else None for f in factors]
     ctx.save_for_backward(*det, *[f for f in fdet if f is not None])
@@ -512,7 +556,7 @@ def _decode_drop_backward(ctx, d_out, d_pen):
         lll = coeffs[0] if (first and (ctx.has[0] or d_pen is not None)) else None
         g, d_hf, d_ml, d_mh = _adjoint(g, C, ctx.filter_rev, lll, coeffs[lvl], ml, factors[lvl],
                                        zeroed[0] if first else False, zeroed[lvl], ctx.dims[lvl][2:], pens,
-                                       ctx.channel_last and lvl == n - 1)
+                                       ctx.channel_last and lvl == n - 1, deterministic=ctx.deterministic)
         d_coef[lvl], d_fac[lvl] = d_hf, d_mh
         if first:
             d_fac[0] = d_ml
@@ -735,25 +779,32 @@ def backward_plan(desc: MlpDesc, n: int, precision: str = 'f16x2', device=None) 
 
 @_on_device
 def backward_raw(desc: MlpDesc, grid_cl, packed, pos, stash, d_out, weights, biases, need_d_pos: bool,
-                 precision: str = 'f16x2'):
+                 precision: str = 'f16x2', deterministic: bool = False):
+    """lfgc_backward_f32 -> (d_grid, d_weights, d_biases, d_pos or None); deterministic: lfgc_backward_det_f32, whose
+    d_grid is bitwise independent of the order of the samples (all NaN if any feature gradient is non-finite)."""
     lib = _lib.load()
     pos = _f32c(pos)
     d_out = _f32c(d_out)
     ps, n = _positions_struct(pos)
     D, H, W, cs = grid_cl.shape
     dev = grid_cl.device
-    d_grid = torch.zeros_like(grid_cl)
+    deterministic = bool(deterministic) and n > 0              # an empty batch returns before anything is written
+    d_grid = torch.empty_like(grid_cl) if deterministic else torch.zeros_like(grid_cl)   # det: every element is written
     d_w = [torch.empty_like(w, dtype=torch.float32, memory_format=torch.contiguous_format) for w in weights]
     d_b = [torch.empty_like(b, dtype=torch.float32, memory_format=torch.contiguous_format) for b in biases]
     d_pos = torch.empty((n, 3), dtype=torch.float32, device=dev) if need_d_pos else None
-    ws_bytes = int(lib.lfgc_backward_workspace_bytes(ctypes.byref(desc), n))
-    ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.lfgc_backward_det_workspace_bytes(ctypes.byref(desc), n, D, H, W) if deterministic else
+                   lib.lfgc_backward_workspace_bytes(ctypes.byref(desc), n))
+    if ws_bytes < 0:
+        check(ws_bytes, 'lfgc_backward_workspace_bytes')
+    ws = torch.empty((max(ws_bytes, 16) + 3) // 4, dtype=torch.float32, device=dev)
     wp, _k1 = _lib.ptr_array([w.data_ptr() for w in d_w])
     bp, _k2 = _lib.ptr_array([b.data_ptr() for b in d_b])
-    check(lib.lfgc_backward_f32(ctypes.byref(desc), ctypes.byref(ps), grid_cl.data_ptr(), D, H, W, packed.data_ptr(),
-                                _lib.PRECISION[precision], stash.data_ptr(), d_out.data_ptr(), d_grid.data_ptr(), wp, bp,
-                                d_pos.data_ptr() if d_pos is not None else None, ws.data_ptr(), ws_bytes,
-                                _stream(grid_cl)), 'lfgc_backward_f32')
+    entry = lib.lfgc_backward_det_f32 if deterministic else lib.lfgc_backward_f32
+    check(entry(ctypes.byref(desc), ctypes.byref(ps), grid_cl.data_ptr(), D, H, W, packed.data_ptr(),
+                _lib.PRECISION[precision], stash.data_ptr(), d_out.data_ptr(), d_grid.data_ptr(), wp, bp,
+                d_pos.data_ptr() if d_pos is not None else None, ws.data_ptr(), ws_bytes,
+                _stream(grid_cl)), 'lfgc_backward_det_f32' if deterministic else 'lfgc_backward_f32')
     return d_grid, d_w, d_b, d_pos
 
 
@@ -771,6 +822,7 @@ class SampleDecodeFn(torch.autograd.Function):
             ctx.precision = precision
             ctx.n_layers = n_layers
             ctx.need_d_pos = pos.requires_grad
+            ctx.deterministic = deterministic_enabled()
             ctx.save_for_backward(pos.detach(), grid_cl.detach(), packed, stash, *[p.detach() for p in params])
         return y.view(-1, 1)
 
@@ -782,7 +834,7 @@ class SampleDecodeFn(torch.autograd.Function):
         L = ctx.n_layers
         weights, biases = params[:L + 1], params[L + 1:]
         d_grid, d_w, d_b, d_pos = backward_raw(ctx.desc, grid_cl, packed, pos, stash, d_y.reshape(-1), weights, biases,
-                                               ctx.need_d_pos, precision=ctx.precision)
+                                               ctx.need_d_pos, precision=ctx.precision, deterministic=ctx.deterministic)
         return (None, d_pos, d_grid, None, None, None) + tuple(d_w) + tuple(d_b)
 
 

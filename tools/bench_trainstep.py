@@ -48,6 +48,9 @@ def main():
                     help='pruning layers on the coefficients + their loss (the reference CLI default is smallify)')
     ap.add_argument('--unfused-drop', action='store_true',
                     help='comparison: apply the drop factors and penalties with torch ops instead of the fused HIP kernels')
+    ap.add_argument('--deterministic', action='store_true',
+                    help='bitwise repeatable gradients (model.deterministic = True): fixed-point grid-gradient scatter, '
+                         'one writer per drop-factor gradient address')
     ap.add_argument('--wavelet', default='db2', help="wavelet basis of the model (db2, haar, ...); db2 is bench.py's")
     args = ap.parse_args()
     from latent_feature_grid_compression_amd.data.Interpolation import trilinear_f_interpolation, trilinear_mse_loss
@@ -57,6 +60,7 @@ def main():
     model = bench.build_model(w, seed=2003, device=dev).train() if args.wavelet == 'db2' else \
         build_model_wavelet(w, 2003, dev, args.wavelet).train()
     model.precision = args.precision
+    model.deterministic = True if args.deterministic else None
     drop_loss = None
     if args.drop_type:
         import torch.nn as nn
@@ -163,6 +167,7 @@ def main():
         out['final_loss'] = float(static_loss)
         out['config'] = 'cfg3 train step replayed from one HIP graph (same work as train_step); drop %s%s' % (
             args.drop_type or 'none', ' (torch ops)' if args.unfused_drop else '')
+        out['deterministic'] = bool(args.deterministic)
         print(json.dumps(out))
         return
     for name, bw in (('fwd_only', False), ('train_step', True)):
@@ -179,6 +184,7 @@ def main():
     out['config'] = 'cfg3: 64^3x32ch grid, MLP 4x128, 32768 lattice samples/step, fp32, Adam; input grad %s; drop %s%s' % (
         'off' if args.no_input_grad else 'on (reference sets requires_grad on positions)', args.drop_type or 'none',
         ' (torch ops)' if args.unfused_drop else '')
+    out['deterministic'] = bool(args.deterministic)
     print(json.dumps(out))
 
 
