@@ -502,6 +502,24 @@ typedef struct lfgc_backward_plan_info {
 
 int lfgc_backward_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out);
 
+/* Gradient of the network output with respect to the sample positions, d out / d pos, and nothing else: what the
+ * reference obtains by marking the positions requires_grad "for gradient calculation of nw" (training/training.py:99) and
+ * differentiating model/Feature_Grid_Model.py:62-75 -- direct columns, Fourier embedding and grid_sample's coordinate
+ * gradient -- without the parameter gradients lfgc_backward_f32 also produces.  Runs the data kernel of lfgc_backward_f32
+ * in a build that writes no dstash, scatters nothing into a d_grid and is followed by no weight-gradient kernel; same
+ * arithmetic per sample, same launch selection (lfgc_input_gradient_plan reports it; nslabs and roles are 0).
+ *   positions   positions->pos must be non-NULL (explicit list only, as the backward)
+ *   stash       device, written by the lfgc_forward_f32 call with the same inputs
+ *   d_out       device (N) upstream gradient, or NULL = ones: the gradient of the (unclamped) output itself
+ *   d_pos       device (N,3), OVERWRITTEN
+ * No workspace, nothing allocated, no synchronisation: graph-capturable like every other entry.  N == 0 returns LFGC_OK at
+ * once.  Zero padding makes the sampler's part zero outside the grid, and the gradient jumps at cell faces. */
+int lfgc_input_gradient_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions,
+                            const float* grid_cl, int D, int H, int W,
+                            const float* packed, int precision, const float* stash, const float* d_out,
+                            float* d_pos, lfgc_stream_t stream);
+int lfgc_input_gradient_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out);
+
 /* The reduced-precision pair under the names SURVEY section 8(b) gives it (BASELINE config 3, "bf16 train step"; the
  * reference itself has no reduced-precision path): exactly lfgc_forward_f32 / lfgc_backward_f32 with precision =
  * LFGC_PRECISION_F16 -- layer GEMMs as single 16-bit products on the matrix pipe, fp32 accumulation, fp32 inputs, outputs
@@ -540,6 +558,13 @@ int lfgc_lattice_positions_f32(const int64_t* flat, int64_t n, const int32_t* re
 int lfgc_lattice_sample_f32(uint64_t seed, int64_t* state, int64_t n, const int32_t* res, const float* min_idx,
                             const float* max_idx, const float* scales, float* raw, float* norm, int64_t* flat_out,
                             lfgc_stream_t stream);
+
+/* The (x_end - x_begin) * res1 * res2 normalised positions of the x-slab [x_begin, x_end) of the volume lattice, row-major
+ * (x, y, z): the positions lfgc_forward_f32 forms for itself when positions->pos == NULL (same device function, same
+ * per-tile arithmetic of visualization/OutputToVTK.py:23-37), written out for entries that take explicit positions only.
+ *   res host int32[3] (each >= 2); tile >= 1 (reference: 32); scales host float[3] (dataset.scales); pos_out device (n,3). */
+int lfgc_lattice_slab_positions_f32(const int32_t* res, int32_t x_begin, int32_t x_end, int32_t tile, const float* scales,
+                                    float* pos_out, lfgc_stream_t stream);
 
 /* trilinear_f_interpolation (data/Interpolation.py:8-44), bit-exact: fp32 lattice coordinates, fp64
  * alpha, fp32 lerps in x, y, z order without contraction.

@@ -119,6 +119,9 @@ SIGNATURES = {
     'lfgc_forward_plan': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_int, c_int, c_int, c_int, c_int, c_int,
                                   POINTER(ForwardPlanInfo)]),
     'lfgc_backward_plan': (c_int, [POINTER(MlpDesc), c_int64, c_int, POINTER(BackwardPlanInfo)]),
+    'lfgc_input_gradient_f32': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
+                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'lfgc_input_gradient_plan': (c_int, [POINTER(MlpDesc), c_int64, c_int, POINTER(BackwardPlanInfo)]),
     'lfgc_forward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'lfgc_backward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
@@ -131,6 +134,7 @@ SIGNATURES = {
                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     'lfgc_lattice_positions_f32': (c_int, [c_void_p, c_int64, POINTER(c_int32), POINTER(c_float), POINTER(c_float),
                                            POINTER(c_float), c_void_p, c_void_p, c_void_p]),
+    'lfgc_lattice_slab_positions_f32': (c_int, [POINTER(c_int32), c_int32, c_int32, c_int32, POINTER(c_float), c_void_p, c_void_p]),
     'lfgc_lattice_sample_f32': (c_int, [c_uint64, c_void_p, c_int64, POINTER(c_int32), POINTER(c_float), POINTER(c_float),
                                         POINTER(c_float), c_void_p, c_void_p, c_void_p, c_void_p]),
     'lfgc_deviation_partial_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -27,13 +27,13 @@ struct LfgcBwdArgs {
     const float* packed;
     int L;
     const float* stash;
-    const float* d_out;        // (N)
+    const float* d_out;        // (N) (the INPUT_ONLY build: or nullptr = ones)
     float* dstash;             // [tiles][L*16*MT][64]
     float* dscale;             // [tiles][L]: the power-of-two scale each tile's dA_l was split with (f16 builds), for the weight kernel
     float* d_grid;             // (D,H,W,Cs), accumulated with float atomics
     float* dfeat;              // nullptr: the data kernel scatters into d_grid itself; else (tiles*32, CH) scratch: it only
                                // writes the feature gradients there and lfgc_bwd_scatter_kernel does the atomics
-    float* d_pos;              // (N,3) or nullptr
+    float* d_pos;              // (N,3) or nullptr (the INPUT_ONLY build: never nullptr)
     long long nbatches;
     unsigned long long* stamps;   // diagnostics builds (-DLFGC_STAMPS, tools/phase_stamps.py bwd): per-wave cycle totals per phase
 };
@@ -160,7 +160,12 @@ constexpr bool lfgc_bwd_offsets_are_the_plans(int L) {
 // PREC (the C-ABI precision code) 0: exact f32 MFMA chain.  1: the chain's GEMMs run f16-split like the default forward
 // build (dA carried as f16 hi+lo fragments, transposed weight images pre-split and scaled; fp32 accumulate, scaled
 // back).  2: reduced precision, the hi halves only (one f16 product).
-template <int CH, int MT, int NF, int WAVES, int PREC>
+// INPUT_ONLY: the build behind lfgc_input_gradient_f32, d out / d pos and nothing else.  The same chain with the same carve
+// and launch geometry, minus everything the parameter gradients need: no dstash and dscale stores, no scatter of the feature
+// gradients (no staging, none of its two barriers, no atomics, no dfeat); all of dX0 is always computed, a.d_out may be
+// nullptr (dy = 1) and a.d_pos is mandatory.  Every difference is an `if constexpr`, so the training instantiations are the
+// kernels they were (DESIGN.md section 3.3 has the resource table).
+template <int CH, int MT, int NF, int WAVES, int PREC, bool INPUT_ONLY = false>
 __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const LfgcBwdArgs a) {
     constexpr bool H16 = PREC != 0;
     constexpr bool SPLIT = PREC == 1;
@@ -249,7 +254,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
         const long long n = tile_idx * LFGC_TILE_SAMPLES + j;
         const bool valid = n < N;
         const long long nc = valid ? n : (N - 1);
-        const float dy = valid ? a.d_out[n] : 0.0f;
+        float dy;
+        if constexpr (INPUT_ONLY) dy = valid ? (a.d_out ? a.d_out[n] : 1.0f) : 0.0f;    // no d_out: the gradient of the output itself
+        else dy = valid ? a.d_out[n] : 0.0f;
         const float* st_tile = a.stash + tile_idx * per_tile;
         float* dst_tile = a.dstash + tile_idx * dper_tile;
 
@@ -269,12 +276,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
             float dA[16 * MT];
             lfgc_snake_bwd<MT>(st_tile + 64 * KS0 + (long long)l * P.stash_layer_floats(), dH, dA, lane);
 #pragma unroll
-            for (int i = 0; i < 16 * MT; ++i) dst_tile[(long long)l * P.stash_layer_floats() + i * 64 + lane] = dA[i];
+            for (int i = 0; i < 16 * MT; ++i) {
+                if constexpr (!INPUT_ONLY) dst_tile[(long long)l * P.stash_layer_floats() + i * 64 + lane] = dA[i];
+            }
             if (H16) {
                 h16x8 Fhi[2 * MT], Flo[2 * MT];
                 float isc;
                 const float sc = lfgc_tile_pow2_scale<16 * MT>(dA, isc);
-                if (lane == 0) a.dscale[tile_idx * L + l] = sc;
+                if constexpr (!INPUT_ONLY) { if (lane == 0) a.dscale[tile_idx * L + l] = sc; }
                 lfgc_split_scaled<2 * MT, SPLIT>(dA, sc, Fhi, Flo);
                 const float* s_row = acquire(l) + j * ST + 8 * hh;
                 const float is = s_inv[l] * isc;
@@ -310,19 +319,23 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
             float dA[16 * MT];
             lfgc_snake_bwd<MT>(st_tile + 64 * KS0, dH, dA, lane);
 #pragma unroll
-            for (int i = 0; i < 16 * MT; ++i) dst_tile[i * 64 + lane] = dA[i];
+            for (int i = 0; i < 16 * MT; ++i) {
+                if constexpr (!INPUT_ONLY) dst_tile[i * 64 + lane] = dA[i];
+            }
             h16x8 Fhi[2 * MT], Flo[2 * MT];
             float isc = 1.0f;
             if (H16) {
                 const float sc = lfgc_tile_pow2_scale<16 * MT>(dA, isc);
-                if (lane == 0) a.dscale[tile_idx * L] = sc;
+                if constexpr (!INPUT_ONLY) { if (lane == 0) a.dscale[tile_idx * L] = sc; }
                 lfgc_split_scaled<2 * MT, SPLIT>(dA, sc, Fhi, Flo);
             }
             const float* s_row = acquire(0) + j * ST + (H16 ? 8 : 4) * hh;
             const float is = H16 ? s_inv[0] * isc : 1.0f;
 #pragma unroll
             for (int m = 0; m < TXA; ++m) {
-                if (m < TXF || a.d_pos) {            // scalar-input rows only when d_pos is wanted (wave-uniform)
+                bool wanted = true;                  // INPUT_ONLY: d_pos is the whole point, every row tile is computed
+                if constexpr (!INPUT_ONLY) wanted = m < TXF || a.d_pos;   // scalar-input rows only when d_pos is wanted (wave-uniform)
+                if (wanted) {
                     f32x16 acc;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -336,7 +349,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
                 }
             }
             if constexpr (NPW > 0) {          // pieces the (few, partly skipped) layer-0 tiles had no k-step for
-                const int done = ((TXF < TXA && !a.d_pos) ? TXF : TXA) * 2 * MT;
+                int done = TXA * 2 * MT;
+                if constexpr (!INPUT_ONLY) done = ((TXF < TXA && !a.d_pos) ? TXF : TXA) * 2 * MT;
                 for (int pi = done; pi < NPW; ++pi) lfgc_dma_piece<WAVES>(dma, pi);
             }
         }
@@ -358,63 +372,94 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
         const bool in_range = (fx0 >= -1.0f) && (fx0 < (float)a.W) && (fy0 >= -1.0f) && (fy0 < (float)a.H) &&
                               (fz0 >= -1.0f) && (fz0 < (float)a.D);
 
-        // ---- scatter d feat into d_grid ----------------------------------------------------------------------
-        // in-kernel (throughput mode: other waves' work covers the atomics' latency): stage [sample][channel] +
-        // per-corner weight / offset in LDS, then one atomic wave-instruction per 64 / CH samples and corner;
-        // deferred (a.dfeat; small batches, one wave per SIMD: 128 dependent-latency atomics per wave were 40 % of
-        // this kernel): only write the feature gradients out, lfgc_bwd_scatter_kernel scatters them at full occupancy
-        const bool stage = a.dfeat == nullptr;            // uniform
-        if (stage) __syncthreads();                       // every wave is done with the layer-0 image: reuse its slot
-        float* s_df = s_ring + ((step - 1) & 1) * SLOT + wave * SC_WAVE;   // [32][SCS]
-        float* s_cw = s_df + 32 * SCS;                    // [32][8] corner weights
-        int* s_co = reinterpret_cast<int*>(s_cw + 32 * 8);   // [32][8] corner row offsets (floats)
-        static_assert(32 * SCS + 32 * 8 + 32 * 8 == SC_WAVE, "a wave's staging is exactly its share of the slot");
-#pragma unroll
-        for (int c4 = 0; c4 < CHH / 4; ++c4) {
-            f32x4 v;
-            v.x = dX[4 * c4 + 0]; v.y = dX[4 * c4 + 1]; v.z = dX[4 * c4 + 2]; v.w = dX[4 * c4 + 3];
-            if (stage) *reinterpret_cast<f32x4*>(s_df + j * SCS + hh * CHH + 4 * c4) = v;
-            else *reinterpret_cast<f32x4*>(a.dfeat + (tile_idx * 32 + j) * CH + hh * CHH + 4 * c4) = v;
-        }
         float gix = 0.0f, giy = 0.0f, giz = 0.0f;
-        if (stage || a.d_pos) {
+        if constexpr (INPUT_ONLY) {
+            // ---- sampler coordinate gradient alone (ATen grid_sampler_3d_backward): the corner loop of the training build
+            // below without its staging.  That build's first staging barrier also told every wave that the layer-0 image's
+            // slot could be written again; nothing writes it here before the next image does, and that DMA is issued behind
+            // the barrier of the NEXT acquire() (the next batch's first layer, or its layer 0 when L == 1), which a wave
+            // reaches only after the MFMAs that read this image: the ring's ordinary rule -- the image of step t is
+            // overwritten after the barrier of step t + 1 -- now holds across the batch boundary as it does inside a batch.
 #pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-            const int dz = corner >> 2, dyc = (corner >> 1) & 1, dx = corner & 1;
-            const int xi = x0 + dx, yi = y0 + dyc, zi = z0 + dz;
-            const bool ok = valid && in_range && xi >= 0 && xi < a.W && yi >= 0 && yi < a.H && zi >= 0 && zi < a.D;
-            const float wxc = dx ? wx1 : wx0, wyc = dyc ? wy1 : wy0, wzc = dz ? wz1 : wz0;
-            const float w = ok ? __fmul_rn(__fmul_rn(wxc, wyc), wzc) : 0.0f;
-            const int xc = min(max(xi, 0), a.W - 1), yc = min(max(yi, 0), a.H - 1), zc = min(max(zi, 0), a.D - 1);
-            const long long off = ((long long)(zc * a.H + yc) * a.W + xc) * a.Cs;
-            if (stage) { if (hh == 0) s_cw[j * 8 + corner] = w; else s_co[j * 8 + corner] = (int)off; }
-            if (a.d_pos && ok) {                           // sampler coordinate gradient (ATen grid_sampler_3d_backward)
-                const float* gp = a.grid + off + hh * CHH;
-                float dot = 0.0f;
+            for (int corner = 0; corner < 8; ++corner) {
+                const int dz = corner >> 2, dyc = (corner >> 1) & 1, dx = corner & 1;
+                const int xi = x0 + dx, yi = y0 + dyc, zi = z0 + dz;
+                const bool ok = valid && in_range && xi >= 0 && xi < a.W && yi >= 0 && yi < a.H && zi >= 0 && zi < a.D;
+                const float wxc = dx ? wx1 : wx0, wyc = dyc ? wy1 : wy0, wzc = dz ? wz1 : wz0;
+                const int xc = min(max(xi, 0), a.W - 1), yc = min(max(yi, 0), a.H - 1), zc = min(max(zi, 0), a.D - 1);
+                const long long off = ((long long)(zc * a.H + yc) * a.W + xc) * a.Cs;
+                if (ok) {
+                    const float* gp = a.grid + off + hh * CHH;
+                    float dot = 0.0f;
 #pragma unroll
-                for (int c4 = 0; c4 < CHH / 4; ++c4) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(gp + 4 * c4);
-                    dot = __builtin_fmaf(v.x, dX[4 * c4 + 0], dot); dot = __builtin_fmaf(v.y, dX[4 * c4 + 1], dot);
-                    dot = __builtin_fmaf(v.z, dX[4 * c4 + 2], dot); dot = __builtin_fmaf(v.w, dX[4 * c4 + 3], dot);
+                    for (int c4 = 0; c4 < CHH / 4; ++c4) {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(gp + 4 * c4);
+                        dot = __builtin_fmaf(v.x, dX[4 * c4 + 0], dot); dot = __builtin_fmaf(v.y, dX[4 * c4 + 1], dot);
+                        dot = __builtin_fmaf(v.z, dX[4 * c4 + 2], dot); dot = __builtin_fmaf(v.w, dX[4 * c4 + 3], dot);
+                    }
+                    gix += (dx ? dot : -dot) * (wyc * wzc);
+                    giy += (dyc ? dot : -dot) * (wxc * wzc);
+                    giz += (dz ? dot : -dot) * (wxc * wyc);
                 }
-                gix += (dx ? dot : -dot) * (wyc * wzc);
-                giy += (dyc ? dot : -dot) * (wxc * wzc);
-                giz += (dz ? dot : -dot) * (wxc * wyc);
             }
-        }
-        }
-        if (stage) {
-            __syncthreads();                              // staging visible to every lane that reads it
-            const int sp = lane / CH, c = lane % CH;
-            if (sp < SPI) {
-                for (int i = 0; i < (32 + SPI - 1) / SPI; ++i) {
-                    const int smp = i * SPI + sp;
-                    if (smp < 32) {
-                        const float v = s_df[smp * SCS + c];
+        } else {
+            // ---- scatter d feat into d_grid ----------------------------------------------------------------------
+            // in-kernel (throughput mode: other waves' work covers the atomics' latency): stage [sample][channel] +
+            // per-corner weight / offset in LDS, then one atomic wave-instruction per 64 / CH samples and corner;
+            // deferred (a.dfeat; small batches, one wave per SIMD: 128 dependent-latency atomics per wave were 40 % of
+            // this kernel): only write the feature gradients out, lfgc_bwd_scatter_kernel scatters them at full occupancy
+            const bool stage = a.dfeat == nullptr;            // uniform
+            if (stage) __syncthreads();                       // every wave is done with the layer-0 image: reuse its slot
+            float* s_df = s_ring + ((step - 1) & 1) * SLOT + wave * SC_WAVE;   // [32][SCS]
+            float* s_cw = s_df + 32 * SCS;                    // [32][8] corner weights
+            int* s_co = reinterpret_cast<int*>(s_cw + 32 * 8);   // [32][8] corner row offsets (floats)
+            static_assert(32 * SCS + 32 * 8 + 32 * 8 == SC_WAVE, "a wave's staging is exactly its share of the slot");
 #pragma unroll
-                        for (int corner = 0; corner < 8; ++corner) {
-                            const float w = s_cw[smp * 8 + corner];
-                            if (w != 0.0f) atomicAdd(a.d_grid + s_co[smp * 8 + corner] + c, v * w);
+            for (int c4 = 0; c4 < CHH / 4; ++c4) {
+                f32x4 v;
+                v.x = dX[4 * c4 + 0]; v.y = dX[4 * c4 + 1]; v.z = dX[4 * c4 + 2]; v.w = dX[4 * c4 + 3];
+                if (stage) *reinterpret_cast<f32x4*>(s_df + j * SCS + hh * CHH + 4 * c4) = v;
+                else *reinterpret_cast<f32x4*>(a.dfeat + (tile_idx * 32 + j) * CH + hh * CHH + 4 * c4) = v;
+            }
+            if (stage || a.d_pos) {
+#pragma unroll
+            for (int corner = 0; corner < 8; ++corner) {
+                const int dz = corner >> 2, dyc = (corner >> 1) & 1, dx = corner & 1;
+                const int xi = x0 + dx, yi = y0 + dyc, zi = z0 + dz;
+                const bool ok = valid && in_range && xi >= 0 && xi < a.W && yi >= 0 && yi < a.H && zi >= 0 && zi < a.D;
+                const float wxc = dx ? wx1 : wx0, wyc = dyc ? wy1 : wy0, wzc = dz ? wz1 : wz0;
+                const float w = ok ? __fmul_rn(__fmul_rn(wxc, wyc), wzc) : 0.0f;
+                const int xc = min(max(xi, 0), a.W - 1), yc = min(max(yi, 0), a.H - 1), zc = min(max(zi, 0), a.D - 1);
+                const long long off = ((long long)(zc * a.H + yc) * a.W + xc) * a.Cs;
+                if (stage) { if (hh == 0) s_cw[j * 8 + corner] = w; else s_co[j * 8 + corner] = (int)off; }
+                if (a.d_pos && ok) {                           // sampler coordinate gradient (ATen grid_sampler_3d_backward)
+                    const float* gp = a.grid + off + hh * CHH;
+                    float dot = 0.0f;
+#pragma unroll
+                    for (int c4 = 0; c4 < CHH / 4; ++c4) {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(gp + 4 * c4);
+                        dot = __builtin_fmaf(v.x, dX[4 * c4 + 0], dot); dot = __builtin_fmaf(v.y, dX[4 * c4 + 1], dot);
+                        dot = __builtin_fmaf(v.z, dX[4 * c4 + 2], dot); dot = __builtin_fmaf(v.w, dX[4 * c4 + 3], dot);
+                    }
+                    gix += (dx ? dot : -dot) * (wyc * wzc);
+                    giy += (dyc ? dot : -dot) * (wxc * wzc);
+                    giz += (dz ? dot : -dot) * (wxc * wyc);
+                }
+            }
+            }
+            if (stage) {
+                __syncthreads();                              // staging visible to every lane that reads it
+                const int sp = lane / CH, c = lane % CH;
+                if (sp < SPI) {
+                    for (int i = 0; i < (32 + SPI - 1) / SPI; ++i) {
+                        const int smp = i * SPI + sp;
+                        if (smp < 32) {
+                            const float v = s_df[smp * SCS + c];
+#pragma unroll
+                            for (int corner = 0; corner < 8; ++corner) {
+                                const float w = s_cw[smp * 8 + corner];
+                                if (w != 0.0f) atomicAdd(a.d_grid + s_co[smp * 8 + corner] + c, v * w);
+                            }
                         }
                     }
                 }
@@ -965,23 +1010,28 @@ static __global__ __launch_bounds__(256) void lfgc_bwd_reduce_kernel(const LfgcR
     if (q == 0 && idx < total) *dst = ((part[0][o] + part[1][o]) + part[2][o]) + part[3][o];
 }
 
-template <int CH, int MT, int NF, int WAVES, int PREC>
+template <int CH, int MT, int NF, int WAVES, int PREC, bool INPUT_ONLY>
 static int lfgc_launch_bwd_data(const LfgcBwdArgs& a, int lds_bytes, int grid_data, hipStream_t stream) {
-    return lfgc_launch<lfgc_bwd_data_kernel<CH, MT, NF, WAVES, PREC>>(dim3(grid_data), dim3(WAVES * 64), lds_bytes, stream, a);
+    return lfgc_launch<lfgc_bwd_data_kernel<CH, MT, NF, WAVES, PREC, INPUT_ONLY>>(dim3(grid_data), dim3(WAVES * 64), lds_bytes,
+                                                                                  stream, a);
 }
 
-// waves = waves per workgroup of the data kernel (4 or 8, chosen by the caller together with a.nbatches)
+// The data kernel's build for (waves, h16): waves = waves per workgroup (4 or 8, chosen by the caller together with
+// a.nbatches), h16 = the C-ABI precision code: 0 exact f32 MFMA chain, 1 f16 hi/lo split, 2 single f16 product.
+template <int CH, int MT, int NF, bool INPUT_ONLY>
+static int lfgc_launch_bwd_data_any(const LfgcBwdArgs& a, int waves, int h16, int lds_bytes, int grid_data, hipStream_t stream) {
+    if (h16 == 1) return waves == 8 ? lfgc_launch_bwd_data<CH, MT, NF, 8, 1, INPUT_ONLY>(a, lds_bytes, grid_data, stream)
+                                    : lfgc_launch_bwd_data<CH, MT, NF, 4, 1, INPUT_ONLY>(a, lds_bytes, grid_data, stream);
+    if (h16 == 2) return waves == 8 ? lfgc_launch_bwd_data<CH, MT, NF, 8, 2, INPUT_ONLY>(a, lds_bytes, grid_data, stream)
+                                    : lfgc_launch_bwd_data<CH, MT, NF, 4, 2, INPUT_ONLY>(a, lds_bytes, grid_data, stream);
+    return waves == 8 ? lfgc_launch_bwd_data<CH, MT, NF, 8, 0, INPUT_ONLY>(a, lds_bytes, grid_data, stream)
+                      : lfgc_launch_bwd_data<CH, MT, NF, 4, 0, INPUT_ONLY>(a, lds_bytes, grid_data, stream);
+}
+
 template <int CH, int MT, int NF>
 static int lfgc_launch_bwd(const LfgcBwdArgs& a, const LfgcWgradArgs& w, int waves, int h16, int lds_bytes, int grid_data,
                            int grid_w, hipStream_t stream, const LfgcDetScatter* det) {
-    int rc;
-    // h16 = the C-ABI precision code: 0 exact f32 MFMA chain, 1 f16 hi/lo split, 2 single f16 product
-    if (h16 == 1) rc = waves == 8 ? lfgc_launch_bwd_data<CH, MT, NF, 8, 1>(a, lds_bytes, grid_data, stream)
-                                  : lfgc_launch_bwd_data<CH, MT, NF, 4, 1>(a, lds_bytes, grid_data, stream);
-    else if (h16 == 2) rc = waves == 8 ? lfgc_launch_bwd_data<CH, MT, NF, 8, 2>(a, lds_bytes, grid_data, stream)
-                                       : lfgc_launch_bwd_data<CH, MT, NF, 4, 2>(a, lds_bytes, grid_data, stream);
-    else rc = waves == 8 ? lfgc_launch_bwd_data<CH, MT, NF, 8, 0>(a, lds_bytes, grid_data, stream)
-                         : lfgc_launch_bwd_data<CH, MT, NF, 4, 0>(a, lds_bytes, grid_data, stream);
+    const int rc = lfgc_launch_bwd_data_any<CH, MT, NF, false>(a, waves, h16, lds_bytes, grid_data, stream);
     if (rc != LFGC_OK) return rc;
     if (a.dfeat) {                                        // deferred scatter of the feature gradients
         const long long blocks = (a.n + 31) / 32;         // 4 waves x 8 samples

@@ -5,6 +5,8 @@
 typedef int LfgcBwdDispatch(int MT, const LfgcBwdArgs& a, const LfgcWgradArgs& w, int waves, int precision, int lds_bytes,
                             int grid_data, int grid_w, hipStream_t stream, const LfgcDetScatter* det);
 LfgcBwdDispatch lfgc_bwd_dispatch_ch8, lfgc_bwd_dispatch_ch16, lfgc_bwd_dispatch_ch24, lfgc_bwd_dispatch_ch32;
+typedef int LfgcIgradDispatch(int MT, const LfgcBwdArgs& a, int waves, int precision, int lds_bytes, int grid_data, hipStream_t stream);
+LfgcIgradDispatch lfgc_igrad_dispatch_ch8, lfgc_igrad_dispatch_ch16, lfgc_igrad_dispatch_ch24, lfgc_igrad_dispatch_ch32;
 
 #ifdef LFGC_STAMPS
 static unsigned long long* g_bwd_stamps = nullptr;
@@ -19,6 +21,7 @@ namespace {
 const int kMaxSlabs = LFGC_MAX_SLABS;   // workgroups of the weight-gradient kernel (one partial slab each)
 // The per-channel instantiation files' entries, by CH / 8 - 1 (CH = 8, 16, 24, 32: lfgc_mlp_supported).
 LfgcBwdDispatch* const kBwd[4] = {lfgc_bwd_dispatch_ch8, lfgc_bwd_dispatch_ch16, lfgc_bwd_dispatch_ch24, lfgc_bwd_dispatch_ch32};
+LfgcIgradDispatch* const kIgrad[4] = {lfgc_igrad_dispatch_ch8, lfgc_igrad_dispatch_ch16, lfgc_igrad_dispatch_ch24, lfgc_igrad_dispatch_ch32};
 
 struct Carve {
     long long ntiles, nbatches;
@@ -213,6 +216,39 @@ extern "C" int lfgc_backward_det_f32(const lfgc_mlp_desc* desc, const lfgc_posit
                                      void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
     return backward_impl(true, desc, positions, grid_cl, D, H, W, packed, precision, stash, d_out, d_grid_cl, d_weights, d_biases,
                          d_pos, workspace, workspace_bytes, stream);
+}
+
+// The input-gradient entry: the data kernel's INPUT_ONLY build under the launch bwd_select picks for the training build
+// (the same carve, waves, passes and grid), and nothing else -- no workspace, no weight-gradient kernel, no reduction.
+extern "C" int lfgc_input_gradient_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out) {
+    const int rc = lfgc_backward_plan(desc, n_samples, precision, out);
+    if (rc == LFGC_OK) out->nslabs = out->roles = 0;      // there is no weight-gradient kernel behind this one
+    return rc;
+}
+
+extern "C" int lfgc_input_gradient_f32(const lfgc_mlp_desc* desc, const lfgc_positions* positions,
+                                       const float* grid_cl, int D, int H, int W,
+                                       const float* packed, int precision, const float* stash, const float* d_out,
+                                       float* d_pos, lfgc_stream_t stream) {
+    if (!desc || !positions || !grid_cl || !packed || !stash || !d_pos) return LFGC_E_NULL;
+    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
+    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
+    if (!positions->pos) return LFGC_E_NULL;            // explicit positions only, like the backward
+    if (positions->n < 0 || D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
+    if ((((uintptr_t)grid_cl) | ((uintptr_t)packed) | ((uintptr_t)stash)) & 15) return LFGC_E_ALIGN;
+    const long long n = positions->n;
+    if (n == 0) return LFGC_OK;
+    const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
+    const lfgc_backward_plan_info b = bwd_select(p, carve(p, n), n);
+
+    LfgcBwdArgs a;
+    a.pos = positions->pos; a.n = n;
+    a.grid = grid_cl; a.D = D; a.H = H; a.W = W; a.Cs = p.CH;
+    a.packed = packed; a.L = p.L; a.stash = stash; a.d_out = d_out;
+    a.dstash = nullptr; a.dscale = nullptr; a.d_grid = nullptr; a.dfeat = nullptr; a.d_pos = d_pos;
+    a.nbatches = b.nbatches;
+    a.stamps = nullptr;
+    return kIgrad[p.CH / 8 - 1](p.MT, a, b.waves, precision, b.lds_bytes, (int)b.grid, (hipStream_t)stream);
 }
 
 extern "C" int lfgc_backward_bf16(const lfgc_mlp_desc* desc, const lfgc_positions* positions, const float* grid_cl, int D, int H,

@@ -56,7 +56,11 @@ struct LfgcFwdArgs {
 
 // Lattice coordinate of voxel v along one axis, formed like field_from_net does per tile
 // (visualization/OutputToVTK.py:23-37) + torch.linspace's CPU formula (start + step*i below the
-// midpoint, end - step*(n-1-i) above).
+// midpoint, end - step*(n-1-i) above).  ATen's build contracts each of the two into ONE fused multiply-add on every host
+// with FMA units (ATEN_CPU_CAPABILITY avx2 / avx512; only the `default` capability rounds the product first), and the
+// reference's recorded tiles (tests/golden/tiles_70x40x33.npz) carry that rounding: so does this function.  The unfused
+// form was off by one ulp of the linspace value (1.2e-7 after 2x - 1) at about a tenth of the coordinates of a lattice
+// whose edge - 1 is no power of two; a 256-voxel edge gives the same bits either way.
 __device__ __forceinline__ float lfgc_lattice_coord(int v, int res, int tile, float scale) {
     const int tb = (v / tile) * tile;
     const int te = min(tb + tile, res);
@@ -74,8 +78,8 @@ __device__ __forceinline__ float lfgc_lattice_coord(int v, int res, int tile, fl
         lin = start;
     } else {
         const float step = __fdiv_rn(__fsub_rn(end, start), (float)(cnt - 1));
-        lin = (i < cnt / 2) ? __fadd_rn(start, __fmul_rn(step, (float)i))
-                            : __fsub_rn(end, __fmul_rn(step, (float)(cnt - i - 1)));
+        lin = (i < cnt / 2) ? __fmaf_rn(step, (float)i, start)
+                            : __fmaf_rn(-step, (float)(cnt - i - 1), end);
     }
     const float nrm = __fsub_rn(__fmul_rn(2.0f, lin), 1.0f);
     return __fmul_rn(scale, nrm);

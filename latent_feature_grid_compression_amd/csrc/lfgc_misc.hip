@@ -1,5 +1,6 @@
 // lfgc_misc.hip -- ground-truth sampler, deviation statistics, parameter packing (gfx950).
 #include "lfgc_common.h"
+#include "lfgc_forward.h"    // lfgc_lattice_coord
 #include <math.h>
 
 namespace {
@@ -121,6 +122,24 @@ __global__ __launch_bounds__(256) void lattice_positions_kernel(const LatticeArg
     a.norm[3 * i + 0] = nrm(r0, a.min0, a.max0, a.sc0);
     a.norm[3 * i + 1] = nrm(r1, a.min1, a.max1, a.sc1);
     a.norm[3 * i + 2] = nrm(r2, a.min2, a.max2, a.sc2);
+}
+
+// Normalised positions of the x-slab [x_begin, x_end) of the volume lattice, row-major (x, y, z): what the fused forward
+// forms in registers in lattice mode, written out -- through that kernel's own lfgc_lattice_coord.  One thread per voxel.
+struct SlabPositionsArgs {
+    float* pos; long long n;
+    int res0, res1, res2, x_begin, tile;
+    float sc0, sc1, sc2;
+};
+
+__global__ __launch_bounds__(256) void lattice_slab_positions_kernel(const SlabPositionsArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const long long plane = (long long)a.res1 * a.res2, rem = i % plane;
+    const int vx = a.x_begin + (int)(i / plane), vy = (int)(rem / a.res2), vz = (int)(rem % a.res2);
+    a.pos[3 * i + 0] = lfgc_lattice_coord(vx, a.res0, a.tile, a.sc0);
+    a.pos[3 * i + 1] = lfgc_lattice_coord(vy, a.res1, a.tile, a.sc1);
+    a.pos[3 * i + 2] = lfgc_lattice_coord(vz, a.res2, a.tile, a.sc2);
 }
 
 // visualization/OutputToVTK.py:53-60 partial sums (fp64 accumulation).
@@ -452,6 +471,24 @@ extern "C" int lfgc_lattice_positions_f32(const int64_t* flat, int64_t n, const 
     a.max0 = max_idx[0]; a.max1 = max_idx[1]; a.max2 = max_idx[2];
     a.sc0 = scales[0]; a.sc1 = scales[1]; a.sc2 = scales[2];
     hipLaunchKernelGGL(lattice_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_lattice_slab_positions_f32(const int32_t* res, int32_t x_begin, int32_t x_end, int32_t tile,
+                                               const float* scales, float* pos_out, lfgc_stream_t stream) {
+    if (!res || !scales || !pos_out) return LFGC_E_NULL;
+    if (res[0] < 2 || res[1] < 2 || res[2] < 2 || tile < 1) return LFGC_E_SHAPE;          // lfgc_fill_positions' rules
+    if (x_begin < 0 || x_end > res[0] || x_end < x_begin) return LFGC_E_SHAPE;
+    const long long n = (long long)(x_end - x_begin) * res[1] * res[2];
+    if (n == 0) return LFGC_OK;
+    const long long blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
+    SlabPositionsArgs a;
+    a.pos = pos_out; a.n = n;
+    a.res0 = res[0]; a.res1 = res[1]; a.res2 = res[2]; a.x_begin = x_begin; a.tile = tile;
+    a.sc0 = scales[0]; a.sc1 = scales[1]; a.sc2 = scales[2];
+    hipLaunchKernelGGL(lattice_slab_positions_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }

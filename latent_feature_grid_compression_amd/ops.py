@@ -713,10 +713,12 @@ def _positions_struct(pos: Optional[torch.Tensor], lattice=None) -> Tuple[Positi
 @_on_device
 def forward_raw(desc: MlpDesc, grid_cl: torch.Tensor, packed: torch.Tensor, pos: Optional[torch.Tensor] = None,
                 lattice=None, clamp: bool = False, want_stash: bool = False, out: Optional[torch.Tensor] = None,
-                precision: str = 'f16x2', range_fallback: bool = True, return_status: bool = False):
+                precision: str = 'f16x2', range_fallback: bool = True, return_status: bool = False,
+                stash: Optional[torch.Tensor] = None):
     """lfgc_forward_f32.  pos (N,3) or lattice=(res, x_begin, x_end, tile).  Returns (y (N,), stash or None)
     [+ the device status word with return_status].  range_fallback=False returns out-of-range samples of the f16
-    builds as NaN instead of redoing the pass on the exact build (diagnostics)."""
+    builds as NaN instead of redoing the pass on the exact build (diagnostics).  stash: with want_stash, a contiguous fp32
+    buffer to write the stash into when it is large enough (a caller that runs chunk after chunk reuses one)."""
     lib = _lib.load()
     _require_hip(grid_cl, packed, pos)
     if pos is not None:
@@ -729,9 +731,13 @@ def forward_raw(desc: MlpDesc, grid_cl: torch.Tensor, packed: torch.Tensor, pos:
         out = torch.empty(n, dtype=torch.float32, device=grid_cl.device)
     if n == 0:
         return out, (torch.empty(0, dtype=torch.float32, device=grid_cl.device) if want_stash else None)
-    stash = None
     if want_stash:
-        stash = torch.empty(int(lib.lfgc_stash_bytes(ctypes.byref(desc), n)) // 4, dtype=torch.float32, device=grid_cl.device)
+        floats = int(lib.lfgc_stash_bytes(ctypes.byref(desc), n)) // 4
+        if (stash is None or stash.numel() < floats or stash.dtype != torch.float32 or not stash.is_contiguous()
+                or stash.device != grid_cl.device):
+            stash = torch.empty(floats, dtype=torch.float32, device=grid_cl.device)
+    else:
+        stash = None
     # range status word of the f16 builds: the library clears it, the kernel sets it, and the exact-fp32 redo the library
     # enqueues behind the kernel is predicated on it -- all in stream order, nothing is read back here
     status = torch.empty(1, dtype=torch.int32, device=grid_cl.device) if (range_fallback and precision != 'fp32') else None
@@ -806,6 +812,55 @@ def backward_raw(desc: MlpDesc, grid_cl, packed, pos, stash, d_out, weights, bia
                 d_pos.data_ptr() if d_pos is not None else None, ws.data_ptr(), ws_bytes,
                 _stream(grid_cl)), 'lfgc_backward_det_f32' if deterministic else 'lfgc_backward_f32')
     return d_grid, d_w, d_b, d_pos
+
+
+def input_gradient_plan(desc: MlpDesc, n: int, precision: str = 'f16x2', device=None) -> SimpleNamespace:
+    """lfgc_input_gradient_plan: the launch input_gradient_raw would make for n samples on `device` (default: the current
+    one).  Fields as backward_plan's; nslabs and roles are 0 (no weight-gradient kernel follows)."""
+    info = _lib.BackwardPlanInfo()
+    with torch.cuda.device(device):
+        check(_lib.load().lfgc_input_gradient_plan(ctypes.byref(desc), int(n), _lib.PRECISION[precision], ctypes.byref(info)),
+              'lfgc_input_gradient_plan')
+    return SimpleNamespace(**{name: int(getattr(info, name)) for name, _t in _lib.BackwardPlanInfo._fields_})
+
+
+@_on_device
+def input_gradient_raw(desc: MlpDesc, grid_cl, packed, pos, stash, d_out=None, precision: str = 'f16x2',
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """lfgc_input_gradient_f32 -> (N,3) = d_out * d y / d pos (d_out None: ones, the gradient of the unclamped output).
+    stash: written by forward_raw(want_stash=True) for the same grid, blob and positions.  out: a contiguous fp32 (N,3)
+    tensor (or view) to write into.  Builds no autograd graph, needs no workspace."""
+    _require_hip(grid_cl, packed, pos, stash, d_out, out)
+    pos = _f32c(pos)
+    ps, n = _positions_struct(pos)
+    D, H, W, cs = grid_cl.shape
+    if cs != grid_channel_stride(desc.grid_channels):
+        raise ValueError('channel-last grid has stride %d, expected %d' % (cs, grid_channel_stride(desc.grid_channels)))
+    if d_out is not None:
+        d_out = _f32c(d_out).reshape(-1)
+        if d_out.numel() != n:
+            raise ValueError('d_out has %d elements for %d positions' % (d_out.numel(), n))
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=grid_cl.device)
+    elif tuple(out.shape) != (n, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('out must be contiguous fp32 of shape (%d, 3)' % n)
+    if n == 0:
+        return out
+    if stash.numel() * 4 < int(_lib.load().lfgc_stash_bytes(ctypes.byref(desc), n)):
+        raise ValueError('stash too small for %d samples' % n)
+    check(_lib.load().lfgc_input_gradient_f32(ctypes.byref(desc), ctypes.byref(ps), grid_cl.data_ptr(), D, H, W,
+                                              packed.data_ptr(), _lib.PRECISION[precision], stash.data_ptr(), _ptr(d_out),
+                                              out.data_ptr(), _stream(grid_cl)), 'lfgc_input_gradient_f32')
+    return out
+
+
+def gradient_chunk_samples(desc: MlpDesc, n: int, max_stash_bytes: int) -> int:
+    """Samples per chunk of a value-and-gradient pass over n samples: the largest multiple of 256 whose stash
+    (lfgc_stash_bytes: whole 256-sample groups) fits max_stash_bytes -- never below 256 and never beyond n rounded up to
+    256.  Host arithmetic only."""
+    per_group = int(_lib.load().lfgc_stash_bytes(ctypes.byref(desc), 256))
+    groups = max(1, int(max_stash_bytes) // per_group)
+    return 256 * max(1, min(groups, (int(n) + 255) // 256))
 
 
 class SampleDecodeFn(torch.autograd.Function):
@@ -1060,6 +1115,21 @@ def lattice_positions(flat: torch.Tensor, res, min_idx, max_idx, scales) -> Tupl
     check(_lib.load().lfgc_lattice_positions_f32(flat.data_ptr(), n, r3, _float3(min_idx), _float3(max_idx), _float3(scales),
                                                  raw.data_ptr(), norm.data_ptr(), _stream(flat)), 'lfgc_lattice_positions_f32')
     return raw, norm
+
+
+def lattice_slab_positions(res, x_begin: int, x_end: int, tile: int, scales, device) -> torch.Tensor:
+    """((x_end - x_begin) * Y * Z, 3) normalised positions of the x-slab [x_begin, x_end) of the volume lattice, row-major
+    (x, y, z): lfgc_lattice_slab_positions_f32, the positions the fused forward forms for itself in lattice mode."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.LfgcError('the slab positions are formed on the MI355X only: got device %s; there is no CPU fallback.' % device)
+    n = (int(x_end) - int(x_begin)) * int(res[1]) * int(res[2])
+    with torch.cuda.device(device):
+        out = torch.empty((max(n, 0), 3), dtype=torch.float32, device=device)
+        r3 = (ctypes.c_int32 * 3)(*[int(x) for x in res])
+        check(_lib.load().lfgc_lattice_slab_positions_f32(r3, int(x_begin), int(x_end), int(tile), _float3(scales),
+                                                          out.data_ptr(), _stream(out)), 'lfgc_lattice_slab_positions_f32')
+    return out
 
 
 @_on_device

@@ -62,6 +62,85 @@ def field_from_net_fused(dataset, net, x_begin: int = 0, x_end: Optional[int] = 
     return y.view(x_end - x_begin, res[1], res[2])
 
 
+def index_units_factor(dataset) -> float:
+    """d(normalised position) / d(voxel index), the same for all three axes: positions_for maps index i_a to
+    scales_a * (2 i_a / max_idx_a - 1) with scales_a = max_idx_a / max_dim, i.e. a slope of 2 / max_dim."""
+    return 2.0 / float(dataset.max_dim)
+
+
+def _row_chunks(net, n_rows: int, row_samples: int, max_stash_bytes: int):
+    """[begin, end) row ranges (relative) whose stash fits max_stash_bytes; at least one row per chunk."""
+    rows = max(1, ops.gradient_chunk_samples(net._descriptor(), n_rows * row_samples, max_stash_bytes) // row_samples)
+    return [(b, min(b + rows, n_rows)) for b in range(0, n_rows, rows)]
+
+
+def gradient_field_from_net(dataset, net, x_begin: int = 0, x_end: Optional[int] = None, tiled_res: int = 32,
+                            out: Optional[torch.Tensor] = None, index_units: bool = False,
+                            max_stash_bytes: int = 1 << 30) -> torch.Tensor:
+    """Gradient of the (unclamped) output of ``net`` with respect to the normalised position at every voxel of the x-slab
+    [x_begin, x_end) of the volume lattice: (x_end - x_begin, Y, Z, 3) on the device.  Chunks of whole x-rows run
+    ops.lattice_slab_positions -> forward with stash -> ops.input_gradient_raw straight into views of the result; the
+    positions are the ones ``field_from_net_fused`` forms inside its kernel.
+
+    ``index_units=True`` multiplies by ``index_units_factor(dataset)`` = 2 / max_dim: the gradient per voxel step.
+    (``finite_difference_trilinear_grad(..., scale=dataset.scales)`` is in the default units of this function;
+    with ``scale=None`` it is per unit of the per-axis [-1, 1] coordinate, max_idx_a / 2 voxel steps.)"""
+    res = dataset.vol_res_touple
+    x_end = res[0] if x_end is None else int(x_end)
+    dev = next(net.parameters()).device
+    shape = (x_end - x_begin, res[1], res[2], 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('out must be contiguous fp32 of shape %s' % (shape,))
+    row = res[1] * res[2]
+    scales = dataset.scales.tolist()
+    precision = getattr(net, 'precision', 'f16x2')
+    with torch.no_grad():
+        grid_cl, packed, desc = net._decoded_channel_last(), net._packed(), net._descriptor()
+        stash = None
+        for b, e in _row_chunks(net, x_end - x_begin, row, max_stash_bytes):
+            n = (e - b) * row
+            pos = ops.lattice_slab_positions(res, x_begin + b, x_begin + e, tiled_res, scales, dev)
+            _, stash = ops.forward_raw(desc, grid_cl, packed, pos=pos, want_stash=True, precision=precision, stash=stash)
+            ops.input_gradient_raw(desc, grid_cl, packed, pos, stash, precision=precision, out=out[b:e].view(n, 3))
+        if index_units:
+            out.mul_(index_units_factor(dataset))
+    return out
+
+
+def gradient_ground_truth(dataset, gt_vol: torch.Tensor, x_begin: int = 0, x_end: Optional[int] = None) -> torch.Tensor:
+    """finite_difference_trilinear_grad of the ground-truth volume at the voxels of the x-slab [x_begin, x_end), with
+    scale=dataset.scales: the derivative with respect to the normalised position, the units of gradient_field_from_net.
+    ((x_end - x_begin) * Y * Z, 3), row-major (x, y, z)."""
+    from ..data.Interpolation import finite_difference_trilinear_grad
+    res = dataset.vol_res_touple
+    x_end = res[0] if x_end is None else int(x_end)
+    dev = gt_vol.device
+    ax = [torch.arange(x_begin, x_end, device=dev), torch.arange(res[1], device=dev), torch.arange(res[2], device=dev)]
+    raw = torch.stack(torch.meshgrid(*ax, indexing='ij'), -1).view(-1, 3).to(torch.float32)
+    return finite_difference_trilinear_grad(raw, gt_vol, dataset.min_idx, dataset.max_idx, dataset.vol_res, scale=dataset.scales)
+
+
+def gradient_deviation_statistics(dataset, net, gt_vol: torch.Tensor, tiled_res: int = 32, max_stash_bytes: int = 1 << 30):
+    """PSNR / L1 / MSE / RMSE (calculate_deviation_statistics' definitions, over all 3 n_voxels components) of the network's
+    gradient field against the central finite differences of the ground-truth volume (gradient_ground_truth) at the same
+    voxels: how well the compressed volume keeps its gradients.  Runs in the chunks of gradient_field_from_net; neither
+    side is ever held for more than a chunk."""
+    res = dataset.vol_res_touple
+    dev = next(net.parameters()).device
+    gt_vol = gt_vol.to(dev)
+    acc = None
+    for b, e in _row_chunks(net, res[0], res[1] * res[2], max_stash_bytes):
+        pred = gradient_field_from_net(dataset, net, b, e, tiled_res, max_stash_bytes=max_stash_bytes)
+        acc = ops.deviation_partial(pred, gradient_ground_truth(dataset, gt_vol, b, e), acc)
+    acc = acc.cpu()
+    n = 3 * dataset.n_voxels
+    mse, l1 = acc[0].item() / n, acc[1].item() / n
+    psnr = 10.0 * float(np.log10((acc[3].item() - acc[2].item()) ** 2 / mse))
+    return psnr, l1, mse, float(np.sqrt(mse))
+
+
 def calculate_deviation_statistics(prediction, ground_truth, verbose: bool = True):
     """PSNR / L1 / MSE / RMSE as the reference defines them (:53-60).  GPU tensors are reduced by the HIP
     kernel with fp64 accumulators; CPU tensors (e.g. the reference-style tile loop's output) by torch."""
