@@ -110,7 +110,16 @@ int lfgc_dwt_level_f32(const float* in, const float* filter_fwd, const float* ta
  *                            builds outer products, :39-57); a dense filter of another length returns LFGC_E_UNSUPPORTED
  * Other lengths return LFGC_E_UNSUPPORTED.  filter_len = 4 is exactly the plain entry point above.  The channel-last pair
  * takes L = 2 and 4 and returns LFGC_E_UNSUPPORTED for L = 6, 8 (compose the channel-first level with
- * lfgc_grid_layout_f32).  The drop pair is declared with the drop entry points below. */
+ * lfgc_grid_layout_f32).  The drop pair is declared with the drop entry points below.
+ * Width limit: a workgroup of the channel-first synthesis stages whole coefficient rows in LDS (at most 160 KB), so the
+ * LAST coefficient extent d2 is bounded per filter length -- every d2 up to
+ *   L = 2: 853    L = 4: 373    L = 6: 169    L = 8: 96
+ * is taken (for any d0, d1, t); past it the synthesis and its drop variant return LFGC_E_UNSUPPORTED before anything is
+ * launched.  The adjoint takes every level the synthesis takes (at the full t its own limit is d2 = 1280, 560, 318, 201).
+ * The forward DWT stages source rows and takes every LAST source extent n2 up to
+ *   L = 2: 2560   L = 4: 1122   L = 6: 638    L = 8: 408
+ * which covers the output 2 d2 + L - 2 of every level inside the synthesis limit.  The lfgc_*_plan queries below answer
+ * for a given shape (tests/test_wavelet_plans_host.py pins these tables). */
 int lfgc_idwt_level_len_f32(const float* lll, const float* hf, const float* filter_rev, const float* taps, int filter_len,
                             float* out, int C, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
 int lfgc_idwt_level_bwd_len_f32(const float* d_out, const float* filter_rev, const float* taps, int filter_len,
@@ -519,6 +528,34 @@ int lfgc_input_gradient_f32(const lfgc_mlp_desc* desc, const lfgc_positions* pos
                             const float* packed, int precision, const float* stash, const float* d_out,
                             float* d_pos, lfgc_stream_t stream);
 int lfgc_input_gradient_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out);
+
+/* The same for the channel-first wavelet levels: which kernel lfgc_idwt_level_drop_len_f32 (synthesis),
+ * lfgc_idwt_level_drop_bwd_det_len_f32 (adjoint) and lfgc_dwt_level_len_f32 (forward DWT), and with them every entry that
+ * forwards to these, launch for a shape.  One selection function per direction in csrc/lfgc_wavelet.hip fills this struct and
+ * the launcher consumes it.  Pure host arithmetic: no device is needed. */
+#define LFGC_WAVELET_TILED_DENSE     0   /* synthesis, 64-tap dense stencil (4 taps, taps == NULL)                    */
+#define LFGC_WAVELET_TILED_SEPARABLE 1   /* synthesis, K + 1 staged planes per 2 output slices                        */
+#define LFGC_WAVELET_SLIDING_WINDOW  2   /* synthesis, 4 taps separable, more than 40 000 output voxels per channel   */
+#define LFGC_WAVELET_ANALYSIS_DENSE     3
+#define LFGC_WAVELET_ANALYSIS_SEPARABLE 4
+typedef struct lfgc_wavelet_plan_info {
+    int32_t kernel;          /* LFGC_WAVELET_* above                                                             */
+    int32_t drop;            /* 1: the DROP build (factors or penalty gradients folded in)                       */
+    int32_t ki;              /* sliding window: planes-per-thread instantiation ceil(len / 256) = 1..3, else 0  */
+    int32_t zchunk;          /* sliding window: output slices per workgroup, else 0                              */
+    int32_t len;             /* staged plane offsets per z-plane                                                 */
+    int32_t lds_bytes;       /* dynamic LDS of the launch                                                        */
+    uint32_t grid[3];        /* workgroups: plane tiles, z tiles or chunks, channels                             */
+} lfgc_wavelet_plan_info;
+
+/* filter_len, C and extents as for the entry itself; has_taps: taps != NULL; has_drop: any of mul_lll / mul_hf given (the
+ * adjoint: or penalty_grads[0] / [1]).  Returns the LFGC_E_* the launch would return for the same shape arguments
+ * (LFGC_E_NULL only for out == NULL); *out is filled on LFGC_OK only. */
+int lfgc_idwt_level_plan(int filter_len, int has_taps, int has_drop, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                         lfgc_wavelet_plan_info* out);
+int lfgc_idwt_level_bwd_plan(int filter_len, int has_taps, int has_drop, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                             lfgc_wavelet_plan_info* out);
+int lfgc_dwt_level_plan(int filter_len, int has_taps, int C, int n0, int n1, int n2, lfgc_wavelet_plan_info* out);
 
 /* The reduced-precision pair under the names SURVEY section 8(b) gives it (BASELINE config 3, "bf16 train step"; the
  * reference itself has no reduced-precision path): exactly lfgc_forward_f32 / lfgc_backward_f32 with precision =

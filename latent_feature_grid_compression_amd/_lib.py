@@ -42,6 +42,14 @@ class BackwardPlanInfo(Structure):
                 ('lds_bytes', c_int32), ('nbatches', c_int64), ('grid', c_int64)]
 
 
+class WaveletPlanInfo(Structure):
+    _fields_ = [('kernel', c_int32), ('drop', c_int32), ('ki', c_int32), ('zchunk', c_int32), ('len', c_int32),
+                ('lds_bytes', c_int32), ('grid', c_uint32 * 3)]
+
+
+WAVELET_KERNELS = ('tiled_dense', 'tiled_separable', 'sliding_window', 'analysis_dense', 'analysis_separable')
+
+
 class PenaltyTerm(Structure):
     _fields_ = [('a', c_void_p), ('b', c_void_p), ('n', c_int64), ('kind', c_int32)]
 
@@ -122,6 +130,9 @@ SIGNATURES = {
     'lfgc_input_gradient_f32': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
                                         c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'lfgc_input_gradient_plan': (c_int, [POINTER(MlpDesc), c_int64, c_int, POINTER(BackwardPlanInfo)]),
+    'lfgc_idwt_level_plan': (c_int, [c_int] * 10 + [POINTER(WaveletPlanInfo)]),
+    'lfgc_idwt_level_bwd_plan': (c_int, [c_int] * 10 + [POINTER(WaveletPlanInfo)]),
+    'lfgc_dwt_level_plan': (c_int, [c_int] * 6 + [POINTER(WaveletPlanInfo)]),
     'lfgc_forward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'lfgc_backward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,

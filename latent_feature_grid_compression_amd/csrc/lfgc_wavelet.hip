@@ -53,7 +53,7 @@ constexpr int kFwdCells = 256;       // synthesis: plane cells per workgroup (on
 // so only the x range of a neighbour needs a select.
 constexpr int kRec = 12;
 
-template <int K> constexpr int filt_floats() { return K == 2 ? 512 : 0; }   // the dense 4-tap filter's LDS slot
+constexpr int filt_floats(int K) { return K == 2 ? 512 : 0; }   // the dense 4-tap filter's LDS slot
 
 // x range of neighbour ex of the cell in column jx (cx = jx - ex in [0, d2)); written so that the bounds that always hold
 // (jx >= 0, jx - (K-1) < d2) are not tested
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void idwt_level_kernel(const IdwtArgs<K> a) {
     constexpr int L = 2 * K;
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     float* s_f = s_dyn;
-    float* s_v = s_dyn + filt_floats<K>();
+    float* s_v = s_dyn + filt_floats(K);
     if (!SEP)
         for (int i = threadIdx.x; i < 512; i += 256) s_f[(i & 63) * 8 + (i >> 6)] = a.filt[i];
     const int n0 = a.d0 + (K - 1), n1 = a.d1 + (K - 1), n2 = a.d2 + (K - 1);
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256) void analysis_kernel(const AnalysisArgs<K> a) 
     constexpr int L = 2 * K;
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     float* s_f = s_dyn;
-    float* s_v = s_dyn + filt_floats<K>();
+    float* s_v = s_dyn + filt_floats(K);
     if (!SEP)
         for (int i = threadIdx.x; i < 512; i += 256) s_f[(i & 63) * 8 + (i >> 6)] = a.filt[i];
     const int plane_cells = a.d1 * a.d2;
@@ -589,24 +589,22 @@ __global__ __launch_bounds__(256) void last_to_first_kernel(const float* __restr
 }
 
 // filter_len -> K, or 0 for a length without kernels; a dense (non-separable) filter must be 4-tap
-inline int half_len(int filter_len, const float* taps) {
+inline int half_len(int filter_len, bool has_taps) {
     if (filter_len != 2 && filter_len != 4 && filter_len != 6 && filter_len != 8) return 0;
-    if (!taps && filter_len != 4) return 0;
+    if (!has_taps && filter_len != 4) return 0;
     return filter_len / 2;
 }
 
-inline int check_level(const void* a, const void* b, const void* c, const void* d, int L, int C, int d0, int d1, int d2,
-                       int t0, int t1, int t2) {
-    if (!a || !b || !c || !d) return LFGC_E_NULL;
+inline int check_level_shape(int L, int C, int d0, int d1, int d2, int t0, int t1, int t2) {
     if (C < 1 || d0 < 1 || d1 < 1 || d2 < 1 || t0 < 1 || t1 < 1 || t2 < 1) return LFGC_E_SHAPE;
     if (t0 > 2 * d0 + L - 2 || t1 > 2 * d1 + L - 2 || t2 > 2 * d2 + L - 2) return LFGC_E_SHAPE;
     return LFGC_OK;
 }
 
-template <auto Kern, typename A>
-int launch_tiled(const A& a, dim3 blocks, int lds_bytes, hipStream_t stream) {
-    if (blocks.y > 65535u || blocks.z > 65535u || lds_bytes > 160 * 1024) return LFGC_E_UNSUPPORTED;
-    return lfgc_launch<Kern>(blocks, dim3(256), lds_bytes, stream, a);
+inline int check_level(const void* a, const void* b, const void* c, const void* d, int L, int C, int d0, int d1, int d2,
+                       int t0, int t1, int t2) {
+    if (!a || !b || !c || !d) return LFGC_E_NULL;
+    return check_level_shape(L, C, d0, d1, d2, t0, t1, t2);
 }
 
 // Runs f(std::bool_constant<drop>): the DROP template argument of the level kernels.
@@ -615,54 +613,106 @@ int with_drop(bool drop, F&& f) {
     return drop ? f(std::true_type()) : f(std::false_type());
 }
 
+// Launch shape of every level kernel: `ptiles` plane tiles x `ztiles` z tiles x C channels with `lds` bytes of dynamic LDS
+// (all 64-bit here: a long row overflows 32 bits long before it fits).  The staged rows must fit 160 KB.
+inline int fill_launch(long long ptiles, long long ztiles, int C, long long len, long long lds, lfgc_wavelet_plan_info* p) {
+    if (ptiles > 0x7fffffffLL || ztiles > 65535 || C > 65535 || lds > 160 * 1024) return LFGC_E_UNSUPPORTED;
+    p->len = (int)len; p->lds_bytes = (int)lds;
+    p->grid[0] = (unsigned)ptiles; p->grid[1] = (unsigned)ztiles; p->grid[2] = (unsigned)C;
+    return LFGC_OK;
+}
+
+// THE kernel selection of the synthesis: launch_idwt launches what *p says and lfgc_idwt_level_plan reports it.
+inline int idwt_select(int K, bool has_taps, bool drop, int C, int d0, int d1, int d2, int t0, int t1, int t2,
+                       lfgc_wavelet_plan_info* p) {
+    *p = lfgc_wavelet_plan_info{};
+    p->drop = drop;
+    const int n0 = d0 + K - 1, n1 = d1 + K - 1, n2 = d2 + K - 1;
+    const int span = (kFwdCells + n2 - 2) / n2;             // rows a run of 256 cells can straddle beyond its first
+    const long long len = (long long)(span + K) * d2 + 2 * K - 2;
+    const long long ptiles = ((long long)n1 * n2 + kFwdCells - 1) / kFwdCells;
+    if ((long long)d0 * d1 * d2 > 0x7fffffffLL / 8 || (long long)t0 * t1 * t2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
+    if (K == 2) {
+        const long long ki = (len + 255) / 256;
+        // Small levels (<= 40 000 output voxels per channel: everything below the last two levels of a 64^3 grid) take the tiled
+        // kernel below: one load -> barrier -> stencil -> store round per workgroup instead of a z walk whose every step waits
+        // for a plane (the arithmetic that should hide it is nothing at these sizes): cfg-3 train step 0.385 -> 0.378 ms.
+        const bool small_level = (long long)t0 * t1 * t2 <= 40000;
+        if (has_taps && ki <= 3 && !small_level) {           // separable filter: sliding window along z
+            p->kernel = LFGC_WAVELET_SLIDING_WINDOW;
+            p->ki = (int)ki;
+            p->zchunk = n0 < 6 ? n0 : 5;
+            return fill_launch(ptiles, (n0 + p->zchunk - 1) / p->zchunk, C, len, 2 * len * kRec * 4, p);
+        }
+    }
+    p->kernel = has_taps ? LFGC_WAVELET_TILED_SEPARABLE : LFGC_WAVELET_TILED_DENSE;
+    return fill_launch(ptiles, (n0 + 1) / 2, C, len, (filt_floats(K) + (K + 1) * len * kRec) * 4, p);
+}
+
 template <int K>
 int launch_idwt(IdwtArgs<K> a, bool drop, const float* taps, hipStream_t stream) {
     if (taps) for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
     a.o0 = (2 * a.d0 + 2 * K - 2 - a.t0) / 2; a.o1 = (2 * a.d1 + 2 * K - 2 - a.t1) / 2; a.o2 = (2 * a.d2 + 2 * K - 2 - a.t2) / 2;
-    const int n0 = a.d0 + K - 1, n1 = a.d1 + K - 1, n2 = a.d2 + K - 1;
-    const int span = (kFwdCells + n2 - 2) / n2;             // rows a run of 256 cells can straddle beyond its first
-    a.len = (span + K) * a.d2 + 2 * K - 2;
-    const long long ptiles = ((long long)n1 * n2 + kFwdCells - 1) / kFwdCells;
-    if (ptiles > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    const dim3 blocks((unsigned)ptiles, (unsigned)((n0 + 1) / 2), (unsigned)a.C);
-    const int lds = (filt_floats<K>() + (K + 1) * a.len * kRec) * 4;
-    if ((long long)a.d0 * a.d1 * a.d2 > 0x7fffffffLL / 8 || (long long)a.t0 * a.t1 * a.t2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    if constexpr (K == 2) {
-    const int ki = (a.len + 255) / 256;
-    // Small levels (<= 40 000 output voxels per channel: everything below the last two levels of a 64^3 grid) take the tiled
-    // kernel below: one load -> barrier -> stencil -> store round per workgroup instead of a z walk whose every step waits
-    // for a plane (the arithmetic that should hide it is nothing at these sizes): cfg-3 train step 0.385 -> 0.378 ms.
-    const bool small_level = (long long)a.t0 * a.t1 * a.t2 <= 40000;
-    if (taps && ki <= 3 && !small_level) {                   // separable filter: sliding window along z
-        a.zchunk = n0 < 6 ? n0 : 5;
-        const dim3 sblocks((unsigned)ptiles, (unsigned)((n0 + a.zchunk - 1) / a.zchunk), (unsigned)a.C);
-        const int slds = 2 * a.len * kRec * 4;
-        return with_drop(drop, [&](auto dc) {
-            constexpr bool DROP = decltype(dc)::value;
-            if (ki == 1) return launch_tiled<idwt_slide_kernel<DROP, 1>>(a, sblocks, slds, stream);
-            if (ki == 2) return launch_tiled<idwt_slide_kernel<DROP, 2>>(a, sblocks, slds, stream);
-            return launch_tiled<idwt_slide_kernel<DROP, 3>>(a, sblocks, slds, stream);
-        });
-    }
-    if (!taps) return with_drop(drop, [&](auto dc) { return launch_tiled<idwt_level_kernel<decltype(dc)::value, false, K>>(a, blocks, lds, stream); });
-    }
-    return with_drop(drop, [&](auto dc) { return launch_tiled<idwt_level_kernel<decltype(dc)::value, true, K>>(a, blocks, lds, stream); });
+    lfgc_wavelet_plan_info p;
+    const int rc = idwt_select(K, taps != nullptr, drop, a.C, a.d0, a.d1, a.d2, a.t0, a.t1, a.t2, &p);
+    if (rc != LFGC_OK) return rc;
+    a.len = p.len;
+    a.zchunk = p.zchunk;
+    const dim3 blocks(p.grid[0], p.grid[1], p.grid[2]);
+    return with_drop(p.drop, [&](auto dc) {
+        constexpr bool DROP = decltype(dc)::value;
+        if constexpr (K == 2) {
+            if (p.kernel == LFGC_WAVELET_SLIDING_WINDOW) {
+                if (p.ki == 1) return lfgc_launch<idwt_slide_kernel<DROP, 1>>(blocks, dim3(256), p.lds_bytes, stream, a);
+                if (p.ki == 2) return lfgc_launch<idwt_slide_kernel<DROP, 2>>(blocks, dim3(256), p.lds_bytes, stream, a);
+                return lfgc_launch<idwt_slide_kernel<DROP, 3>>(blocks, dim3(256), p.lds_bytes, stream, a);
+            }
+            if (p.kernel == LFGC_WAVELET_TILED_DENSE)
+                return lfgc_launch<idwt_level_kernel<DROP, false, K>>(blocks, dim3(256), p.lds_bytes, stream, a);
+        }
+        return lfgc_launch<idwt_level_kernel<DROP, true, K>>(blocks, dim3(256), p.lds_bytes, stream, a);
+    });
+}
+
+// THE kernel selection of the analysis form (adjoint of a level: source extents n = t, lo = the crop offset; forward DWT:
+// lo = L - 2): launch_analysis launches what *p says and lfgc_idwt_level_bwd_plan / lfgc_dwt_level_plan report it.
+inline int analysis_select(int K, bool has_taps, bool drop, int C, int n0, int n1, int n2, int d0, int d1, int d2,
+                           lfgc_wavelet_plan_info* p) {
+    *p = lfgc_wavelet_plan_info{};
+    p->drop = drop;
+    p->kernel = has_taps ? LFGC_WAVELET_ANALYSIS_SEPARABLE : LFGC_WAVELET_ANALYSIS_DENSE;
+    const int span = (kTileCells + d2 - 2) / d2;
+    const long long len = (long long)(2 * span + 2 * K - 1) * n2 + 2 * d2 + 2 * K - 2;
+    const long long ptiles = ((long long)d1 * d2 + kTileCells - 1) / kTileCells;
+    if ((long long)n0 * n1 * n2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
+    return fill_launch(ptiles, (d0 + 1) / 2, C, len, (filt_floats(K) + (2 * K + 2) * len) * 4, p);
 }
 
 template <int K>
 int launch_analysis(AnalysisArgs<K> a, bool drop, const float* taps, hipStream_t stream) {
     if (taps) for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
-    const int span = (kTileCells + a.d2 - 2) / a.d2;
-    a.len = (2 * span + 2 * K - 1) * a.n2 + 2 * a.d2 + 2 * K - 2;
-    const long long ptiles = ((long long)a.d1 * a.d2 + kTileCells - 1) / kTileCells;
-    if (ptiles > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    const dim3 blocks((unsigned)ptiles, (unsigned)((a.d0 + 1) / 2), (unsigned)a.C);
-    const int lds = (filt_floats<K>() + (2 * K + 2) * a.len) * 4;
-    if ((long long)a.n0 * a.n1 * a.n2 > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    if constexpr (K == 2) {
-        if (!taps) return with_drop(drop, [&](auto dc) { return launch_tiled<analysis_kernel<decltype(dc)::value, false, K>>(a, blocks, lds, stream); });
-    }
-    return with_drop(drop, [&](auto dc) { return launch_tiled<analysis_kernel<decltype(dc)::value, true, K>>(a, blocks, lds, stream); });
+    lfgc_wavelet_plan_info p;
+    const int rc = analysis_select(K, taps != nullptr, drop, a.C, a.n0, a.n1, a.n2, a.d0, a.d1, a.d2, &p);
+    if (rc != LFGC_OK) return rc;
+    a.len = p.len;
+    const dim3 blocks(p.grid[0], p.grid[1], p.grid[2]);
+    return with_drop(p.drop, [&](auto dc) {
+        constexpr bool DROP = decltype(dc)::value;
+        if constexpr (K == 2) {
+            if (p.kernel == LFGC_WAVELET_ANALYSIS_DENSE)
+                return lfgc_launch<analysis_kernel<DROP, false, K>>(blocks, dim3(256), p.lds_bytes, stream, a);
+        }
+        return lfgc_launch<analysis_kernel<DROP, true, K>>(blocks, dim3(256), p.lds_bytes, stream, a);
+    });
+}
+
+// extents of one forward-DWT level: _get_padding_size (Torch_Wavelet_Transform.py:59-63): (2L-3)//2 = L-2 on both sides,
+// plus the odd bit on the high side; F.pad slots are (last axis lo, hi, ..., first axis lo, hi) while is_odd is indexed
+// first axis first -> the odd bit of axis a pads axis 2-a.
+inline void dwt_extents(int filter_len, int n0, int n1, int n2, int* d0, int* d1, int* d2) {
+    const int lo = filter_len - 2;
+    const int hi0 = lo + (n2 & 1), hi1 = lo + (n1 & 1), hi2 = lo + (n0 & 1);
+    *d0 = (n0 + lo + hi0 - filter_len) / 2 + 1; *d1 = (n1 + lo + hi1 - filter_len) / 2 + 1; *d2 = (n2 + lo + hi2 - filter_len) / 2 + 1;
 }
 
 // Runs f(std::integral_constant<int, K>) for the half-length K of filter_len (half_len() != 0 checked by the caller).
@@ -696,7 +746,7 @@ extern "C" int lfgc_idwt_level_drop_len_f32(const float* lll, const float* hf, c
                                             const float* mul_hf, float thr_hf, const float* filter_rev, const float* taps,
                                             int filter_len, float* out, int C, int d0, int d1, int d2, int t0, int t1, int t2,
                                             lfgc_stream_t stream) {
-    const int K = half_len(filter_len, taps);
+    const int K = half_len(filter_len, taps != nullptr);
     if (!K) return LFGC_E_UNSUPPORTED;
     const int rc = check_level(lll, hf, taps ? (const void*)taps : (const void*)filter_rev, out, filter_len, C, d0, d1, d2, t0, t1, t2);
     if (rc != LFGC_OK) return rc;
@@ -734,7 +784,7 @@ extern "C" int lfgc_idwt_level_drop_bwd_det_len_f32(const float* d_out, const fl
                                                     float* d_lll, float* d_hf, float* d_mul_lll, float* d_mul_hf,
                                                     int64_t slice_stride, const float* const* penalty_grads, int C,
                                                     int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
-    const int K = half_len(filter_len, taps);
+    const int K = half_len(filter_len, taps != nullptr);
     if (!K) return LFGC_E_UNSUPPORTED;
     const int rc = check_level(d_out, taps ? (const void*)taps : (const void*)filter_rev, d_lll, d_hf, filter_len, C, d0, d1, d2, t0, t1, t2);
     if (rc != LFGC_OK) return rc;
@@ -787,19 +837,15 @@ extern "C" int lfgc_idwt_level_drop_bwd_f32(const float* d_out, const float* fil
 extern "C" int lfgc_dwt_level_len_f32(const float* in, const float* filter_fwd, const float* taps, int filter_len, float* out,
                                       int C, int n0, int n1, int n2, lfgc_stream_t stream) {
     if (!in || (!filter_fwd && !taps) || !out) return LFGC_E_NULL;
-    const int K = half_len(filter_len, taps);
+    const int K = half_len(filter_len, taps != nullptr);
     if (!K) return LFGC_E_UNSUPPORTED;
     if (C < 1 || n0 < 1 || n1 < 1 || n2 < 1) return LFGC_E_SHAPE;
-    // _get_padding_size (Torch_Wavelet_Transform.py:59-63): (2L-3)//2 = L-2 on both sides, plus the odd bit on the high
-    // side; F.pad slots are (last axis lo, hi, ..., first axis lo, hi) while is_odd is indexed first axis first -> the
-    // odd bit of axis a pads axis 2-a.
     const int lo = filter_len - 2;
-    const int hi0 = lo + (n2 & 1), hi1 = lo + (n1 & 1), hi2 = lo + (n0 & 1);
     return with_half_len(K, [&](auto kc) {
         constexpr int KK = decltype(kc)::value;
         AnalysisArgs<KK> a = {};
         a.src = in; a.filt = filter_fwd;
-        a.d0 = (n0 + lo + hi0 - filter_len) / 2 + 1; a.d1 = (n1 + lo + hi1 - filter_len) / 2 + 1; a.d2 = (n2 + lo + hi2 - filter_len) / 2 + 1;
+        dwt_extents(filter_len, n0, n1, n2, &a.d0, &a.d1, &a.d2);
         const long long dvol = (long long)a.d0 * a.d1 * a.d2;
         a.band0 = out; a.bandh = out + dvol;
         a.cstride0 = 8 * dvol; a.cstrideh = 8 * dvol;
@@ -811,6 +857,47 @@ extern "C" int lfgc_dwt_level_len_f32(const float* in, const float* filter_fwd, 
 extern "C" int lfgc_dwt_level_f32(const float* in, const float* filter_fwd, const float* taps, float* out,
                                   int C, int n0, int n1, int n2, lfgc_stream_t stream) {
     return lfgc_dwt_level_len_f32(in, filter_fwd, taps, 4, out, C, n0, n1, n2, stream);
+}
+
+// ---- read-only plan queries (include/lfgc.h): the selections above, nothing launched --------------------------------
+
+extern "C" int lfgc_idwt_level_plan(int filter_len, int has_taps, int has_drop, int C, int d0, int d1, int d2,
+                                    int t0, int t1, int t2, lfgc_wavelet_plan_info* out) {
+    if (!out) return LFGC_E_NULL;
+    const int K = half_len(filter_len, has_taps != 0);
+    if (!K) return LFGC_E_UNSUPPORTED;
+    const int rc = check_level_shape(filter_len, C, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    lfgc_wavelet_plan_info p;
+    const int rs = idwt_select(K, has_taps != 0, has_drop != 0, C, d0, d1, d2, t0, t1, t2, &p);
+    if (rs == LFGC_OK) *out = p;
+    return rs;
+}
+
+extern "C" int lfgc_idwt_level_bwd_plan(int filter_len, int has_taps, int has_drop, int C, int d0, int d1, int d2,
+                                        int t0, int t1, int t2, lfgc_wavelet_plan_info* out) {
+    if (!out) return LFGC_E_NULL;
+    const int K = half_len(filter_len, has_taps != 0);
+    if (!K) return LFGC_E_UNSUPPORTED;
+    const int rc = check_level_shape(filter_len, C, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    lfgc_wavelet_plan_info p;
+    const int rs = analysis_select(K, has_taps != 0, has_drop != 0, C, t0, t1, t2, d0, d1, d2, &p);
+    if (rs == LFGC_OK) *out = p;
+    return rs;
+}
+
+extern "C" int lfgc_dwt_level_plan(int filter_len, int has_taps, int C, int n0, int n1, int n2, lfgc_wavelet_plan_info* out) {
+    if (!out) return LFGC_E_NULL;
+    const int K = half_len(filter_len, has_taps != 0);
+    if (!K) return LFGC_E_UNSUPPORTED;
+    if (C < 1 || n0 < 1 || n1 < 1 || n2 < 1) return LFGC_E_SHAPE;
+    int d0, d1, d2;
+    dwt_extents(filter_len, n0, n1, n2, &d0, &d1, &d2);
+    lfgc_wavelet_plan_info p;
+    const int rs = analysis_select(K, has_taps != 0, false, C, n0, n1, n2, d0, d1, d2, &p);
+    if (rs == LFGC_OK) *out = p;
+    return rs;
 }
 
 extern "C" int lfgc_grid_layout_f32(const float* src, float* dst, int C, int64_t voxels, int channel_stride,

@@ -175,6 +175,28 @@ def filter_taps(filt: torch.Tensor):
 
 _E_UNSUPPORTED = -3
 _NAN = float('nan')
+# Width limits of the channel-first level kernels per filter length (include/lfgc.h: lfgc_idwt_level_len_f32; a workgroup
+# stages whole rows in 160 KB of LDS): the largest last coefficient extent d2 the synthesis takes, the same for the adjoint
+# at the full t, and the largest last source extent n2 of the forward DWT
+SYNTHESIS_MAX_D2 = {2: 853, 4: 373, 6: 169, 8: 96}
+ADJOINT_MAX_D2 = {2: 1280, 4: 560, 6: 318, 8: 201}
+DWT_MAX_N2 = {2: 2560, 4: 1122, 6: 638, 8: 408}
+
+
+def _check_level(code: int, what: str, L: int, d: Sequence[int], t: Sequence[int], adjoint: bool = False) -> None:
+    """check() for the channel-first level entries: LFGC_E_UNSUPPORTED becomes a NotImplementedError that names the limit
+    the level is over -- the width bound of its direction where d2 exceeds it, else the size limits of a launch."""
+    if code == _E_UNSUPPORTED:
+        table = ADJOINT_MAX_D2 if adjoint else SYNTHESIS_MAX_D2
+        if d[2] > SYNTHESIS_MAX_D2[L]:
+            why = ('the last coefficient extent d2 may be at most %d for %d taps in the %s (whole rows are staged in LDS)'
+                   % (table[L], L, 'adjoint at the full t; the synthesis takes at most %d' % SYNTHESIS_MAX_D2[L]
+                      if adjoint else 'synthesis'))
+        else:
+            why = 'a channel holds fewer than 2^28 coefficients and 2^31 outputs, d0 is below 2^17 and C at most 65535'
+        raise NotImplementedError('%s: level d=%s -> t=%s is outside the channel-first wavelet kernels: %s'
+                                  % (what, tuple(d), tuple(t), why))
+    check(code, what)
 
 
 def _thr(v) -> float:
@@ -228,9 +250,9 @@ def _synthesis(lll, hf, filter_rev, target, mul_l=None, thr_l=None, mul_h=None, 
         return out
     filter_rev = _f32c(filter_rev)
     out = torch.empty((C, t[0], t[1], t[2]), dtype=torch.float32, device=lll.device)
-    check(_lib.load().lfgc_idwt_level_drop_len_f32(
+    _check_level(_lib.load().lfgc_idwt_level_drop_len_f32(
         lll.data_ptr(), hf.data_ptr(), _ptr(mul_l), _thr(thr_l), _ptr(mul_h), _thr(thr_h), filter_rev.data_ptr(), taps, L,
-        out.data_ptr(), C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_len_f32')
+        out.data_ptr(), C, d0, d1, d2, t[0], t[1], t[2], _stream(lll)), 'lfgc_idwt_level_drop_len_f32', L, (d0, d1, d2), t)
     return to_channel_last(out) if channel_last else out
 
 
@@ -290,9 +312,9 @@ def _adjoint(d_out, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d,
             'lfgc_idwt_level_cl_drop_bwd_det_len_f32')
     else:
         filter_rev = _f32c(filter_rev)
-        check(_lib.load().lfgc_idwt_level_drop_bwd_det_len_f32(
+        _check_level(_lib.load().lfgc_idwt_level_drop_bwd_det_len_f32(
             d_out.data_ptr(), filter_rev.data_ptr(), taps, L, *operands, d[0], d[1], d[2], t0, t1, t2, _stream(d_out)),
-            'lfgc_idwt_level_drop_bwd_det_len_f32')
+            'lfgc_idwt_level_drop_bwd_det_len_f32', L, d, (t0, t1, t2), adjoint=True)
     if stride:
         for slices, out in ((sl, d_ml), (sh, d_mh)):
             if out is not None:
@@ -402,9 +424,41 @@ def dwt_level(data: torch.Tensor, filter_fwd: torch.Tensor) -> torch.Tensor:
     L = filter_length(filter_fwd)
     d = dwt_out_shape((n0, n1, n2), L)
     out = torch.empty((C, 8, d[0], d[1], d[2]), dtype=torch.float32, device=data.device)
-    check(_lib.load().lfgc_dwt_level_len_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, L, out.data_ptr(), C, n0, n1, n2,
-                                             _stream(data)), 'lfgc_dwt_level_len_f32')
+    code = _lib.load().lfgc_dwt_level_len_f32(data.data_ptr(), filter_fwd.data_ptr(), taps, L, out.data_ptr(), C, n0, n1, n2,
+                                              _stream(data))
+    if code == _E_UNSUPPORTED:
+        raise NotImplementedError('lfgc_dwt_level_len_f32: input %s is outside the forward-DWT kernel: %s' % (
+            (n0, n1, n2), 'the last extent n2 may be at most %d for %d taps (whole rows are staged in LDS)' % (DWT_MAX_N2[L], L)
+            if n2 > DWT_MAX_N2[L] else 'a channel holds fewer than 2^31 values, n0 is below 2^17 and C at most 65535'))
+    check(code, 'lfgc_dwt_level_len_f32')
     return out
+
+
+def _wavelet_plan(entry: str, *args) -> SimpleNamespace:
+    info = _lib.WaveletPlanInfo()
+    check(getattr(_lib.load(), entry)(*[int(v) for v in args], ctypes.byref(info)), entry)
+    return SimpleNamespace(kernel=_lib.WAVELET_KERNELS[info.kernel], drop=bool(info.drop), ki=int(info.ki),
+                           zchunk=int(info.zchunk), len=int(info.len), lds_bytes=int(info.lds_bytes),
+                           grid=tuple(int(v) for v in info.grid))
+
+
+def idwt_level_plan(filter_len: int, C: int, d: Sequence[int], t: Sequence[int], has_taps: bool = True,
+                    has_drop: bool = False) -> SimpleNamespace:
+    """lfgc_idwt_level_plan: the launch idwt_level / idwt_level_drop (has_drop) would make for a level d -> t of C channels,
+    nothing enqueued, no device needed.  has_taps: the filter is separable (filter_taps() is not None).  Fields: kernel
+    (a name of _lib.WAVELET_KERNELS), drop, ki, zchunk, len, lds_bytes, grid (x, y, z workgroups)."""
+    return _wavelet_plan('lfgc_idwt_level_plan', filter_len, has_taps, has_drop, C, *d, *t)
+
+
+def idwt_level_bwd_plan(filter_len: int, C: int, d: Sequence[int], t: Sequence[int], has_taps: bool = True,
+                        has_drop: bool = False) -> SimpleNamespace:
+    """lfgc_idwt_level_bwd_plan: the same for idwt_level_bwd / idwt_level_drop_bwd (has_drop: factors or L2 penalties)."""
+    return _wavelet_plan('lfgc_idwt_level_bwd_plan', filter_len, has_taps, has_drop, C, *d, *t)
+
+
+def dwt_level_plan(filter_len: int, C: int, n: Sequence[int], has_taps: bool = True) -> SimpleNamespace:
+    """lfgc_dwt_level_plan: the same for dwt_level of a (C, n0,n1,n2) input."""
+    return _wavelet_plan('lfgc_dwt_level_plan', filter_len, has_taps, C, *n)
 
 
 @_on_device
