@@ -405,7 +405,8 @@ typedef struct lfgc_positions {
 #define LFGC_PRECISION_F16 2
 
 /* forward().  Replaces model/Feature_Grid_Model.py:62-78 (everything after decode_volume):
- * F.grid_sample(bilinear, align_corners=False, zeros) of the dense grid, Embedder.embed
+ * F.grid_sample(bilinear, align_corners=False, zeros) of the dense grid (the cell arithmetic, shared with the backward:
+ * csrc/lfgc_trilinear.h), Embedder.embed
  * (model/Feature_Embedding.py:14-16), torch.cat, L x (Linear + SnakeAlt), final Linear, optional
  * clamp(-1,1) (eval branch :78).
  *   grid_cl   device (D,H,W,Cs) channel-last dense grid, Cs = lfgc_grid_channel_stride(C)
@@ -516,7 +517,8 @@ int lfgc_backward_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precisi
  * differentiating model/Feature_Grid_Model.py:62-75 -- direct columns, Fourier embedding and grid_sample's coordinate
  * gradient -- without the parameter gradients lfgc_backward_f32 also produces.  Runs the data kernel of lfgc_backward_f32
  * in a build that writes no dstash, scatters nothing into a d_grid and is followed by no weight-gradient kernel; same
- * arithmetic per sample, same launch selection (lfgc_input_gradient_plan reports it; nslabs and roles are 0).
+ * arithmetic per sample (the sampler's cell: csrc/lfgc_trilinear.h), same launch selection (lfgc_input_gradient_plan
+ * reports it; nslabs and roles are 0).
  *   positions   positions->pos must be non-NULL (explicit list only, as the backward)
  *   stash       device, written by the lfgc_forward_f32 call with the same inputs
  *   d_out       device (N) upstream gradient, or NULL = ones: the gradient of the (unclamped) output itself

@@ -18,6 +18,7 @@
 #pragma once
 #include "lfgc_common.h"
 #include "lfgc_forward16.h"      // h16x8, lfgc_split8
+#include "lfgc_trilinear.h"
 
 struct LfgcBwdArgs {
     const float* pos;          // (N,3)
@@ -130,6 +131,23 @@ __device__ __forceinline__ void lfgc_split_scaled(const float* __restrict__ v, f
         if (SPLIT) lfgc_split8(t, Fhi[f], Flo[f]);
         else lfgc_cvt8(t, Fhi[f]);
     }
+}
+
+// Sampler coordinate gradient of one corner (ATen grid_sampler_3d_backward): the corner's grid row `gp` dotted with this
+// lane half's feature gradients, times the other two axes' weights, signed by the corner's side (d = 0: -, 1: +).
+template <int CHH>
+__device__ __forceinline__ void lfgc_corner_coord_grad(const float* __restrict__ gp, const float* dX, int dx, int dy, int dz,
+                                                       float wxc, float wyc, float wzc, float& gix, float& giy, float& giz) {
+    float dot = 0.0f;
+#pragma unroll
+    for (int c4 = 0; c4 < CHH / 4; ++c4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(gp + 4 * c4);
+        dot = __builtin_fmaf(v.x, dX[4 * c4 + 0], dot); dot = __builtin_fmaf(v.y, dX[4 * c4 + 1], dot);
+        dot = __builtin_fmaf(v.z, dX[4 * c4 + 2], dot); dot = __builtin_fmaf(v.w, dX[4 * c4 + 3], dot);
+    }
+    gix += (dx ? dot : -dot) * (wyc * wzc);
+    giy += (dy ? dot : -dot) * (wxc * wzc);
+    giz += (dz ? dot : -dot) * (wxc * wyc);
 }
 
 // Dynamic LDS of lfgc_bwd_data_kernel in floats, in the order the kernel carves it:
@@ -356,21 +374,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
         }
 
         LFGC_BSTAMP(3);
-        // ---- sampler geometry (same arithmetic as the forward) ---------------------------------------------
+        // ---- sampler geometry: the forward's, from the one definition (lfgc_trilinear.h) ---------------------------
         const float* pp = a.pos + 3 * nc;
         const float p0 = pp[0], p1 = pp[1], p2 = pp[2];
-        const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(p0, 1.0f), (float)a.W), 1.0f), 2.0f);
-        const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(p1, 1.0f), (float)a.H), 1.0f), 2.0f);
-        const float iz = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(p2, 1.0f), (float)a.D), 1.0f), 2.0f);
-        const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-        const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)a.W);
-        const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)a.H);
-        const int z0 = (int)fminf(fmaxf(fz0, -2.0f), (float)a.D);
-        const float wx1 = __fsub_rn(ix, fx0), wx0 = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
-        const float wy1 = __fsub_rn(iy, fy0), wy0 = __fsub_rn(__fadd_rn(fy0, 1.0f), iy);
-        const float wz1 = __fsub_rn(iz, fz0), wz0 = __fsub_rn(__fadd_rn(fz0, 1.0f), iz);
-        const bool in_range = (fx0 >= -1.0f) && (fx0 < (float)a.W) && (fy0 >= -1.0f) && (fy0 < (float)a.H) &&
-                              (fz0 >= -1.0f) && (fz0 < (float)a.D);
+        const LfgcAxisCell cx = lfgc_axis_cell(p0, a.W), cy = lfgc_axis_cell(p1, a.H), cz = lfgc_axis_cell(p2, a.D);
+        // corner = 4 dz + 2 dy + dx (ATen's order): does it lie in the grid (of a real sample), and where is its (clamped) row
+        auto corner_ok = [&](int dx, int dyc, int dz) { return valid && cx.inside(dx) && cy.inside(dyc) && cz.inside(dz); };
+        auto corner_off = [&](int dx, int dyc, int dz) {
+            return ((long long)(cz.clamped(dz) * a.H + cy.clamped(dyc)) * a.W + cx.clamped(dx)) * a.Cs;
+        };
 
         float gix = 0.0f, giy = 0.0f, giz = 0.0f;
         if constexpr (INPUT_ONLY) {
@@ -383,24 +395,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) {
                 const int dz = corner >> 2, dyc = (corner >> 1) & 1, dx = corner & 1;
-                const int xi = x0 + dx, yi = y0 + dyc, zi = z0 + dz;
-                const bool ok = valid && in_range && xi >= 0 && xi < a.W && yi >= 0 && yi < a.H && zi >= 0 && zi < a.D;
-                const float wxc = dx ? wx1 : wx0, wyc = dyc ? wy1 : wy0, wzc = dz ? wz1 : wz0;
-                const int xc = min(max(xi, 0), a.W - 1), yc = min(max(yi, 0), a.H - 1), zc = min(max(zi, 0), a.D - 1);
-                const long long off = ((long long)(zc * a.H + yc) * a.W + xc) * a.Cs;
-                if (ok) {
-                    const float* gp = a.grid + off + hh * CHH;
-                    float dot = 0.0f;
-#pragma unroll
-                    for (int c4 = 0; c4 < CHH / 4; ++c4) {
-                        const f32x4 v = *reinterpret_cast<const f32x4*>(gp + 4 * c4);
-                        dot = __builtin_fmaf(v.x, dX[4 * c4 + 0], dot); dot = __builtin_fmaf(v.y, dX[4 * c4 + 1], dot);
-                        dot = __builtin_fmaf(v.z, dX[4 * c4 + 2], dot); dot = __builtin_fmaf(v.w, dX[4 * c4 + 3], dot);
-                    }
-                    gix += (dx ? dot : -dot) * (wyc * wzc);
-                    giy += (dyc ? dot : -dot) * (wxc * wzc);
-                    giz += (dz ? dot : -dot) * (wxc * wyc);
-                }
+                if (corner_ok(dx, dyc, dz))
+                    lfgc_corner_coord_grad<CHH>(a.grid + corner_off(dx, dyc, dz) + hh * CHH, dX, dx, dyc, dz, cx.w[dx], cy.w[dyc],
+                                                cz.w[dz], gix, giy, giz);
             }
         } else {
             // ---- scatter d feat into d_grid ----------------------------------------------------------------------
@@ -425,26 +422,13 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
 #pragma unroll
             for (int corner = 0; corner < 8; ++corner) {
                 const int dz = corner >> 2, dyc = (corner >> 1) & 1, dx = corner & 1;
-                const int xi = x0 + dx, yi = y0 + dyc, zi = z0 + dz;
-                const bool ok = valid && in_range && xi >= 0 && xi < a.W && yi >= 0 && yi < a.H && zi >= 0 && zi < a.D;
-                const float wxc = dx ? wx1 : wx0, wyc = dyc ? wy1 : wy0, wzc = dz ? wz1 : wz0;
-                const float w = ok ? __fmul_rn(__fmul_rn(wxc, wyc), wzc) : 0.0f;
-                const int xc = min(max(xi, 0), a.W - 1), yc = min(max(yi, 0), a.H - 1), zc = min(max(zi, 0), a.D - 1);
-                const long long off = ((long long)(zc * a.H + yc) * a.W + xc) * a.Cs;
+                const bool ok = corner_ok(dx, dyc, dz);
+                const long long off = corner_off(dx, dyc, dz);
+                const float w = ok ? __fmul_rn(__fmul_rn(cx.w[dx], cy.w[dyc]), cz.w[dz]) : 0.0f;
                 if (stage) { if (hh == 0) s_cw[j * 8 + corner] = w; else s_co[j * 8 + corner] = (int)off; }
-                if (a.d_pos && ok) {                           // sampler coordinate gradient (ATen grid_sampler_3d_backward)
-                    const float* gp = a.grid + off + hh * CHH;
-                    float dot = 0.0f;
-#pragma unroll
-                    for (int c4 = 0; c4 < CHH / 4; ++c4) {
-                        const f32x4 v = *reinterpret_cast<const f32x4*>(gp + 4 * c4);
-                        dot = __builtin_fmaf(v.x, dX[4 * c4 + 0], dot); dot = __builtin_fmaf(v.y, dX[4 * c4 + 1], dot);
-                        dot = __builtin_fmaf(v.z, dX[4 * c4 + 2], dot); dot = __builtin_fmaf(v.w, dX[4 * c4 + 3], dot);
-                    }
-                    gix += (dx ? dot : -dot) * (wyc * wzc);
-                    giy += (dyc ? dot : -dot) * (wxc * wzc);
-                    giz += (dz ? dot : -dot) * (wxc * wyc);
-                }
+                if (a.d_pos && ok)
+                    lfgc_corner_coord_grad<CHH>(a.grid + off + hh * CHH, dX, dx, dyc, dz, cx.w[dx], cy.w[dyc], cz.w[dz],
+                                                gix, giy, giz);
             }
             }
             if (stage) {
@@ -470,25 +454,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
         // ---- d_pos = direct columns + Fourier embedding + sampler coordinate gradient ---------------------------
         if (a.d_pos) {
             float sk[NF > 0 ? NF : 1][3], ck[NF > 0 ? NF : 1][3];
-            bool bad = false;
-#pragma unroll
-            for (int k = 0; k < NF; ++k) {
-                const float f = lfgc_freq(k);
-                const float a0 = __fmul_rn(p0, f), a1 = __fmul_rn(p1, f), a2 = __fmul_rn(p2, f);
-                bad |= lfgc_trig_out_of_range(a0) | lfgc_trig_out_of_range(a1) | lfgc_trig_out_of_range(a2);
-                lfgc_sincosf_t<false>(a0, sk[k][0], ck[k][0]);
-                lfgc_sincosf_t<false>(a1, sk[k][1], ck[k][1]);
-                lfgc_sincosf_t<false>(a2, sk[k][2], ck[k][2]);
-            }
-            if (__builtin_expect(__any(bad), 0)) {
-#pragma unroll
-                for (int k = 0; k < NF; ++k) {
-                    const float f = lfgc_freq(k);
-                    lfgc_sincosf_t<true>(__fmul_rn(p0, f), sk[k][0], ck[k][0]);
-                    lfgc_sincosf_t<true>(__fmul_rn(p1, f), sk[k][1], ck[k][1]);
-                    lfgc_sincosf_t<true>(__fmul_rn(p2, f), sk[k][2], ck[k][2]);
-                }
-            }
+            lfgc_fourier_trig<NF>(p0, p1, p2, sk, ck);
             // this lane holds d e[hh*EPH + t] in dX[CHH + t]; evaluate both static mappings, keep this half's
             float dlo[3] = {0.0f, 0.0f, 0.0f}, dhi[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -531,11 +497,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
 
 // Deferred scatter of the feature gradients (small batches): d_grid[corner rows of sample n] += w_corner * dfeat[n].
 // A wave takes 8 samples, 64 / CH at a time (one atomic wave-instruction = that many whole channel rows), every lane
-// forming its sample's corner weights and offsets itself with the forward's arithmetic; thousands of waves, so the
-// float atomics' latency (a cold line per row) is covered by occupancy instead of being waited for 128 times in a row.
-template <int CH>
-__global__ __launch_bounds__(256) void lfgc_bwd_scatter_kernel(const float* __restrict__ pos, const float* __restrict__ dfeat,
-                                                              float* __restrict__ d_grid, long long n, int D, int H, int W, int Cs) {
+// forming its sample's corner weights and offsets itself with the forward's arithmetic (lfgc_trilinear.h); thousands of
+// waves, so the float atomics' latency (a cold line per row) is covered by occupancy instead of being waited for 128 times
+// in a row.  The walk is shared by the float and the fixed-point scatter: add(i, v, w) accumulates v w into element i.
+template <int CH, class ADD>
+__device__ __forceinline__ void lfgc_scatter_walk(const float* __restrict__ pos, const float* __restrict__ dfeat, long long n,
+                                                  int D, int H, int W, int Cs, ADD add) {
     constexpr int SPI = 64 / CH;                          // samples per wave-instruction
     const int lane = threadIdx.x & 63;
     const long long gw = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -546,27 +513,22 @@ __global__ __launch_bounds__(256) void lfgc_bwd_scatter_kernel(const float* __re
         const long long smp = gw * 8 + i * SPI + sp;
         if (i * SPI + sp >= 8 || smp >= n) continue;
         const float p0 = pos[3 * smp], p1 = pos[3 * smp + 1], p2 = pos[3 * smp + 2];
-        const float ix = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p0, 1.0f), (float)W), 1.0f), 0.5f);
-        const float iy = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p1, 1.0f), (float)H), 1.0f), 0.5f);
-        const float iz = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p2, 1.0f), (float)D), 1.0f), 0.5f);
-        const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-        const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)W);
-        const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)H);
-        const int z0 = (int)fminf(fmaxf(fz0, -2.0f), (float)D);
-        float wx[2], wy[2], wz[2];
-        wx[1] = __fsub_rn(ix, fx0); wx[0] = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
-        wy[1] = __fsub_rn(iy, fy0); wy[0] = __fsub_rn(__fadd_rn(fy0, 1.0f), iy);
-        wz[1] = __fsub_rn(iz, fz0); wz[0] = __fsub_rn(__fadd_rn(fz0, 1.0f), iz);
+        const LfgcAxisCell cx = lfgc_axis_cell(p0, W), cy = lfgc_axis_cell(p1, H), cz = lfgc_axis_cell(p2, D);
         const float v = dfeat[smp * CH + c];
 #pragma unroll
         for (int corner = 0; corner < 8; ++corner) {
             const int dz = corner >> 2, dy = (corner >> 1) & 1, dx = corner & 1;
-            const int xi = x0 + dx, yi = y0 + dy, zi = z0 + dz;
-            const bool ok = (unsigned)xi < (unsigned)W && (unsigned)yi < (unsigned)H && (unsigned)zi < (unsigned)D;
-            const float w = __fmul_rn(__fmul_rn(wx[dx], wy[dy]), wz[dz]);
-            if (ok && w != 0.0f) atomicAdd(d_grid + ((long long)(zi * H + yi) * W + xi) * Cs + c, v * w);
+            const bool ok = cx.inside(dx) && cy.inside(dy) && cz.inside(dz);
+            const float w = __fmul_rn(__fmul_rn(cx.w[dx], cy.w[dy]), cz.w[dz]);
+            if (ok && w != 0.0f) add(((long long)((cz.i0 + dz) * H + (cy.i0 + dy)) * W + (cx.i0 + dx)) * Cs + c, v, w);
         }
     }
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void lfgc_bwd_scatter_kernel(const float* __restrict__ pos, const float* __restrict__ dfeat,
+                                                              float* __restrict__ d_grid, long long n, int D, int H, int W, int Cs) {
+    lfgc_scatter_walk<CH>(pos, dfeat, n, D, H, W, Cs, [&](long long i, float v, float w) { atomicAdd(d_grid + i, v * w); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -577,8 +539,8 @@ __global__ __launch_bounds__(256) void lfgc_bwd_scatter_kernel(const float* __re
 //   lfgc_det_zero_kernel     acc = 0, max word = 0 (a kernel, not a memset node: DESIGN.md 3.1)
 //   lfgc_det_max_kernel      max word = max bits of |dfeat| over the n valid rows (unsigned atomicMax: order-independent;
 //                            a non-finite value is any bits >= 0x7f800000 and wins the maximum)
-//   lfgc_bwd_scatter_det_kernel   lfgc_bwd_scatter_kernel op for op up to the fp32 product v w, which is scaled exactly in
-//                            double by 1 / q, rounded to nearest and added with a 64-bit integer atomic
+//   lfgc_bwd_scatter_det_kernel   lfgc_bwd_scatter_kernel's walk (lfgc_scatter_walk); the fp32 product v w is scaled exactly
+//                            in double by 1 / q, rounded to nearest and added with a 64-bit integer atomic
 //   lfgc_det_finish_kernel   d_grid[i] = (float)(acc[i] q) for EVERY element (zeros included: d_grid needs no zero fill);
 //                            max == 0: all zero; non-finite max: all NaN
 struct LfgcDetScatter {
@@ -634,43 +596,13 @@ template <int CH>
 __global__ __launch_bounds__(256) void lfgc_bwd_scatter_det_kernel(const float* __restrict__ pos, const float* __restrict__ dfeat,
                                                                   long long* __restrict__ acc, const unsigned* __restrict__ maxw,
                                                                   long long n, int D, int H, int W, int Cs) {
-    constexpr int SPI = 64 / CH;                          // samples per wave-instruction
-    const int lane = threadIdx.x & 63;
-    const long long gw = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int sp = lane / CH, c = lane % CH;
     const unsigned mb = *maxw;
-    if (sp >= SPI || mb == 0u || mb >= kLfgcDetNonFinite) return;      // nothing to add / the finish pass writes NaN
+    if (mb == 0u || mb >= kLfgcDetNonFinite) return;                   // nothing to add / the finish pass writes NaN
     const double inv_q = lfgc_det_pow2(-lfgc_det_qexp(mb, n));
-#pragma unroll 1
-    for (int i = 0; i < 8 / SPI + (8 % SPI != 0); ++i) {
-        const long long smp = gw * 8 + i * SPI + sp;
-        if (i * SPI + sp >= 8 || smp >= n) continue;
-        const float p0 = pos[3 * smp], p1 = pos[3 * smp + 1], p2 = pos[3 * smp + 2];
-        const float ix = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p0, 1.0f), (float)W), 1.0f), 0.5f);
-        const float iy = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p1, 1.0f), (float)H), 1.0f), 0.5f);
-        const float iz = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p2, 1.0f), (float)D), 1.0f), 0.5f);
-        const float fx0 = floorf(ix), fy0 = floorf(iy), fz0 = floorf(iz);
-        const int x0 = (int)fminf(fmaxf(fx0, -2.0f), (float)W);
-        const int y0 = (int)fminf(fmaxf(fy0, -2.0f), (float)H);
-        const int z0 = (int)fminf(fmaxf(fz0, -2.0f), (float)D);
-        float wx[2], wy[2], wz[2];
-        wx[1] = __fsub_rn(ix, fx0); wx[0] = __fsub_rn(__fadd_rn(fx0, 1.0f), ix);
-        wy[1] = __fsub_rn(iy, fy0); wy[0] = __fsub_rn(__fadd_rn(fy0, 1.0f), iy);
-        wz[1] = __fsub_rn(iz, fz0); wz[0] = __fsub_rn(__fadd_rn(fz0, 1.0f), iz);
-        const float v = dfeat[smp * CH + c];
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-            const int dz = corner >> 2, dy = (corner >> 1) & 1, dx = corner & 1;
-            const int xi = x0 + dx, yi = y0 + dy, zi = z0 + dz;
-            const bool ok = (unsigned)xi < (unsigned)W && (unsigned)yi < (unsigned)H && (unsigned)zi < (unsigned)D;
-            const float w = __fmul_rn(__fmul_rn(wx[dx], wy[dy]), wz[dz]);
-            if (ok && w != 0.0f) {
-                const long long k = __double2ll_rn((double)__fmul_rn(v, w) * inv_q);    // |k| <= 2^B: |v| <= max, w <= 1
-                atomicAdd(reinterpret_cast<unsigned long long*>(acc + ((long long)(zi * H + yi) * W + xi) * Cs + c),
-                          (unsigned long long)k);
-            }
-        }
-    }
+    lfgc_scatter_walk<CH>(pos, dfeat, n, D, H, W, Cs, [&](long long i, float v, float w) {
+        const long long k = __double2ll_rn((double)__fmul_rn(v, w) * inv_q);        // |k| <= 2^B: |v| <= max, w <= 1
+        atomicAdd(reinterpret_cast<unsigned long long*>(acc + i), (unsigned long long)k);
+    });
 }
 
 static __global__ __launch_bounds__(256) void lfgc_det_finish_kernel(const long long* __restrict__ acc,

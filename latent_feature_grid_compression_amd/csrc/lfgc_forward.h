@@ -85,6 +85,44 @@ __device__ __forceinline__ float lfgc_lattice_coord(int v, int res, int tile, fl
     return __fmul_rn(scale, nrm);
 }
 
+// Lattice mode: the coordinate of every voxel index, axis after axis (res0 | res1 | res2 floats), built once per workgroup
+// of nt threads; the caller's barrier publishes it.
+__device__ __forceinline__ void lfgc_fill_coord_table(const LfgcFwdArgs& a, float* s_coord, int tid, int nt) {
+    const int r01 = a.res0 + a.res1, r012 = r01 + a.res2;
+    for (int i = tid; i < r012; i += nt) {
+        s_coord[i] = i < a.res0 ? lfgc_lattice_coord(i, a.res0, a.tile, a.scale0)
+                   : i < r01 ? lfgc_lattice_coord(i - a.res0, a.res1, a.tile, a.scale1)
+                             : lfgc_lattice_coord(i - r01, a.res2, a.tile, a.scale2);
+    }
+}
+
+// sk[k][ax] = sin(f_k p_ax), ck[k][ax] = cos(f_k p_ax): the argument is one fp32 product, the fast evaluation is redone
+// on the slow path by the whole wave when any lane's argument leaves its range.  Shared by the forward's embedding
+// (generic NF) and the backward's d_pos.
+template <int NF>
+__device__ __forceinline__ void lfgc_fourier_trig(float p0, float p1, float p2, float (&sk)[NF > 0 ? NF : 1][3],
+                                                  float (&ck)[NF > 0 ? NF : 1][3]) {
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+        const float f = lfgc_freq(k);
+        const float a0 = __fmul_rn(p0, f), a1 = __fmul_rn(p1, f), a2 = __fmul_rn(p2, f);
+        bad |= lfgc_trig_out_of_range(a0) | lfgc_trig_out_of_range(a1) | lfgc_trig_out_of_range(a2);
+        lfgc_sincosf_t<false>(a0, sk[k][0], ck[k][0]);
+        lfgc_sincosf_t<false>(a1, sk[k][1], ck[k][1]);
+        lfgc_sincosf_t<false>(a2, sk[k][2], ck[k][2]);
+    }
+    if (__builtin_expect(__any(bad), 0)) {   // positions far outside [-1,1], inf or nan
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            const float f = lfgc_freq(k);
+            lfgc_sincosf_t<true>(__fmul_rn(p0, f), sk[k][0], ck[k][0]);
+            lfgc_sincosf_t<true>(__fmul_rn(p1, f), sk[k][1], ck[k][1]);
+            lfgc_sincosf_t<true>(__fmul_rn(p2, f), sk[k][2], ck[k][2]);
+        }
+    }
+}
+
 // Scalar inputs [p | sin f_k p | cos f_k p | 0 pad] of the lane's sample: a lane keeps only its half of the list
 // (E[0 .. EP/2) = entries [hh EP/2, (hh+1) EP/2)).
 template <int NF>
@@ -118,28 +156,13 @@ __device__ __forceinline__ void lfgc_embed_inputs(float p0, float p1, float p2, 
 #pragma unroll
             for (int t = 0; t < EPH; ++t) E[t] = hh ? hi[t] : lo[t];
         } else {
-            float e[EP];
+            float e[EP], sk[NF > 0 ? NF : 1][3], ck[NF > 0 ? NF : 1][3];
             e[0] = p0; e[1] = p1; e[2] = p2;
-            bool bad = false;
+            lfgc_fourier_trig<NF>(p0, p1, p2, sk, ck);
 #pragma unroll
             for (int k = 0; k < NF; ++k) {
-                const float f = lfgc_freq(k);
-                const float a0 = __fmul_rn(p0, f), a1 = __fmul_rn(p1, f), a2 = __fmul_rn(p2, f);
-                bad |= lfgc_trig_out_of_range(a0) | lfgc_trig_out_of_range(a1) | lfgc_trig_out_of_range(a2);
-                float s, c;
-                lfgc_sincosf_t<false>(a0, s, c); e[3 + 6 * k + 0] = s; e[3 + 6 * k + 3] = c;
-                lfgc_sincosf_t<false>(a1, s, c); e[3 + 6 * k + 1] = s; e[3 + 6 * k + 4] = c;
-                lfgc_sincosf_t<false>(a2, s, c); e[3 + 6 * k + 2] = s; e[3 + 6 * k + 5] = c;
-            }
-            if (__builtin_expect(__any(bad), 0)) {   // positions far outside [-1,1], inf or nan
 #pragma unroll
-                for (int k = 0; k < NF; ++k) {
-                    const float f = lfgc_freq(k);
-                    float s, c;
-                    lfgc_sincosf_t<true>(__fmul_rn(p0, f), s, c); e[3 + 6 * k + 0] = s; e[3 + 6 * k + 3] = c;
-                    lfgc_sincosf_t<true>(__fmul_rn(p1, f), s, c); e[3 + 6 * k + 1] = s; e[3 + 6 * k + 4] = c;
-                    lfgc_sincosf_t<true>(__fmul_rn(p2, f), s, c); e[3 + 6 * k + 2] = s; e[3 + 6 * k + 5] = c;
-                }
+                for (int ax = 0; ax < 3; ++ax) { e[3 + 6 * k + ax] = sk[k][ax]; e[3 + 6 * k + 3 + ax] = ck[k][ax]; }
             }
 #pragma unroll
             for (int t = E_; t < EP; ++t) e[t] = 0.0f;
@@ -196,7 +219,7 @@ struct LfgcSampler {
             }
         }
         // ---- trilinear gather: lane (j, hh) interpolates channels [hh*CHH, (hh+1)*CHH) -------------
-        // grid_sampler_unnormalize, align_corners=False: ((p + 1) * size - 1) / 2   (ATen GridSampler.h)
+        // literal copy of lfgc_axis_cell + inside() + clamped() (lfgc_trilinear.h): this statement order pins the kernel's code
         const float ix = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p0, 1.0f), (float)a.W), 1.0f), 0.5f);
         const float iy = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p1, 1.0f), (float)a.H), 1.0f), 0.5f);
         const float iz = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p2, 1.0f), (float)a.D), 1.0f), 0.5f);
@@ -294,7 +317,7 @@ struct LfgcColumnSampler {
     __device__ __forceinline__ void stage_a(const LfgcFwdArgs& a, int vx, int vy, int vz, const float* s_coord,
                                             float* s_col, int lane) {
         p0 = s_coord[vx]; p1 = s_coord[a.res0 + vy]; p2 = s_coord[a.res0 + a.res1 + vz];
-        // grid_sampler_unnormalize, align_corners=False: ((p + 1) * size - 1) / 2   (ATen GridSampler.h)
+        // literal copy of lfgc_axis_cell + inside() + clamped() (lfgc_trilinear.h): this statement order pins the kernel's code
         const float ix = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p0, 1.0f), (float)a.W), 1.0f), 0.5f);
         const float iy = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p1, 1.0f), (float)a.H), 1.0f), 0.5f);
         const float iz = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(p2, 1.0f), (float)a.D), 1.0f), 0.5f);
@@ -495,14 +518,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd_kernel(const LfgcFwdAr
             lfgc_dma_to_lds(a.packed, s_w, blk0, wave, lane, WAVES);      // layer 0 of the first batch -> slot 0
         }
     }
-    if (!a.pos && a.coord_table) {
-        const int r01 = a.res0 + a.res1, r012 = r01 + a.res2;
-        for (int i = tid; i < r012; i += NT) {
-            s_coord[i] = i < a.res0 ? lfgc_lattice_coord(i, a.res0, a.tile, a.scale0)
-                       : i < r01 ? lfgc_lattice_coord(i - a.res0, a.res1, a.tile, a.scale1)
-                                 : lfgc_lattice_coord(i - r01, a.res2, a.tile, a.scale2);
-        }
-    }
+    if (!a.pos && a.coord_table) lfgc_fill_coord_table(a, s_coord, tid, NT);
     __syncthreads();
     unsigned step = 0;                   // streamed: layers executed so far (ring slot = step & 1)
 

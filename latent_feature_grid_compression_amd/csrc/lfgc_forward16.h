@@ -439,7 +439,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
 #endif
         }
     }
-    if (!a.pos && a.coord_table) {
+    if (!a.pos && a.coord_table) {      // literal copy of lfgc_fill_coord_table (lfgc_forward.h): the call moves three CH 16 z-run kernels' code
         const int r01 = a.res0 + a.res1, r012 = r01 + a.res2;
         for (int i = tid; i < r012; i += NT) {
             s_coord[i] = i < a.res0 ? lfgc_lattice_coord(i, a.res0, a.tile, a.scale0)

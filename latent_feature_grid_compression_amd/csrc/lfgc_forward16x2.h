@@ -204,14 +204,7 @@ __global__ __launch_bounds__(256, 1) void lfgc_fwd16x2_kernel(const LfgcFwdArgs 
     if (tid < 16) s_scale[tid] = a.packed[off_h + 16 + tid];
     for (int i = tid; i < L * HP; i += NT) s_bias[i] = a.packed[off_h + 32 + i];
     lfgc_dma_to_lds(hblk, s_w, blkh0, wave, lane, WAVES);
-    {
-        const int r01 = a.res0 + a.res1, r012 = r01 + a.res2;
-        for (int i = tid; i < r012; i += NT) {
-            s_coord[i] = i < a.res0 ? lfgc_lattice_coord(i, a.res0, a.tile, a.scale0)
-                       : i < r01 ? lfgc_lattice_coord(i - a.res0, a.res1, a.tile, a.scale1)
-                                 : lfgc_lattice_coord(i - r01, a.res2, a.tile, a.scale2);
-        }
-    }
+    lfgc_fill_coord_table(a, s_coord, tid, NT);
     __syncthreads();
     unsigned step = 0;
 #ifdef LFGC_STAMPS
