@@ -635,6 +635,62 @@ int lfgc_debug_trig_f32(const float* x, int64_t n, float* sin_out, float* cos_ou
  * accuracy argument for the polynomial path can be re-measured. */
 int lfgc_debug_hwsin_f32(const float* x, int64_t n, float* out, lfgc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Direct volume rendering: the ray bookkeeping around the network evaluation.  Emission / absorption,
+ * front to back, no scattering.  The values (and gradients) of the samples come from lfgc_forward_f32 /
+ * lfgc_input_gradient_f32 between lfgc_ray_samples_f32 and lfgc_ray_composite_f32; the loop is host code
+ * (visualization/Render.py).
+ * All coordinates are the network's normalised coordinates (the volume's box is +-dataset.scales), directions are UNIT
+ * vectors (not checked).  Per-ray arrays have R rows; `live` lists hold ray ids in [0, R) (not checked).  All arithmetic
+ * is fp32 in exactly the stated order, no contraction, correctly rounded division.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Slab test of R rays against [box_min, box_max] (host float[3] each), axes a = 0, 1, 2 in this order, from tn = t_min,
+ * tf = t_max:  d[a] == 0: the axis bounds nothing when box_min[a] <= o[a] <= box_max[a], else the ray misses;  otherwise
+ * inv = 1/d[a], t1 = (box_min[a]-o[a])*inv, t2 = (box_max[a]-o[a])*inv, tn = fmaxf(tn, fminf(t1,t2)),
+ * tf = fminf(tf, fmaxf(t1,t2)).  Hit iff tf > tn; n_steps = (int)ceilf((tf-tn)/dt), at most max_steps.
+ * A miss writes n_steps = 0 and the empty interval t_near = t_far = t_min.
+ *   origins, dirs device (R,3); t_near, t_far device (R); n_steps device int32 (R); t_min finite, dt > 0, max_steps >= 1. */
+int lfgc_ray_clip_f32(const float* origins, const float* dirs, int64_t n_rays, const float* box_min, const float* box_max,
+                      float t_min, float t_max, float dt, int max_steps, float* t_near, float* t_far, int32_t* n_steps,
+                      lfgc_stream_t stream);
+
+/* pos (n_live*S, 3): row j*S + s = sample k = k_next[ray] + s of ray = live[j].  S is a multiple of 32, so a 32-sample
+ * tile of the forward kernel is 32 consecutive steps of one ray.  Segment k is [a, b] with a = tn + (float)k*dt and
+ * b = fminf(a + dt, tf) -- the last segment of a ray is short, not missing --; the sample sits at tm = 0.5f*(a+b),
+ * p = o + tm*d.  Rows with k >= n_steps repeat the ray's last valid sample (finite, inside the box); their value is never
+ * used.  Rays of the list must have n_steps >= 1. */
+int lfgc_ray_samples_f32(const int32_t* live, int64_t n_live, const float* origins, const float* dirs, const float* t_near,
+                         const float* t_far, const int32_t* n_steps, const int32_t* k_next, float dt, int S, float* pos,
+                         lfgc_stream_t stream);
+
+/* Composite the S samples lfgc_ray_samples_f32 laid out for the same list into state (R,4) = premultiplied r, g, b and the
+ * transmittance T per ray (initialised to (0,0,0,1) by the caller, updated in place; 16-byte aligned), then
+ * k_next[ray] += S.  Rays outside the list are not touched.  A ray id may appear once in the list.
+ *   values (n_live*S); grad (n_live*S, 3) or NULL; tf_table (K,4) = r, g, b, extinction per unit length (16-byte aligned),
+ *   K >= 2; tf_scale = (K-1)/(v_max-v_min).
+ * Per sample k < n_steps (later rows contribute nothing):
+ *   len = fmaxf(b - a, 0) of its segment (a step count that the division rounded up puts the last a an ulp past t_far);
+ *   u = fminf(fmaxf((v-v_min)*tf_scale, 0), K-1);  i = min((int)u, K-2);  f = u - i;
+ *   rgba = tab[i] + f*(tab[i+1]-tab[i]);  alpha = 1 - expf(-rgba.w*len);
+ *   shade = 1 without grad, else ka + kd*|g.d|/|g| when |g| > 0 (as fp32 computes it) and ka + kd otherwise: a headlight,
+ *   two-sided diffuse;
+ *   the sample contributes iff 1 - T_before < opacity_limit:  rgb += T*alpha*shade*rgba.rgb, then T *= 1 - alpha.
+ * T never increases, so the contributing samples of a ray are a prefix; 32 samples at a time are folded by a product scan
+ * and a tree sum, whose rounding differs from a sequential loop's by a few ulp per sample. */
+int lfgc_ray_composite_f32(const int32_t* live, int64_t n_live, const float* values, const float* grad, const float* dirs,
+                           const float* t_near, const float* t_far, const int32_t* n_steps, int32_t* k_next, float dt,
+                           int S, const float* tf_table, int K, float v_min, float tf_scale, float opacity_limit, float ka,
+                           float kd, float* state, lfgc_stream_t stream);
+
+/* live_out[0..*count) = the rays r of prev[0..n_prev) (prev == NULL: r = 0..n_prev-1) with k_next[r] < n_steps[r] and
+ * 1 - T[r] < opacity_limit, in the order of prev (ascending ids stay ascending: neighbouring pixels stay neighbours, and
+ * the list does not depend on scheduling).  count: device int64.  live_out must not alias prev. */
+int64_t lfgc_ray_compact_workspace_bytes(int64_t n);
+int lfgc_ray_compact(const int32_t* prev, int64_t n_prev, const int32_t* n_steps, const int32_t* k_next, const float* state,
+                     float opacity_limit, int32_t* live_out, int64_t* count, void* workspace, int64_t workspace_bytes,
+                     lfgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,338 @@
+// lfgc_render.hip -- direct volume rendering around the network evaluation (gfx950): everything a ray marcher needs
+// except the values themselves, which come from lfgc_forward_f32 / lfgc_input_gradient_f32 unchanged.
+//   lfgc_ray_clip_f32        slab test of every ray against the volume's box -> [t_near, t_far], number of steps
+//   lfgc_ray_samples_f32     the next S sample positions of every live ray, S consecutive rows per ray: one 32-sample
+//                            tile of the forward kernel is 32 consecutive steps of ONE ray
+//   lfgc_ray_composite_f32   transfer function, headlight shading and front-to-back compositing of those S samples
+//                            into the per-ray state (premultiplied r, g, b and the transmittance T)
+//   lfgc_ray_compact         order-preserving list of the rays that still have steps left and are not yet opaque
+// All arithmetic is fp32 in the order include/lfgc.h states (the build has no contraction and correctly rounded
+// division), so the clip and the positions can be restated bit for bit on the host.  One writer per ray: no atomics.
+#include "lfgc_common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kPerBlock = 2048;                 // list elements per workgroup in the two compaction passes
+constexpr int kRun = 32;                        // samples of one ray composited per step: one half wave
+
+struct RayBox { float lo[3], hi[3]; };
+
+// ---- clip -----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void ray_clip_kernel(const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                          long long n_rays, const RayBox box, float t_min, float t_max, float dt,
+                                                          int max_steps, float* __restrict__ t_near, float* __restrict__ t_far,
+                                                          int* __restrict__ n_steps) {
+    const long long r = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n_rays) return;
+    float tn = t_min, tf = t_max;
+    bool hit = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float o = origins[r * 3 + a], d = dirs[r * 3 + a];
+        if (d == 0.0f) {
+            if (!(box.lo[a] <= o && o <= box.hi[a])) hit = false;
+        } else {
+            const float inv = 1.0f / d;
+            const float t1 = (box.lo[a] - o) * inv;
+            const float t2 = (box.hi[a] - o) * inv;
+            tn = fmaxf(tn, fminf(t1, t2));
+            tf = fminf(tf, fmaxf(t1, t2));
+        }
+    }
+    hit = hit && tf > tn;
+    int n = 0;
+    if (hit) {
+        const float q = ceilf((tf - tn) / dt);
+        n = q >= (float)max_steps ? max_steps : (int)q;          // the comparison also keeps the conversion in range
+    } else {
+        tn = tf = t_min;                                         // a miss: the empty interval
+    }
+    t_near[r] = tn;
+    t_far[r] = tf;
+    n_steps[r] = n;
+}
+
+// segment k of a ray: [a, b] with a = tn + k dt (never an accumulated sum) and b = min(a + dt, tf)
+__device__ __forceinline__ void ray_segment(float tn, float tf, float dt, int k, float& a, float& b) {
+    a = tn + (float)k * dt;
+    b = fminf(a + dt, tf);
+}
+
+// ---- samples --------------------------------------------------------------------------------------------------------
+// thread = one output row; the 12-byte rows of a wave are consecutive, so its three stores cover 768 contiguous bytes
+__global__ __launch_bounds__(kBlock) void ray_samples_kernel(const int* __restrict__ live, long long n_rows, int S,
+                                                             const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                             const float* __restrict__ t_near, const float* __restrict__ t_far,
+                                                             const int* __restrict__ n_steps, const int* __restrict__ k_next,
+                                                             float dt, float* __restrict__ pos) {
+    const long long row = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (row >= n_rows) return;
+    const long long j = row / S;
+    const int s = (int)(row - j * S);
+    const long long r = live[j];
+    int k = k_next[r] + s;
+    const int n = n_steps[r];
+    if (k > n - 1) k = n - 1;                    // padding rows repeat the last valid sample
+    if (k < 0) k = 0;
+    float a, b;
+    ray_segment(t_near[r], t_far[r], dt, k, a, b);
+    const float tm = 0.5f * (a + b);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pos[row * 3 + c] = origins[r * 3 + c] + tm * dirs[r * 3 + c];
+}
+
+// ---- composite ------------------------------------------------------------------------------------------------------
+// A half wave (32 lanes) owns one ray and walks its S samples in runs of 32: lane l of the half reads value l of the run
+// (one coalesced 128-byte row), forms its own alpha and colour, and the run is folded with a log-step product scan of the
+// (1 - alpha) factors and a butterfly sum of the contributions.  T never increases, so the samples that contribute are a
+// prefix of the run: T after the run is T before the first lane that does not contribute.  The lanes a ray's samples sit
+// on do not depend on the list the ray is in, so neither does a single bit of its result.
+template <bool SHADE>
+__global__ __launch_bounds__(kBlock) void ray_composite_kernel(const int* __restrict__ live, long long n_live, int S,
+                                                               const float* __restrict__ values, const float* __restrict__ grad,
+                                                               const float* __restrict__ dirs, const float* __restrict__ t_near,
+                                                               const float* __restrict__ t_far, const int* __restrict__ n_steps,
+                                                               int* __restrict__ k_next, float dt,
+                                                               const float4* __restrict__ tab, int K, float v_min, float tf_scale,
+                                                               float opacity_limit, float ka, float kd,
+                                                               float4* __restrict__ state) {
+    const int lane = threadIdx.x & (kRun - 1);
+    const long long j = (long long)blockIdx.x * (kBlock / kRun) + (threadIdx.x / kRun);
+    if (j >= n_live) return;                     // a whole half wave leaves: the shuffles below stay inside one half
+    const long long r = live[j];
+    const float tn = t_near[r], tf = t_far[r];
+    const int n = n_steps[r], k0 = k_next[r];
+    float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+    if (SHADE) { dx = dirs[r * 3 + 0]; dy = dirs[r * 3 + 1]; dz = dirs[r * 3 + 2]; }
+    const float4 st = state[r];
+    float cr = st.x, cg = st.y, cb = st.z, T = st.w;
+    const float u_max = (float)(K - 1);
+    for (int s0 = 0; s0 < S; s0 += kRun) {
+        const long long row = j * S + s0 + lane;
+        const int k = k0 + s0 + lane;
+        float alpha = 0.0f, er = 0.0f, eg = 0.0f, eb = 0.0f;
+        if (k < n) {
+            float a, b;
+            ray_segment(tn, tf, dt, k, a, b);
+            const float len = fmaxf(b - a, 0.0f);        // a step count rounded up: the last segment starts an ulp past t_far
+            const float u = fminf(fmaxf((values[row] - v_min) * tf_scale, 0.0f), u_max);
+            int i = (int)u;
+            if (i > K - 2) i = K - 2;
+            const float f = u - (float)i;
+            const float4 c0 = tab[i], c1 = tab[i + 1];
+            const float sigma = c0.w + f * (c1.w - c0.w);
+            alpha = 1.0f - expf(-sigma * len);
+            float shade = 1.0f;
+            if (SHADE) {
+                const float gx = grad[row * 3 + 0], gy = grad[row * 3 + 1], gz = grad[row * 3 + 2];
+                const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
+                shade = gn > 0.0f ? ka + kd * fabsf(gx * dx + gy * dy + gz * dz) / gn : ka + kd;
+            }
+            const float w = alpha * shade;
+            er = w * (c0.x + f * (c1.x - c0.x));
+            eg = w * (c0.y + f * (c1.y - c0.y));
+            eb = w * (c0.z + f * (c1.z - c0.z));
+        }
+        float incl = 1.0f - alpha;               // inclusive product of the factors of lanes 0..lane
+#pragma unroll
+        for (int off = 1; off < kRun; off <<= 1) {
+            const float t = __shfl_up(incl, off, kRun);
+            if (lane >= off) incl *= t;
+        }
+        float excl = __shfl_up(incl, 1, kRun);
+        if (lane == 0) excl = 1.0f;
+        const float t_before = T * excl;
+        // the first lane that is out ends the ray (the rounded products of two scan trees need not be ordered, so the
+        // prefix is cut there explicitly); T after the run: T before that lane, else T times every factor
+        const unsigned long long out_mask =
+            (__ballot(!(1.0f - t_before < opacity_limit)) >> ((threadIdx.x & 32) ? 32 : 0)) & 0xffffffffull;
+        const int first_out = out_mask ? __ffsll((long long)out_mask) - 1 : kRun;
+        const bool in = lane < first_out;
+        float sr = in ? t_before * er : 0.0f, sg = in ? t_before * eg : 0.0f, sb = in ? t_before * eb : 0.0f;
+#pragma unroll
+        for (int off = kRun / 2; off > 0; off >>= 1) {
+            sr += __shfl_xor(sr, off, kRun);
+            sg += __shfl_xor(sg, off, kRun);
+            sb += __shfl_xor(sb, off, kRun);
+        }
+        const float t_all = T * __shfl(incl, kRun - 1, kRun);
+        const float t_cut = __shfl(t_before, first_out & (kRun - 1), kRun);
+        T = out_mask ? t_cut : t_all;
+        cr += sr; cg += sg; cb += sb;
+    }
+    if (lane == 0) {
+        state[r] = make_float4(cr, cg, cb, T);
+        k_next[r] = k0 + S;
+    }
+}
+
+// ---- order-preserving list of the rays still worth marching -----------------------------------------------------------
+// the count / scan / write passes of the checkpoint codec's compaction (lfgc_codec.hip), over ray ids instead of values
+struct RayAlive {
+    const int* prev;             // previous list (ascending ray ids) or NULL = every ray 0..n-1
+    const int* n_steps;
+    const int* k_next;
+    const float4* state;
+    float opacity_limit;
+};
+
+__device__ __forceinline__ bool ray_alive(const RayAlive& s, long long i, long long n, int& ray) {
+    ray = 0;
+    if (i >= n) return false;
+    ray = s.prev ? s.prev[i] : (int)i;
+    return s.k_next[ray] < s.n_steps[ray] && 1.0f - s.state[ray].w < s.opacity_limit;
+}
+
+__global__ __launch_bounds__(kBlock) void alive_count_kernel(const RayAlive s, long long n, unsigned* __restrict__ block_counts) {
+    const long long base = (long long)blockIdx.x * kPerBlock;
+    unsigned c = 0;
+    int ray;
+#pragma unroll
+    for (int j = 0; j < kPerBlock / kBlock; ++j) c += ray_alive(s, base + j * kBlock + threadIdx.x, n, ray);
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    __shared__ unsigned sw[4];
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+}
+
+// exclusive scan of the block counts (one workgroup; 64-bit offsets), total -> *count
+__global__ __launch_bounds__(1024) void alive_scan_kernel(const unsigned* __restrict__ counts, long long* __restrict__ offsets,
+                                                          long long nblocks, long long* __restrict__ total) {
+    __shared__ long long s_wave[16];
+    __shared__ long long s_carry;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (long long b0 = 0; b0 < nblocks; b0 += 1024) {
+        const long long b = b0 + threadIdx.x;
+        const long long v = b < nblocks ? counts[b] : 0;
+        long long incl = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            const long long t = __shfl_up(incl, off);
+            if ((threadIdx.x & 63) >= off) incl += t;
+        }
+        if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
+        __syncthreads();
+        long long wave_off = 0;
+        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) wave_off += s_wave[w];
+        const long long carry = s_carry;
+        if (b < nblocks) offsets[b] = carry + wave_off + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) s_carry = carry + wave_off + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = s_carry;
+}
+
+// element order inside a workgroup's 2048-element chunk: pass j (0..7) x wave w (0..3) x lane
+__global__ __launch_bounds__(kBlock) void alive_write_kernel(const RayAlive s, long long n, const long long* __restrict__ offsets,
+                                                             int* __restrict__ live_out) {
+    const long long base = (long long)blockIdx.x * kPerBlock;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ unsigned s_cnt[8][4];
+    bool flag[8];
+    int ray[8];
+    unsigned long long bal[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        flag[j] = ray_alive(s, base + j * kBlock + threadIdx.x, n, ray[j]);
+        bal[j] = __ballot(flag[j]);
+        if (lane == 0) s_cnt[j][wave] = (unsigned)__popcll(bal[j]);
+    }
+    __syncthreads();
+    long long run = offsets[blockIdx.x];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w == wave && flag[j]) live_out[run + __popcll(bal[j] & ((1ull << lane) - 1ull))] = ray[j];
+            run += s_cnt[j][w];
+        }
+    }
+}
+
+inline bool finite_f(float v) { return v - v == 0.0f; }
+
+}  // namespace
+
+extern "C" int lfgc_ray_clip_f32(const float* origins, const float* dirs, int64_t n_rays, const float* box_min, const float* box_max,
+                                 float t_min, float t_max, float dt, int max_steps, float* t_near, float* t_far, int32_t* n_steps,
+                                 lfgc_stream_t stream) {
+    if (!origins || !dirs || !box_min || !box_max || !t_near || !t_far || !n_steps) return LFGC_E_NULL;
+    if (n_rays < 1 || n_rays > 0x7fffffffLL || max_steps < 1 || !(dt > 0.0f) || !finite_f(dt) || !finite_f(t_min)) return LFGC_E_SHAPE;
+    RayBox box;
+    for (int a = 0; a < 3; ++a) {
+        box.lo[a] = box_min[a];
+        box.hi[a] = box_max[a];
+        if (!(box.lo[a] <= box.hi[a])) return LFGC_E_SHAPE;
+    }
+    hipLaunchKernelGGL(ray_clip_kernel, dim3((unsigned)((n_rays + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                       origins, dirs, (long long)n_rays, box, t_min, t_max, dt, max_steps, t_near, t_far, n_steps);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_ray_samples_f32(const int32_t* live, int64_t n_live, const float* origins, const float* dirs, const float* t_near,
+                                    const float* t_far, const int32_t* n_steps, const int32_t* k_next, float dt, int S, float* pos,
+                                    lfgc_stream_t stream) {
+    if (!live || !origins || !dirs || !t_near || !t_far || !n_steps || !k_next || !pos) return LFGC_E_NULL;
+    if (n_live < 1 || n_live > 0x7fffffffLL || S < 32 || S % 32 != 0 || !(dt > 0.0f)) return LFGC_E_SHAPE;
+    const long long n_rows = (long long)n_live * S;
+    const long long nblocks = (n_rows + kBlock - 1) / kBlock;
+    if (nblocks > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
+    hipLaunchKernelGGL(ray_samples_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, n_rows, S, origins,
+                       dirs, t_near, t_far, n_steps, k_next, dt, pos);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_ray_composite_f32(const int32_t* live, int64_t n_live, const float* values, const float* grad, const float* dirs,
+                                      const float* t_near, const float* t_far, const int32_t* n_steps, int32_t* k_next, float dt,
+                                      int S, const float* tf_table, int K, float v_min, float tf_scale, float opacity_limit, float ka,
+                                      float kd, float* state, lfgc_stream_t stream) {
+    if (!live || !values || !dirs || !t_near || !t_far || !n_steps || !k_next || !tf_table || !state) return LFGC_E_NULL;
+    if (n_live < 1 || n_live > 0x7fffffffLL || S < 32 || S % 32 != 0 || K < 2 || !(dt > 0.0f)) return LFGC_E_SHAPE;
+    if (((uintptr_t)tf_table | (uintptr_t)state) & 15) return LFGC_E_ALIGN;
+    const int per_block = kBlock / kRun;
+    const unsigned nblocks = (unsigned)((n_live + per_block - 1) / per_block);
+    const float4* tab = reinterpret_cast<const float4*>(tf_table);
+    float4* st = reinterpret_cast<float4*>(state);
+    if (grad) hipLaunchKernelGGL(ray_composite_kernel<true>, dim3(nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, (long long)n_live,
+                                 S, values, grad, dirs, t_near, t_far, n_steps, k_next, dt, tab, K, v_min, tf_scale, opacity_limit, ka,
+                                 kd, st);
+    else hipLaunchKernelGGL(ray_composite_kernel<false>, dim3(nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, (long long)n_live,
+                            S, values, grad, dirs, t_near, t_far, n_steps, k_next, dt, tab, K, v_min, tf_scale, opacity_limit, ka, kd,
+                            st);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int64_t lfgc_ray_compact_workspace_bytes(int64_t n) {
+    if (n < 1) return 16;
+    const long long nblocks = (n + kPerBlock - 1) / kPerBlock;
+    return (nblocks + 1) * 8 + nblocks * 4 + 16;
+}
+
+extern "C" int lfgc_ray_compact(const int32_t* prev, int64_t n_prev, const int32_t* n_steps, const int32_t* k_next, const float* state,
+                                float opacity_limit, int32_t* live_out, int64_t* count, void* workspace, int64_t workspace_bytes,
+                                lfgc_stream_t stream) {
+    if (!n_steps || !k_next || !state || !live_out || !count || !workspace) return LFGC_E_NULL;
+    if (n_prev < 1 || n_prev > 0x7fffffffLL) return LFGC_E_SHAPE;
+    if ((uintptr_t)state & 15) return LFGC_E_ALIGN;
+    if (workspace_bytes < lfgc_ray_compact_workspace_bytes(n_prev)) return LFGC_E_WORKSPACE;
+    const long long n = n_prev, nblocks = (n + kPerBlock - 1) / kPerBlock;
+    long long* offsets = reinterpret_cast<long long*>(workspace);
+    unsigned* counts = reinterpret_cast<unsigned*>(offsets + nblocks + 1);
+    RayAlive s;
+    s.prev = prev; s.n_steps = n_steps; s.k_next = k_next; s.state = reinterpret_cast<const float4*>(state);
+    s.opacity_limit = opacity_limit;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(alive_count_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, st, s, n, counts);
+    LFGC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(alive_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, nblocks, reinterpret_cast<long long*>(count));
+    LFGC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(alive_write_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, st, s, n, offsets, live_out);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}

@@ -1234,3 +1234,103 @@ def deviation_partial(pred: torch.Tensor, gt: torch.Tensor, acc: Optional[torch.
     check(lib.lfgc_deviation_partial_f32(pred.data_ptr(), gt.data_ptr(), pred.numel(), acc.data_ptr(), _stream(pred)),
           'lfgc_deviation_partial_f32')
     return acc
+
+
+# ---- direct volume rendering: the ray bookkeeping around the forward kernel -------------------------
+
+def _ray_i32(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous int32 tensor' % what)
+    return t
+
+
+@_on_device
+def ray_clip(origins: torch.Tensor, dirs: torch.Tensor, box_min, box_max, dt: float, max_steps: int,
+             t_min: float = 0.0, t_max: float = float('inf')) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(t_near (R,), t_far (R,), n_steps (R,) int32) of R rays against the box: lfgc_ray_clip_f32.  A miss has n_steps 0.
+    origins, dirs (R,3); dirs are unit vectors."""
+    _require_hip(origins, dirs)
+    origins, dirs = _f32c(origins), _f32c(dirs)
+    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape:
+        raise ValueError('origins and dirs must both be (R, 3), got %s and %s' % (tuple(origins.shape), tuple(dirs.shape)))
+    R = origins.shape[0]
+    t_near = torch.empty(R, dtype=torch.float32, device=origins.device)
+    t_far = torch.empty(R, dtype=torch.float32, device=origins.device)
+    n_steps = torch.empty(R, dtype=torch.int32, device=origins.device)
+    if R:
+        check(_lib.load().lfgc_ray_clip_f32(origins.data_ptr(), dirs.data_ptr(), R, _float3(box_min), _float3(box_max), float(t_min),
+                                            float(t_max), float(dt), int(max_steps), t_near.data_ptr(), t_far.data_ptr(),
+                                            n_steps.data_ptr(), _stream(origins)), 'lfgc_ray_clip_f32')
+    return t_near, t_far, n_steps
+
+
+@_on_device
+def ray_samples(live: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, t_near: torch.Tensor, t_far: torch.Tensor,
+                n_steps: torch.Tensor, k_next: torch.Tensor, dt: float, S: int = 32) -> torch.Tensor:
+    """(len(live) * S, 3) positions: row j*S + s is sample k_next[ray] + s of ray live[j] (lfgc_ray_samples_f32).  S is a
+    multiple of 32; rows past a ray's last step repeat its last valid sample."""
+    _require_hip(live, origins, dirs, t_near, t_far, n_steps, k_next)
+    live = _ray_i32(live, 'live')
+    pos = torch.empty((live.numel() * int(S), 3), dtype=torch.float32, device=live.device)
+    if live.numel():
+        check(_lib.load().lfgc_ray_samples_f32(live.data_ptr(), live.numel(), _f32c(origins).data_ptr(), _f32c(dirs).data_ptr(),
+                                               _f32c(t_near).data_ptr(), _f32c(t_far).data_ptr(), _ray_i32(n_steps, 'n_steps').data_ptr(),
+                                               _ray_i32(k_next, 'k_next').data_ptr(), float(dt), int(S), pos.data_ptr(),
+                                               _stream(live)), 'lfgc_ray_samples_f32')
+    return pos
+
+
+@_on_device
+def ray_composite(live: torch.Tensor, values: torch.Tensor, grad: Optional[torch.Tensor], dirs: torch.Tensor,
+                  t_near: torch.Tensor, t_far: torch.Tensor, n_steps: torch.Tensor, k_next: torch.Tensor, dt: float, S: int,
+                  tf_table: torch.Tensor, v_min: float, v_max: float, opacity_limit: float, state: torch.Tensor,
+                  ka: float = 0.3, kd: float = 0.7) -> None:
+    """Composite the S samples per live ray that ray_samples laid out into state (R,4) in place and advance k_next by S:
+    lfgc_ray_composite_f32.  values (len(live)*S,), grad (len(live)*S, 3) or None, tf_table (K,4)."""
+    _require_hip(live, values, grad, dirs, t_near, t_far, n_steps, k_next, tf_table, state)
+    live = _ray_i32(live, 'live')
+    n_rows = live.numel() * int(S)
+    K = int(tf_table.shape[0])
+    if tf_table.dim() != 2 or tf_table.shape[1] != 4 or K < 2 or tf_table.dtype != torch.float32 or not tf_table.is_contiguous():
+        raise ValueError('tf_table must be a contiguous fp32 (K, 4) tensor with K >= 2')
+    if state.dtype != torch.float32 or not state.is_contiguous() or state.dim() != 2 or state.shape[1] != 4:
+        raise ValueError('state must be a contiguous fp32 (R, 4) tensor')
+    if not float(v_max) > float(v_min):
+        raise ValueError('v_max must exceed v_min')
+    values = _f32c(values).reshape(-1)
+    if values.numel() != n_rows:
+        raise ValueError('%d values for %d rays of %d samples' % (values.numel(), live.numel(), S))
+    if grad is not None:
+        grad = _f32c(grad)
+        if tuple(grad.shape) != (n_rows, 3):
+            raise ValueError('grad must be (%d, 3), got %s' % (n_rows, tuple(grad.shape)))
+    if not live.numel():
+        return
+    tf_scale = (K - 1) / (float(v_max) - float(v_min))
+    check(_lib.load().lfgc_ray_composite_f32(live.data_ptr(), live.numel(), values.data_ptr(), _ptr(grad), _f32c(dirs).data_ptr(),
+                                             _f32c(t_near).data_ptr(), _f32c(t_far).data_ptr(), _ray_i32(n_steps, 'n_steps').data_ptr(),
+                                             _ray_i32(k_next, 'k_next').data_ptr(), float(dt), int(S), tf_table.data_ptr(), K,
+                                             float(v_min), tf_scale, float(opacity_limit), float(ka), float(kd), state.data_ptr(),
+                                             _stream(live)), 'lfgc_ray_composite_f32')
+
+
+@_on_device
+def ray_compact(prev: Optional[torch.Tensor], n_steps: torch.Tensor, k_next: torch.Tensor, state: torch.Tensor,
+                opacity_limit: float) -> torch.Tensor:
+    """The rays of prev (None: all rays) that have steps left (k_next < n_steps) and are not yet opaque
+    (1 - T < opacity_limit), in order (int32).  Synchronises once to learn their number."""
+    _require_hip(prev, n_steps, k_next, state)
+    n_steps, k_next = _ray_i32(n_steps, 'n_steps'), _ray_i32(k_next, 'k_next')
+    if state.dtype != torch.float32 or not state.is_contiguous() or tuple(state.shape) != (n_steps.numel(), 4):
+        raise ValueError('state must be a contiguous fp32 (R, 4) tensor')
+    n = n_steps.numel() if prev is None else _ray_i32(prev, 'prev').numel()
+    out = torch.empty(n, dtype=torch.int32, device=n_steps.device)
+    if n == 0:
+        return out
+    count = torch.zeros(1, dtype=torch.int64, device=n_steps.device)
+    nbytes = int(_lib.load().lfgc_ray_compact_workspace_bytes(n))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=n_steps.device)
+    check(_lib.load().lfgc_ray_compact(_ptr(prev), n, n_steps.data_ptr(), k_next.data_ptr(), state.data_ptr(), float(opacity_limit),
+                                       out.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(n_steps)),
+          'lfgc_ray_compact')
+    return out[:int(count.item())]

@@ -1,0 +1,191 @@
+"""NumPy restatement of the renderer's contract (include/lfgc.h) -- a helper, not a test.
+
+* ``clip`` and ``samples`` in float32, operation for operation as the contract states them (every float32 operation of
+  NumPy is correctly rounded and nothing is contracted, as in the kernels' build), so the device results are expected
+  to be EQUAL, not close.
+* ``composite`` in float64, one sample after the other, including the contribution rule and the shading; its inputs are
+  the float32 numbers the kernel gets (t_near, t_far, dt, values, table), everything after that is float64.
+
+Written from the contract, not from the kernels.  Where the contract leaves a value open it follows the header: a miss
+is the empty interval t_near = t_far = t_min with n_steps 0, the step count is limited to max_steps before it is
+converted to an integer, and a segment's length is never negative (len = max(b - a, 0)).  Also the shared inputs of the host and GPU tests (rays, compositing case)."""
+import numpy as np
+
+F = np.float32
+BOX = (np.array([-1.0, -0.75, -0.5], F), np.array([1.0, 0.75, 0.5], F))     # a non-cubic volume: +-scales
+DT = 0.0371
+
+
+def clip(origins, dirs, box_min, box_max, t_min, t_max, dt, max_steps):
+    o, d = np.asarray(origins, F), np.asarray(dirs, F)
+    bmin, bmax = np.asarray(box_min, F), np.asarray(box_max, F)
+    R = o.shape[0]
+    tn, tf = np.full(R, t_min, F), np.full(R, t_max, F)
+    hit = np.ones(R, bool)
+    with np.errstate(all='ignore'):
+        for a in range(3):
+            zero = d[:, a] == 0
+            inside = (bmin[a] <= o[:, a]) & (o[:, a] <= bmax[a])
+            hit &= ~(zero & ~inside)
+            inv = F(1) / np.where(zero, F(1), d[:, a])
+            t1 = (bmin[a] - o[:, a]) * inv
+            t2 = (bmax[a] - o[:, a]) * inv
+            tn = np.where(zero, tn, np.fmax(tn, np.fmin(t1, t2))).astype(F)
+            tf = np.where(zero, tf, np.fmin(tf, np.fmax(t1, t2))).astype(F)
+        hit &= tf > tn
+        q = np.ceil((tf - tn) / F(dt))
+        assert q.dtype == F
+        n = np.where(q >= F(max_steps), max_steps, np.where(np.isfinite(q), q, 0).astype(np.int64))
+    n = np.where(hit, n, 0).astype(np.int32)
+    tn = np.where(hit, tn, F(t_min)).astype(F)
+    tf = np.where(hit, tf, F(t_min)).astype(F)
+    return tn, tf, n
+
+
+def segments(tn, tf, k, dt):
+    """[a, b] of segment k (float32): a = tn + (float)k*dt, b = fminf(a + dt, tf)."""
+    a = (tn + k.astype(F) * F(dt)).astype(F)
+    b = np.fmin((a + F(dt)).astype(F), tf).astype(F)
+    return a, b
+
+
+def samples(live, origins, dirs, tn, tf, n_steps, k_next, dt, S):
+    o, d = np.asarray(origins, F), np.asarray(dirs, F)
+    r = np.repeat(np.asarray(live, np.int64), S)
+    s = np.tile(np.arange(S, dtype=np.int64), len(live))
+    k = np.maximum(np.minimum(k_next[r].astype(np.int64) + s, n_steps[r].astype(np.int64) - 1), 0)
+    a, b = segments(tn[r], tf[r], k, dt)
+    tm = (F(0.5) * (a + b).astype(F)).astype(F)
+    p = (o[r] + (tm[:, None] * d[r]).astype(F)).astype(F)
+    return p, k
+
+
+def composite(values, grads, dirs, tn, tf, n_steps, dt, table, v_min, v_max, limit, ka=0.3, kd=0.7, k_begin=0, state=None):
+    """float64, sequential.  values (R, M): column m is sample k = k_begin + m of every ray (columns with k >= n_steps are
+    ignored); grads (R, M, 3) or None.  state (R, 4) = premultiplied r, g, b and T, default (0, 0, 0, 1).
+    Returns (state after, margin (R,)): margin = the smallest distance |opacity before a sample - limit| over the samples
+    the ray visits -- a ray whose margin is within rounding could have the contribution rule decided the other way."""
+    values = np.asarray(values, np.float64)
+    R, M = values.shape
+    table = np.asarray(table, np.float64)
+    K = table.shape[0]
+    tf_scale = (K - 1) / (float(v_max) - float(v_min))
+    st = np.tile(np.array([0.0, 0.0, 0.0, 1.0]), (R, 1)) if state is None else np.array(state, np.float64)
+    rgb, T = st[:, :3].copy(), st[:, 3].copy()
+    margin = np.full(R, np.inf)
+    d64 = np.asarray(dirs, np.float64)
+    tn64, tf64, dt64 = np.asarray(tn, np.float64), np.asarray(tf, np.float64), float(F(dt))
+    for m in range(M):
+        k = np.full(R, k_begin + m, np.int64)
+        valid = k < n_steps
+        a = tn64 + k * dt64                                  # the segment in float64: the lengths of a ray add up to its chord
+        length = np.where(valid, np.maximum(np.minimum(a + dt64, tf64) - a, 0.0), 0.0)
+        u = np.clip((values[:, m] - v_min) * tf_scale, 0.0, K - 1)
+        i = np.minimum(u.astype(np.int64), K - 2)
+        f = (u - i)[:, None]
+        rgba = table[i] + f * (table[i + 1] - table[i])
+        alpha = 1.0 - np.exp(-rgba[:, 3] * length)
+        shade = np.ones(R)
+        if grads is not None:
+            g = np.asarray(grads[:, m], np.float64)
+            gn = np.sqrt((g * g).sum(1))
+            with np.errstate(all='ignore'):
+                shade = np.where(gn > 0, ka + kd * np.abs((g * d64).sum(1)) / np.where(gn > 0, gn, 1.0), ka + kd)
+        opacity = 1.0 - T
+        margin = np.where(valid, np.minimum(margin, np.abs(opacity - limit)), margin)
+        use = valid & (opacity < limit)
+        rgb += np.where(use, T * alpha * shade, 0.0)[:, None] * rgba[:, :3]
+        T = np.where(use, T * (1.0 - alpha), T)
+    return np.concatenate([rgb, T[:, None]], 1), margin
+
+
+def composite_bound(n_steps):
+    """4 n_steps 2^-24 absolute per channel: one expf and a few roundings per step, a product of n_steps factors and a sum
+    of n_steps terms <= 1."""
+    return 4.0 * np.maximum(np.asarray(n_steps, np.float64), 1.0) * 2.0 ** -24
+
+
+# ---- shared inputs ------------------------------------------------------------------------------------------------------
+
+def ray_set():
+    """(origins, dirs) float32: a 24 x 20 pinhole image (480 rays, no multiple of 64) looking obliquely at BOX, then 64
+    hand-made rays."""
+    from latent_feature_grid_compression_amd.visualization.Render import pinhole_rays
+    o, d = pinhole_rays((2.3, 1.4, 1.7), (0.1, -0.05, 0.0), (0.0, 0.0, 1.0), 38.0, 24, 20)
+    s = np.sqrt(0.5)
+    t = np.sqrt(1.0 / 3.0)
+    hand = [
+        # one zero direction component: inside / outside the slab of that axis
+        ((-2.0, 0.2, 0.1), (s, s, 0.0)), ((-2.0, 0.2, 0.7), (s, s, 0.0)), ((0.3, -2.0, 0.1), (0.0, s, s)),
+        ((1.5, -2.0, 0.1), (0.0, s, s)), ((0.3, 0.2, -2.0), (s, 0.0, s)), ((0.3, 0.9, -2.0), (s, 0.0, s)),
+        # two zero components: inside / outside
+        ((-3.0, 0.1, 0.2), (1.0, 0.0, 0.0)), ((-3.0, 0.8, 0.2), (1.0, 0.0, 0.0)), ((0.5, 3.0, -0.3), (0.0, -1.0, 0.0)),
+        ((0.5, 3.0, -0.6), (0.0, -1.0, 0.0)), ((0.5, 0.5, 3.0), (0.0, 0.0, -1.0)), ((1.5, 0.5, 3.0), (0.0, 0.0, -1.0)),
+        # three zero components (no direction at all): inside the box, outside it
+        ((0.1, 0.1, 0.1), (0.0, 0.0, 0.0)), ((2.0, 0.1, 0.1), (0.0, 0.0, 0.0)),
+        # origin inside the box
+        ((0.0, 0.0, 0.0), (t, t, t)), ((0.5, -0.5, 0.25), (-s, 0.0, s)), ((-0.9, 0.7, -0.4), (0.6, -0.8, 0.0)),
+        # origin exactly on a face: pointing in, pointing out, along the face
+        ((-1.0, 0.0, 0.0), (1.0, 0.0, 0.0)), ((-1.0, 0.0, 0.0), (-1.0, 0.0, 0.0)), ((1.0, 0.2, 0.1), (0.0, 1.0, 0.0)),
+        ((0.2, 0.75, 0.1), (s, -s, 0.0)), ((0.2, 0.1, 0.5), (0.0, 0.0, 1.0)), ((0.2, 0.1, -0.5), (0.6, 0.0, 0.8)),
+        # pointing away
+        ((3.0, 0.0, 0.0), (1.0, 0.0, 0.0)), ((2.0, 2.0, 2.0), (t, t, t)), ((0.0, -2.0, 0.0), (0.0, -1.0, 0.0)),
+        # grazing an edge: along the edge x = 1, y = 0.75 and across the edge y = 0.75, z = 0.5
+        ((1.0, 0.75, -2.0), (0.0, 0.0, 1.0)), ((0.0, 1.25, 0.0), (0.0, -s, s)), ((0.0, 1.0, 0.75), (0.0, -s, -s)),
+        ((-3.0, 0.75, 0.5), (1.0, 0.0, 0.0)),
+        # through a corner: the diagonal of the box, and a ray that touches the corner (1, 0.75, 0.5) only
+        ((-2.0, -1.5, -1.0), (2.0 / np.sqrt(7.25), 1.5 / np.sqrt(7.25), 1.0 / np.sqrt(7.25))),
+        ((2.0, 1.5, 1.0), (-2.0 / np.sqrt(7.25), -1.5 / np.sqrt(7.25), -1.0 / np.sqrt(7.25))),
+        ((2.0, -0.25, 0.5), (-s, s, 0.0)), ((1.0, 0.75, 1.5), (0.0, 0.0, -1.0)),
+    ]
+    rng = np.random.default_rng(20)
+    while len(hand) < 64:                                     # random rays from a shell around the box, some missing it
+        p = rng.normal(size=3)
+        p = 2.5 * p / np.linalg.norm(p)
+        q = rng.uniform(-1.2, 1.2, 3) * np.array([1.0, 0.75, 0.5])
+        v = (q - p) / np.linalg.norm(q - p)
+        hand.append((tuple(p), tuple(v)))
+    ho = np.array([h[0] for h in hand], F)
+    hd = np.array([h[1] for h in hand], F)
+    return np.concatenate([o.numpy(), ho]).astype(F), np.concatenate([d.numpy(), hd]).astype(F)
+
+
+def clip_cases():
+    """(t_min, t_max) pairs of the clip test: the whole ray, t_min > 0, a finite t_max that ends inside the box."""
+    return [(0.0, np.inf), (0.6, np.inf), (0.0, 3.1), (1.9, 2.6)]
+
+
+def ray_max_steps(dt=DT):
+    from latent_feature_grid_compression_amd.visualization.Render import max_steps_for
+    return max_steps_for(BOX[0], BOX[1], dt)
+
+
+COMPOSITE_SEED = 4
+COMPOSITE_BLOCKS = 3
+
+
+def composite_case(limit, shaded, seed=COMPOSITE_SEED, S=32):
+    """Inputs of the compositing test: 100 rays with the lengths of ray_set()' hits, three chained blocks of S samples,
+    values uniform in [-1.2, 1.2] (the table clamps), a random K = 7 table with rgb <= 1 and extinction <= 6, random
+    gradients with some exactly zero.  Returns a dict of float32 / int32 arrays + the float64 reference and its margins."""
+    rng = np.random.default_rng(seed)
+    o, d = ray_set()
+    tn, tf, n = clip(o, d, BOX[0], BOX[1], 0.0, np.inf, DT, ray_max_steps())
+    hits = np.nonzero(n > 0)[0]
+    pick = np.sort(rng.choice(hits, 100, replace=False))
+    d, tn, tf, n = d[pick], tn[pick], tf[pick], n[pick]
+    M = COMPOSITE_BLOCKS * S
+    values = rng.uniform(-1.2, 1.2, (100, M)).astype(F)
+    table = np.concatenate([rng.uniform(0, 1, (7, 3)), rng.uniform(0, 6, (7, 1))], 1).astype(F)
+    grads = None
+    if shaded:
+        grads = rng.normal(size=(100, M, 3)).astype(F)
+        grads[rng.uniform(size=(100, M)) < 0.1] = 0.0
+    ref, margin = composite(values, grads, d, tn, tf, n, DT, table, -1.0, 1.0, limit)
+    return dict(dirs=d, t_near=tn, t_far=tf, n_steps=n, values=values, grads=grads, table=table, ref=ref, margin=margin,
+                limit=limit, S=S, blocks=COMPOSITE_BLOCKS)
+
+
+def left_out(margin, tol):
+    """Rays whose contribution rule is decided within `tol` of the limit -- at most 2 % of them may be."""
+    return margin < tol

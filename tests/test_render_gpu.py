@@ -1,0 +1,375 @@
+"""GPU tests of the direct volume renderer: the four ray kernels against the NumPy restatement (tests/render_ref.py),
+the marching loop of visualization/Render.py against the oracle's network and ground-truth sampler, and the loop's
+bookkeeping (chunks, compaction, block size), which must not show in the image.
+
+Clip and sample positions are compared for EQUALITY: every operation is an individually rounded fp32 operation in a
+stated order.  Composited images are compared with the float64 restatement within 4 n_steps 2^-24 per channel."""
+import numpy as np
+import pytest
+import torch
+
+import render_ref as RR
+from oracle import ref_torch as R
+from test_hip_forward import build_synth, rel_err, dev  # noqa: F401
+from test_gradient_gpu import _oracle
+
+pytestmark = pytest.mark.gpu
+
+
+def _ops():
+    from latent_feature_grid_compression_amd import ops
+    return ops
+
+
+def _render():
+    from latent_feature_grid_compression_amd.visualization import Render
+    return Render
+
+
+def _t(a, dev_):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev_)
+
+
+# ---- 1. clip and samples, bit for bit -----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('t_min,t_max', RR.clip_cases())
+def test_clip_equals_the_restatement(dev, t_min, t_max):
+    o, d = RR.ray_set()
+    tn, tf, n = _ops().ray_clip(_t(o, dev), _t(d, dev), RR.BOX[0], RR.BOX[1], RR.DT, RR.ray_max_steps(), t_min, t_max)
+    rn, rf, rs = RR.clip(o, d, RR.BOX[0], RR.BOX[1], t_min, t_max, RR.DT, RR.ray_max_steps())
+    assert np.array_equal(n.cpu().numpy(), rs)
+    assert np.array_equal(tn.cpu().numpy(), rn)
+    assert np.array_equal(tf.cpu().numpy(), rf)
+
+
+@pytest.mark.parametrize('k0', [0, 32])
+@pytest.mark.parametrize('S', [32, 64])
+def test_samples_equal_the_restatement(dev, S, k0):
+    ops = _ops()
+    o, d = RR.ray_set()
+    rn, rf, rs = RR.clip(o, d, RR.BOX[0], RR.BOX[1], 0.0, np.inf, RR.DT, RR.ray_max_steps())
+    od, dd = _t(o, dev), _t(d, dev)
+    tn, tf, n = ops.ray_clip(od, dd, RR.BOX[0], RR.BOX[1], RR.DT, RR.ray_max_steps())
+    live = np.nonzero(rs > 0)[0].astype(np.int32)
+    k_next = np.full(o.shape[0], k0, np.int32)
+    pos = ops.ray_samples(_t(live, dev), od, dd, tn, tf, n, _t(k_next, dev), RR.DT, S).cpu().numpy()
+    want, _ = RR.samples(live, o, d, rn, rf, rs, k_next, RR.DT, S)
+    assert pos.shape == (len(live) * S, 3)
+    assert np.array_equal(pos, want)
+    # every position is finite and inside the box up to the rounding of o + t d
+    assert np.isfinite(pos).all()
+    assert (pos >= RR.BOX[0] - 1e-5).all() and (pos <= RR.BOX[1] + 1e-5).all()
+    # padding rows repeat the last valid sample of their ray
+    rows = pos.reshape(len(live), S, 3)
+    ends = rs[live] - k0                                   # samples of this block that are real
+    part = np.nonzero((ends > 0) & (ends < S))[0]
+    assert len(part) > 20
+    for j in part:
+        assert np.array_equal(rows[j, ends[j]:], np.repeat(rows[j, ends[j] - 1:ends[j]], S - ends[j], 0))
+    # a sub-list gives the same rows for the same rays
+    sub = np.ascontiguousarray(live[1::3])
+    pos_sub = ops.ray_samples(_t(sub, dev), od, dd, tn, tf, n, _t(k_next, dev), RR.DT, S).cpu().numpy()
+    assert np.array_equal(pos_sub.reshape(len(sub), S, 3), rows[1::3])
+
+
+# ---- 2. composite against float64 on the same inputs ----------------------------------------------------------------------
+
+def _run_composite_case(case, dev_, extra=10):
+    """Three chained ops.ray_composite calls on the case's 100 rays (+ `extra` rays that are in no list)."""
+    ops = _ops()
+    S, nb = case['S'], case['blocks']
+    pad = lambda a: np.concatenate([a, a[:extra]])        # noqa: E731
+    dirs, tn, tf, n = (_t(pad(case[k]), dev_) for k in ('dirs', 't_near', 't_far', 'n_steps'))
+    R_ = 100 + extra
+    state = torch.zeros((R_, 4), device=dev_)
+    state[:, 3] = 1.0
+    state[100:] = torch.tensor([0.1, 0.2, 0.3, 0.4], device=dev_)
+    k_next = torch.zeros(R_, dtype=torch.int32, device=dev_)
+    k_next[100:] = 7
+    live = torch.arange(100, dtype=torch.int32, device=dev_)
+    table = _t(case['table'], dev_)
+    for b in range(nb):
+        v = _t(case['values'][:, b * S:(b + 1) * S].reshape(-1), dev_)
+        g = None if case['grads'] is None else _t(case['grads'][:, b * S:(b + 1) * S].reshape(-1, 3), dev_)
+        ops.ray_composite(live, v, g, dirs, tn, tf, n, k_next, RR.DT, S, table, -1.0, 1.0, case['limit'], state)
+    return state.cpu().numpy(), k_next.cpu().numpy()
+
+
+@pytest.mark.parametrize('shaded', [False, True])
+@pytest.mark.parametrize('limit', [0.95, 1.0])
+def test_composite_matches_float64(dev, limit, shaded):
+    case = RR.composite_case(limit, shaded)
+    state, k_next = _run_composite_case(case, dev)
+    out = RR.left_out(case['margin'], 1e-5)
+    assert out.sum() <= 0.02 * out.size
+    steps = np.minimum(case['n_steps'], case['blocks'] * case['S'])
+    bound = RR.composite_bound(steps)[:, None]
+    err = np.abs(state[:100].astype(np.float64) - case['ref'])
+    worst = (err / bound)[~out].max()
+    print('composite limit %g shaded %d: max err %.3e, max err / bound %.3f, %d rays left out'
+          % (limit, shaded, err[~out].max(), worst, out.sum()))
+    assert worst <= 1.0
+    assert np.array_equal(k_next[:100], np.full(100, case['blocks'] * case['S'], np.int32))
+    # rays in no list are untouched
+    assert np.array_equal(k_next[100:], np.full(10, 7, np.int32))
+    assert np.array_equal(state[100:], np.tile(np.array([0.1, 0.2, 0.3, 0.4], np.float32), (10, 1)))
+    # T never increases and stays a transmittance
+    assert (state[:100, 3] <= 1.0).all() and (state[:100, 3] >= 0.0).all()
+
+
+# ---- 3. compact --------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('n', [1, 63, 64, 65, 1000, 5000])      # 5000: more than one workgroup of the scan (2048 per group)
+def test_compact_is_the_ordered_predicate(dev, n):
+    ops = _ops()
+    rng = np.random.default_rng(n)
+    limit = 0.9
+    for pattern in ('live', 'dead', 'random'):
+        for from_list in (False, True):
+            R_ = 2 * n if from_list else n
+            n_steps = rng.integers(0, 100, R_).astype(np.int32)
+            k_next = (rng.integers(0, 4, R_) * 32).astype(np.int32)
+            T = rng.uniform(0, 1, R_).astype(np.float32)
+            T[rng.uniform(size=R_) < 0.1] = np.float32(1.0) - np.float32(limit)       # on the limit's edge
+            if pattern == 'live':
+                n_steps[:], k_next[:], T[:] = 50, 32, 0.5
+            elif pattern == 'dead':
+                dead_by_steps = rng.uniform(size=R_) < 0.5
+                k_next[dead_by_steps] = n_steps[dead_by_steps]
+                T[~dead_by_steps] = 0.05
+            state = np.concatenate([rng.uniform(0, 1, (R_, 3)).astype(np.float32), T[:, None]], 1)
+            alive = (k_next < n_steps) & ((np.float32(1.0) - T) < np.float32(limit))
+            prev = np.sort(rng.choice(R_, n, replace=False)).astype(np.int32) if from_list else None
+            want = np.nonzero(alive)[0].astype(np.int32) if prev is None else prev[alive[prev]]
+            got = ops.ray_compact(None if prev is None else _t(prev, dev), _t(n_steps, dev), _t(k_next, dev), _t(state, dev), limit)
+            assert got.dtype == torch.int32
+            assert np.array_equal(got.cpu().numpy(), want), (pattern, from_list)
+            if pattern == 'live':
+                assert len(want) == n
+            if pattern == 'dead':
+                assert len(want) == 0
+
+
+# ---- 4. end to end against the oracle -------------------------------------------------------------------------------------
+
+_TABLE = None
+
+
+def _table():
+    global _TABLE
+    if _TABLE is None:
+        rng = np.random.default_rng(77)
+        _TABLE = np.concatenate([rng.uniform(0, 1, (7, 3)), rng.uniform(0, 6, (7, 1))], 1).astype(np.float32)
+    return _TABLE
+
+
+def _view(dev_, scales):
+    """The 24 x 20 test image of a box +-scales, directions normalised the way Render.render does it."""
+    o, d = _render().pinhole_rays((2.3, 1.4, 1.7), (0.1, -0.05, 0.0), (0.0, 0.0, 1.0), 38.0, 24, 20, device=dev_)
+    return o, d, d / d.norm(dim=1, keepdim=True)
+
+
+def _all_blocks(o, dn, box, step, S=32):
+    """Clip + the positions of EVERY block of every hit ray from the device: (hit ids, t_near, t_far, n_steps (numpy, hit
+    rays), pos (n_hit, M, 3) tensor on the device)."""
+    ops, Rn = _ops(), _render()
+    tn, tf, n = ops.ray_clip(o, dn, box[0], box[1], step, Rn.max_steps_for(box[0], box[1], step))
+    hit = torch.nonzero(n > 0).view(-1).to(torch.int32)
+    nb = (int(n.max()) + S - 1) // S
+    k_next = torch.zeros_like(n)
+    blocks = []
+    for b in range(nb):
+        blocks.append(ops.ray_samples(hit, o, dn, tn, tf, n, k_next, step, S).view(hit.numel(), S, 3))
+        k_next += S
+    h = hit.long()
+    return hit, tn[h].cpu().numpy(), tf[h].cpu().numpy(), n[h].cpu().numpy(), torch.cat(blocks, 1)
+
+
+def _image_of(state, hit, n_rays):
+    """(R, 4) image r, g, b, opacity from the reference's (n_hit, 4) state r, g, b, T."""
+    img = np.zeros((n_rays, 4))
+    img[hit] = state
+    img[hit, 3] = 1.0 - state[:, 3]
+    return img
+
+
+@pytest.mark.parametrize('shaded', [False, True])
+@pytest.mark.parametrize('shape', [(5, 8, 20, 2), (16, 8, 64, 3)])
+def test_render_from_net_matches_the_oracle(dev, shape, shaded):
+    from latent_feature_grid_compression_amd.data.IndexDataset import IndexDataset
+    Rn = _render()
+    C, G, H, L = shape
+    m, _ = build_synth(C, G, H, L, seed=9100 + C + H, dev=dev)
+    m.eval()
+    ds = IndexDataset((33, 25, 17), build_index_table=False)          # scales (1, 0.75, 0.5), default step 1/32
+    scales = ds.scales.tolist()
+    box = ([-s for s in scales], scales)
+    step = 1.0 / float(ds.max_dim)
+    limit, ka, kd = 0.99, 0.3, 0.7
+    tf = Rn.TransferFunction(_table())
+    o, d, dn = _view(dev, scales)
+    got = Rn.render_from_net(ds, m, o, d, tf, opacity_limit=limit, shading='headlight' if shaded else None).cpu().numpy()
+
+    hit, tn, tf_, n, pos = _all_blocks(o, dn, box, step)
+    n_hit, M = pos.shape[:2]
+    y, g = _oracle(m)(pos.reshape(-1, 3))                               # the very positions the device used
+    v = np.clip(y.astype(np.float64), -1.0, 1.0).reshape(n_hit, M)
+    g = g.astype(np.float64).reshape(n_hit, M, 3) if shaded else None
+    dirs = dn[hit.long()].cpu().numpy()
+    args = (dirs, tn, tf_, n, step, _table(), -1.0, 1.0, limit, ka, kd)
+    ref, margin = RR.composite(v, g, *args)
+    # what the project's own forward bound (1e-5 max|v|; 2e-5 max|g| for gradients) is worth in this image
+    rng = np.random.default_rng(5)
+    v2 = v + 1e-5 * np.abs(v).max() * rng.choice([-1.0, 1.0], v.shape)
+    g2 = None if g is None else g + 2e-5 * np.abs(g).max() * rng.choice([-1.0, 1.0], g.shape)
+    ref2, _ = RR.composite(v2, g2, *args)
+    delta = np.abs(ref2 - ref).max()
+    out = RR.left_out(margin, 1e-4)
+    assert out.sum() <= 0.02 * out.size
+    want = _image_of(ref, hit.cpu().numpy(), o.shape[0])
+    err = np.abs(got.astype(np.float64) - want)
+    bound = np.full((o.shape[0], 1), 4.0 * delta)
+    bound[hit.cpu().numpy(), 0] += RR.composite_bound(n)
+    keep = np.ones(o.shape[0], bool)
+    keep[hit.cpu().numpy()[out]] = False
+    print('render %s shaded %d: delta %.3e, max err %.3e, max err / bound %.3f, %d of %d rays left out, %d hit'
+          % (shape, shaded, delta, err[keep].max(), (err / bound)[keep].max(), out.sum(), out.size, n_hit))
+    assert n_hit > 100 and int(n.max()) > 64
+    assert (err / bound)[keep].max() <= 1.0
+    assert np.array_equal(got[np.setdiff1d(np.arange(o.shape[0]), hit.cpu().numpy())], np.zeros((o.shape[0] - n_hit, 4), np.float32))
+
+
+# ---- 5. the driver's bookkeeping is invisible -------------------------------------------------------------------------------
+
+def test_chunks_compaction_and_block_size_do_not_show(dev):
+    ops, Rn = _ops(), _render()
+    m, _ = build_synth(16, 8, 64, 3, seed=9200, dev=dev)
+    m.eval()
+    m.precision = 'fp32'
+    scales = [1.0, 0.75, 0.5]
+    box = ([-s for s in scales], scales)
+    step = 1.0 / 32.0
+    tf = Rn.TransferFunction(_table())
+    o, d, dn = _view(dev, scales)
+    S = 32
+    stats = {}
+    many = Rn.render_from_net(scales, m, o, d, tf, step=step, max_samples_per_launch=64 * S, stats=stats)
+    one = Rn.render_from_net(scales, m, o, d, tf, step=step, max_samples_per_launch=1 << 40)
+    again = Rn.render_from_net(scales, m, o, d, tf, step=step, max_samples_per_launch=1 << 40)
+    assert stats['live'][0] > 128 and stats['blocks'] >= 3             # several chunks, several blocks
+    assert stats['live'] == sorted(stats['live'], reverse=True) and stats['live'][-1] < stats['live'][0]   # rays do drop out
+    # by hand: no compaction at all, every hit ray in every block
+    tn, tf_, n = ops.ray_clip(o, dn, box[0], box[1], step, Rn.max_steps_for(box[0], box[1], step))
+    hit = torch.nonzero(n > 0).view(-1).to(torch.int32)
+    state = torch.zeros((o.shape[0], 4), device=dev)
+    state[:, 3] = 1.0
+    k_next = torch.zeros_like(n)
+    with torch.no_grad():
+        desc, grid_cl, packed = m._descriptor(), m._decoded_channel_last(), m._packed()
+        for _ in range((int(n.max()) + S - 1) // S):
+            pos = ops.ray_samples(hit, o, dn, tn, tf_, n, k_next, step, S)
+            v, _s = ops.forward_raw(desc, grid_cl, packed, pos=pos, clamp=True, precision='fp32')
+            ops.ray_composite(hit, v, None, dn, tn, tf_, n, k_next, step, S, tf.on(dev), tf.v_min, tf.v_max, 0.999, state)
+    state[:, 3] = 1.0 - state[:, 3]
+    assert torch.equal(many, one)
+    assert torch.equal(one, again)
+    assert torch.equal(one, state)
+    assert float(one[:, 3].max()) > 0.2                                # an image, not a blank
+    # S = 64 against S = 32: other scan trees, same image within the compositing bound (limit 1: no sample is decided
+    # differently by a rounding)
+    a = Rn.render_from_net(scales, m, o, d, tf, step=step, opacity_limit=1.0, block_steps=32).cpu().numpy().astype(np.float64)
+    b = Rn.render_from_net(scales, m, o, d, tf, step=step, opacity_limit=1.0, block_steps=64).cpu().numpy().astype(np.float64)
+    bound = RR.composite_bound(n.cpu().numpy())[:, None]
+    print('S = 64 against S = 32: max difference / bound %.3f' % (np.abs(a - b) / bound).max())
+    assert (np.abs(a - b) / bound).max() <= 1.0
+
+
+# ---- 6. ground truth ------------------------------------------------------------------------------------------------------
+
+def test_render_from_volume_matches_the_reference_sampler(dev):
+    from latent_feature_grid_compression_amd.data.IndexDataset import IndexDataset
+    Rn = _render()
+    rng = np.random.default_rng(61)
+    vol = torch.from_numpy(rng.uniform(-1, 1, (12, 10, 9)).astype(np.float32))
+    ds = IndexDataset((12, 10, 9), build_index_table=False)
+    scales = ds.scales.tolist()
+    box = ([-s for s in scales], scales)
+    step = 0.04                                            # (the default, half a voxel = 1/11, would be a single block)
+    tf = Rn.TransferFunction(_table())
+    o, d, dn = _view(dev, scales)
+    got = Rn.render_from_volume(ds, vol.to(dev), o, d, tf, step=step).cpu().numpy()
+    hit, tn, tf_, n, pos = _all_blocks(o, dn, box, step)
+    n_hit, M = pos.shape[:2]
+    raw = Rn.index_positions(ds, pos.reshape(-1, 3)).cpu()
+    v = R.trilinear_f_interpolation(raw, vol, ds.min_idx, ds.max_idx, ds.vol_res).numpy().astype(np.float64).reshape(n_hit, M)
+    ref, margin = RR.composite(v, None, dn[hit.long()].cpu().numpy(), tn, tf_, n, step, _table(), -1.0, 1.0, 0.999)
+    out = RR.left_out(margin, 1e-5)
+    assert out.sum() <= 0.02 * out.size
+    h = hit.cpu().numpy()
+    err = np.abs(got.astype(np.float64) - _image_of(ref, h, o.shape[0]))[h]
+    worst = (err / RR.composite_bound(n)[:, None])[~out].max()
+    print('render_from_volume: max err %.3e, max err / bound %.3f, %d rays left out' % (err[~out].max(), worst, out.sum()))
+    assert n_hit > 100 and int(n.max()) > 32 and worst <= 1.0
+    # image-space quality measure
+    other = Rn.render_from_volume(ds, (0.5 * vol).to(dev), o, d, tf, step=step)
+    x = torch.from_numpy(got).to(dev)
+    assert Rn.image_psnr(x, x) == float('inf')
+    p = Rn.image_psnr(x, other)
+    assert np.isfinite(p) and p > 0.0
+
+
+# ---- 7. edges ---------------------------------------------------------------------------------------------------------------
+
+_BOX1 = ([-1.0, -1.0, -1.0], [1.0, 1.0, 1.0])
+
+
+def _zeros_fn(pos):
+    return torch.zeros(pos.shape[0], device=pos.device)
+
+
+def test_every_ray_misses(dev):
+    Rn = _render()
+    o = torch.tensor([[3.0, 0.0, 0.0]] * 5, device=dev)
+    d = torch.tensor([[1.0, 0.0, 0.0]] * 5, device=dev)
+    tf = Rn.TransferFunction([[1, 1, 1, 5.0], [1, 1, 1, 5.0]])
+    stats = {}
+    img = Rn.render(_zeros_fn, o, d, tf, 0.05, *_BOX1, stats=stats)
+    assert torch.equal(img, torch.zeros(5, 4, device=dev)) and stats['live'] == [] and stats['samples'] == 0
+    assert torch.equal(Rn.background(img, (0.2, 0.4, 0.6)), torch.tensor([[0.2, 0.4, 0.6]] * 5, device=dev))
+    empty = Rn.render(_zeros_fn, o[:0], d[:0], tf, 0.05, *_BOX1)
+    assert empty.shape == (0, 4)
+
+
+@pytest.mark.parametrize('n_rays', [1, 65])
+def test_few_rays_in_a_constant_medium(dev, n_rays):
+    """R = 1 and R = 65 (one ray past a wave) against the closed form 1 - exp(-sigma L) the reference is anchored to."""
+    Rn = _render()
+    sigma, c = 1.7, np.array([0.9, 0.5, 0.2])
+    y = np.linspace(-0.9, 0.9, n_rays) if n_rays > 1 else np.array([0.1])
+    o = torch.tensor(np.stack([np.full(n_rays, -3.0), y, 0.3 * y], 1), dtype=torch.float32, device=dev)
+    d = torch.tensor([[1.0, 0.0, 0.0]] * n_rays, device=dev)
+    tf = Rn.TransferFunction(np.tile(np.array([*c, sigma]), (2, 1)))
+    img = Rn.render(_zeros_fn, o, d, tf, 0.0371, *_BOX1, opacity_limit=1.0).cpu().numpy().astype(np.float64)
+    want = 1.0 - np.exp(-sigma * 2.0)
+    bound = RR.composite_bound(np.ceil(2.0 / 0.0371)) + sigma * 2.0 ** -22          # + the fp32 chord: t_far - t_near at t ~ 4
+    assert np.abs(img[:, 3] - want).max() <= bound
+    assert np.abs(img[:, :3] - want * c[None]).max() <= bound
+
+
+def test_transparent_and_opaque_tables(dev):
+    Rn = _render()
+    o, d, _ = _view(dev, [1.0, 1.0, 1.0])
+    stats = {}
+    clear = Rn.render(_zeros_fn, o, d, Rn.TransferFunction([[1, 1, 1, 0.0], [1, 1, 1, 0.0]]), 0.05, *_BOX1, stats=stats)
+    assert torch.equal(clear, torch.zeros_like(clear)) and stats['blocks'] >= 2      # marched to the end, saw nothing
+    # sigma len > 50 on the shortest chord of this view: the first sample's alpha rounds to exactly 1
+    rn, rf, rs = RR.clip(o.cpu().numpy(), d.cpu().numpy(), _BOX1[0], _BOX1[1], 0.0, np.inf, 0.05, 1000)
+    assert (rf - rn)[rs > 0].min() > 0.005
+    stats = {}
+    solid = Rn.render(_zeros_fn, o, d, Rn.TransferFunction([[0.25, 0.5, 1.0, 1e4], [0.25, 0.5, 1.0, 1e4]]), 0.05, *_BOX1,
+                      stats=stats)
+    assert len(stats['live']) == 1 and stats['live'][0] > 100                        # every ray dropped after block 1
+    hit = solid[:, 3] > 0
+    assert int(hit.sum()) == stats['live'][0]
+    assert torch.equal(solid[hit], torch.tensor([0.25, 0.5, 1.0, 1.0], device=dev).expand(int(hit.sum()), 4))
+    assert torch.equal(solid[~hit], torch.zeros(int((~hit).sum()), 4, device=dev))
