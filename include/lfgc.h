@@ -691,6 +691,39 @@ int lfgc_ray_compact(const int32_t* prev, int64_t n_prev, const int32_t* n_steps
                      float opacity_limit, int32_t* live_out, int64_t* count, void* workspace, int64_t workspace_bytes,
                      lfgc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * First-hit isosurface ray casting: the surface {value == iso} seen along the rays, found by the same
+ * march.  f(v) = v - iso;  inside(v) is f(v) >= 0, so a NaN is not inside.  Sample k of a ray sits at
+ * t_m(k) = 0.5f*(a+b) of its segment [a, b], the position lfgc_ray_samples_f32 emits.  Per ray (R rows each, 16-byte
+ * aligned, updated in place):
+ *   state   (R,4): .x = the ray's last scanned value (the carry), .w = 1 while marching and 0 once bracketed, .y = .z = 0.
+ *                  The caller initialises (0,0,0,1); lfgc_ray_compact with opacity_limit = 1 keeps exactly the marching rays.
+ *   bracket (R,4): t_lo, t_hi, f_lo, f_hi.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Scan the S values lfgc_ray_samples_f32's rows were evaluated to (values (n_live*S), same list, same k_next).  Sample
+ * k = k_next[ray] + s with 1 <= k < n_steps is a crossing iff inside(v[k-1]) != inside(v[k]); v[k-1] of the block's first
+ * sample is the carry state.x, used only when k_next > 0.  Rows with k >= n_steps never cross.  At the FIRST crossing k of
+ * the block:  bracket = (t_m(k-1), t_m(k), v[k-1]-iso, v[k]-iso), state = (v[k], 0, 0, 0), k_next = k.  Without one:
+ * state = (value of the block's last row, 0, 0, 1), k_next += S.  Rays outside the list are not touched; a ray id may
+ * appear once in the list. */
+int lfgc_ray_iso_scan_f32(const int32_t* live, int64_t n_live, const float* values, const float* t_near, const float* t_far,
+                          const int32_t* n_steps, int32_t* k_next, float dt, int S, float iso, float* state, float* bracket,
+                          lfgc_stream_t stream);
+
+/* One bisection step of the brackets of the n rays of `list`.  values (n) or NULL: the value at t_mid = 0.5f*(t_lo+t_hi) of
+ * the bracket as it stands;  f = values[j] - iso;  (f >= 0) == (f_lo >= 0) ? (t_lo, f_lo) = (t_mid, f)
+ * : (t_hi, f_hi) = (t_mid, f).  Then (at once when values is NULL) pos row j = o + t_mid*d with t_mid = 0.5f*(t_lo+t_hi) of
+ * the updated bracket: the next trial.  pos (n,3). */
+int lfgc_ray_iso_refine_f32(const int32_t* list, int64_t n, const float* values, const float* origins, const float* dirs,
+                            float iso, float* bracket, float* pos, lfgc_stream_t stream);
+
+/* q = f_lo/(f_lo - f_hi);  t = t_lo + (t_hi - t_lo)*q, the midpoint 0.5f*(t_lo+t_hi) when q is not finite;
+ * t_hit[j] = fminf(fmaxf(t, t_lo), t_hi);  pos row j = o + t_hit*d.  The two ends differ in inside(), so f_lo != f_hi.
+ * t_hit (n), pos (n,3): rows of the list, not of the rays. */
+int lfgc_ray_iso_finish_f32(const int32_t* list, int64_t n, const float* origins, const float* dirs, const float* bracket,
+                            float* t_hit, float* pos, lfgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

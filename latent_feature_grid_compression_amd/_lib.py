@@ -159,6 +159,9 @@ SIGNATURES = {
     'lfgc_ray_compact_workspace_bytes': (c_int64, [c_int64]),
     'lfgc_ray_compact': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64,
                                  c_void_p]),
+    'lfgc_ray_iso_scan_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 5 + [c_float, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'lfgc_ray_iso_refine_f32': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    'lfgc_ray_iso_finish_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 6),
 }
 
 _lib = None

@@ -6,6 +6,9 @@
 //   lfgc_ray_composite_f32   transfer function, headlight shading and front-to-back compositing of those S samples
 //                            into the per-ray state (premultiplied r, g, b and the transmittance T)
 //   lfgc_ray_compact         order-preserving list of the rays that still have steps left and are not yet opaque
+//   lfgc_ray_iso_scan_f32    first-hit isosurface: the first sign change of v - iso among those S samples -> a bracket
+//   lfgc_ray_iso_refine_f32  one bisection step of every bracket, and the position of the next trial
+//   lfgc_ray_iso_finish_f32  one secant step inside the final bracket: depth and position of the hit
 // All arithmetic is fp32 in the order include/lfgc.h states (the build has no contraction and correctly rounded
 // division), so the clip and the positions can be restated bit for bit on the host.  One writer per ray: no atomics.
 #include "lfgc_common.h"
@@ -252,6 +255,89 @@ __global__ __launch_bounds__(kBlock) void alive_write_kernel(const RayAlive s, l
     }
 }
 
+// ---- isosurface: the first sign change of v - iso along a ray, its bisection and the hit point ---------------------------
+// inside(v) is v - iso >= 0 (a NaN is not inside).  The scan has the composite kernel's form: a half wave owns a ray and
+// walks its S values in runs of 32; lane l sees its predecessor through a shuffle, lane 0 takes the value carried in
+// state.x (the last value of the ray's previous block; meaningful iff k_next > 0) or the previous run's lane 31.  The
+// first crossing of the half's 32 ballot bits ends the ray: its lane writes the bracket, state.w = 0 and k_next = k.
+__global__ __launch_bounds__(kBlock) void ray_iso_scan_kernel(const int* __restrict__ live, long long n_live, int S,
+                                                              const float* __restrict__ values, const float* __restrict__ t_near,
+                                                              const float* __restrict__ t_far, const int* __restrict__ n_steps,
+                                                              int* __restrict__ k_next, float dt, float iso,
+                                                              float4* __restrict__ state, float4* __restrict__ bracket) {
+    const int lane = threadIdx.x & (kRun - 1);
+    const long long j = (long long)blockIdx.x * (kBlock / kRun) + (threadIdx.x / kRun);
+    if (j >= n_live) return;                     // a whole half wave leaves: the shuffles below stay inside one half
+    const long long r = live[j];
+    const int n = n_steps[r], k0 = k_next[r];
+    float last = state[r].x;
+    for (int s0 = 0; s0 < S; s0 += kRun) {
+        const int k = k0 + s0 + lane;
+        const float v = values[j * S + s0 + lane];
+        float prev = __shfl_up(v, 1, kRun);
+        if (lane == 0) prev = last;
+        const bool cross = k >= 1 && k < n && (prev - iso >= 0.0f) != (v - iso >= 0.0f);   // k < n: padding rows never cross
+        const unsigned long long mask = (__ballot(cross) >> ((threadIdx.x & 32) ? 32 : 0)) & 0xffffffffull;
+        if (mask) {                              // the same for all 32 lanes of the half
+            if (lane == __ffsll((long long)mask) - 1) {
+                const float tn = t_near[r], tf = t_far[r];
+                float a, b;
+                ray_segment(tn, tf, dt, k - 1, a, b);
+                const float t_lo = 0.5f * (a + b);
+                ray_segment(tn, tf, dt, k, a, b);
+                bracket[r] = make_float4(t_lo, 0.5f * (a + b), prev - iso, v - iso);
+                state[r] = make_float4(v, 0.0f, 0.0f, 0.0f);
+                k_next[r] = k;
+            }
+            return;
+        }
+        last = __shfl(v, kRun - 1, kRun);
+    }
+    if (lane == 0) {
+        state[r] = make_float4(last, 0.0f, 0.0f, 1.0f);
+        k_next[r] = k0 + S;
+    }
+}
+
+// thread = one bracketed ray of the list: fold the value at the bracket's midpoint in (if given), emit the next midpoint
+__global__ __launch_bounds__(kBlock) void ray_iso_refine_kernel(const int* __restrict__ list, long long n,
+                                                                const float* __restrict__ values, const float* __restrict__ origins,
+                                                                const float* __restrict__ dirs, float iso,
+                                                                float4* __restrict__ bracket, float* __restrict__ pos) {
+    const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const long long r = list[j];
+    float4 br = bracket[r];
+    if (values) {
+        const float tm = 0.5f * (br.x + br.y);
+        const float f = values[j] - iso;
+        if ((f >= 0.0f) == (br.z >= 0.0f)) { br.x = tm; br.z = f; }
+        else { br.y = tm; br.w = f; }
+        bracket[r] = br;
+    }
+    const float tm = 0.5f * (br.x + br.y);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pos[j * 3 + c] = origins[r * 3 + c] + tm * dirs[r * 3 + c];
+}
+
+// thread = one bracketed ray of the list: one secant step inside the final bracket
+__global__ __launch_bounds__(kBlock) void ray_iso_finish_kernel(const int* __restrict__ list, long long n,
+                                                                const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                                const float4* __restrict__ bracket, float* __restrict__ t_hit,
+                                                                float* __restrict__ pos) {
+    const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const long long r = list[j];
+    const float4 br = bracket[r];
+    const float q = br.z / (br.z - br.w);
+    float t = br.x + (br.y - br.x) * q;
+    if (!(q - q == 0.0f)) t = 0.5f * (br.x + br.y);
+    t = fminf(fmaxf(t, br.x), br.y);
+    t_hit[j] = t;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pos[j * 3 + c] = origins[r * 3 + c] + t * dirs[r * 3 + c];
+}
+
 inline bool finite_f(float v) { return v - v == 0.0f; }
 
 }  // namespace
@@ -333,6 +419,42 @@ extern "C" int lfgc_ray_compact(const int32_t* prev, int64_t n_prev, const int32
     hipLaunchKernelGGL(alive_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, nblocks, reinterpret_cast<long long*>(count));
     LFGC_HIP_CHECK_LAUNCH();
     hipLaunchKernelGGL(alive_write_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, st, s, n, offsets, live_out);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_ray_iso_scan_f32(const int32_t* live, int64_t n_live, const float* values, const float* t_near, const float* t_far,
+                                     const int32_t* n_steps, int32_t* k_next, float dt, int S, float iso, float* state, float* bracket,
+                                     lfgc_stream_t stream) {
+    if (!live || !values || !t_near || !t_far || !n_steps || !k_next || !state || !bracket) return LFGC_E_NULL;
+    if (n_live < 1 || n_live > 0x7fffffffLL || S < 32 || S % 32 != 0 || !(dt > 0.0f) || !finite_f(iso)) return LFGC_E_SHAPE;
+    if (((uintptr_t)state | (uintptr_t)bracket) & 15) return LFGC_E_ALIGN;
+    const int per_block = kBlock / kRun;
+    const unsigned nblocks = (unsigned)((n_live + per_block - 1) / per_block);
+    hipLaunchKernelGGL(ray_iso_scan_kernel, dim3(nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values,
+                       t_near, t_far, n_steps, k_next, dt, iso, reinterpret_cast<float4*>(state), reinterpret_cast<float4*>(bracket));
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_ray_iso_refine_f32(const int32_t* list, int64_t n, const float* values, const float* origins, const float* dirs,
+                                       float iso, float* bracket, float* pos, lfgc_stream_t stream) {
+    if (!list || !origins || !dirs || !bracket || !pos) return LFGC_E_NULL;
+    if (n < 1 || n > 0x7fffffffLL || !finite_f(iso)) return LFGC_E_SHAPE;
+    if ((uintptr_t)bracket & 15) return LFGC_E_ALIGN;
+    hipLaunchKernelGGL(ray_iso_refine_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, list,
+                       (long long)n, values, origins, dirs, iso, reinterpret_cast<float4*>(bracket), pos);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_ray_iso_finish_f32(const int32_t* list, int64_t n, const float* origins, const float* dirs, const float* bracket,
+                                       float* t_hit, float* pos, lfgc_stream_t stream) {
+    if (!list || !origins || !dirs || !bracket || !t_hit || !pos) return LFGC_E_NULL;
+    if (n < 1 || n > 0x7fffffffLL) return LFGC_E_SHAPE;
+    if ((uintptr_t)bracket & 15) return LFGC_E_ALIGN;
+    hipLaunchKernelGGL(ray_iso_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, list,
+                       (long long)n, origins, dirs, reinterpret_cast<const float4*>(bracket), t_hit, pos);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }

@@ -1334,3 +1334,77 @@ def ray_compact(prev: Optional[torch.Tensor], n_steps: torch.Tensor, k_next: tor
                                        out.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(n_steps)),
           'lfgc_ray_compact')
     return out[:int(count.item())]
+
+
+# ---- first-hit isosurface ray casting: scan, bisection and hit point around the same forward kernel --
+
+def _ray_f32x4(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 4:
+        raise ValueError('%s must be a contiguous fp32 (R, 4) tensor' % what)
+    return t
+
+
+def _iso_value(iso) -> float:
+    iso = float(iso)
+    if iso != iso or iso in (float('inf'), float('-inf')):
+        raise ValueError('iso must be finite')
+    return iso
+
+
+@_on_device
+def ray_iso_scan(live: torch.Tensor, values: torch.Tensor, t_near: torch.Tensor, t_far: torch.Tensor, n_steps: torch.Tensor,
+                 k_next: torch.Tensor, dt: float, S: int, iso: float, state: torch.Tensor, bracket: torch.Tensor) -> None:
+    """Scan the S values per live ray that ray_samples laid out for the first sign change of value - iso:
+    lfgc_ray_iso_scan_f32.  A ray with a crossing at sample k gets bracket (t_lo, t_hi, f_lo, f_hi), state.w = 0 and
+    k_next = k; the others get their last value into state.x and k_next += S.  state, bracket (R,4), in place."""
+    _require_hip(live, values, t_near, t_far, n_steps, k_next, state, bracket)
+    live = _ray_i32(live, 'live')
+    iso = _iso_value(iso)
+    state, bracket = _ray_f32x4(state, 'state'), _ray_f32x4(bracket, 'bracket')
+    values = _f32c(values).reshape(-1)
+    if values.numel() != live.numel() * int(S):
+        raise ValueError('%d values for %d rays of %d samples' % (values.numel(), live.numel(), S))
+    if not live.numel():
+        return
+    check(_lib.load().lfgc_ray_iso_scan_f32(live.data_ptr(), live.numel(), values.data_ptr(), _f32c(t_near).data_ptr(),
+                                            _f32c(t_far).data_ptr(), _ray_i32(n_steps, 'n_steps').data_ptr(),
+                                            _ray_i32(k_next, 'k_next').data_ptr(), float(dt), int(S), iso, state.data_ptr(),
+                                            bracket.data_ptr(), _stream(live)), 'lfgc_ray_iso_scan_f32')
+
+
+@_on_device
+def ray_iso_refine(rays: torch.Tensor, values: Optional[torch.Tensor], origins: torch.Tensor, dirs: torch.Tensor, iso: float,
+                   bracket: torch.Tensor) -> torch.Tensor:
+    """One bisection step of the brackets of the listed rays (lfgc_ray_iso_refine_f32): values (len(rays),) are the values
+    at the midpoints the previous call returned (None: no update), bracket (R,4) is updated in place.  Returns the
+    (len(rays), 3) positions of the new midpoints."""
+    _require_hip(rays, values, origins, dirs, bracket)
+    rays = _ray_i32(rays, 'rays')
+    iso = _iso_value(iso)
+    bracket = _ray_f32x4(bracket, 'bracket')
+    if values is not None:
+        values = _f32c(values).reshape(-1)
+        if values.numel() != rays.numel():
+            raise ValueError('%d values for %d rays' % (values.numel(), rays.numel()))
+    pos = torch.empty((rays.numel(), 3), dtype=torch.float32, device=rays.device)
+    if rays.numel():
+        check(_lib.load().lfgc_ray_iso_refine_f32(rays.data_ptr(), rays.numel(), _ptr(values), _f32c(origins).data_ptr(),
+                                                  _f32c(dirs).data_ptr(), iso, bracket.data_ptr(), pos.data_ptr(), _stream(rays)),
+              'lfgc_ray_iso_refine_f32')
+    return pos
+
+
+@_on_device
+def ray_iso_finish(rays: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, bracket: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(t_hit (len(rays),), position (len(rays), 3)) of the listed rays: one secant step inside their final brackets
+    (lfgc_ray_iso_finish_f32).  Rows follow the list, not the ray ids."""
+    _require_hip(rays, origins, dirs, bracket)
+    rays = _ray_i32(rays, 'rays')
+    bracket = _ray_f32x4(bracket, 'bracket')
+    t_hit = torch.empty(rays.numel(), dtype=torch.float32, device=rays.device)
+    pos = torch.empty((rays.numel(), 3), dtype=torch.float32, device=rays.device)
+    if rays.numel():
+        check(_lib.load().lfgc_ray_iso_finish_f32(rays.data_ptr(), rays.numel(), _f32c(origins).data_ptr(), _f32c(dirs).data_ptr(),
+                                                  bracket.data_ptr(), t_hit.data_ptr(), pos.data_ptr(), _stream(rays)),
+              'lfgc_ray_iso_finish_f32')
+    return t_hit, pos

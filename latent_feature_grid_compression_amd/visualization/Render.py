@@ -13,11 +13,18 @@ consecutive rows (a 32-sample tile of the forward kernel is 32 consecutive steps
 cells), ``value_fn`` evaluates them, ops.ray_composite folds them into the per-ray state, and ops.ray_compact keeps the
 rays that still have steps left and are not yet opaque.  The one 8-byte read-back of that list's length per block of
 ``block_steps`` steps is the only synchronisation.  There is no CPU form: CPU tensors raise LfgcError.
+
+First-hit isosurfaces use the same loop with ops.ray_iso_scan in the place of the compositing:
+
+    hits = isosurface_from_net(dataset, net, origins, dirs, iso=0.2)                     # IsoHits: hit, t, position, normal, value
+    image = background(shade_isosurface(hits, dirs), (0.0, 0.0, 0.0))
+
+``isosurface_from_volume`` is the ground truth's surface and ``surface_deviation`` the distance between the two.
 """
 from __future__ import annotations
 
 import math
-from typing import Callable, Optional, Sequence, Tuple
+from typing import Callable, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -257,3 +264,222 @@ def image_psnr(a: torch.Tensor, b: torch.Tensor, peak: float = 1.0) -> float:
         raise ValueError('images differ in shape: %s and %s' % (tuple(a.shape), tuple(b.shape)))
     mse = float(((a.double() - b.double()) ** 2).mean())
     return float('inf') if mse == 0.0 else 10.0 * math.log10(peak * peak / mse)
+
+
+# ---- first-hit isosurface ray casting -------------------------------------------------------------------------------------
+
+class IsoHits(NamedTuple):
+    """Result of ``isosurface``, one row per ray."""
+    hit: torch.Tensor          # (R,) bool
+    t: torch.Tensor            # (R,) depth along the unit direction; inf for a miss
+    position: torch.Tensor     # (R, 3) hit point; 0 for a miss
+    normal: torch.Tensor       # (R, 3) unit normal facing the viewer (n . d <= 0); 0 for a miss, a zero gradient or normals=False
+    value: torch.Tensor        # (R,) the value value_fn returns at the hit point; 0 for a miss
+    t_lo: torch.Tensor         # (R,) the final bracket, t_lo <= t <= t_hi: value - iso changes sign between its ends; inf for a miss
+    t_hi: torch.Tensor
+
+
+def isosurface(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, iso: float, step: float, box_min, box_max,
+               block_steps: int = 32, refine_steps: int = 8, normals: bool = True, max_samples_per_launch: int = 1 << 22,
+               t_min: float = 0.0, t_max: float = float('inf'), stats: Optional[dict] = None) -> IsoHits:
+    """The first point of every ray on the surface value == iso inside the box: an ``IsoHits`` tuple.
+
+    ``value_fn(pos (n, 3))`` returns the n values; with ``normals=True`` it is called once more, at the hit points only,
+    as ``value_fn(pos, gradient=True)`` and must then return (values, gradients (n, 3)).  The normal is +-g / |g| with
+    the sign that faces the viewer.  ``dirs`` are normalised here.
+
+    A ray is sampled at the midpoints of its ``step``-long segments, as ``render`` samples it.  The first pair of
+    neighbouring samples on different sides of ``iso`` (either direction: entering or leaving the set value >= iso
+    both hit) brackets the surface; ``refine_steps`` bisections, each one evaluation per bracketed ray, shrink the
+    bracket to step * 2^-refine_steps, and one secant step inside it gives ``t``.  A surface the ray crosses twice
+    between two neighbouring samples is not seen.  There are NO CAPS: a ray that is already inside the set where it
+    enters the box reports the point where it leaves the set, not the box face.
+
+    Loop: clip -> compact the hits -> read the count; while rays march: for chunks of the list with
+    chunk * block_steps <= max_samples_per_launch: samples -> value_fn -> scan; then compact (drops the bracketed rays and
+    those without steps left) and read the count.  Then over the bracketed rays: refine -> value_fn, ``refine_steps``
+    times, and finish.  Every kernel treats a ray by itself, so with a ``value_fn`` that does so too a ray's result does
+    not depend on the list or chunk it sits in.
+
+    ``stats``: a dict that receives 'live' (marching rays per block), 'samples' (rows evaluated in the march), 'blocks',
+    'bracketed' (rays with a hit) and 'refine_samples' (rows evaluated for the bisection and at the hit points)."""
+    S = int(block_steps)
+    if S < 32 or S % 32:
+        raise ValueError('block_steps must be a positive multiple of 32')
+    if not float(step) > 0.0:
+        raise ValueError('step must be positive')
+    iso = float(iso)
+    if not math.isfinite(iso):
+        raise ValueError('iso must be finite')
+    n_refine = int(refine_steps)
+    if n_refine != refine_steps or not 0 <= n_refine <= 64:
+        raise ValueError('refine_steps must be an integer in [0, 64]')
+    ops._require_hip(origins, dirs)
+    origins, dirs = ops._f32c(origins.detach()), ops._f32c(dirs.detach())
+    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape:
+        raise ValueError('origins and dirs must both be (R, 3)')
+    dirs = dirs / dirs.norm(dim=1, keepdim=True)
+    R, dev = origins.shape[0], origins.device
+    max_steps = max_steps_for(box_min, box_max, step)
+    if max_steps > (1 << 30):
+        raise ValueError('step %g is too small for the box: more than 2^30 steps per ray' % step)
+    chunk = max(1, int(max_samples_per_launch) // S)
+    state = torch.zeros((R, 4), dtype=torch.float32, device=dev)
+    state[:, 3] = 1.0
+    bracket = torch.zeros((R, 4), dtype=torch.float32, device=dev)
+    live_counts, n_samples, n_refined = [], 0, 0
+    if R:
+        t_near, t_far, n_steps = ops.ray_clip(origins, dirs, box_min, box_max, step, max_steps, t_min, t_max)
+        k_next = torch.zeros(R, dtype=torch.int32, device=dev)
+        live = ops.ray_compact(None, n_steps, k_next, state, 1.0)
+        while live.numel():
+            live_counts.append(int(live.numel()))
+            for b in range(0, live.numel(), chunk):
+                part = live[b:b + chunk]
+                pos = ops.ray_samples(part, origins, dirs, t_near, t_far, n_steps, k_next, step, S)
+                ops.ray_iso_scan(part, value_fn(pos), t_near, t_far, n_steps, k_next, step, S, iso, state, bracket)
+                n_samples += pos.shape[0]
+            live = ops.ray_compact(live, n_steps, k_next, state, 1.0)
+    hit = state[:, 3] == 0.0
+    found = torch.nonzero(hit).view(-1).to(torch.int32)
+    t = torch.full((R,), float('inf'), dtype=torch.float32, device=dev)
+    position = torch.zeros((R, 3), dtype=torch.float32, device=dev)
+    normal = torch.zeros((R, 3), dtype=torch.float32, device=dev)
+    value = torch.zeros(R, dtype=torch.float32, device=dev)
+    per_launch = max(1, int(max_samples_per_launch))
+    for b in range(0, found.numel(), per_launch):
+        part = found[b:b + per_launch]
+        idx = part.long()
+        values = None
+        for _ in range(n_refine):
+            values = value_fn(ops.ray_iso_refine(part, values, origins, dirs, iso, bracket))
+        if values is not None:
+            ops.ray_iso_refine(part, values, origins, dirs, iso, bracket)       # folds the last values in
+        t_hit, p_hit = ops.ray_iso_finish(part, origins, dirs, bracket)
+        n_refined += (n_refine + 1) * part.numel()
+        t[idx], position[idx] = t_hit, p_hit
+        if normals:
+            out = value_fn(p_hit, gradient=True)
+            if not isinstance(out, (tuple, list)) or len(out) != 2 or out[1] is None:
+                raise ValueError('normals=True needs value_fn(pos, gradient=True) to return (values, gradients)')
+            g = out[1].reshape(-1, 3).to(torch.float32)
+            gn = g.norm(dim=1, keepdim=True)
+            unit = torch.where(gn > 0, g / gn, torch.zeros_like(g))
+            away = (unit * dirs[idx]).sum(1, keepdim=True) > 0
+            normal[idx] = torch.where(away, -unit, unit)
+            value[idx] = out[0].reshape(-1).to(torch.float32)
+        else:
+            value[idx] = value_fn(p_hit).reshape(-1).to(torch.float32)
+    inf = torch.full_like(t, float('inf'))
+    if stats is not None:
+        stats.update(live=live_counts, samples=n_samples, blocks=len(live_counts), bracketed=int(found.numel()),
+                     refine_samples=n_refined)
+    return IsoHits(hit, t, position, normal, value, torch.where(hit, bracket[:, 0], inf), torch.where(hit, bracket[:, 1], inf))
+
+
+def _iso_step(dataset_or_scales, step):
+    if step is None:
+        if not hasattr(dataset_or_scales, 'max_dim'):
+            raise ValueError('the default step needs a dataset (max_dim); pass step explicitly with bare scales')
+        step = 1.0 / float(dataset_or_scales.max_dim)
+    return step
+
+
+def isosurface_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: torch.Tensor, iso: float,
+                        step: Optional[float] = None, **kwargs) -> IsoHits:
+    """``isosurface`` of the compressed model: the values are the clamped eval-mode output of ``net`` (ops.forward_raw under
+    no_grad, exactly as ``render_from_net`` evaluates it), the normals come from ``net.value_and_gradient`` in eval mode
+    at the hit points only, the box is +-scales, ``step`` defaults to half a voxel.  The output is clamped to [-1, 1], so
+    ``iso`` must lie strictly inside that range.  Honours ``net.precision``; the bisection evaluates one sample per
+    bracketed ray, so a forward tile then holds samples of 32 different rays."""
+    if not -1.0 < float(iso) < 1.0:
+        raise ValueError('iso must lie inside the clamp range (-1, 1) of the eval-mode output, got %r' % (iso,))
+    ops._require_hip(origins, dirs)
+    scales = _scales_of(dataset_or_scales)
+    step = _iso_step(dataset_or_scales, step)
+    if kwargs.get('normals', True) and net.training:
+        raise ValueError('normals come from net.value_and_gradient in eval mode: call net.eval() first')
+    precision = getattr(net, 'precision', 'f16x2')
+    with torch.no_grad():
+        desc, grid_cl, packed = net._descriptor(), net._decoded_channel_last(), net._packed()
+
+    def value_fn(pos, gradient=False):
+        if gradient:
+            v, g = net.value_and_gradient(pos)
+            return v.view(-1), g
+        with torch.no_grad():
+            return ops.forward_raw(desc, grid_cl, packed, pos=pos, clamp=True, precision=precision)[0]
+    return isosurface(value_fn, origins, dirs, iso, step, [-s for s in scales], scales, **kwargs)
+
+
+def isosurface_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, iso: float,
+                           step: Optional[float] = None, **kwargs) -> IsoHits:
+    """The same loop over the ground truth: samples are mapped back to index units (``index_positions``) and read with the
+    trilinear sampler ops.gt_interp.  Normals are central differences of that sampler at +- half a voxel along each axis
+    (six more samples per hit, once per frame, plain torch; one-sided where half a voxel would leave the volume).  Same rays, same iso, same step as ``isosurface_from_net``
+    -> ``surface_deviation`` of the two is the surface-space quality of the compression."""
+    ops._require_hip(origins, dirs, volume)
+    scales = _scales_of(dataset)
+    step = _iso_step(dataset, step)
+    volume = ops._f32c(volume.detach())
+    mn, mx, res = dataset.min_idx.tolist(), dataset.max_idx.tolist(), dataset.vol_res.tolist()
+
+    def sample(pos):
+        return ops.gt_interp(index_positions(dataset, pos), volume, mn, mx, res).reshape(-1)
+
+    def value_fn(pos, gradient=False):
+        v = sample(pos)
+        if not gradient:
+            return v
+        # half a voxel in normalised units, per axis: index = (pos / scale + 1) / 2 * (max_idx - min_idx) + min_idx.  The two
+        # ends are kept inside the box, so the difference is one-sided, over the distance that is left, at a face.
+        sc = dataset.scales.to(pos.device, torch.float32)
+        h = sc / (dataset.max_idx - dataset.min_idx).clamp(min=1).to(pos.device, torch.float32)
+        g = torch.empty_like(pos)
+        for a in range(3):
+            e = torch.zeros(3, dtype=torch.float32, device=pos.device)
+            e[a] = h[a]
+            hi, lo = torch.minimum(pos + e, sc), torch.maximum(pos - e, -sc)
+            g[:, a] = (sample(hi) - sample(lo)) / (hi[:, a] - lo[:, a])
+        return v, g
+    return isosurface(value_fn, origins, dirs, iso, step, [-s for s in scales], scales, **kwargs)
+
+
+def shade_isosurface(hits: IsoHits, dirs: torch.Tensor, colour=(1.0, 1.0, 1.0), ka: float = 0.3, kd: float = 0.7, ks: float = 0.0,
+                     shininess: float = 32.0) -> torch.Tensor:
+    """(R, 4) premultiplied r, g, b and opacity (1 on a hit, 0 otherwise) of an ``isosurface`` result under a headlight:
+    colour * (ka + kd |n.d|) + ks |n.d|^shininess, two-sided, d the unit viewing direction.  A hit without a normal
+    (zero gradient, normals=False) gets the ambient term alone.  ``background`` puts the result over a colour."""
+    dirs = dirs.to(hits.normal.dtype)
+    if dirs.shape != hits.normal.shape:
+        raise ValueError('dirs must be (R, 3) like the hits, got %s' % (tuple(dirs.shape),))
+    d = dirs / dirs.norm(dim=1, keepdim=True)
+    c = (hits.normal * d).sum(1, keepdim=True).abs()
+    col = torch.as_tensor(colour, dtype=c.dtype, device=c.device).reshape(1, 3)
+    rgb = col * (float(ka) + float(kd) * c) + float(ks) * c ** float(shininess)
+    alpha = hits.hit.to(c.dtype).view(-1, 1)
+    return torch.cat([rgb * alpha, alpha], 1)
+
+
+def surface_deviation(hits_a: IsoHits, hits_b: IsoHits) -> dict:
+    """How far two ``isosurface`` results of the same rays are apart -- the surface counterpart of ``image_psnr``:
+    'mismatch' (fraction of rays that hit in exactly one of the two), 'common' (rays that hit in both), and over those
+    'depth_rms', 'depth_max' (of t_a - t_b, absolute) and 'angle_mean', 'angle_max' (degrees between the normals; rays
+    with a zero normal in either result are left out of the angles).  All zero where there is nothing to compare."""
+    if hits_a.hit.shape != hits_b.hit.shape:
+        raise ValueError('the two results differ in their number of rays')
+    both = hits_a.hit & hits_b.hit
+    R, n = hits_a.hit.numel(), int(both.sum())
+    out = {'mismatch': float((hits_a.hit ^ hits_b.hit).sum()) / R if R else 0.0, 'common': n,
+           'depth_rms': 0.0, 'depth_max': 0.0, 'angle_mean': 0.0, 'angle_max': 0.0}
+    if n:
+        dt_ = (hits_a.t[both].double() - hits_b.t[both].double()).abs()
+        out['depth_rms'], out['depth_max'] = float((dt_ ** 2).mean().sqrt()), float(dt_.max())
+        na, nb = hits_a.normal[both].double(), hits_b.normal[both].double()
+        ok = (na.norm(dim=1) > 0) & (nb.norm(dim=1) > 0)
+        if bool(ok.any()):
+            na, nb = na[ok], nb[ok]
+            # atan2 of |a x b| and a . b: exact zero for equal normals, accurate at small angles (acos is neither)
+            ang = torch.rad2deg(torch.atan2(torch.linalg.cross(na, nb).norm(dim=1), (na * nb).sum(1)))
+            out['angle_mean'], out['angle_max'] = float(ang.mean()), float(ang.max())
+    return out

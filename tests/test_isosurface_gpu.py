@@ -1,0 +1,371 @@
+"""GPU tests of the first-hit isosurface ray caster: the three kernels against the NumPy restatement (tests/iso_ref.py)
+for EQUALITY -- every operation is an individually rounded fp32 operation in a stated order --, the loop of
+Render.isosurface against closed forms (sphere, plane) and against the oracle's network, and the loop's bookkeeping
+(block size, chunks, ray order), which must not show in a single bit of the result."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import iso_ref as IR
+import render_ref as RR
+from test_hip_forward import build_synth, dev  # noqa: F401
+from test_gradient_gpu import _oracle, TOL
+
+pytestmark = pytest.mark.gpu
+
+
+def _ops():
+    from latent_feature_grid_compression_amd import ops
+    return ops
+
+
+def _render():
+    from latent_feature_grid_compression_amd.visualization import Render
+    return Render
+
+
+def _t(a, dev_):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev_)
+
+
+def _same(a, b):
+    """np.array_equal that lets a NaN equal a NaN (the scan test carries NaN values on purpose)."""
+    return np.array_equal(a, b, equal_nan=True)
+
+
+# ---- 1. scan, bit for bit ---------------------------------------------------------------------------------------------------
+
+_EXTRA = 10
+_SENTINEL_STATE, _SENTINEL_BRACKET, _SENTINEL_K = (0.1, 0.2, 0.3, 0.4), (1.0, 2.0, 3.0, 4.0), 7
+
+
+def _device_chain(case, rays, dev_):
+    """Three chained ops.ray_iso_scan calls with ops.ray_compact (opacity_limit 1) between them, on the case's rays + ten
+    rays that are in no list."""
+    ops = _ops()
+    S = case['S']
+    pad = lambda a: np.concatenate([a, a[:_EXTRA]])        # noqa: E731
+    tn, tf, n = (_t(pad(case[k]), dev_) for k in ('t_near', 't_far', 'n_steps'))
+    R_ = len(case['n_steps'])
+    state = torch.zeros((R_ + _EXTRA, 4), device=dev_)
+    state[:, 3] = 1.0
+    state[R_:] = torch.tensor(_SENTINEL_STATE, device=dev_)
+    bracket = torch.zeros((R_ + _EXTRA, 4), device=dev_)
+    bracket[R_:] = torch.tensor(_SENTINEL_BRACKET, device=dev_)
+    k_next = torch.zeros(R_ + _EXTRA, dtype=torch.int32, device=dev_)
+    k_next[R_:] = _SENTINEL_K
+    live = _t(np.asarray(rays, np.int32), dev_)
+    lists = []
+    for b in range(IR.SCAN_BLOCKS):
+        lists.append(live.cpu().numpy())
+        if live.numel():
+            v = _t(case['V'][lists[-1], b * S:(b + 1) * S].reshape(-1), dev_)
+            ops.ray_iso_scan(live, v, tn, tf, n, k_next, RR.DT, S, case['iso'], state, bracket)
+            live = ops.ray_compact(live, n, k_next, state, 1.0)
+    return state.cpu().numpy(), bracket.cpu().numpy(), k_next.cpu().numpy(), lists
+
+
+def _one_of_each(case):
+    """Nine rays: one for each place a first crossing can sit, the one that needs the carry first."""
+    live, tags = case['live'], case['tags']
+    order = ('block_first', 'run_first', 'run_last', 'nan', 'padding', 'equal', 'two', 'last_valid', 'none')
+    return np.array([live[tags[live] == t][0] for t in order], np.int32)
+
+
+@pytest.mark.parametrize('n_list', [1, 2, 8, 9, 'all'])      # 8 rays fill a workgroup (256 / 32), 9 start a second one
+@pytest.mark.parametrize('S', [32, 64])
+def test_scan_equals_the_restatement(dev, S, n_list):
+    case = IR.scan_case(S)
+    if n_list == 'all':
+        rays = case['live']
+    else:
+        rays = np.sort(_one_of_each(case)[:n_list])
+        assert S in case['expect'][rays]                        # also the list of one ray is found through the carry
+    state, bracket, k_next, lists = _device_chain(case, rays, dev)
+    r_state, r_bracket, r_k, r_lists = IR.scan_chain(case, rays)
+    R_ = len(case['n_steps'])
+    for got, want in zip(lists, r_lists):
+        assert np.array_equal(got, want)                        # the compaction keeps exactly the marching rays, in order
+    assert _same(state[:R_], r_state)                           # carry and finished flag
+    assert _same(bracket[:R_], r_bracket)
+    assert np.array_equal(k_next[:R_], r_k)
+    hit = state[:R_, 3] == 0
+    assert np.array_equal(k_next[:R_][rays][hit[rays]], case['expect'][rays][hit[rays]])
+    assert np.array_equal(hit[rays], case['expect'][rays] >= 0)
+    # rays in no list: the ten extra ones and every ray of the case that is not in `rays`, bitwise
+    assert np.array_equal(state[R_:], np.tile(np.array(_SENTINEL_STATE, np.float32), (_EXTRA, 1)))
+    assert np.array_equal(bracket[R_:], np.tile(np.array(_SENTINEL_BRACKET, np.float32), (_EXTRA, 1)))
+    assert np.array_equal(k_next[R_:], np.full(_EXTRA, _SENTINEL_K, np.int32))
+    rest = np.setdiff1d(np.arange(R_), rays)
+    assert np.array_equal(state[rest], np.tile(np.array([0, 0, 0, 1], np.float32), (len(rest), 1)))
+    assert not bracket[rest].any() and not k_next[rest].any()
+
+
+@pytest.mark.parametrize('S', [32, 64])
+def test_a_sub_list_scans_to_the_same_rays(dev, S):
+    case = IR.scan_case(S)
+    full = _device_chain(case, case['live'], dev)
+    sub = np.ascontiguousarray(case['live'][1::3])
+    part = _device_chain(case, sub, dev)
+    for a, b in zip(full[:3], part[:3]):
+        assert _same(a[sub], b[sub])
+
+
+# ---- 2. refine and finish, bit for bit, through the loop -----------------------------------------------------------------------
+
+_QUAD_ISO = -0.3          # |p|^2 = 0.8: a sphere that holds most of the box -- rays enter it, start inside it and leave it
+
+
+def _quad_torch(pos, gradient=False):
+    """0.5 - ((x x + y y) + z z), one rounded fp32 operation per torch call."""
+    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+    return torch.full_like(x, 0.5) - ((x * x + y * y) + z * z)
+
+
+def _quad_numpy(p):
+    p = np.asarray(p, np.float32)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return (np.float32(0.5) - ((x * x + y * y).astype(np.float32) + z * z).astype(np.float32)).astype(np.float32)
+
+
+def _directed_ray_set(dev_):
+    """render_ref.ray_set() without its ray that has no direction; (origins, dirs as given, dirs as Render normalises them)."""
+    o, d = RR.ray_set()
+    keep = np.abs(d).sum(1) > 0
+    o, d = _t(o[keep], dev_), _t(d[keep], dev_)
+    return o, d, d / d.norm(dim=1, keepdim=True)
+
+
+@pytest.mark.parametrize('refine_steps', [0, 1, 8])
+def test_refine_and_finish_equal_the_restatement(dev, refine_steps):
+    Rn = _render()
+    o, d, dn = _directed_ray_set(dev)
+    stats = {}
+    res = Rn.isosurface(_quad_torch, o, d, _QUAD_ISO, RR.DT, RR.BOX[0], RR.BOX[1], refine_steps=refine_steps, normals=False,
+                        stats=stats)
+    ref = IR.march(_quad_numpy, o.cpu().numpy(), dn.cpu().numpy(), _QUAD_ISO, RR.DT, RR.BOX, refine_steps)
+    assert ref['hit'].sum() > 150 and (~ref['hit']).sum() > 150 and (ref['k'] > 32).sum() > 10      # also in the second block
+    assert stats['bracketed'] == ref['hit'].sum() and stats['blocks'] >= 2
+    assert np.array_equal(res.hit.cpu().numpy(), ref['hit'])
+    for name in ('t_lo', 't_hi', 't', 'position'):
+        assert np.array_equal(getattr(res, name).cpu().numpy(), ref[name]), name
+    h = ref['hit']
+    assert np.array_equal(res.value.cpu().numpy()[h], _quad_numpy(ref['position'][h]))
+    assert not res.normal.any() and not res.value[~res.hit].any() and not res.position[~res.hit].any()
+    width = ref['t_hi'][h].astype(np.float64) - ref['t_lo'][h]
+    assert (width <= RR.DT * 2.0 ** -refine_steps + 2 * np.spacing(ref['t_hi'][h])).all()
+
+
+# ---- 3. the analytic sphere ------------------------------------------------------------------------------------------------
+
+_REFINE = 8
+
+
+def _sphere_fn(dev_):
+    c = torch.tensor(IR.SPHERE_C, dtype=torch.float32, device=dev_)
+    r = torch.tensor(IR.SPHERE_R, dtype=torch.float32, device=dev_)
+
+    def fn(pos, gradient=False):                             # elementwise: a ray's value depends on nothing but its position
+        q = pos - c
+        dist = torch.sqrt((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2])
+        return (r - dist, -q / dist[:, None]) if gradient else r - dist
+    return fn
+
+
+def _sphere(dev_, which, **kw):
+    """(origins, directions as Render normalises them (numpy), result)."""
+    o, d = IR.sphere_rays(which)
+    d_dev = _t(d, dev_)
+    res = _render().isosurface(_sphere_fn(dev_), _t(o, dev_), d_dev, 0.0, IR.SPHERE_DT, IR.BOX1[0], IR.BOX1[1],
+                               refine_steps=_REFINE, **kw)
+    return o, (d_dev / d_dev.norm(dim=1, keepdim=True)).cpu().numpy(), res
+
+
+@pytest.mark.parametrize('which', ['pinhole', 'ortho'])
+def test_analytic_sphere(dev, which):
+    """v = r - |p - c| with r = 0.6 in the +-1 box, dt = 1/32.  |t - t_true| <= dt 2^-8 + 8 2^-24 max(1, t) against the
+    float64 closed form; normals within 2 bound / r + 1e-5 of (p - c) / r."""
+    r, dt = IR.SPHERE_R, IR.SPHERE_DT
+    o, d, res = _sphere(dev, which)
+    b, t_true, n_true = IR.sphere_truth(o, d)
+    hit, t = res.hit.cpu().numpy(), res.t.cpu().numpy().astype(np.float64)
+    sure = b < math.sqrt(r * r - dt * dt)
+    grazing = (b < r) & ~sure
+    print('%s: %d rays, %d surely hit, %d miss, %d in the grazing band' % (which, len(b), sure.sum(), (b > r).sum(), grazing.sum()))
+    assert sure.sum() > 300 and (b > r).sum() > 300
+    assert grazing.sum() <= 0.02 * (b < r).sum()
+    assert not hit[b > r].any() and np.isinf(t[b > r]).all()
+    assert hit[sure].all()
+    bound = IR.depth_bound(dt, _REFINE, t_true[sure])
+    err = np.abs(t[sure] - t_true[sure])
+    print('%s: max depth error %.3e, max error / bound %.3f' % (which, err.max(), (err / bound).max()))
+    assert (err <= bound).all()
+    n = res.normal.cpu().numpy().astype(np.float64)
+    n_err = np.linalg.norm(n[sure] - n_true[sure], axis=1)
+    print('%s: max normal error %.3e, max error / bound %.3f' % (which, n_err.max(), (n_err / (2 * bound / r + 1e-5)).max()))
+    assert (n_err <= 2 * bound / r + 1e-5).all()
+    assert ((n * d.astype(np.float64)).sum(1) <= 1e-6).all()                 # facing the viewer
+    assert np.abs(np.linalg.norm(n[hit], axis=1) - 1.0).max() <= 1e-6 and not n[~hit].any()
+    p = res.position.cpu().numpy().astype(np.float64)
+    assert np.abs(np.linalg.norm(p[sure] - IR.SPHERE_C, axis=1) - r).max() <= bound.max() + 1e-6
+    assert np.abs(res.value.cpu().numpy()[sure]).max() <= bound.max() + 1e-6  # v is a distance: |v(hit)| <= |t - t_true|
+
+
+# ---- 4. bookkeeping does not show ---------------------------------------------------------------------------------------------
+
+_FIELDS = ('hit', 't', 'position', 'normal', 'value', 't_lo', 't_hi')
+
+
+def test_block_size_chunks_and_ray_order_do_not_show(dev):
+    Rn = _render()
+    o, _, base = _sphere(dev, 'pinhole')
+    d = IR.sphere_rays('pinhole')[1]
+    assert int(base.hit.sum()) > 300
+    stats = {}
+    _, _, wide = _sphere(dev, 'pinhole', block_steps=64)
+    _, _, chunked = _sphere(dev, 'pinhole', max_samples_per_launch=64, stats=stats)      # 2 rays per march launch
+    assert stats['live'][0] >= 3 * 2 and stats['bracketed'] >= 3 * 64                    # >= 3 chunks in the march and after it
+    perm = np.random.default_rng(8).permutation(o.shape[0])
+    shuffled = Rn.isosurface(_sphere_fn(dev), _t(o[perm], dev), _t(d[perm], dev), 0.0, IR.SPHERE_DT, IR.BOX1[0], IR.BOX1[1],
+                             refine_steps=_REFINE)
+    perm_d = _t(perm, dev)
+    for name in _FIELDS:
+        a = getattr(base, name)
+        assert torch.equal(a, getattr(wide, name)), name
+        assert torch.equal(a, getattr(chunked, name)), name
+        assert torch.equal(a[perm_d], getattr(shuffled, name)), name
+
+
+# ---- 5. the network, end to end -------------------------------------------------------------------------------------------------
+
+_NET_SHAPE, _NET_SEED = (5, 8, 20, 2), 9301      # values -0.54 .. -0.12 along the test's rays, 0.1 .. 0.6 per unit length
+_NET_ISO = -0.294          # their median.  By the oracle alone (CPU): 323 of 576 rays hit, 1 is left out
+_NEAR = 2e-5               # twice the forward parity bound of 1e-5: inside it the sign of value - iso can legitimately differ
+_NET_REFINE = 3            # the bracket ends stay 4e-3 apart.  After 8 bisections (1.2e-4) most bracket ends would lie within
+                           # 2e-5 of iso by construction, and most hits would have to be left out
+
+
+@pytest.mark.parametrize('precision', ['f16x2', 'fp32'])
+def test_isosurface_from_net_against_the_oracle(dev, precision):
+    Rn = _render()
+    m, _ = build_synth(*_NET_SHAPE, seed=_NET_SEED, dev=dev)
+    m.eval()
+    m.precision = precision
+    scales = [1.0, 0.75, 0.5]
+    box = (np.array([-s for s in scales], np.float32), np.array(scales, np.float32))
+    step, iso = 1.0 / 32.0, _NET_ISO
+    o, d = Rn.pinhole_rays((2.3, 1.4, 1.7), (0.1, -0.05, 0.0), (0.0, 0.0, 1.0), 38.0, 24, 24, device=dev)
+    dn = d / d.norm(dim=1, keepdim=True)
+    stats = {}
+    res = Rn.isosurface_from_net(scales, m, o, d, iso, step=step, refine_steps=_NET_REFINE, stats=stats)
+    o_, dn_ = o.cpu().numpy(), dn.cpu().numpy()
+    R_ = o_.shape[0]
+    oracle = _oracle(m)
+
+    def value_of(p):
+        return np.clip(oracle(torch.from_numpy(np.ascontiguousarray(p, np.float32)))[0].astype(np.float64), -1.0, 1.0)
+
+    # the oracle's march: its values at every sample midpoint (render_ref's positions are the device's, bit for bit)
+    tn, tf, n = RR.clip(o_, dn_, box[0], box[1], 0.0, np.inf, step, Rn.max_steps_for(box[0], box[1], step))
+    live = np.nonzero(n > 0)[0]
+    M = int(n.max())
+    pos, _ = RR.samples(live, o_, dn_, tn, tf, n, np.zeros(R_, np.int32), step, M)
+    V = value_of(pos).reshape(len(live), M)
+    valid = np.arange(M)[None, :] < n[live][:, None]
+    ins = V >= iso
+    cross = (ins[:, 1:] != ins[:, :-1]) & valid[:, 1:]
+    has = cross.any(1)
+    k_first = np.where(has, cross.argmax(1) + 1, M)                       # the oracle's first crossing; M: none
+    deciding = valid & (np.arange(M)[None, :] <= k_first[:, None])        # up to the hit; all of them for a miss
+    left_out = np.zeros(R_, bool)
+    left_out[live] = ((np.abs(V - iso) < _NEAR) & deciding).any(1)
+    hit_or, k_or = np.zeros(R_, bool), np.full(R_, -1)
+    hit_or[live], k_or[live] = has, np.where(has, k_first, -1)
+    assert hit_or.sum() >= R_ / 4                                          # by the oracle alone
+    # the device's result and the oracle's values at its bracket ends
+    hit = res.hit.cpu().numpy()
+    t, t_lo, t_hi = (getattr(res, k).cpu().numpy() for k in ('t', 't_lo', 't_hi'))
+    rays = np.nonzero(hit)[0]
+    f_lo = value_of(IR._at(o_, dn_, rays, t_lo[rays])) - iso
+    f_hi = value_of(IR._at(o_, dn_, rays, t_hi[rays])) - iso
+    left_out[rays] |= (np.abs(f_lo) < _NEAR) | (np.abs(f_hi) < _NEAR)
+    print('%s: %d of %d rays hit (oracle %d), %d left out, %d blocks, %d bracketed'
+          % (precision, hit.sum(), R_, hit_or.sum(), left_out.sum(), stats['blocks'], stats['bracketed']))
+    assert left_out.sum() <= 0.05 * R_
+    keep = ~left_out
+    assert np.array_equal(hit[keep], hit_or[keep])                         # a miss has no crossing in the oracle either
+    assert np.isinf(t[~hit]).all() and stats['blocks'] >= 2 and stats['bracketed'] == hit.sum()
+    ok = keep[rays]
+    assert ((f_lo >= 0) != (f_hi >= 0))[ok].all()                          # opposite sides of iso
+    assert (t_lo[rays] <= t[rays]).all() and (t[rays] <= t_hi[rays]).all()
+    width = t_hi[rays].astype(np.float64) - t_lo[rays]
+    assert (width <= step * 2.0 ** -_NET_REFINE + np.spacing(t_hi[rays])).all()
+    for r in rays[ok]:                                                      # no crossing before the bracket
+        tm = IR.t_mid(np.full(n[r], tn[r]), np.full(n[r], tf[r]), np.arange(n[r]), step)
+        k = int(np.searchsorted(tm, t_hi[r], 'left'))                      # the bracket lies in [t_m(k-1), t_m(k)]
+        assert 1 <= k < n[r] and tm[k - 1] <= t_lo[r] and k == k_or[r], (r, k, k_or[r])
+    # normals: the oracle's autograd gradient at the returned positions, turned to face the viewer
+    p_hit = res.position[res.hit]
+    _, g = oracle(p_hit)
+    g = g.astype(np.float64)
+    nrm = res.normal.cpu().numpy().astype(np.float64)[rays]
+    d_hit = dn_[rays].astype(np.float64)
+    assert ((nrm * d_hit).sum(1) <= 1e-6).all()
+    want = np.where(((nrm * g).sum(1) >= 0)[:, None], g, -g)
+    err = np.abs(nrm * np.linalg.norm(g, axis=1, keepdims=True) - want).max() / np.abs(g).max()
+    print('%s: normal error %.3e of the largest gradient entry' % (precision, err))
+    assert err <= TOL[precision]
+
+
+# ---- 6. ground truth and the deviation measure -----------------------------------------------------------------------------------
+
+def test_isosurface_from_volume_finds_the_plane(dev):
+    """A volume linear in its indices: its trilinear ground truth is linear, every level set a plane.  In normalised
+    coordinates index_i = 16 (x_i + s_i) for the (33, 25, 17) volume, so value = 0.5 a . (x + s) - 0.6."""
+    from latent_feature_grid_compression_amd.data.IndexDataset import IndexDataset
+    Rn = _render()
+    res_ = (33, 25, 17)
+    a = np.array([0.9, -0.5, 0.7])
+    i, j, k = np.meshgrid(*[np.arange(v, dtype=np.float64) for v in res_], indexing='ij')
+    vol = torch.from_numpy(((a[0] * i + a[1] * j + a[2] * k) / 32.0 - 0.6).astype(np.float32)).to(dev)
+    ds = IndexDataset(res_, build_index_table=False)
+    s = np.array(ds.scales.tolist())
+    assert float(ds.max_dim) == 32.0
+    step, iso = 1.0 / 32.0, -0.15
+    o, d = Rn.pinhole_rays((2.3, 1.4, 1.7), (0.1, -0.05, 0.0), (0.0, 0.0, 1.0), 38.0, 32, 32, device=dev)
+    dn = (d / d.norm(dim=1, keepdim=True)).cpu().numpy().astype(np.float64)
+    stats = {}
+    hits = Rn.isosurface_from_volume(ds, vol, o, d, iso, refine_steps=_REFINE, stats=stats)       # default step: 1 / max_dim
+    g = 0.5 * a
+    o64 = o.cpu().numpy().astype(np.float64)
+    slope = dn @ g
+    t_true = (iso + 0.6 - (o64 + s) @ g) / slope
+    tn, tf, n = RR.clip(o.cpu().numpy(), dn.astype(np.float32), -s.astype(np.float32), s.astype(np.float32), 0.0, np.inf, step,
+                        Rn.max_steps_for(-s, s, step))
+    # the crossing a step inside the chord and a slope that keeps the value's fp32 rounding (1e-7) far below the bound
+    sure = (n > 2) & (np.abs(slope) > 0.2) & (t_true > tn + step) & (t_true < tf - step)
+    hit, t = hits.hit.cpu().numpy(), hits.t.cpu().numpy().astype(np.float64)
+    assert sure.sum() > 100 and hit[sure].all() and not hit[n == 0].any()
+    bound = IR.depth_bound(step, _REFINE, t_true[sure])
+    err = np.abs(t[sure] - t_true[sure])
+    print('plane in the ground truth: %d sure rays, max depth error %.3e, max error / bound %.3f' % (sure.sum(), err.max(), (err / bound).max()))
+    assert (err <= bound).all()
+    # central differences of a linear field: the plane's normal, facing the viewer
+    inner = sure & (np.abs(hits.position.cpu().numpy()) < s - 2.0 / 32.0).all(1)          # the +- half voxel stays inside the volume
+    assert inner.sum() > 50
+    want = -np.sign(slope)[:, None] * g[None] / np.linalg.norm(g)
+    assert np.abs(hits.normal.cpu().numpy()[inner] - want[inner]).max() <= 1e-4
+    # the deviation measure: nothing against itself, a known shift against a volume moved by a constant
+    same = Rn.surface_deviation(hits, hits)
+    assert same == {'mismatch': 0.0, 'common': int(hit.sum()), 'depth_rms': 0.0, 'depth_max': 0.0, 'angle_mean': 0.0,
+                    'angle_max': 0.0}
+    other = Rn.isosurface_from_volume(ds, vol + 0.01, o, d, iso, refine_steps=_REFINE)
+    dev_ = Rn.surface_deviation(hits, other)
+    both = sure & other.hit.cpu().numpy()
+    shift = np.abs(0.01 / slope[both])                                                   # the plane moves by 0.01 / |g.d| along a ray
+    assert dev_['common'] >= both.sum() > 100 and dev_['mismatch'] <= 0.05
+    assert shift.min() - 2 * bound.max() <= dev_['depth_max'] and dev_['depth_rms'] > 0.0
+    assert np.abs(np.abs(t[both] - other.t.cpu().numpy()[both]) - shift).max() <= 2 * bound.max()
+    assert dev_['angle_max'] <= 0.5                                                      # the same plane, seen a little deeper

@@ -1,7 +1,10 @@
 """Time of one direct-volume-rendered frame of the cfg-3 synthetic model (visualization/Render.py):
 a 1024^2 pinhole view of the 256^3 volume's box at the default step (half a voxel), without and with headlight shading.
 
-    python tools/bench_render.py [--size 1024] [--frames 3] [--precision f16x2]          # on the GPU box
+    python tools/bench_render.py [--size 1024] [--frames 3] [--precision f16x2] [--iso VALUE]     # on the GPU box
+
+With --iso VALUE a third mode follows: a first-hit isosurface frame (Render.isosurface, normals included) of the same
+model and rays at that isovalue, timed the same way next to the two DVR frames, with the number of bracketed rays.
 
 Prints, per mode: ms per frame (wall clock around whole frames, synchronised), samples evaluated and samples/s, the
 live-ray count per block of 32 steps, the share of GPU time in the ray kernels against the network evaluation (HIP events
@@ -25,6 +28,7 @@ def main() -> None:
     ap.add_argument('--frames', type=int, default=3)
     ap.add_argument('--precision', default='f16x2')
     ap.add_argument('--opacity-limit', type=float, default=0.999)
+    ap.add_argument('--iso', type=float, default=None, help='also time an isosurface frame at this isovalue')
     args = ap.parse_args()
 
     import numpy as np
@@ -57,20 +61,31 @@ def main() -> None:
         val, g = m.value_and_gradient(pos)
         return val.view(-1), g
 
+    def plain_or_shaded(pos, gradient=False):
+        return shaded(pos) if gradient else plain(pos)
+
+    def frame(mode, fn, **kw):
+        if mode == 'isosurface':
+            return Render.isosurface(fn, o, d, args.iso, step, box[0], box[1], **kw)
+        return Render.render(fn, o, d, tf, step, box[0], box[1], opacity_limit=args.opacity_limit,
+                             shading=None if mode == 'unshaded' else 'headlight', **kw)
+
     summary = {'size': args.size, 'step': step, 'precision': args.precision, 'opacity_limit': args.opacity_limit}
-    for mode, fn in (('unshaded', plain), ('headlight', shaded)):
-        kw = dict(opacity_limit=args.opacity_limit, shading=None if mode == 'unshaded' else 'headlight')
+    modes = [('unshaded', plain), ('headlight', shaded)] + ([('isosurface', plain_or_shaded)] if args.iso is not None else [])
+    ray_ops = ('ray_clip', 'ray_samples', 'ray_composite', 'ray_compact', 'ray_iso_scan', 'ray_iso_refine', 'ray_iso_finish')
+    for mode, fn in modes:
         stats = {}
-        Render.render(fn, o, d, tf, step, box[0], box[1], stats=stats, **kw)             # warm-up
+        frame(mode, fn, stats=stats)                                                       # warm-up
         torch.cuda.synchronize()
         ms = []
         for _ in range(args.frames):
             t0 = time.perf_counter()
-            img = Render.render(fn, o, d, tf, step, box[0], box[1], **kw)
+            img = frame(mode, fn)
             torch.cuda.synchronize()
             ms.append((time.perf_counter() - t0) * 1e3)
         # one instrumented frame: an event pair around every launch group
-        spans = {'clip': [], 'samples': [], 'composite': [], 'compact': [], 'value_fn': []}
+        spans = {name[4:]: [] for name in ray_ops}
+        spans['value_fn'] = []
         kept = []
 
         def timed(name, f):
@@ -83,19 +98,29 @@ def main() -> None:
                 return r
             return g
 
-        def fn_kept(pos):
+        def fn_kept(pos, *a, **k):
             kept.append(pos)
-            return fn(pos)
-        saved = (ops.ray_clip, ops.ray_samples, ops.ray_composite, ops.ray_compact)
+            return fn(pos, *a, **k)
+        saved = {name: getattr(ops, name) for name in ray_ops}
         try:
-            ops.ray_clip, ops.ray_samples = timed('clip', saved[0]), timed('samples', saved[1])
-            ops.ray_composite, ops.ray_compact = timed('composite', saved[2]), timed('compact', saved[3])
-            Render.render(timed('value_fn', fn_kept), o, d, tf, step, box[0], box[1], **kw)
+            for name in ray_ops:
+                setattr(ops, name, timed(name[4:], saved[name]))
+            seen = [float('inf'), float('-inf')]
+
+            def fn_range(pos, *a, **k):                       # the value range of the march, outside the timed span
+                r = timed_fn(pos, *a, **k)
+                if mode == 'isosurface' and not k.get('gradient'):
+                    lo, hi = torch.aminmax(r)
+                    seen[0], seen[1] = min(seen[0], float(lo)), max(seen[1], float(hi))
+                return r
+            timed_fn = timed('value_fn', fn_kept)
+            frame(mode, fn_range if mode == 'isosurface' else timed_fn)
         finally:
-            ops.ray_clip, ops.ray_samples, ops.ray_composite, ops.ray_compact = saved
+            for name in ray_ops:
+                setattr(ops, name, saved[name])
         torch.cuda.synchronize()
         gpu = {k: float(sum(a.elapsed_time(b) for a, b in v_)) for k, v_ in spans.items()}
-        new = gpu['clip'] + gpu['samples'] + gpu['composite'] + gpu['compact']
+        new = sum(v_ for k, v_ in gpu.items() if k != 'value_fn')
         # ops.forward_raw alone on the same positions, launch by launch
         for p in kept[:2]:
             plain(p)
@@ -106,20 +131,28 @@ def main() -> None:
         e1.record()
         torch.cuda.synchronize()
         fwd_ms = e0.elapsed_time(e1)
-        n = stats['samples']
+        n = stats['samples'] + stats.get('refine_samples', 0)
         best = min(ms)
         print('[%s] %.1f ms per frame (best of %d: %s)' % (mode, best, len(ms), ' '.join('%.1f' % x for x in ms)))
         print('[%s] %d samples in %d blocks of 32 steps, %d launches: %.2f Gsamples/s over the frame' % (
             mode, n, stats['blocks'], len(kept), n / best / 1e6))
         print('[%s] live rays per block: %s' % (mode, ' '.join(str(x) for x in stats['live'])))
-        print('[%s] GPU time of the instrumented frame: value_fn %.1f ms, ray kernels %.1f ms (clip %.2f, samples %.1f, '
-              'composite %.1f, compact %.1f) = %.1f %% of value_fn' % (mode, gpu['value_fn'], new, gpu['clip'], gpu['samples'],
-                                                                   gpu['composite'], gpu['compact'], 100.0 * new / gpu['value_fn']))
+        split = ', '.join('%s %.2f' % (k, v_) for k, v_ in gpu.items() if k != 'value_fn' and spans[k])
+        print('[%s] GPU time of the instrumented frame: value_fn %.1f ms, ray kernels %.1f ms (%s) = %.1f %% of value_fn'
+              % (mode, gpu['value_fn'], new, split, 100.0 * new / gpu['value_fn']))
         print('[%s] ops.forward_raw alone on the same positions: %.1f ms = %.2f Gsamples/s' % (mode, fwd_ms, n / fwd_ms / 1e6))
-        print('[%s] image: mean opacity %.3f, %d of %d rays hit' % (mode, float(img[:, 3].mean()), stats['live'][0] if stats['live'] else 0,
-                                                                  o.shape[0]), flush=True)
+        if mode == 'isosurface':
+            print('[%s] iso %g: %d rays bracketed of %d that hit the box; %d samples in the march, %d in %d bisections, at the '
+                  'hit points and for the normals; values seen in [%.4f, %.4f]'
+                  % (mode, args.iso, stats['bracketed'], stats['live'][0] if stats['live'] else 0, stats['samples'],
+                     stats['refine_samples'], 8, seen[0], seen[1]), flush=True)
+        else:
+            print('[%s] image: mean opacity %.3f, %d of %d rays hit' % (mode, float(img[:, 3].mean()),
+                                                                      stats['live'][0] if stats['live'] else 0, o.shape[0]), flush=True)
         summary[mode] = {'frame_ms': ms, 'samples': n, 'blocks': stats['blocks'], 'live': stats['live'], 'gpu_ms': gpu,
                          'ray_kernels_ms': new, 'forward_alone_ms': fwd_ms}
+        if mode == 'isosurface':
+            summary[mode].update(iso=args.iso, bracketed=stats['bracketed'], refine_samples=stats['refine_samples'])
         del kept, img
         torch.cuda.empty_cache()
     print(json.dumps(summary), flush=True)
