@@ -724,6 +724,52 @@ int lfgc_ray_iso_refine_f32(const int32_t* list, int64_t n, const float* values,
 int lfgc_ray_iso_finish_f32(const int32_t* list, int64_t n, const float* origins, const float* dirs, const float* bracket,
                             float* t_hit, float* pos, lfgc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Isosurface triangle meshes: marching tetrahedra on the Kuhn triangulation of the volume lattice, one
+ * x-slab at a time.  The loop is host code (visualization/Mesh.py): values of the slab (lfgc_forward_f32 in lattice mode)
+ * -> count -> read the two totals -> emit -> lfgc_ray_iso_refine_f32 / lfgc_ray_iso_finish_f32 on the emitted brackets
+ * with list = 0..n-1.
+ *   values  device (nx, ny, nz), z contiguous: nx consecutive x-planes of the lattice, of which the first n_owner are the
+ *           slab's OWNER planes.  A slab with owner planes [x0, x1) of a volume of X planes is given the planes
+ *           [x0, min(x1 + 2, X)): planes beyond the ones passed must be beyond the volume.  1 <= n_owner <= nx; ny, nz >= 2;
+ *           nx*ny*nz <= 2^27 (else LFGC_E_UNSUPPORTED).
+ *   inside(v) is v - iso >= 0 in fp32 (v == iso is inside, a NaN is not), as in the ray caster.
+ *   Edges: type ty = 1..7 with offset o = (ty>>2 & 1, ty>>1 & 1, ty & 1) in (x, y, z).  Edge (p, ty) joins its owner p to
+ *           p + o, exists when p + o is a lattice point, and carries a mesh vertex when inside() differs at its ends.
+ *           Vertices are ordered by ascending (x, y, z, ty) of the owner.
+ *   Cells:  (x, y, z) with x < X-1 etc. hold six tetrahedra, one per permutation pi of (0,1,2) in lexicographic order:
+ *           corners w0 = (0,0,0), w1 = w0 + e[pi0], w2 = w1 + e[pi1], w3 = (1,1,1).  With m = the 4-bit inside mask of
+ *           (w0..w3): one corner a alone on its side, the others b < c < d: triangle (ab, ac, ad); two inside a < b, two
+ *           outside c < d: (ac, ad, bd) then (ac, bd, bc); xy = the vertex on the edge between corners x and y.  A triangle
+ *           whose normal (q1-q0) x (q2-q0), taken at the edge midpoints of the unit cube, does not point from the centroid of
+ *           the inside corners to that of the outside corners has its second and third vertex swapped: normals point out of
+ *           {v >= iso}.  Triangles are ordered by cell (x, y, z), then tetrahedron, then as listed.
+ * The result does not depend on how the volume is cut into slabs.  No atomics: two runs give the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace for a slab of these extents (16 for extents the entries refuse). */
+int64_t lfgc_iso_mesh_workspace_bytes(int32_t nx, int32_t n_owner, int32_t ny, int32_t nz);
+
+/* Classify the points of the planes [0, min(n_owner+1, nx)) (7-bit crossing-edge flag) and the cells below the planes
+ * [0, min(n_owner, nx-1)) (0..12 triangles) and leave both and their exclusive prefix sums in the workspace (16-byte
+ * aligned), for lfgc_iso_mesh_emit_f32.  totals device int64[2]: [0] the vertices owned by the owner planes, [1] the
+ * triangles of the cells whose lowest corner lies in them. */
+int lfgc_iso_mesh_count_f32(const float* values, int32_t nx, int32_t n_owner, int32_t ny, int32_t nz, float iso,
+                            int64_t* totals, void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+
+/* After lfgc_iso_mesh_count_f32 with the same values, extents, iso and workspace.  Per owned crossing edge, in order, row j:
+ *   origins (n,3) = P(p) = (xs[x], ys[y], zs[z]);  dirs (n,3) = P(p+o) - P(p) per component (not unit vectors);
+ *   bracket (n,4) = (0, 1, v(p) - iso, v(p+o) - iso), 16-byte aligned: the vertex is what lfgc_ray_iso_finish_f32 makes of it.
+ * Per triangle, in order, three int32 vertex indices vertex_base + rank, where the ranks count this slab's vertices from 0
+ * and run on into the plane after the owner planes (the next slab's first vertices, when it starts at that plane with
+ * vertex_base + totals[0] as its base).  The caller keeps vertex_base + the slab's ranks below 2^31.
+ *   xs device (nx): the slab's planes; ys device (ny); zs device (nz).  n_vertices, n_triangles: rows of the outputs, the
+ *   totals of the count; rows past them are not written; both 0 returns at once. */
+int lfgc_iso_mesh_emit_f32(const float* values, int32_t nx, int32_t n_owner, int32_t ny, int32_t nz, float iso,
+                           const float* xs, const float* ys, const float* zs, int64_t vertex_base,
+                           const void* workspace, int64_t workspace_bytes, int64_t n_vertices, int64_t n_triangles,
+                           float* origins, float* dirs, float* bracket, int32_t* triangles, lfgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,10 @@ SIGNATURES = {
     'lfgc_ray_iso_scan_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 5 + [c_float, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'lfgc_ray_iso_refine_f32': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     'lfgc_ray_iso_finish_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 6),
+    'lfgc_iso_mesh_workspace_bytes': (c_int64, [c_int32] * 4),
+    'lfgc_iso_mesh_count_f32': (c_int, [c_void_p] + [c_int32] * 4 + [c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    'lfgc_iso_mesh_emit_f32': (c_int, [c_void_p] + [c_int32] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p] +
+                               [c_int64] * 3 + [c_void_p] * 5),
 }
 
 _lib = None

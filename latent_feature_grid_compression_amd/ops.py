@@ -1408,3 +1408,61 @@ def ray_iso_finish(rays: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor
                                                   bracket.data_ptr(), t_hit.data_ptr(), pos.data_ptr(), _stream(rays)),
               'lfgc_ray_iso_finish_f32')
     return t_hit, pos
+
+
+# ---- isosurface triangle meshes: classification, compaction and connectivity of one x-slab ------------
+
+def _mesh_slab(values: torch.Tensor, n_owner: int):
+    if values.dtype != torch.float32 or not values.is_contiguous() or values.dim() != 3:
+        raise ValueError('values must be a contiguous fp32 (nx, Y, Z) tensor')
+    nx, ny, nz = (int(v) for v in values.shape)
+    n_owner = int(n_owner)
+    if not 1 <= n_owner <= nx or ny < 2 or nz < 2:
+        raise ValueError('a slab needs 1 <= n_owner <= nx planes and Y, Z >= 2, got n_owner %d of %s' % (n_owner, (nx, ny, nz)))
+    return nx, n_owner, ny, nz
+
+
+@_on_device
+def iso_mesh_count(values: torch.Tensor, n_owner: int, iso: float) -> Tuple[torch.Tensor, int, int]:
+    """(workspace, vertices, triangles) of the slab ``values`` (nx, Y, Z) whose first n_owner planes own their edges:
+    lfgc_iso_mesh_count_f32.  The workspace goes to iso_mesh_emit unchanged.  Synchronises once to read the two totals."""
+    _require_hip(values)
+    iso = _iso_value(iso)
+    nx, n_owner, ny, nz = _mesh_slab(values, n_owner)
+    lib = _lib.load()
+    nbytes = int(lib.lfgc_iso_mesh_workspace_bytes(nx, n_owner, ny, nz))
+    ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=values.device)
+    totals = torch.zeros(2, dtype=torch.int64, device=values.device)
+    check(lib.lfgc_iso_mesh_count_f32(values.data_ptr(), nx, n_owner, ny, nz, iso, totals.data_ptr(), ws.data_ptr(),
+                                      ws.numel() * 8, _stream(values)), 'lfgc_iso_mesh_count_f32')
+    n_vertices, n_triangles = totals.tolist()
+    return ws, int(n_vertices), int(n_triangles)
+
+
+@_on_device
+def iso_mesh_emit(values: torch.Tensor, n_owner: int, iso: float, xs: torch.Tensor, ys: torch.Tensor, zs: torch.Tensor,
+                  vertex_base: int, workspace: torch.Tensor, n_vertices: int, n_triangles: int):
+    """(origins (n,3), dirs (n,3), bracket (n,4), triangles (T,3) int32) of the slab iso_mesh_count has just classified:
+    lfgc_iso_mesh_emit_f32.  xs (nx,), ys (Y,), zs (Z,): the coordinates of the slab's planes, rows and columns; triangle
+    indices are vertex_base + the slab's ranks.  The brackets are finished by ray_iso_refine / ray_iso_finish."""
+    _require_hip(values, xs, ys, zs, workspace)
+    iso = _iso_value(iso)
+    nx, n_owner, ny, nz = _mesh_slab(values, n_owner)
+    xs, ys, zs = _f32c(xs), _f32c(ys), _f32c(zs)
+    if (xs.numel(), ys.numel(), zs.numel()) != (nx, ny, nz):
+        raise ValueError('axis tables of %d, %d, %d entries for a slab of %s' % (xs.numel(), ys.numel(), zs.numel(), (nx, ny, nz)))
+    n_vertices, n_triangles, vertex_base = int(n_vertices), int(n_triangles), int(vertex_base)
+    if n_vertices < 0 or n_triangles < 0 or not 0 <= vertex_base < 2 ** 31:
+        raise ValueError('n_vertices, n_triangles must be >= 0 and vertex_base in [0, 2^31)')
+    if workspace.dtype != torch.int64 or not workspace.is_contiguous():
+        raise ValueError('workspace must be the tensor iso_mesh_count returned')
+    dev = values.device
+    origins = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    dirs = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    bracket = torch.empty((n_vertices, 4), dtype=torch.float32, device=dev)
+    triangles = torch.empty((n_triangles, 3), dtype=torch.int32, device=dev)
+    check(_lib.load().lfgc_iso_mesh_emit_f32(values.data_ptr(), nx, n_owner, ny, nz, iso, xs.data_ptr(), ys.data_ptr(), zs.data_ptr(),
+                                             vertex_base, workspace.data_ptr(), workspace.numel() * 8, n_vertices, n_triangles,
+                                             _ptr(origins), _ptr(dirs), _ptr(bracket), _ptr(triangles), _stream(values)),
+          'lfgc_iso_mesh_emit_f32')
+    return origins, dirs, bracket, triangles

@@ -10,7 +10,7 @@
   (torch.distributed, one process per GPU), and assembles the volume with a gather to the root rank or an
   all-gather (RCCL over xGMI on MI355X; gloo in the CPU tests), received straight into views of the output.
   Tiles are independent, the decoded grid is replicated: there is no other communication.
-VTK file output (pyevtk) is out of scope.
+VTK file output of the dense volume (pyevtk) is out of scope; a level set leaves as a mesh through visualization/Mesh.py.
 """
 from __future__ import annotations
 

@@ -421,10 +421,20 @@ def isosurface_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor,
     ops._require_hip(origins, dirs, volume)
     scales = _scales_of(dataset)
     step = _iso_step(dataset, step)
+    value_fn = volume_value_fn(dataset, volume)
+    return isosurface(value_fn, origins, dirs, iso, step, [-s for s in scales], scales, **kwargs)
+
+
+def volume_value_fn(dataset, volume: torch.Tensor, sampler: Optional[Callable] = None) -> Callable:
+    """``value_fn(pos, gradient=False)`` of the ground truth for ``isosurface`` and Mesh.isosurface_mesh: the trilinear
+    sampler at normalised positions, and with ``gradient=True`` (values, central differences at +- half a voxel).
+    ``sampler(index positions (n, 3), volume)`` replaces ops.gt_interp (Mesh.mesh_value_residual on host tensors)."""
     volume = ops._f32c(volume.detach())
     mn, mx, res = dataset.min_idx.tolist(), dataset.max_idx.tolist(), dataset.vol_res.tolist()
 
     def sample(pos):
+        if sampler is not None:
+            return sampler(index_positions(dataset, pos), volume).reshape(-1)
         return ops.gt_interp(index_positions(dataset, pos), volume, mn, mx, res).reshape(-1)
 
     def value_fn(pos, gradient=False):
@@ -442,7 +452,7 @@ def isosurface_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor,
             hi, lo = torch.minimum(pos + e, sc), torch.maximum(pos - e, -sc)
             g[:, a] = (sample(hi) - sample(lo)) / (hi[:, a] - lo[:, a])
         return v, g
-    return isosurface(value_fn, origins, dirs, iso, step, [-s for s in scales], scales, **kwargs)
+    return value_fn
 
 
 def shade_isosurface(hits: IsoHits, dirs: torch.Tensor, colour=(1.0, 1.0, 1.0), ka: float = 0.3, kd: float = 0.7, ks: float = 0.0,

@@ -1,0 +1,301 @@
+"""GPU tests of the isosurface mesh extraction: lfgc_iso_mesh_count_f32 / lfgc_iso_mesh_emit_f32 against the NumPy
+restatement (tests/mesh_ref.py) for EQUALITY -- totals, edges, brackets, triangles --, the slab loop of
+Mesh.isosurface_mesh on analytic value functions (every slab size gives the same bits), and the smallest build_synth
+model end to end against the oracle's lattice values and gradients."""
+import numpy as np
+import pytest
+import torch
+
+import mesh_ref as MR
+from test_hip_forward import build_synth, dev  # noqa: F401
+from test_gradient_gpu import TOL
+
+pytestmark = pytest.mark.gpu
+
+_ROWS = 5                  # sentinel rows after every output
+
+
+def _ops():
+    from latent_feature_grid_compression_amd import ops
+    return ops
+
+
+def _mesh():
+    from latent_feature_grid_compression_amd.visualization import Mesh
+    return Mesh
+
+
+def _t(a, dev_):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev_)
+
+
+def _same(a, b):
+    return np.array_equal(a, b, equal_nan=True)
+
+
+# ---- 1. count and emit, bit for bit ------------------------------------------------------------------------------------------
+
+def _emit_with_sentinels(values, n_owner, iso, tabs, base, dev_):
+    """The two C entries through the binding itself, with outputs that carry _ROWS sentinel rows past the totals."""
+    from latent_feature_grid_compression_amd import _lib
+    lib = _lib.load()
+    v = _t(values, dev_)
+    nx, ny, nz = values.shape
+    xs, ys, zs = (_t(t, dev_) for t in tabs)
+    nbytes = lib.lfgc_iso_mesh_workspace_bytes(nx, n_owner, ny, nz)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev_)
+    totals = torch.full((2,), -7, dtype=torch.int64, device=dev_)
+    stream = torch.cuda.current_stream(dev_).cuda_stream
+    _lib.check(lib.lfgc_iso_mesh_count_f32(v.data_ptr(), nx, n_owner, ny, nz, iso, totals.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                           stream), 'count')
+    V, T = totals.tolist()
+    o = torch.full((V + _ROWS, 3), 11.0, device=dev_)
+    d = torch.full((V + _ROWS, 3), 12.0, device=dev_)
+    br = torch.full((V + _ROWS, 4), 13.0, device=dev_)
+    tr = torch.full((T + _ROWS, 3), -14, dtype=torch.int32, device=dev_)
+    _lib.check(lib.lfgc_iso_mesh_emit_f32(v.data_ptr(), nx, n_owner, ny, nz, iso, xs.data_ptr(), ys.data_ptr(), zs.data_ptr(), base,
+                                          ws.data_ptr(), ws.numel() * 8, V, T, o.data_ptr(), d.data_ptr(), br.data_ptr(),
+                                          tr.data_ptr(), stream), 'emit')
+    torch.cuda.synchronize()
+    for a, s in ((o, 11.0), (d, 12.0), (br, 13.0), (tr, -14)):
+        assert bool((a[a.shape[0] - _ROWS:] == s).all())                       # nothing written past the outputs
+    return V, T, o[:V].cpu().numpy(), d[:V].cpu().numpy(), br[:V].cpu().numpy(), tr[:T].cpu().numpy()
+
+
+@pytest.mark.parametrize('shape', MR.GPU_LATTICES)
+def test_count_and_emit_equal_the_restatement(dev, shape):
+    """Random values with planted NaNs and values == iso, irregular axis tables; the whole lattice as one slab and as slabs
+    of 1 and 2 owner planes (the planes past the owners only rank the edges the last cells reference)."""
+    v, tabs, iso = MR.random_case(shape, 100 + MR.GPU_LATTICES.index(shape))
+    X = shape[0]
+    cuts = {(0, X, X)}
+    for owner in (1, 2):
+        cuts |= set(MR.slabs(X, owner)[:2] + MR.slabs(X, owner)[-2:])         # first and last slabs of the loop
+    cuts |= {(X - 1, X, X)} | ({(X - 2, X - 1, X)} if X > 2 else set())       # one and two planes: nx - n_owner = 0 and 1
+    for x0, x1, xe in sorted(cuts):
+        vals, xs = v[x0:xe], tabs[0][x0:xe]
+        base = 1000 * x0 + 3
+        want_V, want_T = MR.count(vals, x1 - x0, iso)
+        V, T, o, d, br, tr = _emit_with_sentinels(vals, x1 - x0, iso, (xs, tabs[1], tabs[2]), base, dev)
+        assert (V, T) == (want_V, want_T), (x0, x1, xe)
+        r_o, r_d, r_br, r_tr = MR.emit(vals, x1 - x0, iso, xs, tabs[1], tabs[2], base)
+        assert np.array_equal(o, r_o) and np.array_equal(d, r_d), (x0, x1, xe)
+        assert _same(br, r_br), (x0, x1, xe)
+        assert np.array_equal(tr, r_tr), (x0, x1, xe)
+
+
+@pytest.mark.parametrize('value', [1.0, -1.0])
+def test_all_inside_and_all_outside_give_nothing(dev, value):
+    shape = (5, 6, 7)
+    tabs = [np.linspace(-1, 1, n).astype(np.float32) for n in shape]
+    V, T, o, d, br, tr = _emit_with_sentinels(np.full(shape, value, np.float32), 5, 0.25, tabs, 0, dev)
+    assert (V, T) == (0, 0) and o.shape == (0, 3) and tr.shape == (0, 3)
+    ws, V, T = _ops().iso_mesh_count(torch.full(shape, value, device=dev), 3, 0.25)
+    assert (V, T) == (0, 0)
+
+
+def test_two_runs_give_the_same_bits(dev):
+    v, tabs, iso = MR.random_case((33, 9, 34), 102)
+    a = _emit_with_sentinels(v, 33, iso, tabs, 0, dev)
+    b = _emit_with_sentinels(v, 33, iso, tabs, 0, dev)
+    assert a[:2] == b[:2] and all(_same(x, y) for x, y in zip(a[2:], b[2:]))
+
+
+# ---- 2. the loop on analytic value functions -----------------------------------------------------------------------------------
+
+_QUAD_ISO = -0.3
+_QUAD_RES = (13, 12, 11)
+
+
+def _quad_torch(pos, gradient=False):
+    """0.5 - ((x x + y y) + z z), one rounded fp32 operation per torch call (the ray caster's test function)."""
+    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+    v = torch.full_like(x, 0.5) - ((x * x + y * y) + z * z)
+    return (v, -2.0 * pos) if gradient else v
+
+
+def _quad_numpy(p):
+    p = np.asarray(p, np.float32)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return (np.float32(0.5) - ((x * x + y * y).astype(np.float32) + z * z).astype(np.float32)).astype(np.float32)
+
+
+def _quad_case(dev_):
+    """Lattice of linspace(-0.8, 0.95): the sphere |p|^2 = 0.8 leaves it through the three low faces and closes inside the
+    three high ones.  Returns (numpy tables, lattice values, slab function, device tables)."""
+    tabs = [np.linspace(-0.8, 0.95, n).astype(np.float32) for n in _QUAD_RES]
+    P = np.stack(np.meshgrid(*tabs, indexing='ij'), -1).reshape(-1, 3)
+    lat = _quad_numpy(P).reshape(_QUAD_RES)
+    lat_d = _t(lat, dev_)
+    return tabs, lat, (lambda b, e: lat_d[b:e]), tuple(_t(t, dev_) for t in tabs)
+
+
+@pytest.mark.parametrize('refine_steps', [0, 3])
+def test_the_loop_equals_the_restatement_whatever_the_slabs(dev, refine_steps):
+    Mesh = _mesh()
+    tabs, lat, slab_fn, tabs_d = _quad_case(dev)
+    ref = MR.mesh(lat, *tabs, _QUAD_ISO, refine_steps, _quad_numpy)
+    assert len(ref['vertices']) > 300 and len(ref['triangles']) > 600
+    plane = _QUAD_RES[1] * _QUAD_RES[2]
+    meshes = []
+    for owner, n_slabs in ((None, 1), (1, 11), (2, 6), (5, 3)):
+        stats = {}
+        m = Mesh.isosurface_mesh(slab_fn, _quad_torch, _QUAD_RES, tabs_d, _QUAD_ISO, refine_steps=refine_steps,
+                                 max_slab_voxels=(1 << 24) if owner is None else (owner + 2) * plane, stats=stats)
+        assert stats['slabs'] == n_slabs == len(MR.slabs(_QUAD_RES[0], owner))
+        meshes.append(m)
+    base = meshes[0]
+    assert np.array_equal(base.vertices.cpu().numpy(), ref['vertices'])
+    assert np.array_equal(base.triangles.cpu().numpy(), ref['triangles'])
+    assert np.array_equal(base.bracket.cpu().numpy(), ref['bracket'])
+    assert np.array_equal(base.edge_lo.cpu().numpy(), ref['origins'])
+    assert np.array_equal(base.edge_hi.cpu().numpy(), (ref['origins'] + ref['dirs']).astype(np.float32))
+    assert np.array_equal(base.values.cpu().numpy(), ref['values'])
+    assert base.triangles.dtype == torch.int32 and base.iso == _QUAD_ISO
+    for m in meshes[1:]:
+        for name in ('vertices', 'triangles', 'normals', 'values', 'edge_lo', 'edge_hi', 'bracket'):
+            assert torch.equal(getattr(base, name), getattr(m, name)), name
+    # the sphere's outward normal is the direction of lower values: -g / |g| = p / |p|, and it agrees with every triangle
+    p = base.vertices.double()
+    assert float((base.normals.double() - p / p.norm(dim=1, keepdim=True)).abs().max()) <= 1e-6
+    agree, _ = MR.winding_agreement(base.vertices.cpu().numpy(), ref['triangles'], base.normals.cpu().numpy())
+    assert agree == 1.0
+    none = Mesh.isosurface_mesh(slab_fn, _quad_torch, _QUAD_RES, tabs_d, _QUAD_ISO, refine_steps=refine_steps, normals=False)
+    assert none.normals is None and torch.equal(none.vertices, base.vertices) and torch.equal(none.values, base.values)
+    empty = Mesh.isosurface_mesh(slab_fn, _quad_torch, _QUAD_RES, tabs_d, 0.75, refine_steps=refine_steps)      # above the maximum
+    assert empty.vertices.shape == (0, 3) and empty.triangles.shape == (0, 3) and empty.normals.shape == (0, 3)
+
+
+def test_the_ground_truth_mesh_of_a_linear_volume_is_its_plane(dev):
+    """A volume linear in its indices: the level set is a plane, found on every edge by the secant step alone; the mesh's
+    residual against the same volume vanishes and against a shifted volume is the shift."""
+    from latent_feature_grid_compression_amd.data.IndexDataset import IndexDataset
+    Mesh = _mesh()
+    res_ = (9, 7, 6)
+    a = np.array([0.9, -0.5, 0.7])
+    i, j, k = np.meshgrid(*[np.arange(v, dtype=np.float64) for v in res_], indexing='ij')
+    vol = torch.from_numpy(((a[0] * i + a[1] * j + a[2] * k) / 8.0 - 0.4).astype(np.float32)).to(dev)
+    ds = IndexDataset(res_, build_index_table=False)
+    mesh = Mesh.isosurface_mesh_from_volume(ds, vol, 0.05, refine_steps=2)
+    assert mesh.vertices.shape[0] > 50 and mesh.triangles.shape[0] > 80
+    assert float((mesh.values - 0.05).abs().max()) <= 1e-6
+    g = 4.0 * a / 8.0                                               # d value / d normalised position: index = 4 (pos + scales)
+    want = torch.tensor(-g / np.linalg.norm(g), dtype=torch.float32, device=dev)
+    inner = (mesh.vertices.abs() < ds.scales.to(dev) - 0.13).all(1)         # the +- half voxel stays inside the volume
+    assert int(inner.sum()) > 10 and float((mesh.normals[inner] - want).abs().max()) <= 1e-4
+    r = Mesh.mesh_value_residual(mesh, ds, vol)
+    assert r['max'] <= 1e-6 and r['distance_max'] <= 1e-4
+    r = Mesh.mesh_value_residual(mesh, ds, vol + 0.01)
+    assert abs(r['rms'] - 0.01) <= 1e-6 and abs(r['distance_rms'] - 0.01 / (np.linalg.norm(g) * 0.25)) <= 1e-3
+    area = Mesh.mesh_area(mesh)
+    assert 0.5 < area < 4.0
+
+
+# ---- 3. the network, end to end ---------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope='module')
+def net_meshes(dev):
+    """The smallest build_synth model on the (24, 20, 17) lattice: meshes at refine_steps 0 and NET_REFINE in the default
+    precision, and the refined one in full precision."""
+    Mesh = _mesh()
+    m, _ = build_synth(*MR.NET_SHAPE, seed=MR.NET_SEED, dev=dev)
+    m.eval()
+    ds = MR.net_lattice_tables()[0]
+    out = {}
+    m.precision = 'f16x2'
+    out['coarse'] = Mesh.isosurface_mesh_from_net(ds, m, MR.NET_ISO, refine_steps=0)
+    out['fine'] = Mesh.isosurface_mesh_from_net(ds, m, MR.NET_ISO, refine_steps=MR.NET_REFINE, max_slab_voxels=7 * 20 * 17)
+    m.precision = 'fp32'
+    out['fp32'] = Mesh.isosurface_mesh_from_net(ds, m, MR.NET_ISO, refine_steps=MR.NET_REFINE)
+    out['coarse_fp32'] = Mesh.isosurface_mesh_from_net(ds, m, MR.NET_ISO, refine_steps=0)
+    out['tables'] = Mesh.lattice_axis_tables(MR.NET_RES, ds.scales.tolist(), dev)
+    return out
+
+
+def test_lattice_axis_tables_are_the_lattice_kernels_positions(dev, net_meshes):
+    """Separable, and equal to the positions the fused forward forms for itself -- also across tile boundaries."""
+    from latent_feature_grid_compression_amd.data.IndexDataset import IndexDataset
+    Mesh, ops = _mesh(), _ops()
+    _, tabs, pos = MR.net_lattice_tables()
+    for got, want in zip(net_meshes['tables'], tabs):
+        assert np.array_equal(got.cpu().numpy(), want)
+    res_ = (70, 40, 33)
+    ds = IndexDataset(res_, build_index_table=False)
+    xs, ys, zs = Mesh.lattice_axis_tables(res_, ds.scales.tolist(), dev)
+    full = ops.lattice_slab_positions(res_, 0, res_[0], 32, ds.scales.tolist(), dev).view(*res_, 3)
+    assert torch.equal(full[..., 0], xs.view(-1, 1, 1).expand(res_))
+    assert torch.equal(full[..., 1], ys.view(1, -1, 1).expand(res_))
+    assert torch.equal(full[..., 2], zs.view(1, 1, -1).expand(res_))
+
+
+def test_net_mesh_triangles_equal_the_oracles(dev, net_meshes):
+    """No oracle lattice value lies within 1e-4 of iso (test_mesh_host.py), the forward's parity bound is 2e-5: the inside
+    bits, and with them the connectivity, cannot differ -- whatever the slabs and the precision."""
+    case = MR.oracle_net_case()
+    want = case['coarse']['triangles']
+    for name in ('coarse', 'fine', 'fp32', 'coarse_fp32'):
+        mesh = net_meshes[name]
+        assert mesh.vertices.shape[0] == len(case['coarse']['vertices']), name
+        assert np.array_equal(mesh.triangles.cpu().numpy(), want), name
+        assert np.array_equal(mesh.edge_lo.cpu().numpy(), case['coarse']['origins']), name
+
+
+def test_net_mesh_brackets_keep_the_sign_change(dev, net_meshes):
+    """The bracket is what lfgc_ray_iso_refine_f32 left: f = value - iso of the model at its two ends.  A sign test."""
+    for name in ('fine', 'fp32'):
+        br = net_meshes[name].bracket.cpu().numpy()
+        assert ((br[:, 2] >= 0) != (br[:, 3] >= 0)).all(), name
+        assert (br[:, 0] <= br[:, 1]).all() and (br[:, 1] - br[:, 0] <= 2.0 ** -MR.NET_REFINE).all() and (br[:, 0] >= 0).all() \
+            and (br[:, 1] <= 1).all(), name
+    br = net_meshes['coarse'].bracket.cpu().numpy()
+    assert (br[:, 0] == 0).all() and (br[:, 1] == 1).all() and ((br[:, 2] >= 0) != (br[:, 3] >= 0)).all()
+
+
+def test_net_mesh_refinement_brings_the_values_to_iso(dev, net_meshes):
+    rms = [float(((net_meshes[k].values.double() - MR.NET_ISO) ** 2).mean().sqrt()) for k in ('coarse', 'fine')]
+    print('rms(value - iso): %.3e at 0 steps, %.3e at %d steps, ratio %.1f' % (rms[0], rms[1], MR.NET_REFINE, rms[0] / rms[1]))
+    assert rms[1] < rms[0] / 16
+
+
+def test_net_mesh_normals_agree_with_the_winding(dev, net_meshes):
+    mesh = net_meshes['fine']
+    n = mesh.normals.cpu().numpy().astype(np.float64)
+    assert np.abs(np.linalg.norm(n, axis=1) - 1.0).max() <= 1e-6
+    agree, count = MR.winding_agreement(mesh.vertices.cpu().numpy(), mesh.triangles.cpu().numpy(), n)
+    print('normal . triangle normal > 0 on %.4f of %d incidences' % (agree, count))
+    assert agree >= 0.99
+    # and they are the oracle's: -g / |g| of its autograd gradient at the same points
+    _, g = MR.oracle_net()(mesh.vertices.cpu().numpy(), gradient=True)
+    g = g.astype(np.float64)
+    err = np.abs(-n * np.linalg.norm(g, axis=1, keepdims=True) - g).max() / np.abs(g).max()
+    print('normal error %.3e of the largest gradient entry' % err)
+    assert err <= TOL['f16x2']
+
+
+def test_net_mesh_in_full_precision_is_the_same_surface(dev, net_meshes):
+    """The default (f16-split) build against net.precision = 'fp32', both at NET_REFINE steps: identical triangles, and every
+    vertex within the forward tolerance times the length of its edge."""
+    a, b = net_meshes['fine'], net_meshes['fp32']
+    assert torch.equal(a.triangles, b.triangles) and torch.equal(a.edge_lo, b.edge_lo) and torch.equal(a.edge_hi, b.edge_hi)
+    edge = (a.edge_hi - a.edge_lo).double().norm(dim=1)
+    moved = (a.vertices - b.vertices).double().norm(dim=1)
+    ratio = moved / (TOL['fp32'] * edge)
+    print('fp32 against f16x2: max vertex shift %.3e, max shift / (tol * edge) %.3f, above 1: %d of %d'
+          % (float(moved.max()), float(ratio.max()), int((ratio > 1).sum()), ratio.numel()))
+    assert bool((moved <= TOL['fp32'] * edge).all())
+
+
+def test_net_mesh_vertex_shift_follows_the_value_change_along_the_edge(dev, net_meshes):
+    """Why a vertex moves between the two builds: by the change of the edge's two end values over the value's variation
+    along the edge.  With the end values within the forward tolerance tol * max|y| of each other, the secant's root moves
+    by at most 2 tol max|y| / |f_lo - f_hi| of the edge's length (plus float32 rounding of the position).  Checked on the
+    unrefined meshes, whose brackets hold the lattice values themselves."""
+    a, b = net_meshes['coarse'], net_meshes['coarse_fp32']
+    assert torch.equal(a.triangles, b.triangles)
+    edge = (a.edge_hi - a.edge_lo).double().norm(dim=1)
+    moved = (a.vertices - b.vertices).double().norm(dim=1)
+    span = (b.bracket[:, 2] - b.bracket[:, 3]).double().abs()
+    y_max = float(np.abs(MR.oracle_net_case()['lattice']).max())
+    bound = edge * 2.0 * TOL['fp32'] * y_max / span + 4 * 2.0 ** -24
+    print('unrefined: max vertex shift %.3e, max shift / bound %.3f' % (float(moved.max()), float((moved / bound).max())))
+    assert bool((moved <= bound).all())
