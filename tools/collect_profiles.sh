@@ -1,14 +1,20 @@
 #!/bin/bash
 # Collects the round's profile evidence on the GPU box (run through gpurun from the repository root):
 #   bash tools/collect_profiles.sh <tag>      -> gpurun_out/<tag>/...   (copy what is to be judged into profiles/<round>/)
+#   bash tools/collect_profiles.sh <tag> pmc-f16x2   -> only the default build's headline counter passes; the written
+#       bench_headline_pmc.json is the committed profiles/r3 one with its f16x2 entries replaced (after a change to that kernel)
 # rocprofv3 runs: --kernel-trace --stats alone; every --pmc set in a run of its own (FETCH_SIZE and WRITE_SIZE cannot
 # share a pass); the profiled program is always `python3 <script>` directly after `--`.
 set -u
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$1
+MODE=${2:-all}
+PRECS="f16x2 fp32"
+[ "$MODE" = pmc-f16x2 ] && PRECS="f16x2"
 mkdir -p $O
 cd $R
+if [ "$MODE" = all ]; then
 echo "== full bench run"; python3 bench.py --full > $O/bench_default_run.log 2>&1; tail -c 400 $O/bench_default_run.log; echo
 # --stats averages over EVERY launch, warm-up included (the first launches of a process run 5-25 % long); the summary beside
 # it is made from the per-dispatch trace with the first WARM launches of each kernel dropped: median, mean, min, max.  That
@@ -43,22 +49,23 @@ for wl in cfg2 cfg5; do
   cp $(ls $O/kt_$wl/*/*kernel_stats.csv | head -1) $O/bench_${wl}_f16x2_kernel_stats.csv
   summarize $(ls $O/kt_$wl/*/*kernel_trace.csv | head -1) $O/bench_${wl}_f16x2_kernel_summary.csv 1
 done
+fi
 echo "== PMC passes (headline)"
 i=0
-for prec in f16x2 fp32; do
+for prec in $PRECS; do
   for set in "FETCH_SIZE" "WRITE_SIZE" \
              "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA" \
              "SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE" \
              "SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_CVT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_IFETCH SQ_INSTS_VALU_MFMA_MOPS_F16"; do
     i=$((i+1))
-    rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/pmc_$i -- python3 bench.py --precision $prec --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $O/pmc_$i.log 2>&1
+    timeout -k 10 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/pmc_$i -- python3 bench.py --precision $prec --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $O/pmc_$i.log 2>&1 || { tail -5 $O/pmc_$i.log; exit 1; }
     echo "$prec|$set" > $O/pmc_$i/what.txt
   done
 done
 python3 - <<PY
 import csv, glob, json, collections, os
 O='$O'
-res={'f16x2':{}, 'fp32':{}}
+res={p:{} for p in '$PRECS'.split()}
 for d in sorted(glob.glob(O+'/pmc_*/')):
     what=open(d+'what.txt').read().strip(); prec=what.split('|')[0]
     for f in glob.glob(d+'*/*counter_collection.csv'):
@@ -77,11 +84,15 @@ for prec in res:
         out['hbm'][prec]={'FETCH_SIZE_KB':res[prec]['FETCH_SIZE'],'WRITE_SIZE_KB':res[prec]['WRITE_SIZE'],
                           'hbm_bytes_per_launch': int(2*res[prec]['FETCH_SIZE']*1024+res[prec]['WRITE_SIZE']*1024),
                           'algorithmic_bytes_per_launch': 16777216*1040}
+if '$MODE' == 'pmc-f16x2':            # the other build's kernel is unchanged: its committed entries stay
+    old = json.load(open('$R/profiles/r3/bench_headline_pmc.json'))
+    old['hbm'].update(out['hbm']); old['sq_counters'].update(res); out = old
 json.dump(out, open(O+'/bench_headline_pmc.json','w'), indent=1)
 print(json.dumps(out['hbm']))
 for prec in res:
     print(prec, {k: round(v) for k,v in res[prec].items()})
 PY
+[ "$MODE" = all ] || { rm -rf $O/pmc_*/; ls $O; exit 0; }
 echo "== train step (graph replay)"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_ts -- python3 tools/bench_trainstep.py --graph --steps 40 --warmup 5 > $O/kt_ts.log 2>&1
 cp $(ls $O/kt_ts/*/*kernel_stats.csv | head -1) $O/trainstep_cfg3_graph_kernel_stats.csv

@@ -1,7 +1,7 @@
 """Diagnostics: per-phase wave cycles of the f16-split forward kernel on the headline launch, from in-kernel s_memtime
 stamps (a separate library built with -DLFGC_STAMPS; the shipped library executes no stamp).
 
-    python tools/phase_stamps.py build      # here (hipcc, no GPU needed)
+    python tools/phase_stamps.py build [DEF ...]   # here (hipcc, no GPU needed); further -D switches, e.g. LFGC_MATE_PRIO_NONE
     python tools/phase_stamps.py run        # on the GPU box (via gpurun)
 """
 import ctypes
@@ -16,7 +16,7 @@ LIB = os.path.join(OUT, 'liblfgc_stamps.so')
 if sys.argv[1] == 'build':
     from latent_feature_grid_compression_amd.build import build_variant
     os.makedirs(OUT, exist_ok=True)
-    build_variant(LIB, ['LFGC_STAMPS=1'])
+    build_variant(LIB, ['LFGC_STAMPS=1'] + sys.argv[2:])
 else:
     os.environ['LFGC_LIB_PATH'] = LIB
     import numpy as np
@@ -65,7 +65,8 @@ else:
                 y, _ = ops.forward_raw(model._descriptor(), grid, packed, lattice=(res, 0, w['vol'], 32), clamp=True)
         torch.cuda.synchronize()
     s = buf.cpu().numpy().reshape(nslots, 20).astype(np.float64)
-    s = s[s[:, 16] > 0]
+    slot = np.nonzero(s[:, 16] > 0)[0]          # slot = workgroup * waves per workgroup + wave
+    s = s[slot]
     ntiles = (32768 if train else w['vol'] ** 3) / 32 / len(s)
     names = {0: 'loop/tail+store', 1: 'wait for own weight-DMA pieces', 2: 'inputs issue (positions, corner loads)',
              3: 'barrier before layer 0', 4: 'layer 0 (+ embed, interpolate, split)', 5: 'barrier before layer 1', 6: 'layer 1',
@@ -79,3 +80,12 @@ else:
         if v > 0:
             print('  %-32s %9.0f cycles per tile  %5.1f %%' % (names[k], v / ntiles, 100 * v / tot))
     print('  %-32s %9.0f cycles per tile' % ('sum', s[:, :16].sum(axis=1).mean() / ntiles))
+    # who waits: 8-wave workgroups put waves w and w + 4 on one SIMD, and the mean above hides the skew between them
+    with torch.no_grad():
+        plan = ops.forward_plan(model._descriptor(), grid, **(dict(pos=pos, want_stash=True) if train else dict(lattice=(res, 0, w['vol'], 32))))
+    if plan.waves == 8:
+        old, young = s[slot % 8 < 4], s[slot % 8 >= 4]
+        print('  %-32s %9s %9s   cycles per tile' % ('by wave half', 'waves 0-3', 'waves 4-7'))
+        for k in (1, 3, 5, 7, 9):
+            print('  %-32s %9.0f %9.0f' % (names[k], old[:, k].mean() / ntiles, young[:, k].mean() / ntiles))
+        print('  %-32s %9.0f %9.0f' % ('the four barriers', old[:, 3:10:2].sum(axis=1).mean() / ntiles, young[:, 3:10:2].sum(axis=1).mean() / ntiles))
