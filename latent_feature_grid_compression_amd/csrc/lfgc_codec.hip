@@ -9,13 +9,13 @@
 //   lfgc_codec_dequant_f32     labels (`bits` wide, MSB first) -> codebook values (read_in_data_quantized :255-275)
 //   lfgc_codec_expand_f32      re-insertion of the zeros by the mask (:297-306)
 // Byte / index work, bound by HBM: every kernel streams its input once with coalesced rows; prefix sums are
-// block-count + single-block scan + rank-in-block from wave ballots.  Integer results are bit-exact by construction.
-#include "lfgc_common.h"
+// block-count + single-block scan + rank-in-block from wave ballots (lfgc_select.h).  Integer results are bit-exact by
+// construction.
+#include "lfgc_select.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kPerBlock = 2048;                 // elements per workgroup in the two stream-compaction passes
 
 // ---- mask -----------------------------------------------------------------------------------------------------------
 // thread = one output byte = 8 consecutive coefficients (two 16-byte loads when aligned)
@@ -33,92 +33,41 @@ __global__ __launch_bounds__(kBlock) void mask_kernel(const float* __restrict__ 
     mask[j] = (unsigned char)b;
 }
 
-// ---- order-preserving selection: flag(i) true -> out[rank(i)] ---------------------------------------------------------
-// element order inside a workgroup's 2048-element chunk: pass j (0..7) x wave w (0..3) x lane
-struct SelectSrc {
-    const float* x;              // flag = x[i] != 0                         (compaction)
-    const unsigned char* mask;   // flag = bit (bit_offset + i), MSB first   (expansion)
-    long long bit_offset;
+// ---- order-preserving selection (lfgc_select.h): the codec's predicates and sinks ----------------------------------------
+struct NonZero {                 // compaction: flag = x[i] != 0, the item is the value
+    typedef float Item;
+    const float* x;
+    __device__ __forceinline__ bool operator()(long long i, long long n, float& v) const {
+        v = i < n ? x[i] : 0.0f;
+        return v != 0.0f;
+    }
 };
 
-__device__ __forceinline__ bool select_flag(const SelectSrc& s, long long i, long long n) {
-    if (i >= n) return false;
-    if (s.x) return s.x[i] != 0.0f;
-    const long long b = s.bit_offset + i;
-    return (s.mask[b >> 3] >> (7 - (int)(b & 7))) & 1;
-}
-
-__global__ __launch_bounds__(kBlock) void select_count_kernel(const SelectSrc s, long long n, unsigned* __restrict__ block_counts) {
-    const long long base = (long long)blockIdx.x * kPerBlock;
-    unsigned c = 0;
-#pragma unroll
-    for (int j = 0; j < kPerBlock / kBlock; ++j) c += select_flag(s, base + j * kBlock + threadIdx.x, n);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
-    __shared__ unsigned sw[4];
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
-}
-
-// exclusive scan of the block counts in place (one workgroup; 64-bit offsets), total -> *count
-__global__ __launch_bounds__(1024) void scan_kernel(unsigned* __restrict__ counts, long long* __restrict__ offsets,
-                                                    long long nblocks, long long* __restrict__ total) {
-    __shared__ long long s_wave[16];
-    __shared__ long long s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (long long b0 = 0; b0 < nblocks; b0 += 1024) {
-        const long long b = b0 + threadIdx.x;
-        const long long v = b < nblocks ? counts[b] : 0;
-        long long incl = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long t = __shfl_up(incl, off);
-            if ((threadIdx.x & 63) >= off) incl += t;
-        }
-        if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        long long wave_off = 0;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) wave_off += s_wave[w];
-        const long long carry = s_carry;
-        if (b < nblocks) offsets[b] = carry + wave_off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + wave_off + incl;
-        __syncthreads();
+struct MaskBit {                 // expansion: flag = bit (bit_offset + i) of the mask, MSB first
+    struct Item {};
+    const unsigned char* mask;
+    long long bit_offset;
+    __device__ __forceinline__ bool operator()(long long i, long long n, Item&) const {
+        if (i >= n) return false;
+        const long long b = bit_offset + i;
+        return (mask[b >> 3] >> (7 - (int)(b & 7))) & 1;
     }
-    if (threadIdx.x == 0) *total = s_carry;
-}
+};
 
-// COMPACT: out[rank] = x[i] for flagged i.   !COMPACT (expand): out[i] = flagged ? values[rank] : 0
-template <bool COMPACT>
-__global__ __launch_bounds__(kBlock) void select_write_kernel(const SelectSrc s, long long n, const long long* __restrict__ offsets,
-                                                              const float* __restrict__ values, float* __restrict__ out) {
-    const long long base = (long long)blockIdx.x * kPerBlock;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ unsigned s_cnt[8][4];
-    bool flag[8];
-    unsigned long long bal[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        flag[j] = select_flag(s, base + j * kBlock + threadIdx.x, n);
-        bal[j] = __ballot(flag[j]);
-        if (lane == 0) s_cnt[j][wave] = (unsigned)__popcll(bal[j]);
+struct CompactSink {             // out[rank] = x[i] for flagged i
+    float* out;
+    __device__ __forceinline__ void operator()(long long, long long, bool flag, long long rank, const float& v) const {
+        if (flag) out[rank] = v;
     }
-    __syncthreads();
-    long long run = offsets[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w == wave) {
-                const long long i = base + j * kBlock + threadIdx.x;
-                const long long rank = run + __popcll(bal[j] & ((1ull << lane) - 1ull));
-                if (COMPACT) { if (flag[j]) out[rank] = s.x[i]; }
-                else if (i < n) out[i] = flag[j] ? values[rank] : 0.0f;
-            }
-            run += s_cnt[j][w];
-        }
+};
+
+struct ExpandSink {              // out[i] = flagged ? values[rank] : 0, every i < n written
+    const float* values;
+    float* out;
+    __device__ __forceinline__ void operator()(long long i, long long n, bool flag, long long rank, const MaskBit::Item&) const {
+        if (i < n) out[i] = flag ? values[rank] : 0.0f;
     }
-}
+};
 
 // ---- 1-D k-means --------------------------------------------------------------------------------------------------------
 // centres are kept sorted: a value belongs to the interval between the midpoints of neighbouring centres, found by
@@ -334,24 +283,6 @@ inline unsigned blocks_cap(long long n, int per, long long cap) {
     return (unsigned)(g < 1 ? 1 : g);
 }
 
-int run_select(const SelectSrc& s, long long n, const float* values, float* out, long long* count, void* workspace,
-               long long workspace_bytes, bool compact, hipStream_t stream) {
-    const long long nblocks = (n + kPerBlock - 1) / kPerBlock;
-    if (workspace_bytes < lfgc_codec_select_workspace_bytes(n)) return LFGC_E_WORKSPACE;
-    if (nblocks > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    long long* offsets = reinterpret_cast<long long*>(workspace);
-    unsigned* counts = reinterpret_cast<unsigned*>(offsets + nblocks + 1);
-    long long* total = count ? count : offsets + nblocks;
-    hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, stream, s, n, counts);
-    LFGC_HIP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, stream, counts, offsets, nblocks, total);
-    LFGC_HIP_CHECK_LAUNCH();
-    if (compact) hipLaunchKernelGGL(select_write_kernel<true>, dim3((unsigned)nblocks), dim3(kBlock), 0, stream, s, n, offsets, values, out);
-    else hipLaunchKernelGGL(select_write_kernel<false>, dim3((unsigned)nblocks), dim3(kBlock), 0, stream, s, n, offsets, values, out);
-    LFGC_HIP_CHECK_LAUNCH();
-    return LFGC_OK;
-}
-
 }  // namespace
 
 extern "C" int lfgc_codec_mask_f32(const float* x, int64_t n, uint8_t* mask, lfgc_stream_t stream) {
@@ -364,26 +295,21 @@ extern "C" int lfgc_codec_mask_f32(const float* x, int64_t n, uint8_t* mask, lfg
     return LFGC_OK;
 }
 
-extern "C" int64_t lfgc_codec_select_workspace_bytes(int64_t n) {
-    if (n < 1) return 16;
-    const long long nblocks = (n + kPerBlock - 1) / kPerBlock;
-    return (nblocks + 1) * 8 + nblocks * 4 + 16;
-}
+extern "C" int64_t lfgc_codec_select_workspace_bytes(int64_t n) { return lfgc_select_workspace(n); }
 
 extern "C" int lfgc_codec_compact_f32(const float* x, int64_t n, float* out, int64_t* count, void* workspace,
                                       int64_t workspace_bytes, lfgc_stream_t stream) {
     if (!x || !out || !count || !workspace) return LFGC_E_NULL;
     if (n < 1) return LFGC_E_SHAPE;
-    SelectSrc s; s.x = x; s.mask = nullptr; s.bit_offset = 0;
-    return run_select(s, n, nullptr, out, reinterpret_cast<long long*>(count), workspace, workspace_bytes, true, (hipStream_t)stream);
+    return lfgc_select(NonZero{x}, CompactSink{out}, n, reinterpret_cast<long long*>(count), workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }
 
 extern "C" int lfgc_codec_expand_f32(const uint8_t* mask, int64_t bit_offset, int64_t n, const float* values, float* out,
                                      void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
     if (!mask || !values || !out || !workspace) return LFGC_E_NULL;
     if (n < 1 || bit_offset < 0) return LFGC_E_SHAPE;
-    SelectSrc s; s.x = nullptr; s.mask = mask; s.bit_offset = bit_offset;
-    return run_select(s, n, values, out, nullptr, workspace, workspace_bytes, false, (hipStream_t)stream);
+    return lfgc_select(MaskBit{mask, bit_offset}, ExpandSink{values, out}, n, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int64_t lfgc_codec_kmeans_workspace_bytes(int k) {

@@ -3,15 +3,15 @@
 // vertex positions from lfgc_ray_iso_refine_f32 / lfgc_ray_iso_finish_f32 on the brackets emitted here; what this file adds
 // is the classification, the stream compaction and the connectivity between them.
 //   lfgc_iso_mesh_count_f32  classify every lattice point (7-bit crossing-edge flag) and every cell (0..12 triangles), exclusive
-//                            prefix sums of both in the count / scan / write pattern of lfgc_ray_compact, the two totals
+//                            prefix sums of both with the block sum and the scan of lfgc_select.h, the two totals
 //   lfgc_iso_mesh_emit_f32   per owned crossing edge its origin, direction and bracket; per triangle three vertex indices
 // A thread owns one lattice point (and the cell whose lowest corner it is); consecutive lanes walk z, the contiguous axis, so
 // the eight corner loads of a wave are eight contiguous rows.  No atomics: every output address has one writer.
-#include "lfgc_common.h"
+#include "lfgc_select.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kSelectBlock;            // the classify pass ends in lfgc_select_block_sum
 constexpr int kItems = 8;                       // lattice points per thread in the count and prefix passes
 constexpr int kPerBlock = kBlock * kItems;
 constexpr long long kMaxPoints = 1ll << 27;     // 12 triangles and 7 vertices per point stay below 2^31 in a slab
@@ -131,58 +131,25 @@ __device__ __forceinline__ unsigned classify(const Slab& s, const float* __restr
 __global__ __launch_bounds__(kBlock) void mesh_classify_kernel(const Slab s, const float* __restrict__ values, Workspace w,
                                                                unsigned nblocks) {
     const unsigned base = blockIdx.x * (unsigned)kPerBlock;
-    unsigned cv = 0, ct = 0;
+    unsigned c[2] = {0, 0};                                 // vertices, triangles
 #pragma unroll
     for (int j = 0; j < kItems; ++j) {
         const unsigned i = base + j * kBlock + threadIdx.x;
         unsigned code = 0;
         if (i < s.npts) code = classify(s, values, i);
         w.codes[i] = (unsigned short)code;                  // the padded tail is zeroed: the prefix pass reads whole chunks
-        cv += __popc(code & 0x7fu);
-        ct += code >> 8;
+        c[0] += __popc(code & 0x7fu);
+        c[1] += code >> 8;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        cv += __shfl_down(cv, off);
-        ct += __shfl_down(ct, off);
-    }
-    __shared__ unsigned sv[4], st[4];
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = cv; st[threadIdx.x >> 6] = ct; }
-    __syncthreads();
+    lfgc_select_block_sum(c);
     if (threadIdx.x == 0) {
-        w.block_counts[blockIdx.x] = sv[0] + sv[1] + sv[2] + sv[3];
-        w.block_counts[nblocks + blockIdx.x] = st[0] + st[1] + st[2] + st[3];
+        w.block_counts[blockIdx.x] = c[0];
+        w.block_counts[nblocks + blockIdx.x] = c[1];
     }
 }
 
-// pass 2: exclusive scan of the block counts; workgroup 0 the vertices, workgroup 1 the triangles.  totals[1] = all
-// triangles; totals[0] = all vertices when every classified point is an owner (else pass 3 writes it).
-__global__ __launch_bounds__(1024) void mesh_scan_kernel(Workspace w, long long nblocks, bool all_owned, long long* __restrict__ totals) {
-    const unsigned* counts = w.block_counts + blockIdx.x * nblocks;
-    long long* offsets = w.offsets + blockIdx.x * nblocks;
-    __shared__ long long s_wave[16];
-    __shared__ long long s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (long long b0 = 0; b0 < nblocks; b0 += 1024) {
-        const long long b = b0 + threadIdx.x;
-        const long long v = b < nblocks ? counts[b] : 0;
-        long long incl = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long t = __shfl_up(incl, off);
-            if ((threadIdx.x & 63) >= off) incl += t;
-        }
-        if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        long long wave_off = 0;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) wave_off += s_wave[k];
-        const long long carry = s_carry;
-        if (b < nblocks) offsets[b] = carry + wave_off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + wave_off + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && (blockIdx.x == 1 || all_owned)) totals[blockIdx.x] = s_carry;
-}
+// pass 2: lfgc_select_scan of the block counts, array 0 the vertices, array 1 the triangles.  totals[1] = all triangles;
+// totals[0] = all vertices when every classified point is an owner (else pass 3 writes it).
 
 // pass 3: exclusive prefix of every point.  A thread takes 8 consecutive points (one 16-byte load of codes, two 32-byte
 // stores of prefixes); the thread sums are scanned across the workgroup.
@@ -331,8 +298,9 @@ extern "C" int lfgc_iso_mesh_count_f32(const float* values, int32_t nx, int32_t 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(mesh_classify_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, s, values, w, (unsigned)nb);
     LFGC_HIP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(1024), 0, st, w, nb, s.v_split == s.npts, reinterpret_cast<long long*>(totals));
-    LFGC_HIP_CHECK_LAUNCH();
+    long long* tot = reinterpret_cast<long long*>(totals);
+    const int rc = lfgc_select_scan(w.block_counts, w.offsets, nb, 2, LfgcScanTotals{{s.v_split == s.npts ? tot : nullptr, tot + 1}}, st);
+    if (rc != LFGC_OK) return rc;
     hipLaunchKernelGGL(mesh_prefix_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, s, w, (unsigned)nb, reinterpret_cast<long long*>(totals));
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;

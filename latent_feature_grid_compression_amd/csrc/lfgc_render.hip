@@ -11,12 +11,11 @@
 //   lfgc_ray_iso_finish_f32  one secant step inside the final bracket: depth and position of the hit
 // All arithmetic is fp32 in the order include/lfgc.h states (the build has no contraction and correctly rounded
 // division), so the clip and the positions can be restated bit for bit on the host.  One writer per ray: no atomics.
-#include "lfgc_common.h"
+#include "lfgc_select.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kPerBlock = 2048;                 // list elements per workgroup in the two compaction passes
 constexpr int kRun = 32;                        // samples of one ray composited per step: one half wave
 
 struct RayBox { float lo[3], hi[3]; };
@@ -171,89 +170,28 @@ __global__ __launch_bounds__(kBlock) void ray_composite_kernel(const int* __rest
 }
 
 // ---- order-preserving list of the rays still worth marching -----------------------------------------------------------
-// the count / scan / write passes of the checkpoint codec's compaction (lfgc_codec.hip), over ray ids instead of values
+// the selection of lfgc_select.h over ray ids: the item is the ray, the sink appends it
 struct RayAlive {
+    typedef int Item;
     const int* prev;             // previous list (ascending ray ids) or NULL = every ray 0..n-1
     const int* n_steps;
     const int* k_next;
     const float4* state;
     float opacity_limit;
+    __device__ __forceinline__ bool operator()(long long i, long long n, int& ray) const {
+        ray = 0;
+        if (i >= n) return false;
+        ray = prev ? prev[i] : (int)i;
+        return k_next[ray] < n_steps[ray] && 1.0f - state[ray].w < opacity_limit;
+    }
 };
 
-__device__ __forceinline__ bool ray_alive(const RayAlive& s, long long i, long long n, int& ray) {
-    ray = 0;
-    if (i >= n) return false;
-    ray = s.prev ? s.prev[i] : (int)i;
-    return s.k_next[ray] < s.n_steps[ray] && 1.0f - s.state[ray].w < s.opacity_limit;
-}
-
-__global__ __launch_bounds__(kBlock) void alive_count_kernel(const RayAlive s, long long n, unsigned* __restrict__ block_counts) {
-    const long long base = (long long)blockIdx.x * kPerBlock;
-    unsigned c = 0;
-    int ray;
-#pragma unroll
-    for (int j = 0; j < kPerBlock / kBlock; ++j) c += ray_alive(s, base + j * kBlock + threadIdx.x, n, ray);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
-    __shared__ unsigned sw[4];
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
-}
-
-// exclusive scan of the block counts (one workgroup; 64-bit offsets), total -> *count
-__global__ __launch_bounds__(1024) void alive_scan_kernel(const unsigned* __restrict__ counts, long long* __restrict__ offsets,
-                                                          long long nblocks, long long* __restrict__ total) {
-    __shared__ long long s_wave[16];
-    __shared__ long long s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (long long b0 = 0; b0 < nblocks; b0 += 1024) {
-        const long long b = b0 + threadIdx.x;
-        const long long v = b < nblocks ? counts[b] : 0;
-        long long incl = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long t = __shfl_up(incl, off);
-            if ((threadIdx.x & 63) >= off) incl += t;
-        }
-        if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        long long wave_off = 0;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) wave_off += s_wave[w];
-        const long long carry = s_carry;
-        if (b < nblocks) offsets[b] = carry + wave_off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + wave_off + incl;
-        __syncthreads();
+struct RayListSink {
+    int* live_out;
+    __device__ __forceinline__ void operator()(long long, long long, bool flag, long long rank, const int& ray) const {
+        if (flag) live_out[rank] = ray;
     }
-    if (threadIdx.x == 0) *total = s_carry;
-}
-
-// element order inside a workgroup's 2048-element chunk: pass j (0..7) x wave w (0..3) x lane
-__global__ __launch_bounds__(kBlock) void alive_write_kernel(const RayAlive s, long long n, const long long* __restrict__ offsets,
-                                                             int* __restrict__ live_out) {
-    const long long base = (long long)blockIdx.x * kPerBlock;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ unsigned s_cnt[8][4];
-    bool flag[8];
-    int ray[8];
-    unsigned long long bal[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        flag[j] = ray_alive(s, base + j * kBlock + threadIdx.x, n, ray[j]);
-        bal[j] = __ballot(flag[j]);
-        if (lane == 0) s_cnt[j][wave] = (unsigned)__popcll(bal[j]);
-    }
-    __syncthreads();
-    long long run = offsets[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w == wave && flag[j]) live_out[run + __popcll(bal[j] & ((1ull << lane) - 1ull))] = ray[j];
-            run += s_cnt[j][w];
-        }
-    }
-}
+};
 
 // ---- isosurface: the first sign change of v - iso along a ray, its bisection and the hit point ---------------------------
 // inside(v) is v - iso >= 0 (a NaN is not inside).  The scan has the composite kernel's form: a half wave owns a ray and
@@ -394,11 +332,7 @@ extern "C" int lfgc_ray_composite_f32(const int32_t* live, int64_t n_live, const
     return LFGC_OK;
 }
 
-extern "C" int64_t lfgc_ray_compact_workspace_bytes(int64_t n) {
-    if (n < 1) return 16;
-    const long long nblocks = (n + kPerBlock - 1) / kPerBlock;
-    return (nblocks + 1) * 8 + nblocks * 4 + 16;
-}
+extern "C" int64_t lfgc_ray_compact_workspace_bytes(int64_t n) { return lfgc_select_workspace(n); }
 
 extern "C" int lfgc_ray_compact(const int32_t* prev, int64_t n_prev, const int32_t* n_steps, const int32_t* k_next, const float* state,
                                 float opacity_limit, int32_t* live_out, int64_t* count, void* workspace, int64_t workspace_bytes,
@@ -406,21 +340,9 @@ extern "C" int lfgc_ray_compact(const int32_t* prev, int64_t n_prev, const int32
     if (!n_steps || !k_next || !state || !live_out || !count || !workspace) return LFGC_E_NULL;
     if (n_prev < 1 || n_prev > 0x7fffffffLL) return LFGC_E_SHAPE;
     if ((uintptr_t)state & 15) return LFGC_E_ALIGN;
-    if (workspace_bytes < lfgc_ray_compact_workspace_bytes(n_prev)) return LFGC_E_WORKSPACE;
-    const long long n = n_prev, nblocks = (n + kPerBlock - 1) / kPerBlock;
-    long long* offsets = reinterpret_cast<long long*>(workspace);
-    unsigned* counts = reinterpret_cast<unsigned*>(offsets + nblocks + 1);
-    RayAlive s;
-    s.prev = prev; s.n_steps = n_steps; s.k_next = k_next; s.state = reinterpret_cast<const float4*>(state);
-    s.opacity_limit = opacity_limit;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(alive_count_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, st, s, n, counts);
-    LFGC_HIP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(alive_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, nblocks, reinterpret_cast<long long*>(count));
-    LFGC_HIP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(alive_write_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, st, s, n, offsets, live_out);
-    LFGC_HIP_CHECK_LAUNCH();
-    return LFGC_OK;
+    const RayAlive alive = {prev, n_steps, k_next, reinterpret_cast<const float4*>(state), opacity_limit};
+    return lfgc_select(alive, RayListSink{live_out}, n_prev, reinterpret_cast<long long*>(count), workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }
 
 extern "C" int lfgc_ray_iso_scan_f32(const int32_t* live, int64_t n_live, const float* values, const float* t_near, const float* t_far,

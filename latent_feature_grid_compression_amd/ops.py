@@ -954,8 +954,9 @@ def _flat_f32(x: torch.Tensor) -> torch.Tensor:
     return _f32c(x.detach()).reshape(-1)
 
 
-def _select_workspace(n: int, device) -> torch.Tensor:
-    nbytes = int(_lib.load().lfgc_codec_select_workspace_bytes(int(n)))
+def _select_workspace(n: int, device, query: str = 'lfgc_codec_select_workspace_bytes') -> torch.Tensor:
+    """Scratch of one order-preserving selection over n elements (csrc/lfgc_select.h), sized by the entry's own query."""
+    nbytes = int(getattr(_lib.load(), query)(int(n)))
     return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
 
 
@@ -1328,8 +1329,7 @@ def ray_compact(prev: Optional[torch.Tensor], n_steps: torch.Tensor, k_next: tor
     if n == 0:
         return out
     count = torch.zeros(1, dtype=torch.int64, device=n_steps.device)
-    nbytes = int(_lib.load().lfgc_ray_compact_workspace_bytes(n))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=n_steps.device)
+    ws = _select_workspace(n, n_steps.device, 'lfgc_ray_compact_workspace_bytes')
     check(_lib.load().lfgc_ray_compact(_ptr(prev), n, n_steps.data_ptr(), k_next.data_ptr(), state.data_ptr(), float(opacity_limit),
                                        out.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(n_steps)),
           'lfgc_ray_compact')

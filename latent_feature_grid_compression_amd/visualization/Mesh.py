@@ -103,12 +103,7 @@ def isosurface_mesh(value_slab_fn: Callable, point_fn: Callable, res: Sequence[i
             raise ValueError('the mesh reaches 2^31 vertices: triangle indices are int32')
         origins, dirs, bracket, tris = ops.iso_mesh_emit(vals, x1 - x0, iso, xs[x0:xe], ys, zs, n_vertices, ws, V, T)
         every = torch.arange(V, dtype=torch.int32, device=dev)
-        values = None
-        for _ in range(n_refine if V else 0):
-            values = point_fn(ops.ray_iso_refine(every, values, origins, dirs, iso, bracket))
-        if values is not None:
-            ops.ray_iso_refine(every, values, origins, dirs, iso, bracket)         # folds the last values in
-        _, pos = ops.ray_iso_finish(every, origins, dirs, bracket)
+        _, pos = Render._refine_and_finish(point_fn, every, origins, dirs, iso, bracket, n_refine if V else 0)
         if not V:                                                                   # nothing to evaluate: empty rows
             out = torch.empty(0, dtype=torch.float32, device=dev)
             if normals:
@@ -167,21 +162,11 @@ def isosurface_mesh_from_net(dataset, net, iso: float, tiled_res: int = 32, **kw
         raise LfgcError('the mesh is extracted on the MI355X only: the model is on %s; there is no CPU fallback.' % dev)
     if kwargs.get('normals', True) and net.training:
         raise ValueError('normals come from net.value_and_gradient in eval mode: call net.eval() first')
-    precision = getattr(net, 'precision', 'f16x2')
     tables = lattice_axis_tables(res, dataset.scales.tolist(), dev, tiled_res)
-    with torch.no_grad():
-        desc, grid_cl, packed = net._descriptor(), net._decoded_channel_last(), net._packed()
 
     def value_slab_fn(x_begin, x_end):
         return field_from_net_fused(dataset, net, x_begin, x_end, tiled_res)
-
-    def point_fn(pos, gradient=False):
-        if gradient:
-            v, g = net.value_and_gradient(pos)
-            return v.view(-1), g
-        with torch.no_grad():
-            return ops.forward_raw(desc, grid_cl, packed, pos=pos, clamp=True, precision=precision)[0]
-    return isosurface_mesh(value_slab_fn, point_fn, res, tables, iso, **kwargs)
+    return isosurface_mesh(value_slab_fn, Render._net_value_fn(net), res, tables, iso, **kwargs)
 
 
 def volume_axis_tables(dataset, device):

@@ -24,6 +24,7 @@ First-hit isosurfaces use the same loop with ops.ray_iso_scan in the place of th
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 from typing import Callable, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -124,6 +125,50 @@ def max_steps_for(box_min, box_max, step: float) -> int:
     return max(32, int(math.ceil(2.0 * diag / float(step))))
 
 
+def _march(chunk_step: Callable, origins: torch.Tensor, dirs: torch.Tensor, step: float, box_min, box_max, block_steps: int,
+           opacity_limit: float, max_samples_per_launch: int, t_min: float, t_max: float, stats: Optional[dict],
+           n_buffers: int = 0) -> SimpleNamespace:
+    """The marching loop of ``render`` and ``isosurface`` (their docstrings describe it) with ``chunk_step(rays, part, pos)``
+    in the place of the compositing: it evaluates the ``block_steps`` positions per ray of ``part`` laid out in ``pos`` and
+    folds them into ``rays.state`` and ``rays.k_next``.  Returns ``rays``: origins, unit dirs, state (R, 4) and ``n_buffers``
+    more zeroed (R, 4) ``buffers``; with R > 0 also t_near, t_far, n_steps, k_next.  ``stats``: 'live', 'samples', 'blocks'."""
+    S = int(block_steps)
+    if S < 32 or S % 32:
+        raise ValueError('block_steps must be a positive multiple of 32')
+    if not float(step) > 0.0:
+        raise ValueError('step must be positive')
+    ops._require_hip(origins, dirs)
+    origins, dirs = ops._f32c(origins.detach()), ops._f32c(dirs.detach())
+    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape:
+        raise ValueError('origins and dirs must both be (R, 3)')
+    dirs = dirs / dirs.norm(dim=1, keepdim=True)
+    R, dev = origins.shape[0], origins.device
+    max_steps = max_steps_for(box_min, box_max, step)
+    if max_steps > (1 << 30):
+        raise ValueError('step %g is too small for the box: more than 2^30 steps per ray' % step)
+    chunk = max(1, int(max_samples_per_launch) // S)
+    state = torch.zeros((R, 4), dtype=torch.float32, device=dev)
+    state[:, 3] = 1.0
+    buffers = [torch.zeros((R, 4), dtype=torch.float32, device=dev) for _ in range(n_buffers)]
+    rays = SimpleNamespace(origins=origins, dirs=dirs, state=state, buffers=buffers)
+    live_counts, n_samples = [], 0
+    if R:
+        rays.t_near, rays.t_far, rays.n_steps = ops.ray_clip(origins, dirs, box_min, box_max, step, max_steps, t_min, t_max)
+        rays.k_next = torch.zeros(R, dtype=torch.int32, device=dev)
+        live = ops.ray_compact(None, rays.n_steps, rays.k_next, state, opacity_limit)
+        while live.numel():
+            live_counts.append(int(live.numel()))
+            for b in range(0, live.numel(), chunk):
+                part = live[b:b + chunk]
+                pos = ops.ray_samples(part, origins, dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S)
+                chunk_step(rays, part, pos)
+                n_samples += pos.shape[0]
+            live = ops.ray_compact(live, rays.n_steps, rays.k_next, state, opacity_limit)
+    if stats is not None:
+        stats.update(live=live_counts, samples=n_samples, blocks=len(live_counts))
+    return rays
+
+
 def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: TransferFunction, step: float, box_min, box_max,
            block_steps: int = 32, opacity_limit: float = 0.999, shading: Optional[str] = None,
            max_samples_per_launch: int = 1 << 22, ka: float = 0.3, kd: float = 0.7, t_min: float = 0.0,
@@ -144,45 +189,19 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
     ops._require_hip(origins, dirs)
     if shading not in (None, 'headlight'):
         raise ValueError("shading must be None or 'headlight'")
-    S = int(block_steps)
-    if S < 32 or S % 32:
-        raise ValueError('block_steps must be a positive multiple of 32')
-    if not float(step) > 0.0:
-        raise ValueError('step must be positive')
     if not 0.0 < float(opacity_limit) <= 1.0:
         raise ValueError('opacity_limit must lie in (0, 1]')
-    origins, dirs = ops._f32c(origins.detach()), ops._f32c(dirs.detach())
-    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape:
-        raise ValueError('origins and dirs must both be (R, 3)')
-    dirs = dirs / dirs.norm(dim=1, keepdim=True)
-    R, dev = origins.shape[0], origins.device
-    max_steps = max_steps_for(box_min, box_max, step)
-    if max_steps > (1 << 30):
-        raise ValueError('step %g is too small for the box: more than 2^30 steps per ray' % step)
-    chunk = max(1, int(max_samples_per_launch) // S)
-    table = tf.on(dev)
-    state = torch.zeros((R, 4), dtype=torch.float32, device=dev)
-    state[:, 3] = 1.0
-    live_counts, n_samples = [], 0
-    if R:
-        t_near, t_far, n_steps = ops.ray_clip(origins, dirs, box_min, box_max, step, max_steps, t_min, t_max)
-        k_next = torch.zeros(R, dtype=torch.int32, device=dev)
-        live = ops.ray_compact(None, n_steps, k_next, state, opacity_limit)
-        while live.numel():
-            live_counts.append(int(live.numel()))
-            for b in range(0, live.numel(), chunk):
-                part = live[b:b + chunk]
-                pos = ops.ray_samples(part, origins, dirs, t_near, t_far, n_steps, k_next, step, S)
-                out = value_fn(pos)
-                values, grad = out if shading else (out, None)
-                if shading and grad is None:
-                    raise ValueError("shading='headlight' needs value_fn to return (values, gradients)")
-                ops.ray_composite(part, values, grad, dirs, t_near, t_far, n_steps, k_next, step, S, table, tf.v_min, tf.v_max,
-                                  opacity_limit, state, ka, kd)
-                n_samples += pos.shape[0]
-            live = ops.ray_compact(live, n_steps, k_next, state, opacity_limit)
-    if stats is not None:
-        stats.update(live=live_counts, samples=n_samples, blocks=len(live_counts))
+    S, table = int(block_steps), tf.on(origins.device)
+
+    def composite(rays, part, pos):
+        out = value_fn(pos)
+        values, grad = out if shading else (out, None)
+        if shading and grad is None:
+            raise ValueError("shading='headlight' needs value_fn to return (values, gradients)")
+        ops.ray_composite(part, values, grad, rays.dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S, table,
+                          tf.v_min, tf.v_max, opacity_limit, rays.state, ka, kd)
+    state = _march(composite, origins, dirs, step, box_min, box_max, block_steps, opacity_limit, max_samples_per_launch, t_min,
+                   t_max, stats).state
     state[:, 3] = 1.0 - state[:, 3]
     return state
 
@@ -209,26 +228,40 @@ def render_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: torch.T
     ``net.precision``; the decoded grid and the packed weights come from the eval-mode caches under their usual rule."""
     ops._require_hip(origins, dirs)
     scales = _scales_of(dataset_or_scales)
+    step = _default_step(dataset_or_scales, step)
+    shading = bool(kwargs.get('shading'))
+    if shading and net.training:
+        raise ValueError("shading='headlight' evaluates net.value_and_gradient in eval mode: call net.eval() first")
+    net_fn = _net_value_fn(net, values=not shading)
+    return render(lambda pos: net_fn(pos, gradient=shading), origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
+
+
+def _default_step(dataset_or_scales, step):
+    """``step``, or half a voxel of the dataset's volume where it is None."""
     if step is None:
         if not hasattr(dataset_or_scales, 'max_dim'):
             raise ValueError('the default step needs a dataset (max_dim); pass step explicitly with bare scales')
         step = 1.0 / float(dataset_or_scales.max_dim)
-    precision = getattr(net, 'precision', 'f16x2')
-    if kwargs.get('shading'):
-        if net.training:
-            raise ValueError("shading='headlight' evaluates net.value_and_gradient in eval mode: call net.eval() first")
+    return step
 
-        def value_fn(pos):
-            v, g = net.value_and_gradient(pos)
-            return v.view(-1), g
-    else:
+
+def _net_value_fn(net, values: bool = True) -> Callable:
+    """``value_fn(pos, gradient=False)`` of the compressed model for ``render``, ``isosurface`` and Mesh.isosurface_mesh:
+    the clamped eval-mode output of ``net`` (ops.forward_raw under no_grad), and with ``gradient=True`` (values, gradients)
+    of ``net.value_and_gradient``.  Honours ``net.precision``; the decoded grid and the packed weights come from the
+    eval-mode caches under their usual rule, here and now -- unless ``values=False`` says that only gradient calls follow."""
+    precision = getattr(net, 'precision', 'f16x2')
+    if values:
         with torch.no_grad():
             desc, grid_cl, packed = net._descriptor(), net._decoded_channel_last(), net._packed()
 
-        def value_fn(pos):
-            with torch.no_grad():
-                return ops.forward_raw(desc, grid_cl, packed, pos=pos, clamp=True, precision=precision)[0]
-    return render(value_fn, origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
+    def value_fn(pos, gradient=False):
+        if gradient:
+            v, g = net.value_and_gradient(pos)
+            return v.view(-1), g
+        with torch.no_grad():
+            return ops.forward_raw(desc, grid_cl, packed, pos=pos, clamp=True, precision=precision)[0]
+    return value_fn
 
 
 def index_positions(dataset, pos: torch.Tensor) -> torch.Tensor:
@@ -303,43 +336,21 @@ def isosurface(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, is
 
     ``stats``: a dict that receives 'live' (marching rays per block), 'samples' (rows evaluated in the march), 'blocks',
     'bracketed' (rays with a hit) and 'refine_samples' (rows evaluated for the bisection and at the hit points)."""
-    S = int(block_steps)
-    if S < 32 or S % 32:
-        raise ValueError('block_steps must be a positive multiple of 32')
-    if not float(step) > 0.0:
-        raise ValueError('step must be positive')
     iso = float(iso)
     if not math.isfinite(iso):
         raise ValueError('iso must be finite')
     n_refine = int(refine_steps)
     if n_refine != refine_steps or not 0 <= n_refine <= 64:
         raise ValueError('refine_steps must be an integer in [0, 64]')
-    ops._require_hip(origins, dirs)
-    origins, dirs = ops._f32c(origins.detach()), ops._f32c(dirs.detach())
-    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape:
-        raise ValueError('origins and dirs must both be (R, 3)')
-    dirs = dirs / dirs.norm(dim=1, keepdim=True)
+    S = int(block_steps)
+
+    def scan(rays, part, pos):
+        ops.ray_iso_scan(part, value_fn(pos), rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S, iso, rays.state,
+                         rays.buffers[0])
+    rays = _march(scan, origins, dirs, step, box_min, box_max, block_steps, 1.0, max_samples_per_launch, t_min, t_max, stats,
+                  n_buffers=1)
+    origins, dirs, state, bracket = rays.origins, rays.dirs, rays.state, rays.buffers[0]
     R, dev = origins.shape[0], origins.device
-    max_steps = max_steps_for(box_min, box_max, step)
-    if max_steps > (1 << 30):
-        raise ValueError('step %g is too small for the box: more than 2^30 steps per ray' % step)
-    chunk = max(1, int(max_samples_per_launch) // S)
-    state = torch.zeros((R, 4), dtype=torch.float32, device=dev)
-    state[:, 3] = 1.0
-    bracket = torch.zeros((R, 4), dtype=torch.float32, device=dev)
-    live_counts, n_samples, n_refined = [], 0, 0
-    if R:
-        t_near, t_far, n_steps = ops.ray_clip(origins, dirs, box_min, box_max, step, max_steps, t_min, t_max)
-        k_next = torch.zeros(R, dtype=torch.int32, device=dev)
-        live = ops.ray_compact(None, n_steps, k_next, state, 1.0)
-        while live.numel():
-            live_counts.append(int(live.numel()))
-            for b in range(0, live.numel(), chunk):
-                part = live[b:b + chunk]
-                pos = ops.ray_samples(part, origins, dirs, t_near, t_far, n_steps, k_next, step, S)
-                ops.ray_iso_scan(part, value_fn(pos), t_near, t_far, n_steps, k_next, step, S, iso, state, bracket)
-                n_samples += pos.shape[0]
-            live = ops.ray_compact(live, n_steps, k_next, state, 1.0)
     hit = state[:, 3] == 0.0
     found = torch.nonzero(hit).view(-1).to(torch.int32)
     t = torch.full((R,), float('inf'), dtype=torch.float32, device=dev)
@@ -347,15 +358,11 @@ def isosurface(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, is
     normal = torch.zeros((R, 3), dtype=torch.float32, device=dev)
     value = torch.zeros(R, dtype=torch.float32, device=dev)
     per_launch = max(1, int(max_samples_per_launch))
+    n_refined = 0
     for b in range(0, found.numel(), per_launch):
         part = found[b:b + per_launch]
         idx = part.long()
-        values = None
-        for _ in range(n_refine):
-            values = value_fn(ops.ray_iso_refine(part, values, origins, dirs, iso, bracket))
-        if values is not None:
-            ops.ray_iso_refine(part, values, origins, dirs, iso, bracket)       # folds the last values in
-        t_hit, p_hit = ops.ray_iso_finish(part, origins, dirs, bracket)
+        t_hit, p_hit = _refine_and_finish(value_fn, part, origins, dirs, iso, bracket, n_refine)
         n_refined += (n_refine + 1) * part.numel()
         t[idx], position[idx] = t_hit, p_hit
         if normals:
@@ -372,17 +379,20 @@ def isosurface(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, is
             value[idx] = value_fn(p_hit).reshape(-1).to(torch.float32)
     inf = torch.full_like(t, float('inf'))
     if stats is not None:
-        stats.update(live=live_counts, samples=n_samples, blocks=len(live_counts), bracketed=int(found.numel()),
-                     refine_samples=n_refined)
+        stats.update(bracketed=int(found.numel()), refine_samples=n_refined)
     return IsoHits(hit, t, position, normal, value, torch.where(hit, bracket[:, 0], inf), torch.where(hit, bracket[:, 1], inf))
 
 
-def _iso_step(dataset_or_scales, step):
-    if step is None:
-        if not hasattr(dataset_or_scales, 'max_dim'):
-            raise ValueError('the default step needs a dataset (max_dim); pass step explicitly with bare scales')
-        step = 1.0 / float(dataset_or_scales.max_dim)
-    return step
+def _refine_and_finish(value_fn: Callable, rows: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, iso: float,
+                       bracket: torch.Tensor, n_refine: int):
+    """(t, position) of the brackets of ``rows``: ``n_refine`` bisections, each one ``value_fn`` call with one trial point
+    per row, then the secant step inside what is left (ops.ray_iso_refine, ops.ray_iso_finish).  ``bracket`` in place."""
+    values = None
+    for _ in range(n_refine):
+        values = value_fn(ops.ray_iso_refine(rows, values, origins, dirs, iso, bracket))
+    if values is not None:
+        ops.ray_iso_refine(rows, values, origins, dirs, iso, bracket)           # folds the last values in
+    return ops.ray_iso_finish(rows, origins, dirs, bracket)
 
 
 def isosurface_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: torch.Tensor, iso: float,
@@ -396,20 +406,10 @@ def isosurface_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: tor
         raise ValueError('iso must lie inside the clamp range (-1, 1) of the eval-mode output, got %r' % (iso,))
     ops._require_hip(origins, dirs)
     scales = _scales_of(dataset_or_scales)
-    step = _iso_step(dataset_or_scales, step)
+    step = _default_step(dataset_or_scales, step)
     if kwargs.get('normals', True) and net.training:
         raise ValueError('normals come from net.value_and_gradient in eval mode: call net.eval() first')
-    precision = getattr(net, 'precision', 'f16x2')
-    with torch.no_grad():
-        desc, grid_cl, packed = net._descriptor(), net._decoded_channel_last(), net._packed()
-
-    def value_fn(pos, gradient=False):
-        if gradient:
-            v, g = net.value_and_gradient(pos)
-            return v.view(-1), g
-        with torch.no_grad():
-            return ops.forward_raw(desc, grid_cl, packed, pos=pos, clamp=True, precision=precision)[0]
-    return isosurface(value_fn, origins, dirs, iso, step, [-s for s in scales], scales, **kwargs)
+    return isosurface(_net_value_fn(net), origins, dirs, iso, step, [-s for s in scales], scales, **kwargs)
 
 
 def isosurface_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, iso: float,
@@ -420,7 +420,7 @@ def isosurface_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor,
     -> ``surface_deviation`` of the two is the surface-space quality of the compression."""
     ops._require_hip(origins, dirs, volume)
     scales = _scales_of(dataset)
-    step = _iso_step(dataset, step)
+    step = _default_step(dataset, step)
     value_fn = volume_value_fn(dataset, volume)
     return isosurface(value_fn, origins, dirs, iso, step, [-s for s in scales], scales, **kwargs)
 

@@ -309,7 +309,9 @@ def random_case(shape, seed, iso=0.25):
     return v, tabs, iso
 
 
-GPU_LATTICES = ((2, 2, 2), (5, 6, 7), (33, 9, 34), (3, 3, 130), (2, 5, 3))
+GPU_LATTICES = ((2, 2, 2), (5, 6, 7), (33, 9, 34), (3, 3, 130), (2, 5, 3),
+                (3, 300, 300))                     # 132 block counts: the scan of them (csrc/lfgc_select.hip) passes one wave
+CARRY_LATTICE = (5, 520, 1030)                     # 1308 block counts per array: past one round of 1024 of that scan
 
 
 # ---- the network case of the GPU test (conditions checked on the CPU in test_mesh_host.py) -----------------------------------

@@ -83,8 +83,12 @@ def test_store_writes_the_reference_format(dev, tmp_path):
         assert np.array_equal(back['net_layers.%d.weight' % i].cpu().numpy().reshape(-1), ours['weights'][i])
 
 
-@pytest.mark.parametrize('n', [1, 7, 8, 9, 63, 64, 65, 2047, 2048, 2049, 100003, 1 << 20])
-@pytest.mark.parametrize('density', [0.0, 0.3, 1.0])
+_CARRY_N = 2048 * 1024 + 2049          # 1026 block counts: the scan's second round of 1024 holds two live entries
+
+
+@pytest.mark.parametrize('density,n', [(d, n) for d in (0.0, 0.3, 1.0)
+                                       for n in (1, 7, 8, 9, 63, 64, 65, 2047, 2048, 2049, 100003, 1 << 20)]
+                         + [(0.3, _CARRY_N), (1.0, _CARRY_N)])
 def test_mask_compact_expand_bit_exact(dev, n, density):
     from latent_feature_grid_compression_amd import ops
     rng = np.random.default_rng(n + int(density * 10))

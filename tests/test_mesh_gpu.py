@@ -2,6 +2,8 @@
 restatement (tests/mesh_ref.py) for EQUALITY -- totals, edges, brackets, triangles --, the slab loop of
 Mesh.isosurface_mesh on analytic value functions (every slab size gives the same bits), and the smallest build_synth
 model end to end against the oracle's lattice values and gradients."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -82,6 +84,29 @@ def test_count_and_emit_equal_the_restatement(dev, shape):
         assert np.array_equal(o, r_o) and np.array_equal(d, r_d), (x0, x1, xe)
         assert _same(br, r_br), (x0, x1, xe)
         assert np.array_equal(tr, r_tr), (x0, x1, xe)
+
+
+@functools.lru_cache(maxsize=None)
+def _carry_case():
+    tabs, P = MR.lattice(MR.CARRY_LATTICE)
+    return tabs, MR.sphere_field(P), 0.05
+
+
+@pytest.mark.parametrize('n_owner', [5, 2])
+def test_count_and_emit_across_the_scans_carry(dev, n_owner):
+    """2 678 000 points = 1308 block counts per array: the scan of them takes two rounds of 1024 and hands its carry over, in
+    the vertex array and in the triangle array that starts 1308 entries later.  n_owner = 5: every point owns, the scan
+    writes both totals; n_owner = 2: three planes are ranked, v_split lies in the middle, the prefix pass writes the vertex
+    total."""
+    tabs, vals, iso = _carry_case()
+    want_V, want_T = MR.count(vals, n_owner, iso)
+    assert want_V > 100000 and want_T > 200000
+    V, T, o, d, br, tr = _emit_with_sentinels(vals, n_owner, iso, tabs, 7, dev)
+    assert (V, T) == (want_V, want_T)
+    r_o, r_d, r_br, r_tr = MR.emit(vals, n_owner, iso, *tabs, 7)
+    assert np.array_equal(o, r_o) and np.array_equal(d, r_d)
+    assert _same(br, r_br)
+    assert np.array_equal(tr, r_tr)
 
 
 @pytest.mark.parametrize('value', [1.0, -1.0])

@@ -119,35 +119,49 @@ def test_composite_matches_float64(dev, limit, shaded):
 
 # ---- 3. compact --------------------------------------------------------------------------------------------------------
 
+def _compact_case(dev, rng, n, pattern, from_list, limit=0.9):
+    """ops.ray_compact of n list entries against the NumPy predicate; returns the expected list."""
+    R_ = 2 * n if from_list else n
+    n_steps = rng.integers(0, 100, R_).astype(np.int32)
+    k_next = (rng.integers(0, 4, R_) * 32).astype(np.int32)
+    T = rng.uniform(0, 1, R_).astype(np.float32)
+    T[rng.uniform(size=R_) < 0.1] = np.float32(1.0) - np.float32(limit)       # on the limit's edge
+    if pattern == 'live':
+        n_steps[:], k_next[:], T[:] = 50, 32, 0.5
+    elif pattern == 'dead':
+        dead_by_steps = rng.uniform(size=R_) < 0.5
+        k_next[dead_by_steps] = n_steps[dead_by_steps]
+        T[~dead_by_steps] = 0.05
+    state = np.concatenate([rng.uniform(0, 1, (R_, 3)).astype(np.float32), T[:, None]], 1)
+    alive = (k_next < n_steps) & ((np.float32(1.0) - T) < np.float32(limit))
+    prev = np.sort(rng.choice(R_, n, replace=False)).astype(np.int32) if from_list else None
+    want = np.nonzero(alive)[0].astype(np.int32) if prev is None else prev[alive[prev]]
+    got = _ops().ray_compact(None if prev is None else _t(prev, dev), _t(n_steps, dev), _t(k_next, dev), _t(state, dev), limit)
+    assert got.dtype == torch.int32
+    assert np.array_equal(got.cpu().numpy(), want), (pattern, from_list)
+    return want
+
+
 @pytest.mark.parametrize('n', [1, 63, 64, 65, 1000, 5000])      # 5000: more than one workgroup of the scan (2048 per group)
 def test_compact_is_the_ordered_predicate(dev, n):
-    ops = _ops()
     rng = np.random.default_rng(n)
-    limit = 0.9
     for pattern in ('live', 'dead', 'random'):
         for from_list in (False, True):
-            R_ = 2 * n if from_list else n
-            n_steps = rng.integers(0, 100, R_).astype(np.int32)
-            k_next = (rng.integers(0, 4, R_) * 32).astype(np.int32)
-            T = rng.uniform(0, 1, R_).astype(np.float32)
-            T[rng.uniform(size=R_) < 0.1] = np.float32(1.0) - np.float32(limit)       # on the limit's edge
-            if pattern == 'live':
-                n_steps[:], k_next[:], T[:] = 50, 32, 0.5
-            elif pattern == 'dead':
-                dead_by_steps = rng.uniform(size=R_) < 0.5
-                k_next[dead_by_steps] = n_steps[dead_by_steps]
-                T[~dead_by_steps] = 0.05
-            state = np.concatenate([rng.uniform(0, 1, (R_, 3)).astype(np.float32), T[:, None]], 1)
-            alive = (k_next < n_steps) & ((np.float32(1.0) - T) < np.float32(limit))
-            prev = np.sort(rng.choice(R_, n, replace=False)).astype(np.int32) if from_list else None
-            want = np.nonzero(alive)[0].astype(np.int32) if prev is None else prev[alive[prev]]
-            got = ops.ray_compact(None if prev is None else _t(prev, dev), _t(n_steps, dev), _t(k_next, dev), _t(state, dev), limit)
-            assert got.dtype == torch.int32
-            assert np.array_equal(got.cpu().numpy(), want), (pattern, from_list)
+            want = _compact_case(dev, rng, n, pattern, from_list)
             if pattern == 'live':
                 assert len(want) == n
             if pattern == 'dead':
                 assert len(want) == 0
+
+
+def test_compact_across_the_scans_carry(dev):
+    """1026 block counts: the scan of them (csrc/lfgc_select.hip) takes a second round of 1024 that holds two live entries and
+    the first round's carry.  From all rays, and from a sorted list of that length."""
+    n = 2048 * 1024 + 2049
+    rng = np.random.default_rng(n)
+    for from_list in (False, True):
+        want = _compact_case(dev, rng, n, 'random', from_list)
+        assert 0 < len(want) < n
 
 
 # ---- 4. end to end against the oracle -------------------------------------------------------------------------------------
