@@ -770,6 +770,47 @@ int lfgc_iso_mesh_emit_f32(const float* values, int32_t nx, int32_t n_owner, int
                            const void* workspace, int64_t workspace_bytes, int64_t n_vertices, int64_t n_triangles,
                            float* origins, float* dirs, float* bracket, int32_t* triangles, lfgc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Empty-space skipping for the direct volume renderer.  The volume lattice has res = (X, Y, Z) points
+ * and cells = res - 1 per axis.  Bricks have an edge of B >= 1 cells: nb_a = ceil(cells_a / B) per axis, brick i of an axis
+ * holds the lattice points i B .. min((i+1) B, res-1) inclusive, so a face plane belongs to both neighbours.  Tables are
+ * row-major (nbx, nby, nbz).  No atomics, one writer per brick and per ray: two runs give the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Fold the lattice values of the planes [x_begin, x_end) (values device (x_end-x_begin, Y, Z), z contiguous) into
+ * minmax device (nbx, nby, nbz, 2) fp32 = (min, max), 8-byte aligned, which the caller initialises to (+inf, -inf): every
+ * brick that holds one of the slab's planes is folded with those of its points that the slab holds; the others are not
+ * touched.  A NaN makes its bricks (-inf, +inf).  Launches are stream-ordered and min / max are exact, so the table does
+ * not depend on how the volume is cut into slabs, and the volume need not be resident.
+ *   res host int32[3], each >= 2; 0 <= x_begin < x_end <= X. */
+int lfgc_brick_minmax_f32(const float* values, const int32_t* res, int32_t x_begin, int32_t x_end, int32_t B, float* minmax,
+                          lfgc_stream_t stream);
+
+/* occ[b] (device uint8, n_bricks) = 0 iff the brick is empty under the transfer function, else 1.  With lo = min - margin,
+ * hi = max + margin and u(v) = fminf(fmaxf((v-v_min)*tf_scale, 0), K-1) -- lfgc_ray_composite_f32's expression, tf_scale the
+ * float it is given -- the brick is empty iff the extinction tab[i].w is zero for every row i = floorf(u(lo)) ..
+ * ceilf(u(hi)).  u is monotone in fp32, so every value in [lo, hi] interpolates between rows of that range: the composite
+ * kernel gives such a sample the extinction 0 exactly.
+ *   minmax device (n_bricks, 2), 8-byte aligned; tf_table (K,4), 16-byte aligned, K >= 2; margin >= 0. */
+int lfgc_brick_occupancy_f32(const float* minmax, int64_t n_bricks, const float* tf_table, int K, float v_min, float tf_scale,
+                             float margin, uint8_t* occ, lfgc_stream_t stream);
+
+/* For every ray of live[0..n_list) (live == NULL: the rays 0..n_list-1), while k_next < n_steps: look at the samples
+ * k = k_next .. min(k_next + S, n_steps) - 1 at lfgc_ray_samples_f32's positions, operation for operation (segment [a, b],
+ * tm = 0.5f*(a+b), p = o + tm*d).  Per axis q = (p - box_min)/(box_max - box_min)*(float)cells, one rounding per operation,
+ * c_lo = (int)fminf(fmaxf(floorf(q - g), 0), cells-1) and c_hi the same with q + g; the sample touches the bricks
+ * {c_lo/B, c_hi/B} of each axis, at most 8.  The guard g = 1/16 cell covers the rounding difference between this q and the
+ * index coordinate the samplers form for themselves (lfgc_gt_interp_f32, the forward kernel's grid lookup) for up to 2^16
+ * lattice points per axis.  If no sample of the block touches a brick with occ != 0: k_next += S, skipped[ray] += 1, and
+ * again; otherwise the ray is left there.  k_next only moves in multiples of S, so the blocks that follow hold the rows they
+ * would have held anyway.  Neither state nor a ray outside the list is touched; a ray id may appear once in the list.
+ *   box_min < box_max host float[3]; cells host int32[3], each >= 1; occ device uint8 (nbx, nby, nbz); skipped device
+ *   int32 (R), zeroed by the caller; S a multiple of 32. */
+int lfgc_ray_skip_f32(const int32_t* live, int64_t n_list, const float* origins, const float* dirs, const float* t_near,
+                      const float* t_far, const int32_t* n_steps, int32_t* k_next, float dt, int S, const float* box_min,
+                      const float* box_max, const int32_t* cells, int32_t B, const uint8_t* occ, int32_t* skipped,
+                      lfgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,10 @@ SIGNATURES = {
     'lfgc_iso_mesh_count_f32': (c_int, [c_void_p] + [c_int32] * 4 + [c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     'lfgc_iso_mesh_emit_f32': (c_int, [c_void_p] + [c_int32] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p] +
                                [c_int64] * 3 + [c_void_p] * 5),
+    'lfgc_brick_minmax_f32': (c_int, [c_void_p, POINTER(c_int32), c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    'lfgc_brick_occupancy_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_void_p]),
+    'lfgc_ray_skip_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 6 + [c_float, c_int, POINTER(c_float), POINTER(c_float),
+                                                                       POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1410,6 +1410,89 @@ def ray_iso_finish(rays: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor
     return t_hit, pos
 
 
+# ---- empty-space skipping: brick ranges, occupancy under a transfer function, the jump over empty blocks
+
+def _int3(v):
+    return (ctypes.c_int32 * 3)(*[int(x) for x in v])
+
+
+def brick_counts(cells, brick: int) -> Tuple[int, int, int]:
+    """Bricks per axis for ``cells`` = res - 1 lattice cells per axis and an edge of ``brick`` cells: ceil(cells / brick)."""
+    brick = int(brick)
+    if brick < 1 or min(int(c) for c in cells) < 1:
+        raise ValueError('brick edge and cells per axis must be >= 1')
+    return tuple((int(c) + brick - 1) // brick for c in cells)
+
+
+def brick_table(res, brick: int, device) -> torch.Tensor:
+    """(nbx, nby, nbz, 2) fp32 table of (+inf, -inf) for a lattice of ``res`` points: the start of ops.brick_minmax."""
+    t = torch.empty(brick_counts([int(r) - 1 for r in res], brick) + (2,), dtype=torch.float32, device=device)
+    t[..., 0], t[..., 1] = float('inf'), float('-inf')
+    return t
+
+
+@_on_device
+def brick_minmax(values: torch.Tensor, res, x_begin: int, x_end: int, brick: int, minmax: torch.Tensor) -> torch.Tensor:
+    """Fold the lattice planes [x_begin, x_end) of a volume of ``res`` points, given as values (x_end - x_begin, Y, Z), into
+    minmax (nbx, nby, nbz, 2) in place (lfgc_brick_minmax_f32); ``brick_table`` makes the empty table."""
+    _require_hip(values, minmax)
+    res = [int(r) for r in res]
+    x_begin, x_end = int(x_begin), int(x_end)
+    if values.dtype != torch.float32 or not values.is_contiguous() or tuple(values.shape) != (x_end - x_begin, res[1], res[2]):
+        raise ValueError('values must be a contiguous fp32 %s tensor, got %s' % ((x_end - x_begin, res[1], res[2]), tuple(values.shape)))
+    want = brick_counts([r - 1 for r in res], brick) + (2,)
+    if minmax.dtype != torch.float32 or not minmax.is_contiguous() or tuple(minmax.shape) != want:
+        raise ValueError('minmax must be a contiguous fp32 %s tensor' % (want,))
+    check(_lib.load().lfgc_brick_minmax_f32(values.data_ptr(), _int3(res), x_begin, x_end, int(brick), minmax.data_ptr(),
+                                            _stream(values)), 'lfgc_brick_minmax_f32')
+    return minmax
+
+
+@_on_device
+def brick_occupancy(minmax: torch.Tensor, tf_table: torch.Tensor, v_min: float, v_max: float, margin: float) -> torch.Tensor:
+    """uint8 table, one entry per brick of minmax (..., 2): 0 where the extinction of tf_table (K, 4) is zero on all of
+    [min - margin, max + margin], else 1 (lfgc_brick_occupancy_f32).  v_min, v_max as ops.ray_composite takes them."""
+    _require_hip(minmax, tf_table)
+    K = int(tf_table.shape[0])
+    if tf_table.dim() != 2 or tf_table.shape[1] != 4 or K < 2 or tf_table.dtype != torch.float32 or not tf_table.is_contiguous():
+        raise ValueError('tf_table must be a contiguous fp32 (K, 4) tensor with K >= 2')
+    if minmax.dtype != torch.float32 or not minmax.is_contiguous() or minmax.dim() < 2 or minmax.shape[-1] != 2:
+        raise ValueError('minmax must be a contiguous fp32 (..., 2) tensor')
+    if not float(v_max) > float(v_min):
+        raise ValueError('v_max must exceed v_min')
+    if not float(margin) >= 0.0:
+        raise ValueError('margin must be >= 0')
+    occ = torch.empty(minmax.shape[:-1], dtype=torch.uint8, device=minmax.device)
+    if occ.numel():
+        tf_scale = (K - 1) / (float(v_max) - float(v_min))
+        check(_lib.load().lfgc_brick_occupancy_f32(minmax.data_ptr(), occ.numel(), tf_table.data_ptr(), K, float(v_min), tf_scale,
+                                                   float(margin), occ.data_ptr(), _stream(minmax)), 'lfgc_brick_occupancy_f32')
+    return occ
+
+
+@_on_device
+def ray_skip(live: Optional[torch.Tensor], origins: torch.Tensor, dirs: torch.Tensor, t_near: torch.Tensor, t_far: torch.Tensor,
+             n_steps: torch.Tensor, k_next: torch.Tensor, dt: float, S: int, box_min, box_max, cells, brick: int,
+             occ: torch.Tensor, skipped: torch.Tensor) -> None:
+    """Advance k_next of the rays of live (None: all rays) by S while none of their next S samples touches an occupied
+    brick, and count the jumps in skipped (R,) int32, both in place: lfgc_ray_skip_f32.  occ (nbx, nby, nbz) uint8 for
+    ``cells`` lattice cells per axis and bricks of ``brick`` cells."""
+    _require_hip(live, origins, dirs, t_near, t_far, n_steps, k_next, occ, skipped)
+    n_steps, k_next, skipped = _ray_i32(n_steps, 'n_steps'), _ray_i32(k_next, 'k_next'), _ray_i32(skipped, 'skipped')
+    if skipped.numel() != n_steps.numel() or k_next.numel() != n_steps.numel():
+        raise ValueError('n_steps, k_next and skipped must have one entry per ray')
+    cells = [int(c) for c in cells]
+    if occ.dtype != torch.uint8 or not occ.is_contiguous() or tuple(occ.shape) != brick_counts(cells, brick):
+        raise ValueError('occ must be a contiguous uint8 %s tensor, got %s' % (brick_counts(cells, brick), tuple(occ.shape)))
+    n = n_steps.numel() if live is None else _ray_i32(live, 'live').numel()
+    if not n:
+        return
+    check(_lib.load().lfgc_ray_skip_f32(_ptr(live), n, _f32c(origins).data_ptr(), _f32c(dirs).data_ptr(), _f32c(t_near).data_ptr(),
+                                        _f32c(t_far).data_ptr(), n_steps.data_ptr(), k_next.data_ptr(), float(dt), int(S),
+                                        _float3(box_min), _float3(box_max), _int3(cells), int(brick), occ.data_ptr(),
+                                        skipped.data_ptr(), _stream(n_steps)), 'lfgc_ray_skip_f32')
+
+
 # ---- isosurface triangle meshes: classification, compaction and connectivity of one x-slab (DESIGN.md 3.3.1) ------------
 
 def _mesh_slab(values: torch.Tensor, n_owner: int):

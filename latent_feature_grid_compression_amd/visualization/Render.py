@@ -14,6 +14,10 @@ cells), ``value_fn`` evaluates them, ops.ray_composite folds them into the per-r
 rays that still have steps left and are not yet opaque.  The one 8-byte read-back of that list's length per block of
 ``block_steps`` steps is the only synchronisation.  There is no CPU form: CPU tensors raise LfgcError.
 
+Empty-space skipping: ``render_from_net(..., skip=BrickRanges.from_net(dataset, net))`` lets every ray jump over the
+blocks of ``block_steps`` steps that lie in bricks of the volume where the transfer function is transparent over the
+brick's value range (ops.ray_skip after the clip and after each compositing); the model is not evaluated there.
+
 First-hit isosurfaces use the same loop with ops.ray_iso_scan in the place of the compositing:
 
     hits = isosurface_from_net(dataset, net, origins, dirs, iso=0.2)                     # IsoHits: hit, t, position, normal, value
@@ -127,11 +131,16 @@ def max_steps_for(box_min, box_max, step: float) -> int:
 
 def _march(chunk_step: Callable, origins: torch.Tensor, dirs: torch.Tensor, step: float, box_min, box_max, block_steps: int,
            opacity_limit: float, max_samples_per_launch: int, t_min: float, t_max: float, stats: Optional[dict],
-           n_buffers: int = 0) -> SimpleNamespace:
+           n_buffers: int = 0, skip: Optional[SimpleNamespace] = None) -> SimpleNamespace:
     """The marching loop of ``render`` and ``isosurface`` (their docstrings describe it) with ``chunk_step(rays, part, pos)``
     in the place of the compositing: it evaluates the ``block_steps`` positions per ray of ``part`` laid out in ``pos`` and
     folds them into ``rays.state`` and ``rays.k_next``.  Returns ``rays``: origins, unit dirs, state (R, 4) and ``n_buffers``
-    more zeroed (R, 4) ``buffers``; with R > 0 also t_near, t_far, n_steps, k_next.  ``stats``: 'live', 'samples', 'blocks'."""
+    more zeroed (R, 4) ``buffers``; with R > 0 also t_near, t_far, n_steps, k_next.  ``stats``: 'live', 'samples', 'blocks'.
+
+    ``skip`` (occ, cells, brick: an occupancy table of ``BrickRanges``): ops.ray_skip moves every ray over its empty
+    blocks once after the clip and, for the rays of a chunk, after each ``chunk_step`` -- before the compaction that
+    follows anyway, so there is no further compaction or read-back.  ``rays.skipped`` counts the jumps per ray and
+    ``stats`` also gets 'skipped_blocks'."""
     S = int(block_steps)
     if S < 32 or S % 32:
         raise ValueError('block_steps must be a positive multiple of 32')
@@ -155,6 +164,14 @@ def _march(chunk_step: Callable, origins: torch.Tensor, dirs: torch.Tensor, step
     if R:
         rays.t_near, rays.t_far, rays.n_steps = ops.ray_clip(origins, dirs, box_min, box_max, step, max_steps, t_min, t_max)
         rays.k_next = torch.zeros(R, dtype=torch.int32, device=dev)
+        jump = None
+        if skip is not None:
+            rays.skipped = torch.zeros(R, dtype=torch.int32, device=dev)
+
+            def jump(part):
+                ops.ray_skip(part, origins, dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S, box_min, box_max,
+                             skip.cells, skip.brick, skip.occ, rays.skipped)
+            jump(None)
         live = ops.ray_compact(None, rays.n_steps, rays.k_next, state, opacity_limit)
         while live.numel():
             live_counts.append(int(live.numel()))
@@ -163,17 +180,27 @@ def _march(chunk_step: Callable, origins: torch.Tensor, dirs: torch.Tensor, step
                 pos = ops.ray_samples(part, origins, dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S)
                 chunk_step(rays, part, pos)
                 n_samples += pos.shape[0]
+                if jump is not None:
+                    jump(part)
             live = ops.ray_compact(live, rays.n_steps, rays.k_next, state, opacity_limit)
     if stats is not None:
         stats.update(live=live_counts, samples=n_samples, blocks=len(live_counts))
+        if skip is not None:
+            stats.update(skipped_blocks=int(rays.skipped.sum()) if R else 0)
     return rays
 
 
 def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: TransferFunction, step: float, box_min, box_max,
            block_steps: int = 32, opacity_limit: float = 0.999, shading: Optional[str] = None,
            max_samples_per_launch: int = 1 << 22, ka: float = 0.3, kd: float = 0.7, t_min: float = 0.0,
-           t_max: float = float('inf'), stats: Optional[dict] = None) -> torch.Tensor:
+           t_max: float = float('inf'), stats: Optional[dict] = None, skip: Optional['BrickRanges'] = None,
+           skip_margin: Optional[float] = None) -> torch.Tensor:
     """(R, 4): premultiplied r, g, b and the opacity 1 - T of every ray (``background`` puts it over a colour).
+
+    ``skip``: ``BrickRanges`` of the field ``value_fn`` evaluates, over the same box.  A ray then jumps over every block of
+    ``block_steps`` steps whose samples all lie in bricks where ``tf`` is transparent on the brick's value range widened by
+    ``skip_margin`` (default: ``skip.default_margin``); ``value_fn`` is not called there.  Where every skipped sample has
+    an extinction of exactly zero the image is the unskipped image bit for bit; ``stats`` also gets 'skipped_blocks'.
 
     ``value_fn(pos (n, 3))`` returns the n values, or (values, gradients (n, 3)) when ``shading='headlight'`` (two-sided
     diffuse with the light at the eye: ka + kd |g.d| / |g|).  ``step`` is the sample distance in normalised units; a ray's
@@ -200,8 +227,12 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
             raise ValueError("shading='headlight' needs value_fn to return (values, gradients)")
         ops.ray_composite(part, values, grad, rays.dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S, table,
                           tf.v_min, tf.v_max, opacity_limit, rays.state, ka, kd)
+    table_of = None
+    if skip is not None:
+        skip.check_box(box_min, box_max)
+        table_of = SimpleNamespace(occ=skip.occupancy(tf, skip_margin, origins.device), cells=skip.cells, brick=skip.brick)
     state = _march(composite, origins, dirs, step, box_min, box_max, block_steps, opacity_limit, max_samples_per_launch, t_min,
-                   t_max, stats).state
+                   t_max, stats, skip=table_of).state
     state[:, 3] = 1.0 - state[:, 3]
     return state
 
@@ -225,10 +256,16 @@ def render_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: torch.T
     """``render`` of the compressed model: the values are the clamped eval-mode output of ``net`` (ops.forward_raw under
     no_grad; ``net.value_and_gradient`` in eval mode when ``shading='headlight'``), the box is +-scales.  ``step`` defaults
     to half a voxel of the volume, 1 / max_dim in normalised units (an IndexDataset is needed for that).  Honours
-    ``net.precision``; the decoded grid and the packed weights come from the eval-mode caches under their usual rule."""
+    ``net.precision``; the decoded grid and the packed weights come from the eval-mode caches under their usual rule.
+
+    ``skip=BrickRanges.from_net(dataset, net)`` (``render``) skips the blocks that lie in bricks ``tf`` is transparent
+    in, gradient evaluations included; ``skip_margin`` defaults to NET_SKIP_MARGIN.  Ranges taken before the model's
+    parameters were last updated raise ValueError."""
     ops._require_hip(origins, dirs)
     scales = _scales_of(dataset_or_scales)
     step = _default_step(dataset_or_scales, step)
+    if kwargs.get('skip') is not None:
+        kwargs['skip'].check_fresh(net)
     shading = bool(kwargs.get('shading'))
     if shading and net.training:
         raise ValueError("shading='headlight' evaluates net.value_and_gradient in eval mode: call net.eval() first")
@@ -276,7 +313,8 @@ def render_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor, dir
                        step: Optional[float] = None, **kwargs) -> torch.Tensor:
     """The same loop over the ground truth: samples are mapped back to index units (``index_positions``) and read with the
     trilinear sampler ops.gt_interp.  Same rays, same transfer function, same step as ``render_from_net`` ->
-    ``image_psnr`` of the two is the image-space quality of the compression.  Unshaded only."""
+    ``image_psnr`` of the two is the image-space quality of the compression.  Unshaded only.
+    ``skip=BrickRanges.from_volume(dataset, volume)`` skips empty space; the image stays the same bit for bit."""
     ops._require_hip(origins, dirs, volume)
     if kwargs.get('shading'):
         raise ValueError('render_from_volume has no gradients: shading is not available')
@@ -289,6 +327,146 @@ def render_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor, dir
     def value_fn(pos):
         return ops.gt_interp(index_positions(dataset, pos), volume, mn, mx, res)
     return render(value_fn, origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
+
+
+# ---- empty-space skipping: value ranges of bricks of the field -------------------------------------------------------------
+
+VOLUME_SKIP_MARGIN = 1e-5     # the three nested fp32 lerps of ops.gt_interp leave their corners' range by < 1e-6 for |v| <= 1
+# Twice the larger brick_range_excess of two cfg-3 models at supersample=1, B=8, rounded up to one digit:
+# 1.6e-3 with random weights, 0.13 after 113 train steps on the smooth volume.  A guard against an unmeasured model, wide
+# enough to leave little to skip; measure brick_range_excess for the model at hand and pass skip_margin to do better.
+NET_SKIP_MARGIN = 0.3
+_SKIP_GUARD = 0.0625          # include/lfgc.h, lfgc_ray_skip_f32: 1/16 cell around a sample's cell coordinate
+
+
+class BrickRanges:
+    """(min, max) of a field over bricks of ``brick``^3 lattice cells, for ``render(..., skip=ranges)``.
+
+    ``minmax`` (nbx, nby, nbz, 2) on the device; ``cells`` lattice cells per axis of the lattice the ranges were taken on
+    (``supersample`` times the volume's), ``brick`` the brick edge in those cells; the box is +-``scales``.  The ranges
+    bound the field at the lattice points.  Between them a trilinear field stays inside the range of its cell's corners
+    up to rounding -- skipping the ground truth is exact --, the network does so only as far as it is smooth at the
+    lattice's scale: ``brick_range_excess`` measures that, and ``default_margin`` widens every range by it."""
+
+    def __init__(self, minmax: torch.Tensor, cells, brick: int, scales, default_margin: float, versions=None):
+        self.minmax, self.cells, self.brick = minmax, tuple(int(c) for c in cells), int(brick)
+        self.scales = [float(s) for s in scales]
+        self.default_margin = float(default_margin)
+        self.versions = versions
+        self._occ = {}
+
+    @classmethod
+    def from_volume(cls, dataset, volume: torch.Tensor, brick: int = 8) -> 'BrickRanges':
+        """Ranges of the ground truth ``render_from_volume`` samples: exact bounds of the trilinear sampler up to rounding."""
+        ops._require_hip(volume)
+        volume = ops._f32c(volume.detach())
+        res = dataset.vol_res_touple
+        if tuple(volume.shape) != tuple(res):
+            raise ValueError('volume %s does not have the shape of the dataset %s' % (tuple(volume.shape), tuple(res)))
+        minmax = ops.brick_minmax(volume, res, 0, res[0], brick, ops.brick_table(res, brick, volume.device))
+        return cls(minmax, [r - 1 for r in res], brick, _scales_of(dataset), VOLUME_SKIP_MARGIN)
+
+    @classmethod
+    def from_net(cls, dataset, net, brick: int = 8, supersample: int = 1, max_slab_voxels: int = 1 << 24,
+                 timings: Optional[dict] = None) -> 'BrickRanges':
+        """Ranges of the compressed model at the points of the volume's lattice: the clamped eval-mode values the renderer
+        composites (OutputToVTK.field_from_net_fused), folded x-slab by x-slab of at most ``max_slab_voxels`` values, so
+        the volume is never resident.  ``supersample=n`` takes them on an n times finer lattice over the same box (brick
+        edge n * ``brick`` fine cells: the same bricks).  Remembers the parameters' versions: ``render_from_net`` refuses
+        ranges of a model that has been updated since.  ``timings`` receives 'forward_ms' and 'reduce_ms' (device time)."""
+        from ..data.IndexDataset import IndexDataset
+        from .OutputToVTK import field_from_net_fused
+        n = int(supersample)
+        if n < 1 or n != supersample:
+            raise ValueError('supersample must be a positive integer')
+        cells = [int(r) - 1 for r in dataset.vol_res_touple]
+        fine = dataset if n == 1 else IndexDataset(tuple(n * c + 1 for c in cells), build_index_table=False)
+        res, edge = fine.vol_res_touple, n * int(brick)
+        dev = next(net.parameters()).device
+        versions = [p._version for p in net.parameters()]
+        minmax = ops.brick_table(res, edge, dev)
+        planes = max(1, int(max_slab_voxels) // (res[1] * res[2]))
+        spans = []
+        for xb in range(0, res[0], planes):
+            xe = min(xb + planes, res[0])
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timings is not None else None
+            if ev:
+                ev[0].record()
+            values = field_from_net_fused(fine, net, xb, xe)
+            if ev:
+                ev[1].record()
+            ops.brick_minmax(values, res, xb, xe, edge, minmax)
+            if ev:
+                ev[2].record()
+                spans.append(ev)
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            timings.update(forward_ms=float(sum(e[0].elapsed_time(e[1]) for e in spans)),
+                           reduce_ms=float(sum(e[1].elapsed_time(e[2]) for e in spans)), slabs=len(spans))
+        return cls(minmax, [n * c for c in cells], edge, _scales_of(dataset), NET_SKIP_MARGIN, versions)
+
+    def occupancy(self, tf: TransferFunction, margin: Optional[float] = None, device=None) -> torch.Tensor:
+        """uint8 (nbx, nby, nbz) on the device: 0 where ``tf`` is transparent over the brick's range widened by ``margin``
+        (default ``default_margin``), else 1 (ops.brick_occupancy).  Cached per (tf, margin)."""
+        margin = self.default_margin if margin is None else float(margin)
+        if device is not None and torch.device(device).type == 'cuda' and self.minmax.device != _with_index(device):
+            raise ValueError('the ranges live on %s, the rays on %s' % (self.minmax.device, device))
+        occ = self._occ.get((tf, margin))
+        if occ is None:
+            occ = self._occ[(tf, margin)] = ops.brick_occupancy(self.minmax, tf.on(self.minmax.device), tf.v_min, tf.v_max, margin)
+        return occ
+
+    def check_box(self, box_min, box_max) -> None:
+        f32 = lambda v: torch.tensor([float(x) for x in v], dtype=torch.float32)          # noqa: E731
+        if not (torch.equal(f32(box_min), -f32(self.scales)) and torch.equal(f32(box_max), f32(self.scales))):
+            raise ValueError('the ranges cover the box +-%s, the render %s .. %s' % (self.scales, list(box_min), list(box_max)))
+
+    def check_fresh(self, net) -> None:
+        if self.versions is not None and [p._version for p in net.parameters()] != self.versions:
+            raise ValueError('the brick ranges are stale: the parameters of the model have been updated since '
+                             'BrickRanges.from_net; a stale table silently drops structure -- build the ranges again')
+
+    def touched_bricks(self, pos: torch.Tensor) -> torch.Tensor:
+        """(n, 8) int64: the flat indices into the (nbx, nby, nbz) tables of the bricks the positions (n, 3) touch -- the
+        torch form of lfgc_ray_skip_f32's lookup, fp32 operation for operation (entries repeat where the guarded cell
+        coordinates fall into one brick)."""
+        pos = pos.to(torch.float32)
+        lo = -torch.tensor(self.scales, dtype=torch.float32, device=pos.device)
+        ext = torch.tensor(self.scales, dtype=torch.float32, device=pos.device) - lo
+        cells = torch.tensor(self.cells, dtype=torch.float32, device=pos.device)
+        q = (pos - lo) / ext * cells
+        top = cells - 1.0
+        zero = torch.zeros_like(top)
+        pair = [torch.div(torch.minimum(torch.maximum(torch.floor(q + g), zero), top).long(), self.brick, rounding_mode='floor')
+                for g in (-_SKIP_GUARD, _SKIP_GUARD)]
+        _, nby, nbz = ops.brick_counts(self.cells, self.brick)
+        return torch.stack([(pair[i][:, 0] * nby + pair[j][:, 1]) * nbz + pair[k][:, 2]
+                            for i in (0, 1) for j in (0, 1) for k in (0, 1)], 1)
+
+
+def _with_index(device) -> torch.device:
+    device = torch.device(device)
+    return torch.device('cuda', torch.cuda.current_device()) if device.type == 'cuda' and device.index is None else device
+
+
+def brick_range_excess(ranges: BrickRanges, value_fn: Callable, n: int = 1 << 20, seed: int = 0) -> float:
+    """The largest amount by which ``value_fn`` at ``n`` uniform random positions of the box leaves the range of EVERY
+    brick the position touches (0 when each value lies in the range of one of them): what the ranges, taken at lattice
+    points, miss of the field between them.  A ``skip_margin`` above it makes skipping exact at these positions."""
+    dev = ranges.minmax.device
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    hi = torch.tensor(ranges.scales, dtype=torch.float32, device=dev)
+    flat = ranges.minmax.view(-1, 2)
+    worst = 0.0
+    for b in range(0, int(n), 1 << 20):
+        m = min(1 << 20, int(n) - b)
+        pos = ((2.0 * torch.rand((m, 3), generator=gen, device=dev) - 1.0) * hi).contiguous()
+        v = value_fn(pos).reshape(-1, 1).to(torch.float32)
+        mm = flat[ranges.touched_bricks(pos)]                                   # (m, 8, 2)
+        out = torch.maximum(mm[..., 0] - v, v - mm[..., 1]).clamp_min(0.0).amin(1)
+        worst = max(worst, float(out.max()))
+    return worst
 
 
 def image_psnr(a: torch.Tensor, b: torch.Tensor, peak: float = 1.0) -> float:

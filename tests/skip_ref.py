@@ -1,0 +1,138 @@
+"""NumPy restatement of the empty-space skipping contract (include/lfgc.h) -- a helper, not a test.
+
+* ``brick_minmax``: the (min, max) of every brick by brute force over the lattice points the brick holds.
+* ``occupancy``: the floor .. ceil row rule in float32, operation for operation.
+* ``skip``: the loop of lfgc_ray_skip_f32 with the sample positions and the cell coordinates in float32, operation for
+  operation (every float32 operation of NumPy is correctly rounded and nothing is contracted, as in the kernels' build),
+  so the device results are expected to be EQUAL.
+
+Written from the contract, not from the kernels.  Also the shared scene of the host and GPU tests."""
+import numpy as np
+
+import render_ref as RR
+
+F = np.float32
+GUARD = F(0.0625)
+
+
+def brick_counts(cells, B):
+    return tuple((int(c) + B - 1) // B for c in cells)
+
+
+def brick_minmax(vol, B):
+    """(nbx, nby, nbz, 2) float32: brick i of an axis holds the points i B .. min((i+1) B, res-1); a NaN -> (-inf, +inf)."""
+    vol = np.asarray(vol, F)
+    nb = brick_counts([s - 1 for s in vol.shape], B)
+    out = np.empty(nb + (2,), F)
+    for i in range(nb[0]):
+        for j in range(nb[1]):
+            for k in range(nb[2]):
+                sub = vol[i * B:min((i + 1) * B, vol.shape[0] - 1) + 1, j * B:min((j + 1) * B, vol.shape[1] - 1) + 1,
+                          k * B:min((k + 1) * B, vol.shape[2] - 1) + 1]
+                out[i, j, k] = (-np.inf, np.inf) if np.isnan(sub).any() else (sub.min(), sub.max())
+    return out
+
+
+def tf_coordinate(v, K, v_min, v_max):
+    """u(v) = fminf(fmaxf((v - v_min) * tf_scale, 0), K - 1) in float32, tf_scale the float ops.ray_composite passes."""
+    tf_scale = F((K - 1) / (float(v_max) - float(v_min)))
+    with np.errstate(all='ignore'):
+        return np.fmin(np.fmax(((np.asarray(v, F) - F(v_min)).astype(F) * tf_scale).astype(F), F(0)), F(K - 1)).astype(F)
+
+
+def occupancy(minmax, table, v_min, v_max, margin):
+    """uint8 per brick: 0 iff the extinction of every row floor(u(min - margin)) .. ceil(u(max + margin)) is zero."""
+    minmax = np.asarray(minmax, F)
+    ext = np.asarray(table, F)[:, 3]
+    K = len(ext)
+    with np.errstate(all='ignore'):
+        lo = (minmax[..., 0] - F(margin)).astype(F)
+        hi = (minmax[..., 1] + F(margin)).astype(F)
+    i0 = np.floor(tf_coordinate(lo, K, v_min, v_max)).astype(np.int64)
+    i1 = np.ceil(tf_coordinate(hi, K, v_min, v_max)).astype(np.int64)
+    occ = np.zeros(minmax.shape[:-1], np.uint8)
+    for at in np.ndindex(*occ.shape):
+        occ[at] = 1 if (ext[i0[at]:i1[at] + 1] != 0).any() else 0
+    return occ
+
+
+def touched(p, box_min, box_max, cells, B):
+    """(n, 8) flat brick indices of the positions p (n, 3): per axis q = (p - box_min) / (box_max - box_min) * (float)cells,
+    c = clamp(floor(q -+ g), 0, cells - 1), bricks c / B."""
+    p = np.asarray(p, F)
+    bmin, bmax = np.asarray(box_min, F), np.asarray(box_max, F)
+    cells = np.asarray(cells, np.int64)
+    ext = (bmax - bmin).astype(F)
+    q = (((p - bmin).astype(F) / ext).astype(F) * cells.astype(F)).astype(F)
+    top = (cells - 1).astype(F)
+    pair = [np.fmin(np.fmax(np.floor((q + g).astype(F)), F(0)), top).astype(np.int64) // B for g in (-GUARD, GUARD)]
+    _, nby, nbz = brick_counts(cells, B)
+    return np.stack([(pair[i][:, 0] * nby + pair[j][:, 1]) * nbz + pair[k][:, 2]
+                     for i in (0, 1) for j in (0, 1) for k in (0, 1)], 1)
+
+
+def skip(rays, origins, dirs, tn, tf, n_steps, k_next, dt, S, box_min, box_max, cells, B, occ):
+    """(k_next, skipped) after the skip loop over the listed rays; rays outside the list keep their k_next."""
+    o, d = np.asarray(origins, F), np.asarray(dirs, F)
+    k_next = np.array(k_next, np.int32)
+    skipped = np.zeros(len(k_next), np.int32)
+    flat = np.asarray(occ).reshape(-1)
+    for r in rays:
+        n = int(n_steps[r])
+        while k_next[r] < n:
+            k = np.arange(k_next[r], min(k_next[r] + S, n), dtype=np.int64)
+            a, b = RR.segments(tn[r], tf[r], k, dt)
+            tm = (F(0.5) * (a + b).astype(F)).astype(F)
+            p = (o[r][None, :] + (tm[:, None] * d[r][None, :]).astype(F)).astype(F)
+            if flat[touched(p, box_min, box_max, cells, B)].any():
+                break
+            k_next[r] += S
+            skipped[r] += 1
+    return k_next, skipped
+
+
+def march(origins, dirs, tn, tf, n_steps, dt, S, box_min, box_max, cells, B, occ):
+    """(blocks, skipped, evaluated) of a whole march without early termination: blocks = sum ceil(n_steps / S)."""
+    R = len(n_steps)
+    k = np.zeros(R, np.int32)
+    rays = np.nonzero(n_steps > 0)[0]
+    skipped = evaluated = 0
+    while len(rays):
+        k, s = skip(rays, origins, dirs, tn, tf, n_steps, k, dt, S, box_min, box_max, cells, B, occ)
+        skipped += int(s.sum())
+        rays = rays[k[rays] < n_steps[rays]]
+        evaluated += len(rays)
+        k[rays] += S
+        rays = rays[k[rays] < n_steps[rays]]
+    return int(((n_steps + S - 1) // S).sum()), skipped, evaluated
+
+
+# ---- the scene of the ground-truth test -------------------------------------------------------------------------------------
+
+SCENE_RES = (40, 36, 33)
+SCENE_BRICK = 4
+SCENE_EXTINCTION = (0.0, 0.0, 0.0, 4.0, 8.0)
+SCENE_STEP = 1.0 / 39.0
+
+
+def scene_scales():
+    m = max(SCENE_RES) - 1
+    return [F(r - 1) / F(m) for r in SCENE_RES]                # IndexDataset.scales = max_idx / max_dim in float32
+
+
+def scene_volume():
+    """2 exp(-r^2 / (2 0.25^2)) - 1 about (0.1, -0.05, 0) at the lattice points of the box +-scales (float32)."""
+    ax = [float(s) * (2.0 * np.arange(r) / (r - 1) - 1.0) for s, r in zip(scene_scales(), SCENE_RES)]
+    x, y, z = np.meshgrid(*ax, indexing='ij')
+    r2 = (x - 0.1) ** 2 + (y + 0.05) ** 2 + z ** 2
+    return (2.0 * np.exp(-r2 / (2.0 * 0.25 ** 2)) - 1.0).astype(F)
+
+
+def scene_table():
+    c = np.linspace(0.2, 1.0, 5)
+    return np.stack([c, 0.5 * c, 1.0 - 0.5 * c, np.array(SCENE_EXTINCTION)], 1).astype(F)
+
+
+def scene_rays(device=None):
+    from latent_feature_grid_compression_amd.visualization.Render import pinhole_rays
+    return pinhole_rays((1.9, 1.3, 1.6), (0.1, -0.05, 0.0), (0.0, 0.0, 1.0), 40.0, 24, 20, device=device)

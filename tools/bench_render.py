@@ -6,6 +6,12 @@ a 1024^2 pinhole view of the 256^3 volume's box at the default step (half a voxe
 With --iso VALUE a third mode follows: a first-hit isosurface frame (Render.isosurface, normals included) of the same
 model and rays at that isovalue, timed the same way next to the two DVR frames, with the number of bracketed rays.
 
+With --skip the unshaded frame is then rendered with and without empty-space skipping (Render.BrickRanges), alternating
+in the same run: time to build the ranges (forward and reduction), occupied share of the bricks, samples, skipped
+blocks, live rays per block, ms per frame of both, GPU time of the skip kernel, the difference of the two images, and
+Render.brick_range_excess of this model and of cfg 3 after a short training run on bench.py's smooth volume -- the two
+measurements Render.NET_SKIP_MARGIN is derived from (twice the larger, rounded up to one significant digit).
+
 Prints, per mode: ms per frame (wall clock around whole frames, synchronised), samples evaluated and samples/s, the
 live-ray count per block of 32 steps, the share of GPU time in the ray kernels against the network evaluation (HIP events
 around every launch of one extra, instrumented frame), and the rate of ops.forward_raw alone on the same positions in the
@@ -29,6 +35,15 @@ def main() -> None:
     ap.add_argument('--precision', default='f16x2')
     ap.add_argument('--opacity-limit', type=float, default=0.999)
     ap.add_argument('--iso', type=float, default=None, help='also time an isosurface frame at this isovalue')
+    ap.add_argument('--modes', default='', help='comma-separated subset of unshaded,headlight,isosurface to time (default: all)')
+    ap.add_argument('--zero-below', type=float, default=0.5,
+                    help='share of the value range, from its lower end, over which the table has no extinction (the scene: 0.5)')
+    ap.add_argument('--skip', action='store_true', help='also compare the unshaded frame with and without empty-space skipping')
+    ap.add_argument('--brick', type=int, default=8, help='--skip: brick edge in cells')
+    ap.add_argument('--skip-margin', default=None,
+                    help="--skip: margin of the brick ranges; default Render.NET_SKIP_MARGIN, 'auto' = the margin derived in this run")
+    ap.add_argument('--skip-trained-steps', type=int, default=113,
+                    help='--skip: train steps of the second model brick_range_excess is measured on (0: leave it out)')
     args = ap.parse_args()
 
     import numpy as np
@@ -47,7 +62,8 @@ def main() -> None:
     box = ([-s for s in scales], scales)
     # grey-to-warm ramp, extinction 0 below the middle of the value range and rising to 12 per unit length above it
     v = np.linspace(0.0, 1.0, 9)
-    table = np.stack([0.3 + 0.7 * v, 0.3 + 0.4 * v, 0.4 - 0.3 * v, 12.0 * np.clip(2.0 * v - 1.0, 0.0, 1.0)], 1)
+    ramp = 2.0 * v - 1.0 if args.zero_below == 0.5 else (v - args.zero_below) / (1.0 - args.zero_below)
+    table = np.stack([0.3 + 0.7 * v, 0.3 + 0.4 * v, 0.4 - 0.3 * v, 12.0 * np.clip(ramp, 0.0, 1.0)], 1)
     tf = Render.TransferFunction(table)
     o, d = Render.pinhole_rays((2.6, 1.7, 1.4), (0.0, 0.0, 0.0), (0.0, 0.0, 1.0), 35.0, args.size, args.size, device=dev)
     with torch.no_grad():
@@ -70,8 +86,11 @@ def main() -> None:
         return Render.render(fn, o, d, tf, step, box[0], box[1], opacity_limit=args.opacity_limit,
                              shading=None if mode == 'unshaded' else 'headlight', **kw)
 
-    summary = {'size': args.size, 'step': step, 'precision': args.precision, 'opacity_limit': args.opacity_limit}
+    summary = {'size': args.size, 'step': step, 'precision': args.precision, 'opacity_limit': args.opacity_limit,
+               'zero_below': args.zero_below}
     modes = [('unshaded', plain), ('headlight', shaded)] + ([('isosurface', plain_or_shaded)] if args.iso is not None else [])
+    if args.modes:
+        modes = [x for x in modes if x[0] in args.modes.split(',')]
     ray_ops = ('ray_clip', 'ray_samples', 'ray_composite', 'ray_compact', 'ray_iso_scan', 'ray_iso_refine', 'ray_iso_finish')
     for mode, fn in modes:
         stats = {}
@@ -155,7 +174,105 @@ def main() -> None:
             summary[mode].update(iso=args.iso, bracketed=stats['bracketed'], refine_samples=stats['refine_samples'])
         del kept, img
         torch.cuda.empty_cache()
+    if args.skip:
+        summary['skip'] = skip_report(args, m, ds, tf, o, d, step, box, plain)
     print(json.dumps(summary), flush=True)
+
+
+def one_digit_up(x: float) -> float:
+    """x rounded up to one significant digit (0 stays 0)."""
+    import math
+    if not x > 0.0:
+        return 0.0
+    e = math.floor(math.log10(x))
+    return math.ceil(x / 10.0 ** e - 1e-9) * 10.0 ** e
+
+
+def skip_report(args, m, ds, tf, o, d, step, box, plain) -> dict:
+    """--skip: the unshaded frame with and without empty-space skipping (Render.BrickRanges), alternating in one run."""
+    import statistics
+    import torch
+    import bench
+    from latent_feature_grid_compression_amd import ops
+    from latent_feature_grid_compression_amd.visualization import Render
+    dev = o.device
+    Render.BrickRanges.from_net(ds, m, brick=args.brick)                                   # warm-up
+    build = {}
+    t0 = time.perf_counter()
+    ranges = Render.BrickRanges.from_net(ds, m, brick=args.brick, timings=build)
+    build['wall_ms'] = (time.perf_counter() - t0) * 1e3
+    excess = Render.brick_range_excess(ranges, plain)
+    # the second model of the margin's derivation: cfg 3 after a short training run on the smooth volume
+    trained = None
+    if args.skip_trained_steps > 0:
+        ctx = bench.cfg3_train_setup(dev, args.precision)
+        for _ in range(args.skip_trained_steps):
+            ctx['step']()
+        tm = ctx['model'].eval()
+        with torch.no_grad():
+            tdesc, tgrid, tpacked = tm._descriptor(), tm._decoded_channel_last(), tm._packed()
+
+        def trained_fn(pos):
+            with torch.no_grad():
+                return ops.forward_raw(tdesc, tgrid, tpacked, pos=pos, clamp=True, precision=args.precision)[0]
+        t_ranges = Render.BrickRanges.from_net(ctx['ds'], tm, brick=args.brick)
+        trained = {'steps': args.skip_trained_steps, 'excess': Render.brick_range_excess(t_ranges, trained_fn),
+                   'value_range': [float(t_ranges.minmax[..., 0].min()), float(t_ranges.minmax[..., 1].max())]}
+        del ctx, tm, tdesc, tgrid, tpacked, t_ranges
+        torch.cuda.empty_cache()
+    derived = one_digit_up(2.0 * max(excess, trained['excess'] if trained else 0.0))
+    margin = ranges.default_margin if args.skip_margin is None else (derived if args.skip_margin == 'auto' else float(args.skip_margin))
+    occ = ranges.occupancy(tf, margin)
+
+    def frame(skip, stats=None):
+        return Render.render(plain, o, d, tf, step, box[0], box[1], opacity_limit=args.opacity_limit, stats=stats,
+                             skip=ranges if skip else None, skip_margin=margin if skip else None)
+    st = {False: {}, True: {}}
+    img = {k: frame(k, st[k]) for k in (False, True)}                                      # warm-up, stats and the two images
+    torch.cuda.synchronize()
+    ms = {False: [], True: []}
+    for _ in range(args.frames):                                                           # alternating, same process
+        for k in (False, True):
+            t0 = time.perf_counter()
+            frame(k)
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    spans, saved = [], ops.ray_skip
+
+    def timed_skip(*a, **k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        saved(*a, **k)
+        e1.record()
+        spans.append((e0, e1))
+    try:
+        ops.ray_skip = timed_skip
+        frame(True)
+    finally:
+        ops.ray_skip = saved
+    torch.cuda.synchronize()
+    skip_ms = float(sum(a.elapsed_time(b) for a, b in spans))
+    diff = float((img[True] - img[False]).abs().max())
+    out = {'brick': args.brick, 'margin': margin, 'derived_margin': derived, 'build_ms': build, 'excess_random': excess,
+           'trained': trained, 'bricks': int(occ.numel()), 'occupied_share': float(occ.float().mean()),
+           'samples': [st[False]['samples'], st[True]['samples']], 'skipped_blocks': st[True]['skipped_blocks'],
+           'blocks': [st[False]['blocks'], st[True]['blocks']], 'live': st[True]['live'],
+           'frame_ms': [ms[False], ms[True]], 'skip_kernel_ms': skip_ms, 'skip_launches': len(spans), 'max_abs': diff,
+           'psnr_dB': Render.image_psnr(img[True], img[False])}
+    fmt = lambda v: 'min %.1f median %.1f max %.1f' % (min(v), statistics.median(v), max(v))      # noqa: E731
+    print('[skip] ranges of %s bricks of %d^3 cells: %.2f ms forward + %.2f ms reduction on the GPU in %d slabs (%.1f ms wall)'
+          % (tuple(occ.shape), args.brick, build['forward_ms'], build['reduce_ms'], build['slabs'], build['wall_ms']))
+    print('[skip] brick_range_excess: %.3e (this model)%s -> derived margin %g; margin used %g'
+          % (excess, '' if trained is None else ', %.3e (cfg 3 after %d train steps on the smooth volume, values in [%.3f, %.3f])'
+             % (trained['excess'], trained['steps'], *trained['value_range']), derived, margin))
+    print('[skip] %.1f %% of the bricks occupied; samples %d -> %d (%.1f %%), %d blocks of 32 steps skipped'
+          % (100.0 * out['occupied_share'], out['samples'][0], out['samples'][1], 100.0 * out['samples'][1] / max(out['samples'][0], 1),
+             out['skipped_blocks']))
+    print('[skip] live rays per block with skipping: %s' % ' '.join(str(x) for x in out['live']))
+    print('[skip] ms per frame over %d alternating frames: without %s; with %s' % (args.frames, fmt(ms[False]), fmt(ms[True])))
+    print('[skip] GPU time of the skip kernel: %.2f ms in %d launches; the two frames differ by max abs %.3e, PSNR %.1f dB'
+          % (skip_ms, len(spans), diff, out['psnr_dB']), flush=True)
+    return out
 
 
 if __name__ == '__main__':
