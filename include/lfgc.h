@@ -469,7 +469,7 @@ int lfgc_det_quantum_exp(uint32_t max_bits, int64_t n_samples);
 /* Read-only launch-plan queries: which kernel build and launch shape lfgc_forward_f32 / lfgc_backward_f32 pick for these
  * arguments on the current device.  The launchers consume the very structs these entries fill (one selection function
  * each, csrc/lfgc_capi_forward.hip and csrc/lfgc_backward.hip), so a query cannot drift from a launch.  Nothing is
- * enqueued and no device pointer is read; the diagnostics environment knobs (LFGC_NO_ZRUN, LFGC_FWD_WAVES, LFGC_FWD_X2,
+ * enqueued and no device pointer is read; the diagnostics environment knobs (LFGC_NO_ZRUN, LFGC_FWD_WAVES,
  * LFGC_WGRAD_NO_SPLIT) are honoured exactly as by the launch.  For tests and tools that must know which compiled
  * instantiation a shape reaches. */
 typedef struct lfgc_forward_launch {
@@ -479,7 +479,7 @@ typedef struct lfgc_forward_launch {
     int32_t zrun;            /* lattice mode, f16 builds: z-run tiles + column sampler                         */
     int32_t nzc;             /* z cells a z-run tile's column holds (2 when zrun == 0)                          */
     int32_t tiles_per_row;   /* z-run: ceil(res2 / 32), else 1                                                   */
-    int32_t x2;              /* z-run: the two-tiles-per-wave kernel (LFGC_FWD_X2)                              */
+    int32_t x2;              /* reserved: always 0                                                               */
     int32_t lds_bytes;       /* dynamic LDS of the launch                                                        */
     int64_t nbatches;        /* passes of one workgroup-sized batch of tiles                                     */
     int64_t ntiles;          /* z-run: tiles of the slab, else 0                                                 */

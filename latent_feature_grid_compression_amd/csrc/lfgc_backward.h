@@ -239,10 +239,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
     const unsigned long long bst_t0 = bst_last;
 #endif
 
-#ifndef LFGC_BWD_DMA_BURST
-#define LFGC_BWD_DMA_BURST 0         // diagnostics: 1 = every wave issues its pieces back to back after the barrier (round 2)
-#endif
-    constexpr int NPW = (H16 && !LFGC_BWD_DMA_BURST) ? ((TBMAX / 4 + 63) / 64 + WAVES - 1) / WAVES : 0;   // pieces per wave and image
+    constexpr int NPW = H16 ? ((TBMAX / 4 + 63) / 64 + WAVES - 1) / WAVES : 0;   // pieces per wave and image
     LfgcDmaPlan dma = {a.packed, s_ring, tblk1 / 4, __builtin_amdgcn_readfirstlane(wave), (unsigned)lane * 16u, 0ull, 0u};
     const long long N = a.n;
     for (long long batch = blockIdx.x; batch < a.nbatches; batch += gridDim.x) {
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_bwd_data_kernel(const Lfgc
             LFGC_BSTAMP(2);                                   // wait for stores / DMA + barrier
             const float* img = s_ring + (step & 1) * SLOT;
             const int ln = (l == 0) ? L - 1 : l - 1;
-            if (H16 && !LFGC_BWD_DMA_BURST) {
+            if (H16) {
                 // streamed piece by piece under this step's MFMAs (always a real block: after the last batch the slot is
                 // filled once more for nobody, which keeps the MFMA loops free of branches)
                 dma.src = image_src(ln);

@@ -125,10 +125,6 @@ int fwd_select(const lfgc_mlp_desc* desc, const lfgc_positions* positions, int D
             l.lds_bytes = (int)with_columns;
             l.waves = fwd_env_waves(l.resident, (!l.resident && (ntiles + 7) / 8 >= num_cus()) ? 8 : 4);
             l.nbatches = (ntiles + l.waves - 1) / l.waves;
-            // experimental (LFGC_FWD_X2=1): two tiles per wave, one wave per SIMD (lfgc_forward16x2.h; 32 channels x 128 wide)
-            if (!l.resident && p.CH == 32 && p.MT == 4 && (ntiles + 7) / 8 >= num_cus() && getenv("LFGC_FWD_X2")) {
-                l.x2 = 1; l.waves = 4; l.nbatches = (ntiles + 7) / 8;
-            }
         }
     }
     fwd_set_grid(&l);
@@ -145,7 +141,7 @@ int fwd_select(const lfgc_mlp_desc* desc, const lfgc_positions* positions, int D
 
 void fwd_apply_launch(const lfgc_forward_launch& l, LfgcFwdArgs* a) {
     a->resident = l.resident; a->waves = l.waves; a->coord_table = l.coord_table; a->nbatches = l.nbatches;
-    a->zrun = l.zrun; a->nzc = l.nzc; a->tiles_per_row = l.tiles_per_row; a->ntiles = l.ntiles; a->x2 = l.x2;
+    a->zrun = l.zrun; a->nzc = l.nzc; a->tiles_per_row = l.tiles_per_row; a->ntiles = l.ntiles;
 }
 }  // namespace
 

@@ -340,9 +340,6 @@ __device__ __forceinline__ void lfgc_dma_piece(const LfgcDmaPlan& d, int pi) {
                                      (__attribute__((address_space(3))) void*)(d.dst + 4 * base), 16, 0, 0);
 }
 
-#ifndef LFGC_DMA_POLICY
-#define LFGC_DMA_POLICY ""
-#endif
 // Piece PI (a compile-time index) of a block of NVEC vectors (compile-time too).  Where every wave's piece PI lies wholly
 // inside the block -- all but the last one or two -- its addresses are the wave's block bases (lfgc_dma_plan_block) plus
 // constants: 3 scalar instructions and the load, against 10 for the clamped form.  A lone instruction stream gets one
@@ -352,7 +349,7 @@ __device__ __forceinline__ void lfgc_dma_piece_ct(const LfgcDmaPlan& d) {
     if constexpr ((NWAVES - 1 + PI * NWAVES) * 64 + 64 <= NVEC) {
         const unsigned long long sp = d.src_w + (unsigned long long)PI * NWAVES * 1024ull;
         const unsigned lds_addr = d.dst_w + (unsigned)PI * NWAVES * 1024u;
-        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" LFGC_DMA_POLICY :: "s"(lds_addr), "v"(d.lane16), "s"(sp) : "memory");
+        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(lds_addr), "v"(d.lane16), "s"(sp) : "memory");
     } else {
         lfgc_dma_piece<NWAVES>(d, PI);
     }

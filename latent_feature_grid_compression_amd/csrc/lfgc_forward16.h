@@ -263,68 +263,32 @@ __device__ __forceinline__ void lfgc_tile_gaps(const float* __restrict__ arow, c
 
 // Mate priority (8-wave streamed kernels only: waves w and w + 4 share a SIMD).  Both at priority 0 the older mate
 // (waves 0-3) wins the issue arbitration for a whole layer, reaches the ring barrier first and waits there while the
-// younger one finishes alone; a static priority for the younger half only swaps the two roles.  A pattern hands the
-// lead over inside the layer instead: lfgc_mate_prio is the priority of a wave half during output tile m of a layer,
-// 0 everywhere else (input phase, tail, barriers, waits).  Issue order only: no result bit depends on it.
-//   THREEQ     waves 4-7 lead tiles [0, 3 MT/4); waves 0-3 win the rest by age.  The default: priority pulls harder than
-//              age, and at MT = 4 both mates then reach the hidden layers' barriers within 0.4 k cycles of each other
-//              (profiles/r9; MT = 2 gives HALF, MT = 1 nothing -- neither was measured)
-//   HALF       waves 4-7 lead tiles [0, MT/2)
-//   HALF_BOTH  as HALF, and waves 0-3 at priority 1 during tiles [MT/2, MT)
-//   ALT        waves 4-7 lead the even tiles
-// One -D switch each for same-tree A/Bs (tools/ab_forward.py): LFGC_MATE_PRIO_NONE / _THREEQ / _HALF / _HALF_BOTH / _ALT.
-#define LFGC_MATE_NONE 0
-#define LFGC_MATE_HALF 1
-#define LFGC_MATE_HALF_BOTH 2
-#define LFGC_MATE_ALT 3
-#define LFGC_MATE_THREEQ 4
-#if defined(LFGC_MATE_PRIO_NONE)
-#define LFGC_MATE_PRIO LFGC_MATE_NONE
-#elif defined(LFGC_MATE_PRIO_HALF)
-#define LFGC_MATE_PRIO LFGC_MATE_HALF
-#elif defined(LFGC_MATE_PRIO_HALF_BOTH)
-#define LFGC_MATE_PRIO LFGC_MATE_HALF_BOTH
-#elif defined(LFGC_MATE_PRIO_ALT)
-#define LFGC_MATE_PRIO LFGC_MATE_ALT
-#else
-#define LFGC_MATE_PRIO LFGC_MATE_THREEQ
-#endif
-// `first_layer`: layer 0 (MT tiles of KS16_0 * 3 MFMAs) could take a row of its own; handing over after 2, 3 or 4 of its 4
-// tiles was measured and 3, the hidden layers' row, was the fastest (profiles/r9/ab_handover_position.log).
-constexpr int lfgc_mate_prio(bool first_layer, int m, int MT, bool younger) {
-    (void)first_layer;
-    if (m < 0 || m >= MT) return 0;
-    switch (LFGC_MATE_PRIO) {
-        case LFGC_MATE_HALF: return younger && m < MT / 2;
-        case LFGC_MATE_THREEQ: return younger && m < 3 * MT / 4;
-        case LFGC_MATE_HALF_BOTH: return younger == (m < MT / 2);
-        case LFGC_MATE_ALT: return younger && m % 2 == 0;
-        default: return 0;
-    }
-}
-// s_setprio PRIO for one half of the workgroup's waves.  s_setprio takes an immediate and the half is a run-time value,
-// so it sits behind one scalar compare-and-skip on `wave_s` (an SGPR: wave-uniform by construction; s_setprio ignores
-// EXEC).  The skip stays inside the asm statement: written as an `if`, it cuts the layer's instruction stream into
-// basic blocks, and the register allocator then spills into the gaps (3 to 67 VGPRs with the three patterns).
-template <int PRIO, bool YOUNGER, int WAVES>
+// younger one finishes alone; a static priority for the younger half only swaps the two roles.  The lead is handed
+// over inside the layer instead: waves 4-7 run output tiles [0, 3 MT/4) of every layer at priority 1 and waves 0-3
+// win the rest by age; priority 0 everywhere else (input phase, tail, barriers, waits).  Priority pulls harder than
+// age, and at MT = 4 both mates then reach the hidden layers' barriers within 0.4 k cycles of each other (profiles/r9;
+// MT = 2 leads tile 0 only, MT = 1 nothing -- neither was measured).  Issue order only: no result bit depends on it.
+// Tried and slower: hand-over at mid-layer, mid-layer with priority 1 for waves 0-3 afterwards, even tiles only, and a
+// hand-over position of its own for layer 0 (profiles/r9/ab_mate_priority.log, ab_handover_position.log).
+// -DLFGC_MATE_PRIO_NONE: no priority change at all, the baseline of same-tree A/Bs (tools/ab_forward.py).
+constexpr int lfgc_mate_prio(int m, int MT) { return m >= 0 && m < 3 * MT / 4; }
+// s_setprio PRIO for the younger half of the workgroup's waves.  s_setprio takes an immediate and the half is a run-time
+// value, so it sits behind one scalar compare-and-skip on `wave_s` (an SGPR: wave-uniform by construction; s_setprio
+// ignores EXEC).  The skip stays inside the asm statement: written as an `if`, it cuts the layer's instruction stream
+// into basic blocks, and the register allocator then spills into the gaps (3 to 67 VGPRs with the patterns tried).
+template <int PRIO, int WAVES>
 __device__ __forceinline__ void lfgc_setprio_half(int wave_s) {
-    if constexpr (YOUNGER)
-        asm volatile("s_cmp_lt_i32 %0, %1\n\ts_cbranch_scc1 .Llfgc_mate%=\n\ts_setprio %2\n.Llfgc_mate%=:"
-                     :: "s"(wave_s), "n"(WAVES / 2), "n"(PRIO) : "scc");
-    else
-        asm volatile("s_cmp_ge_i32 %0, %1\n\ts_cbranch_scc1 .Llfgc_mate%=\n\ts_setprio %2\n.Llfgc_mate%=:"
-                     :: "s"(wave_s), "n"(WAVES / 2), "n"(PRIO) : "scc");
+    asm volatile("s_cmp_lt_i32 %0, %1\n\ts_cbranch_scc1 .Llfgc_mate%=\n\ts_setprio %2\n.Llfgc_mate%=:"
+                 :: "s"(wave_s), "n"(WAVES / 2), "n"(PRIO) : "scc");
 }
-// The change point at the top of output tile M (M = MT: the end of the layer): at most one s_setprio per wave half,
-// between two tiles' gaps, never inside them.
-template <bool ACTIVE, bool FIRST_LAYER, int M, int MT, int WAVES>
+// The change point at the top of output tile M (M = MT: the end of the layer): at most one s_setprio, between two
+// tiles' gaps, never inside them.
+template <bool ACTIVE, int M, int MT, int WAVES>
 __device__ __forceinline__ void lfgc_mate_prio_at(int wave_s) {
-    if constexpr (ACTIVE && LFGC_MATE_PRIO != LFGC_MATE_NONE) {
-        constexpr int y0 = lfgc_mate_prio(FIRST_LAYER, M - 1, MT, true), y1 = lfgc_mate_prio(FIRST_LAYER, M, MT, true);
-        constexpr int o0 = lfgc_mate_prio(FIRST_LAYER, M - 1, MT, false), o1 = lfgc_mate_prio(FIRST_LAYER, M, MT, false);
-        if constexpr (y0 != y1) lfgc_setprio_half<y1, true, WAVES>(wave_s);
-        if constexpr (o0 != o1) lfgc_setprio_half<o1, false, WAVES>(wave_s);
-    }
+#ifndef LFGC_MATE_PRIO_NONE
+    if constexpr (ACTIVE && lfgc_mate_prio(M - 1, MT) != lfgc_mate_prio(M, MT))
+        lfgc_setprio_half<lfgc_mate_prio(M, MT), WAVES>(wave_s);
+#endif
 }
 
 // What a layer leaves for the next one to finish: the accumulator of its last output tile and that tile's constants.
@@ -366,7 +330,7 @@ __device__ __forceinline__ void lfgc_layer_fwd16(const float* __restrict__ s_blk
 
     constexpr bool MATES = WAVES == 8 && NP > 0;             // 8-wave streamed kernel: two mates per SIMD (lfgc_mate_prio)
     f32x16 accs[2];
-    lfgc_mate_prio_at<MATES, !HAS_CARRY, 0, MT, WAVES>(dma.wave);
+    lfgc_mate_prio_at<MATES, 0, MT, WAVES>(dma.wave);
     {   // tile 0: shadows the previous layer's last tile, which produces this layer's last two input fragments
         LfgcEpilogue<STASH, false, SPLIT> ep;
         u32x4 ehi[2], elo[2];
@@ -389,7 +353,7 @@ __device__ __forceinline__ void lfgc_layer_fwd16(const float* __restrict__ s_blk
         ep.inv_scale = inv_scale; ep.bias = bias_l + 32 * (m - 1); ep.wf = wf_l + 32 * (m - 1);
         ep.stash = STASH ? stash_l + (m - 1) * (16 * 64) : nullptr;
         u32x4 ehi[2], elo[2];
-        lfgc_mate_prio_at<MATES, !HAS_CARRY, m, MT, WAVES>(dma.wave);
+        lfgc_mate_prio_at<MATES, m, MT, WAVES>(dma.wave);
         lfgc_tile_gaps<KS16, SPLIT, G, false, NP, NVEC, m * G, DSPAN, WAVES>(s_row + 32 * m * S, m + 1 < MT ? s_row + 32 * (m + 1) * S : nullptr,
                                               INhi, INlo, accs[m & 1], w, ep, accs[(m - 1) & 1], ehi, elo, ydot, tmax, dma);
         if (!LAST) {
@@ -397,7 +361,7 @@ __device__ __forceinline__ void lfgc_layer_fwd16(const float* __restrict__ s_blk
             OUTlo[2 * (m - 1)] = elo[0]; OUTlo[2 * (m - 1) + 1] = elo[1];
         }
     });
-    lfgc_mate_prio_at<MATES, !HAS_CARRY, MT, MT, WAVES>(dma.wave);       // back to 0 for the tail / the next barrier
+    lfgc_mate_prio_at<MATES, MT, MT, WAVES>(dma.wave);       // back to 0 for the tail / the next barrier
     // the last tile: finished here for the head, otherwise owed to the next layer
     if (LAST) {
         LfgcEpilogue<STASH, true, SPLIT> ep;
@@ -422,20 +386,20 @@ __device__ __forceinline__ void lfgc_layer_fwd16(const float* __restrict__ s_blk
 #define LFGC_STAMP(k) do { } while (0)
 #endif
 
-// Dynamic LDS of the f16 kernels (lfgc_fwd16_kernel and lfgc_fwd16x2_kernel) in floats, in the order they carve it:
+// Dynamic LDS of the f16 kernels (lfgc_fwd16_kernel) in floats, in the order they carve it:
 //   s_final [Wf (HP) | bf (4)] | s_scale 16 | s_bias LFGC_MAX_LAYERS x HP | s_w: every f16-split block (resident) or a ring
 //   of 2 slots of the larger block (streamed) | s_coord: the coordinate tables, `table_floats` = res0 + res1 + res2
-//   | z-run launches (nzc > 0) only: the tables rounded up to 4 floats, then 8 columns per workgroup -- 8 waves x 1 tile or
-//   4 waves x 2 tiles -- of nzc rows of col_row() floats (LfgcColumnSampler).
+//   | z-run launches (nzc > 0) only: the tables rounded up to 4 floats, then 8 columns per workgroup -- one per wave; 4-wave
+//   workgroups use the first four -- of nzc rows of col_row() floats (LfgcColumnSampler).
 // The host's launch selection sizes the allocation with these functions; the kernels static_assert their carve against them.
-constexpr int LFGC_ZRUN_COLUMNS = 8;     // columns a z-run workgroup holds: one per wave (<= 8 waves), or two for each of 4 waves
+constexpr int LFGC_ZRUN_COLUMNS = 8;     // columns a z-run workgroup holds: one per wave (<= 8 waves)
 constexpr int lfgc_fwd16_lds_head(const LfgcPlan& p) { return p.HP + 4 + 16 + LFGC_MAX_LAYERS * p.HP; }
 constexpr int lfgc_fwd16_lds_ring_slot(const LfgcPlan& p) { return p.blkh0 > p.blkh1 ? p.blkh0 : p.blkh1; }
 constexpr long long lfgc_fwd16_lds_floats(const LfgcPlan& p, bool resident, long long table_floats, int nzc) {
     const long long weights = lfgc_fwd16_lds_head(p) + (resident ? p.hblk_floats() : 2 * lfgc_fwd16_lds_ring_slot(p));
     return nzc > 0 ? weights + ((table_floats + 3) & ~3LL) + (long long)LFGC_ZRUN_COLUMNS * nzc * p.col_row() : weights + table_floats;
 }
-// The blob offsets both f16 kernels spell out at run time (off_final, off_h, the reads at off_h + 16 / + 32 / + 32 +
+// The blob offsets the f16 kernels spell out at run time (off_final, off_h, the reads at off_h + 16 / + 32 / + 32 +
 // LFGC_MAX_LAYERS * HP, hblk) and their stash tile stride, repeated here for a given L and compared with the plan's.
 template <int CH, int MT, int NF>
 constexpr bool lfgc_fwd16_offsets_are_the_plans(int L) {
@@ -519,13 +483,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
     }
     __syncthreads();
     unsigned step = 0;
-#if (LFGC_ABLATE & 8) && defined(LFGC_ANTIPHASE)
-    // diagnostics: with the barriers gone, start the second wave of every SIMD LFGC_ANTIPHASE x 8k cycles late
-    if (wave >= WAVES / 2) {
-#pragma unroll 1
-        for (int i = 0; i < LFGC_ANTIPHASE; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
 #ifdef LFGC_STAMPS
     unsigned long long st_acc[16] = {0};
     unsigned long long st_last = __builtin_amdgcn_s_memtime();

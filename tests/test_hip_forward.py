@@ -504,30 +504,22 @@ def test_lattice_zrun_column_sampler(dev, C, G, H, L, res, slab):
     assert plans['gather'].zrun == 0 and plans['gather'].nzc == 2
 
 
-def test_two_tiles_per_wave_kernel_is_the_same_function(dev):
-    """`LFGC_FWD_X2=1` (csrc/lfgc_forward16x2.h: two 32-sample tiles per wave, one wave per SIMD -- the variant VERDICT r2
-    asked for, kept opt-in because it measured 7 % slower) computes every sample with the same instruction sequence as the
-    default z-run kernel: bit-identical volumes at the headline net on a lattice big enough for the host to select it."""
+def test_default_zrun_kernel_at_the_headline_net_matches_the_oracle(dev):
+    """The 8-wave streamed z-run kernel at the headline net (32 channels, 128 wide, 4 layers) on a lattice big enough for
+    the host to select 8-wave workgroups: finite everywhere, and a few tiles against the oracle."""
     from latent_feature_grid_compression_amd import ops
     m, sm = build_synth(32, 64, 128, 4, seed=4321, dev=dev)
     m.eval()
     res = (72, 64, 256)                      # 72 * 64 rows x 8 runs = 36 864 tiles >= 8 per CU
-    outs = {}
-    for mode in ('x1', 'x2'):
-        if mode == 'x2':
-            os.environ['LFGC_FWD_X2'] = '1'
-        try:
-            with torch.no_grad():
-                y, _ = ops.forward_raw(m._descriptor(), m._decoded_channel_last(), m._packed(), lattice=(res, 3, 70, 32), clamp=True)
-            outs[mode] = y.cpu()
-        finally:
-            os.environ.pop('LFGC_FWD_X2', None)
-    assert bool(torch.isfinite(outs['x1']).all())
-    assert torch.equal(outs['x1'], outs['x2'])
-    # and the function is the right one: a few tiles against the oracle
+    with torch.no_grad():
+        plan = ops.forward_plan(m._descriptor(), m._decoded_channel_last(), lattice=(res, 3, 70, 32))
+        y, _ = ops.forward_raw(m._descriptor(), m._decoded_channel_last(), m._packed(), lattice=(res, 3, 70, 32), clamp=True)
+    assert (plan.zrun, plan.resident, plan.waves, plan.x2) == (1, 0, 8, 0)
+    out = y.cpu()
+    assert bool(torch.isfinite(out).all())
     rds = R.VolumeIndexing(res)
     dense = R.decode_volume(sm['coeffs'], sm['shape_array'], sm['filter_rev'])
-    vol = outs['x2'].view(67, 64, 256)
+    vol = out.view(67, 64, 256)
     for b in [(32, 64, 0, 32, 96, 128), (64, 72, 32, 64, 224, 256)]:
         pos = R.tile_positions(rds, b).reshape(-1, 3)
         ref = R.forward_from_grid(dense, sm['weights'], sm['biases'], pos, 2).clamp(-1, 1).reshape(b[1] - b[0], b[3] - b[2], b[5] - b[4])

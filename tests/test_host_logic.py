@@ -81,6 +81,28 @@ def test_pure_host_entry_points(built_lib):
     assert lib.lfgc_lattice_sample_f32(0, None, 1, None, None, None, None, None, None, None, None) == -1
 
 
+def test_forward_plan_has_no_two_tile_variant(built_lib, monkeypatch):
+    """The two-tiles-per-wave kernel and its LFGC_FWD_X2 switch are gone: at the headline net on the lattice whose plan
+    the switch used to change (32 channels x 128 wide, (72, 64, 256), slab x 3..70: 34 304 z-run tiles), the plan is the
+    8-wave z-run launch with the reserved field x2 at 0, with or without the variable set.  Host only: the query reads
+    the grid's shape and nothing else, so a stand-in with the shape of the decoded 64^3 grid takes the tensor's place."""
+    from types import SimpleNamespace
+    from latent_feature_grid_compression_amd import _lib, ops
+    for k in [k for k in os.environ if k.startswith('LFGC_') and k != 'LFGC_LIB_PATH']:
+        monkeypatch.delenv(k)
+    desc = _lib.MlpDesc(32, 128, 4, 2, 3, 1)
+    grid_cl = SimpleNamespace(shape=(64, 64, 64, 32), is_cuda=True)
+    plan = lambda: ops.forward_plan(desc, grid_cl, lattice=((72, 64, 256), 3, 70, 32), precision='f16x2', want_stash=False)
+    default = plan()
+    monkeypatch.setenv('LFGC_FWD_X2', '1')
+    with_switch = plan()
+    assert default == with_switch
+    for p in (default, with_switch):
+        assert p.x2 == 0 and p.zrun == 1
+        assert (p.CH, p.MT, p.resident, p.ntiles) == (32, 4, 0, 67 * 64 * 8)
+        assert p.redo is not None and p.redo.x2 == 0
+
+
 def test_philox_restatement_matches_published_vectors():
     """Random123's kat_vectors for philox4x32-10: the checker of test_fused_lattice_sampler is itself pinned."""
     from philox_ref import philox4x32_10
