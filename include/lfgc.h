@@ -806,6 +806,7 @@ int lfgc_brick_occupancy_f32(const float* minmax, int64_t n_bricks, const float*
  * would have held anyway.  Neither state nor a ray outside the list is touched; a ray id may appear once in the list.
  *   box_min < box_max host float[3]; cells host int32[3], each >= 1; occ device uint8 (nbx, nby, nbz); skipped device
  *   int32 (R), zeroed by the caller; S a multiple of 32. */
+#define LFGC_RAY_SKIP_GUARD 0.0625f          /* the guard g above, in cells */
 int lfgc_ray_skip_f32(const int32_t* live, int64_t n_list, const float* origins, const float* dirs, const float* t_near,
                       const float* t_far, const int32_t* n_steps, int32_t* k_next, float dt, int S, const float* box_min,
                       const float* box_max, const int32_t* cells, int32_t B, const uint8_t* occ, int32_t* skipped,

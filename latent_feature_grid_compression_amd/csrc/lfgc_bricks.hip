@@ -5,23 +5,20 @@
 //   lfgc_brick_occupancy_f32  brick -> 1 iff the transfer function's extinction is not zero on all of [min - margin, max + margin]
 //   lfgc_ray_skip_f32         k_next += S while none of the next S samples of a ray touches an occupied brick
 // One writer per brick and per ray, plain vector stores: no atomics, and two runs give the same bits.
-#include "lfgc_common.h"
+// The samples a ray is tested at and the table rows a value falls between are lfgc_ray.h's, as in lfgc_render.hip.
+#include "lfgc_ray.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kRun = 32;                        // samples of one ray tested per ballot: one half wave
-constexpr float kGuard = 0.0625f;               // 1/16 cell around a sample's cell coordinate (include/lfgc.h)
 
 // ---- ranges -------------------------------------------------------------------------------------------------------------
 // Workgroup = the bricks (bx, by, bz0 .. bz0 + nbpb) of one z-chunk.  Thread t owns the z columns z0 + t + 256 m of the
 // chunk (one column when B <= 255): it walks the brick's planes and rows that the slab holds, consecutive lanes reading
 // consecutive z, and leaves its (min, max) in LDS; thread b then folds the columns of brick bz0 + b with what the table
 // holds and writes the pair back.  A NaN counts as (-inf, +inf), which min and max keep.
-__global__ __launch_bounds__(kBlock) void brick_minmax_kernel(const float* __restrict__ values, int X, int Y, int Z, int x_begin,
-                                                              int x_end, int B, int bx_first, int nby, int nbz, int nbpb,
-                                                              float2* __restrict__ minmax) {
-    __shared__ float s_lo[kBlock], s_hi[kBlock];
+__global__ __launch_bounds__(kRayBlock) void brick_minmax_kernel(const float* __restrict__ values, int X, int Y, int Z, int x_begin,
+                                                                 int x_end, int B, int bx_first, int nby, int nbz, int nbpb,
+                                                                 float2* __restrict__ minmax) {
+    __shared__ float s_lo[kRayBlock], s_hi[kRayBlock];
     const int t = threadIdx.x;
     const int bx = bx_first + (int)blockIdx.z, by = (int)blockIdx.y, bz0 = (int)blockIdx.x * nbpb;
     const long long Bl = B;
@@ -30,7 +27,7 @@ __global__ __launch_bounds__(kBlock) void brick_minmax_kernel(const float* __res
     const long long z0 = bz0 * Bl;
     const long long z_last = min((long long)min(bz0 + nbpb, nbz) * Bl, (long long)Z - 1);      // inclusive
     float lo = __builtin_inff(), hi = -__builtin_inff();
-    for (long long z = z0 + t; z <= z_last; z += kBlock)
+    for (long long z = z0 + t; z <= z_last; z += kRayBlock)
         for (int x = xa; x <= xb; ++x)
             for (int y = ya; y <= yb; ++y) {
                 const float v = values[((long long)(x - x_begin) * Y + y) * Z + z];
@@ -46,8 +43,9 @@ __global__ __launch_bounds__(kBlock) void brick_minmax_kernel(const float* __res
         // columns of the brick: local offsets t B .. (t + 1) B of the chunk; with B > 255 the chunk is one brick spread over
         // all threads
         const long long span = z_last - z0;                                                   // last local offset
-        const int ia = B <= kBlock - 1 ? t * B : 0;
-        const int ib = (int)min(B <= kBlock - 1 ? (long long)(t + 1) * B : (long long)kBlock - 1, min(span, (long long)kBlock - 1));
+        const int ia = B <= kRayBlock - 1 ? t * B : 0;
+        const int ib = (int)min(B <= kRayBlock - 1 ? (long long)(t + 1) * B : (long long)kRayBlock - 1,
+                                min(span, (long long)kRayBlock - 1));
         const long long at = ((long long)bx * nby + by) * nbz + bz;
         float2 mm = minmax[at];
         for (int i = ia; i <= ib; ++i) {
@@ -59,19 +57,15 @@ __global__ __launch_bounds__(kBlock) void brick_minmax_kernel(const float* __res
 }
 
 // ---- occupancy ----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float tf_coordinate(float v, float v_min, float tf_scale, float u_max) {
-    return fminf(fmaxf((v - v_min) * tf_scale, 0.0f), u_max);      // the composite kernel's expression
-}
-
-__global__ __launch_bounds__(kBlock) void brick_occupancy_kernel(const float2* __restrict__ minmax, long long n_bricks,
-                                                                 const float4* __restrict__ tab, int K, float v_min, float tf_scale,
-                                                                 float margin, unsigned char* __restrict__ occ) {
-    const long long b = (long long)blockIdx.x * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kRayBlock) void brick_occupancy_kernel(const float2* __restrict__ minmax, long long n_bricks,
+                                                                    const float4* __restrict__ tab, int K, float v_min, float tf_scale,
+                                                                    float margin, unsigned char* __restrict__ occ) {
+    const long long b = (long long)blockIdx.x * kRayBlock + threadIdx.x;
     if (b >= n_bricks) return;
     const float2 mm = minmax[b];
     const float u_max = (float)(K - 1);
-    const int i0 = (int)floorf(tf_coordinate(mm.x - margin, v_min, tf_scale, u_max));
-    const int i1 = (int)ceilf(tf_coordinate(mm.y + margin, v_min, tf_scale, u_max));
+    const int i0 = (int)floorf(lfgc_tf_coordinate(mm.x - margin, v_min, tf_scale, u_max));
+    const int i1 = (int)ceilf(lfgc_tf_coordinate(mm.y + margin, v_min, tf_scale, u_max));
     bool seen = false;
     for (int i = i0; i <= i1; ++i) seen = seen || tab[i].w != 0.0f;
     occ[b] = seen ? 1 : 0;
@@ -83,33 +77,26 @@ struct SkipGrid {
     int cells[3], nb[3], B;
 };
 
-// segment k of a ray, as lfgc_render.hip forms it
-__device__ __forceinline__ void ray_segment(float tn, float tf, float dt, int k, float& a, float& b) {
-    a = tn + (float)k * dt;
-    b = fminf(a + dt, tf);
-}
-
 // the two bricks a coordinate can lie in along one axis
 __device__ __forceinline__ void brick_pair(float p, const SkipGrid& g, int a, int& b0, int& b1) {
     const float q = (p - g.lo[a]) / g.ext[a] * g.cells_f[a];
     const float top = (float)(g.cells[a] - 1);
-    b0 = (int)fminf(fmaxf(floorf(q - kGuard), 0.0f), top) / g.B;
-    b1 = (int)fminf(fmaxf(floorf(q + kGuard), 0.0f), top) / g.B;
+    b0 = (int)fminf(fmaxf(floorf(q - LFGC_RAY_SKIP_GUARD), 0.0f), top) / g.B;
+    b1 = (int)fminf(fmaxf(floorf(q + LFGC_RAY_SKIP_GUARD), 0.0f), top) / g.B;
 }
 
 // A half wave owns a ray, as in the composite kernel: lane l tests sample l of each run of 32, one ballot per run, each
 // half reads its own 32 bits.  The halves of a wave leave the loop at different trip counts; nothing here needs the other
 // half's lanes (no shuffles), and a ballot counts inactive lanes as 0.
-__global__ __launch_bounds__(kBlock) void ray_skip_kernel(const int* __restrict__ live, long long n_list, int S,
-                                                          const float* __restrict__ origins, const float* __restrict__ dirs,
-                                                          const float* __restrict__ t_near, const float* __restrict__ t_far,
-                                                          const int* __restrict__ n_steps, int* __restrict__ k_next, float dt,
-                                                          const SkipGrid g, const unsigned char* __restrict__ occ,
-                                                          int* __restrict__ skipped) {
-    const int lane = threadIdx.x & (kRun - 1);
-    const long long j = (long long)blockIdx.x * (kBlock / kRun) + (threadIdx.x / kRun);
-    if (j >= n_list) return;
-    const long long r = live ? live[j] : j;
+__global__ __launch_bounds__(kRayBlock) void ray_skip_kernel(const int* __restrict__ live, long long n_list, int S,
+                                                             const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                             const float* __restrict__ t_near, const float* __restrict__ t_far,
+                                                             const int* __restrict__ n_steps, int* __restrict__ k_next, float dt,
+                                                             const SkipGrid g, const unsigned char* __restrict__ occ,
+                                                             int* __restrict__ skipped) {
+    const LfgcHalfWave hw;
+    if (hw.j >= n_list) return;
+    const long long r = live ? live[hw.j] : hw.j;
     const int n = n_steps[r];
     int k0 = k_next[r];
     if (k0 >= n) return;
@@ -119,36 +106,31 @@ __global__ __launch_bounds__(kBlock) void ray_skip_kernel(const int* __restrict_
     int jumped = 0;
     while (k0 < n) {
         bool found = false;                      // the same for all 32 lanes of the half
-        for (int s0 = 0; s0 < S && !found; s0 += kRun) {
-            const int k = k0 + s0 + lane;
+        for (int s0 = 0; s0 < S && !found; s0 += kRayRun) {
+            const int k = k0 + s0 + hw.lane;
             bool touches = false;
             if (k < n) {
-                float a, b;
-                ray_segment(tn, tf, dt, k, a, b);
-                const float tm = 0.5f * (a + b);
+                const float tm = lfgc_ray_midpoint(tn, tf, dt, k);
                 int x0, x1, y0, y1, z0, z1;
-                brick_pair(ox + tm * dx, g, 0, x0, x1);
-                brick_pair(oy + tm * dy, g, 1, y0, y1);
-                brick_pair(oz + tm * dz, g, 2, z0, z1);
+                brick_pair(lfgc_ray_point(ox, dx, tm), g, 0, x0, x1);
+                brick_pair(lfgc_ray_point(oy, dy, tm), g, 1, y0, y1);
+                brick_pair(lfgc_ray_point(oz, dz, tm), g, 2, z0, z1);
                 const long long r00 = ((long long)x0 * g.nb[1] + y0) * g.nb[2], r01 = ((long long)x0 * g.nb[1] + y1) * g.nb[2];
                 const long long r10 = ((long long)x1 * g.nb[1] + y0) * g.nb[2], r11 = ((long long)x1 * g.nb[1] + y1) * g.nb[2];
                 touches = (occ[r00 + z0] | occ[r00 + z1] | occ[r01 + z0] | occ[r01 + z1] |
                            occ[r10 + z0] | occ[r10 + z1] | occ[r11 + z0] | occ[r11 + z1]) != 0;
             }
-            const unsigned long long mask = (__ballot(touches) >> ((threadIdx.x & 32) ? 32 : 0)) & 0xffffffffull;
-            found = mask != 0;
+            found = hw.ballot(touches) != 0;
         }
         if (found) break;
         k0 += S;
         ++jumped;
     }
-    if (lane == 0 && jumped) {
+    if (hw.lane == 0 && jumped) {
         k_next[r] = k0;
         skipped[r] += jumped;
     }
 }
-
-inline bool finite_f(float v) { return v - v == 0.0f; }
 
 inline int bricks_along(int cells, int B) { return (int)(((long long)cells + B - 1) / B); }
 
@@ -165,12 +147,12 @@ extern "C" int lfgc_brick_minmax_f32(const float* values, const int32_t* res, in
     const int bx_first = x_begin % B == 0 && x_begin > 0 ? x_begin / B - 1 : (x_begin / B < nbx ? x_begin / B : nbx - 1);
     const int bx_last = (x_end - 1) / B < nbx ? (x_end - 1) / B : nbx - 1;
     // bricks of one workgroup along z: their columns fit its 256 threads, and the chunks are of about equal size
-    const int most = B <= kBlock - 1 ? (kBlock - 1) / B : 1;
+    const int most = B <= kRayBlock - 1 ? (kRayBlock - 1) / B : 1;
     const int chunks = (nbz + most - 1) / most;
     const int nbpb = (nbz + chunks - 1) / chunks;
     if (nby > 65535 || bx_last - bx_first + 1 > 65535) return LFGC_E_UNSUPPORTED;
     hipLaunchKernelGGL(brick_minmax_kernel, dim3((unsigned)((nbz + nbpb - 1) / nbpb), (unsigned)nby, (unsigned)(bx_last - bx_first + 1)),
-                       dim3(kBlock), 0, (hipStream_t)stream, values, X, Y, Z, x_begin, x_end, B, bx_first, nby, nbz, nbpb,
+                       dim3(kRayBlock), 0, (hipStream_t)stream, values, X, Y, Z, x_begin, x_end, B, bx_first, nby, nbz, nbpb,
                        reinterpret_cast<float2*>(minmax));
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
@@ -179,11 +161,11 @@ extern "C" int lfgc_brick_minmax_f32(const float* values, const int32_t* res, in
 extern "C" int lfgc_brick_occupancy_f32(const float* minmax, int64_t n_bricks, const float* tf_table, int K, float v_min,
                                         float tf_scale, float margin, uint8_t* occ, lfgc_stream_t stream) {
     if (!minmax || !tf_table || !occ) return LFGC_E_NULL;
-    if (n_bricks < 1 || n_bricks > 0x7fffffffLL || K < 2 || !(tf_scale > 0.0f) || !finite_f(tf_scale) || !finite_f(v_min) ||
-        !(margin >= 0.0f) || !finite_f(margin))
+    if (n_bricks < 1 || n_bricks > 0x7fffffffLL || K < 2 || !(tf_scale > 0.0f) || !lfgc_finite(tf_scale) || !lfgc_finite(v_min) ||
+        !(margin >= 0.0f) || !lfgc_finite(margin))
         return LFGC_E_SHAPE;
     if (((uintptr_t)minmax & 7) || ((uintptr_t)tf_table & 15)) return LFGC_E_ALIGN;
-    hipLaunchKernelGGL(brick_occupancy_kernel, dim3((unsigned)((n_bricks + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(brick_occupancy_kernel, dim3(lfgc_row_grid(n_bricks)), dim3(kRayBlock), 0,
                        (hipStream_t)stream, reinterpret_cast<const float2*>(minmax), (long long)n_bricks,
                        reinterpret_cast<const float4*>(tf_table), K, v_min, tf_scale, margin, occ);
     LFGC_HIP_CHECK_LAUNCH();
@@ -196,21 +178,19 @@ extern "C" int lfgc_ray_skip_f32(const int32_t* live, int64_t n_list, const floa
                                  lfgc_stream_t stream) {
     if (!origins || !dirs || !t_near || !t_far || !n_steps || !k_next || !box_min || !box_max || !cells || !occ || !skipped)
         return LFGC_E_NULL;
-    if (n_list < 1 || n_list > 0x7fffffffLL || S < 32 || S % 32 != 0 || !(dt > 0.0f) || B < 1) return LFGC_E_SHAPE;
+    if (lfgc_ray_list_check(n_list, S, dt) != LFGC_OK || B < 1) return LFGC_E_SHAPE;
     SkipGrid g;
     g.B = B;
     for (int a = 0; a < 3; ++a) {
-        if (!(box_min[a] < box_max[a]) || !finite_f(box_min[a]) || !finite_f(box_max[a]) || cells[a] < 1) return LFGC_E_SHAPE;
+        if (!(box_min[a] < box_max[a]) || !lfgc_finite(box_min[a]) || !lfgc_finite(box_max[a]) || cells[a] < 1) return LFGC_E_SHAPE;
         g.lo[a] = box_min[a];
         g.ext[a] = box_max[a] - box_min[a];
         g.cells[a] = cells[a];
         g.cells_f[a] = (float)cells[a];
         g.nb[a] = bricks_along(cells[a], B);
     }
-    const int per_block = kBlock / kRun;
-    const unsigned nblocks = (unsigned)((n_list + per_block - 1) / per_block);
-    hipLaunchKernelGGL(ray_skip_kernel, dim3(nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, (long long)n_list, S, origins, dirs,
-                       t_near, t_far, n_steps, k_next, dt, g, occ, skipped);
+    hipLaunchKernelGGL(ray_skip_kernel, dim3(lfgc_half_wave_grid(n_list)), dim3(kRayBlock), 0, (hipStream_t)stream, live,
+                       (long long)n_list, S, origins, dirs, t_near, t_far, n_steps, k_next, dt, g, occ, skipped);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }

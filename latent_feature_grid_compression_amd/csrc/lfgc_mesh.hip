@@ -7,6 +7,7 @@
 //   lfgc_iso_mesh_emit_f32   per owned crossing edge its origin, direction and bracket; per triangle three vertex indices
 // A thread owns one lattice point (and the cell whose lowest corner it is); consecutive lanes walk z, the contiguous axis, so
 // the eight corner loads of a wave are eight contiguous rows.  No atomics: every output address has one writer.
+#include "lfgc_ray.h"
 #include "lfgc_select.h"
 
 namespace {
@@ -72,8 +73,6 @@ inline long long carve(void* base, long long npts, Workspace* w) {
     return at;
 }
 
-__device__ __forceinline__ bool inside(float v, float iso) { return v - iso >= 0.0f; }     // a NaN is not inside
-
 __device__ __forceinline__ void point_of(const Slab& s, unsigned i, int& lx, int& y, int& z) {
     lx = (int)(i / s.plane);
     const unsigned r = i - (unsigned)lx * s.plane;
@@ -87,12 +86,12 @@ __device__ __forceinline__ unsigned corner_offset(const Slab& s, int c) {
 
 // inside bits of the 8 corners of the cell at point i (bit c; corners outside the slab read as the point itself)
 __device__ __forceinline__ unsigned corner_bits(const Slab& s, const float* __restrict__ values, unsigned i, unsigned exist) {
-    const unsigned in0 = inside(values[i], s.iso) ? 1u : 0u;
+    const unsigned in0 = lfgc_iso_inside(values[i], s.iso) ? 1u : 0u;
     unsigned cm = in0;
 #pragma unroll
     for (int c = 1; c < 8; ++c) {
         unsigned in = in0;
-        if (exist >> c & 1) in = inside(values[i + corner_offset(s, c)], s.iso) ? 1u : 0u;
+        if (exist >> c & 1) in = lfgc_iso_inside(values[i + corner_offset(s, c)], s.iso) ? 1u : 0u;
         cm |= in << c;
     }
     return cm;
@@ -260,11 +259,9 @@ __global__ __launch_bounds__(kBlock) void mesh_triangles_kernel(const Slab s, co
     }
 }
 
-inline bool finite_f(float v) { return v - v == 0.0f; }
-
 // LFGC_OK and the slab's plan, or the argument error
 inline int make_slab(int nx, int n_owner, int ny, int nz, float iso, Slab* s) {
-    if (nx < 1 || n_owner < 1 || n_owner > nx || ny < 2 || nz < 2 || !finite_f(iso)) return LFGC_E_SHAPE;
+    if (nx < 1 || n_owner < 1 || n_owner > nx || ny < 2 || nz < 2 || !lfgc_finite(iso)) return LFGC_E_SHAPE;
     if ((long long)nx * ny * nz > kMaxPoints) return LFGC_E_UNSUPPORTED;
     s->nx = nx; s->ny = ny; s->nz = nz;
     s->nf = n_owner + 1 < nx ? n_owner + 1 : nx;

@@ -1,0 +1,61 @@
+// lfgc_ray.h -- where a ray's samples are defined (gfx950), once, for lfgc_render.hip, lfgc_bricks.hip and
+// lfgc_mesh.hip: the skip kernel looks at the positions the samples kernel writes and sees a value's table rows as the
+// composite kernel does by construction.  fp32 in the order include/lfgc.h states, one rounding per operation.
+#pragma once
+#include "lfgc_common.h"
+
+constexpr int kRayBlock = 256;                  // threads per workgroup of the ray and brick kernels
+constexpr int kRayRun = 32;                     // samples of one ray handled per step: one half wave
+
+// segment k of a ray: [a, b] with a = tn + k dt (never an accumulated sum) and b = min(a + dt, tf)
+__device__ __forceinline__ void lfgc_ray_segment(float tn, float tf, float dt, int k, float& a, float& b) {
+    a = tn + (float)k * dt;
+    b = fminf(a + dt, tf);
+}
+__device__ __forceinline__ float lfgc_ray_midpoint(float tn, float tf, float dt, int k) {      // the parameter of sample k
+    float a, b;
+    lfgc_ray_segment(tn, tf, dt, k, a, b);
+    return 0.5f * (a + b);
+}
+
+// one component of the point o + t d, and component c of it for row r of the (R, 3) tables
+__device__ __forceinline__ float lfgc_ray_point(float o, float d, float t) { return o + t * d; }
+__device__ __forceinline__ float lfgc_ray_point(const float* origins, const float* dirs, long long r, int c, float t) {
+    return lfgc_ray_point(origins[r * 3 + c], dirs[r * 3 + c], t);
+}
+
+// A half wave (32 lanes) owns entry j of a ray list and walks the ray's samples in runs of kRayRun, lane l on sample l of
+// the run.  A kernel leaves with `if (hw.j >= n) return;` before its first shuffle or ballot: a whole half leaves together.
+struct LfgcHalfWave {
+    int lane;
+    long long j;
+    __device__ __forceinline__ LfgcHalfWave()
+        : lane(threadIdx.x & (kRayRun - 1)), j((long long)blockIdx.x * (kRayBlock / kRayRun) + (threadIdx.x / kRayRun)) {}
+    __device__ __forceinline__ unsigned long long ballot(bool p) const {      // this half's 32 bits; an inactive lane counts as 0
+        return (__ballot(p) >> ((threadIdx.x & 32) ? 32 : 0)) & 0xffffffffull;
+    }
+    // the first set lane of such a mask, or kRayRun
+    __device__ __forceinline__ static int first(unsigned long long mask) { return mask ? __ffsll((long long)mask) - 1 : kRayRun; }
+};
+
+__device__ __forceinline__ bool lfgc_iso_inside(float v, float iso) { return v - iso >= 0.0f; }      // a NaN is not inside
+
+// the row coordinate of value v in a transfer-function table of u_max + 1 rows
+__device__ __forceinline__ float lfgc_tf_coordinate(float v, float v_min, float tf_scale, float u_max) {
+    return fminf(fmaxf((v - v_min) * tf_scale, 0.0f), u_max);
+}
+
+// ---- host side of the entries ---------------------------------------------------------------------------------------------
+inline bool lfgc_finite(float v) { return v - v == 0.0f; }
+
+// a launch over a list of n rays with S samples each at step dt: LFGC_OK or the argument error
+inline int lfgc_ray_list_check(int64_t n, int S, float dt) {
+    return n < 1 || n > 0x7fffffffLL || S < kRayRun || S % kRayRun != 0 || !(dt > 0.0f) ? LFGC_E_SHAPE : LFGC_OK;
+}
+// workgroups of a launch with one half wave per list entry
+inline unsigned lfgc_half_wave_grid(int64_t n) { return (unsigned)((n + kRayBlock / kRayRun - 1) / (kRayBlock / kRayRun)); }
+// workgroups of a launch with one thread per row (n_rows >= 1), or 0 where that takes more than 2^31 - 1 of them
+inline unsigned lfgc_row_grid(long long n_rows) {
+    const long long nblocks = (n_rows + kRayBlock - 1) / kRayBlock;
+    return nblocks > 0x7fffffffLL ? 0u : (unsigned)nblocks;
+}

@@ -11,21 +11,20 @@
 //   lfgc_ray_iso_finish_f32  one secant step inside the final bracket: depth and position of the hit
 // All arithmetic is fp32 in the order include/lfgc.h states (the build has no contraction and correctly rounded
 // division), so the clip and the positions can be restated bit for bit on the host.  One writer per ray: no atomics.
+// Segments, sample points, the table coordinate and the half wave that owns a ray are lfgc_ray.h's.
+#include "lfgc_ray.h"
 #include "lfgc_select.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kRun = 32;                        // samples of one ray composited per step: one half wave
-
 struct RayBox { float lo[3], hi[3]; };
 
 // ---- clip -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void ray_clip_kernel(const float* __restrict__ origins, const float* __restrict__ dirs,
-                                                          long long n_rays, const RayBox box, float t_min, float t_max, float dt,
-                                                          int max_steps, float* __restrict__ t_near, float* __restrict__ t_far,
-                                                          int* __restrict__ n_steps) {
-    const long long r = (long long)blockIdx.x * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kRayBlock) void ray_clip_kernel(const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                             long long n_rays, const RayBox box, float t_min, float t_max, float dt,
+                                                             int max_steps, float* __restrict__ t_near, float* __restrict__ t_far,
+                                                             int* __restrict__ n_steps) {
+    const long long r = (long long)blockIdx.x * kRayBlock + threadIdx.x;
     if (r >= n_rays) return;
     float tn = t_min, tf = t_max;
     bool hit = true;
@@ -55,20 +54,14 @@ __global__ __launch_bounds__(kBlock) void ray_clip_kernel(const float* __restric
     n_steps[r] = n;
 }
 
-// segment k of a ray: [a, b] with a = tn + k dt (never an accumulated sum) and b = min(a + dt, tf)
-__device__ __forceinline__ void ray_segment(float tn, float tf, float dt, int k, float& a, float& b) {
-    a = tn + (float)k * dt;
-    b = fminf(a + dt, tf);
-}
-
 // ---- samples --------------------------------------------------------------------------------------------------------
 // thread = one output row; the 12-byte rows of a wave are consecutive, so its three stores cover 768 contiguous bytes
-__global__ __launch_bounds__(kBlock) void ray_samples_kernel(const int* __restrict__ live, long long n_rows, int S,
-                                                             const float* __restrict__ origins, const float* __restrict__ dirs,
-                                                             const float* __restrict__ t_near, const float* __restrict__ t_far,
-                                                             const int* __restrict__ n_steps, const int* __restrict__ k_next,
-                                                             float dt, float* __restrict__ pos) {
-    const long long row = (long long)blockIdx.x * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kRayBlock) void ray_samples_kernel(const int* __restrict__ live, long long n_rows, int S,
+                                                                const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                                const float* __restrict__ t_near, const float* __restrict__ t_far,
+                                                                const int* __restrict__ n_steps, const int* __restrict__ k_next,
+                                                                float dt, float* __restrict__ pos) {
+    const long long row = (long long)blockIdx.x * kRayBlock + threadIdx.x;
     if (row >= n_rows) return;
     const long long j = row / S;
     const int s = (int)(row - j * S);
@@ -77,11 +70,9 @@ __global__ __launch_bounds__(kBlock) void ray_samples_kernel(const int* __restri
     const int n = n_steps[r];
     if (k > n - 1) k = n - 1;                    // padding rows repeat the last valid sample
     if (k < 0) k = 0;
-    float a, b;
-    ray_segment(t_near[r], t_far[r], dt, k, a, b);
-    const float tm = 0.5f * (a + b);
+    const float tm = lfgc_ray_midpoint(t_near[r], t_far[r], dt, k);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) pos[row * 3 + c] = origins[r * 3 + c] + tm * dirs[r * 3 + c];
+    for (int c = 0; c < 3; ++c) pos[row * 3 + c] = lfgc_ray_point(origins, dirs, r, c, tm);
 }
 
 // ---- composite ------------------------------------------------------------------------------------------------------
@@ -91,18 +82,17 @@ __global__ __launch_bounds__(kBlock) void ray_samples_kernel(const int* __restri
 // prefix of the run: T after the run is T before the first lane that does not contribute.  The lanes a ray's samples sit
 // on do not depend on the list the ray is in, so neither does a single bit of its result.
 template <bool SHADE>
-__global__ __launch_bounds__(kBlock) void ray_composite_kernel(const int* __restrict__ live, long long n_live, int S,
-                                                               const float* __restrict__ values, const float* __restrict__ grad,
-                                                               const float* __restrict__ dirs, const float* __restrict__ t_near,
-                                                               const float* __restrict__ t_far, const int* __restrict__ n_steps,
-                                                               int* __restrict__ k_next, float dt,
-                                                               const float4* __restrict__ tab, int K, float v_min, float tf_scale,
-                                                               float opacity_limit, float ka, float kd,
-                                                               float4* __restrict__ state) {
-    const int lane = threadIdx.x & (kRun - 1);
-    const long long j = (long long)blockIdx.x * (kBlock / kRun) + (threadIdx.x / kRun);
-    if (j >= n_live) return;                     // a whole half wave leaves: the shuffles below stay inside one half
-    const long long r = live[j];
+__global__ __launch_bounds__(kRayBlock) void ray_composite_kernel(const int* __restrict__ live, long long n_live, int S,
+                                                                  const float* __restrict__ values, const float* __restrict__ grad,
+                                                                  const float* __restrict__ dirs, const float* __restrict__ t_near,
+                                                                  const float* __restrict__ t_far, const int* __restrict__ n_steps,
+                                                                  int* __restrict__ k_next, float dt,
+                                                                  const float4* __restrict__ tab, int K, float v_min, float tf_scale,
+                                                                  float opacity_limit, float ka, float kd,
+                                                                  float4* __restrict__ state) {
+    const LfgcHalfWave hw;
+    if (hw.j >= n_live) return;                  // a whole half wave leaves: the shuffles below stay inside one half
+    const long long r = live[hw.j];
     const float tn = t_near[r], tf = t_far[r];
     const int n = n_steps[r], k0 = k_next[r];
     float dx = 0.0f, dy = 0.0f, dz = 0.0f;
@@ -110,15 +100,15 @@ __global__ __launch_bounds__(kBlock) void ray_composite_kernel(const int* __rest
     const float4 st = state[r];
     float cr = st.x, cg = st.y, cb = st.z, T = st.w;
     const float u_max = (float)(K - 1);
-    for (int s0 = 0; s0 < S; s0 += kRun) {
-        const long long row = j * S + s0 + lane;
-        const int k = k0 + s0 + lane;
+    for (int s0 = 0; s0 < S; s0 += kRayRun) {
+        const long long row = hw.j * S + s0 + hw.lane;
+        const int k = k0 + s0 + hw.lane;
         float alpha = 0.0f, er = 0.0f, eg = 0.0f, eb = 0.0f;
         if (k < n) {
             float a, b;
-            ray_segment(tn, tf, dt, k, a, b);
+            lfgc_ray_segment(tn, tf, dt, k, a, b);
             const float len = fmaxf(b - a, 0.0f);        // a step count rounded up: the last segment starts an ulp past t_far
-            const float u = fminf(fmaxf((values[row] - v_min) * tf_scale, 0.0f), u_max);
+            const float u = lfgc_tf_coordinate(values[row], v_min, tf_scale, u_max);
             int i = (int)u;
             if (i > K - 2) i = K - 2;
             const float f = u - (float)i;
@@ -138,32 +128,31 @@ __global__ __launch_bounds__(kBlock) void ray_composite_kernel(const int* __rest
         }
         float incl = 1.0f - alpha;               // inclusive product of the factors of lanes 0..lane
 #pragma unroll
-        for (int off = 1; off < kRun; off <<= 1) {
-            const float t = __shfl_up(incl, off, kRun);
-            if (lane >= off) incl *= t;
+        for (int off = 1; off < kRayRun; off <<= 1) {
+            const float t = __shfl_up(incl, off, kRayRun);
+            if (hw.lane >= off) incl *= t;
         }
-        float excl = __shfl_up(incl, 1, kRun);
-        if (lane == 0) excl = 1.0f;
+        float excl = __shfl_up(incl, 1, kRayRun);
+        if (hw.lane == 0) excl = 1.0f;
         const float t_before = T * excl;
         // the first lane that is out ends the ray (the rounded products of two scan trees need not be ordered, so the
         // prefix is cut there explicitly); T after the run: T before that lane, else T times every factor
-        const unsigned long long out_mask =
-            (__ballot(!(1.0f - t_before < opacity_limit)) >> ((threadIdx.x & 32) ? 32 : 0)) & 0xffffffffull;
-        const int first_out = out_mask ? __ffsll((long long)out_mask) - 1 : kRun;
-        const bool in = lane < first_out;
+        const unsigned long long out_mask = hw.ballot(!(1.0f - t_before < opacity_limit));
+        const int first_out = LfgcHalfWave::first(out_mask);
+        const bool in = hw.lane < first_out;
         float sr = in ? t_before * er : 0.0f, sg = in ? t_before * eg : 0.0f, sb = in ? t_before * eb : 0.0f;
 #pragma unroll
-        for (int off = kRun / 2; off > 0; off >>= 1) {
-            sr += __shfl_xor(sr, off, kRun);
-            sg += __shfl_xor(sg, off, kRun);
-            sb += __shfl_xor(sb, off, kRun);
+        for (int off = kRayRun / 2; off > 0; off >>= 1) {
+            sr += __shfl_xor(sr, off, kRayRun);
+            sg += __shfl_xor(sg, off, kRayRun);
+            sb += __shfl_xor(sb, off, kRayRun);
         }
-        const float t_all = T * __shfl(incl, kRun - 1, kRun);
-        const float t_cut = __shfl(t_before, first_out & (kRun - 1), kRun);
+        const float t_all = T * __shfl(incl, kRayRun - 1, kRayRun);
+        const float t_cut = __shfl(t_before, first_out & (kRayRun - 1), kRayRun);
         T = out_mask ? t_cut : t_all;
         cr += sr; cg += sg; cb += sb;
     }
-    if (lane == 0) {
+    if (hw.lane == 0) {
         state[r] = make_float4(cr, cg, cb, T);
         k_next[r] = k0 + S;
     }
@@ -194,55 +183,50 @@ struct RayListSink {
 };
 
 // ---- isosurface: the first sign change of v - iso along a ray, its bisection and the hit point ---------------------------
-// inside(v) is v - iso >= 0 (a NaN is not inside).  The scan has the composite kernel's form: a half wave owns a ray and
+// inside(v) is lfgc_iso_inside: v - iso >= 0.  The scan has the composite kernel's form: a half wave owns a ray and
 // walks its S values in runs of 32; lane l sees its predecessor through a shuffle, lane 0 takes the value carried in
 // state.x (the last value of the ray's previous block; meaningful iff k_next > 0) or the previous run's lane 31.  The
 // first crossing of the half's 32 ballot bits ends the ray: its lane writes the bracket, state.w = 0 and k_next = k.
-__global__ __launch_bounds__(kBlock) void ray_iso_scan_kernel(const int* __restrict__ live, long long n_live, int S,
-                                                              const float* __restrict__ values, const float* __restrict__ t_near,
-                                                              const float* __restrict__ t_far, const int* __restrict__ n_steps,
-                                                              int* __restrict__ k_next, float dt, float iso,
-                                                              float4* __restrict__ state, float4* __restrict__ bracket) {
-    const int lane = threadIdx.x & (kRun - 1);
-    const long long j = (long long)blockIdx.x * (kBlock / kRun) + (threadIdx.x / kRun);
-    if (j >= n_live) return;                     // a whole half wave leaves: the shuffles below stay inside one half
-    const long long r = live[j];
+__global__ __launch_bounds__(kRayBlock) void ray_iso_scan_kernel(const int* __restrict__ live, long long n_live, int S,
+                                                                 const float* __restrict__ values, const float* __restrict__ t_near,
+                                                                 const float* __restrict__ t_far, const int* __restrict__ n_steps,
+                                                                 int* __restrict__ k_next, float dt, float iso,
+                                                                 float4* __restrict__ state, float4* __restrict__ bracket) {
+    const LfgcHalfWave hw;
+    if (hw.j >= n_live) return;                  // a whole half wave leaves: the shuffles below stay inside one half
+    const long long r = live[hw.j];
     const int n = n_steps[r], k0 = k_next[r];
     float last = state[r].x;
-    for (int s0 = 0; s0 < S; s0 += kRun) {
-        const int k = k0 + s0 + lane;
-        const float v = values[j * S + s0 + lane];
-        float prev = __shfl_up(v, 1, kRun);
-        if (lane == 0) prev = last;
-        const bool cross = k >= 1 && k < n && (prev - iso >= 0.0f) != (v - iso >= 0.0f);   // k < n: padding rows never cross
-        const unsigned long long mask = (__ballot(cross) >> ((threadIdx.x & 32) ? 32 : 0)) & 0xffffffffull;
+    for (int s0 = 0; s0 < S; s0 += kRayRun) {
+        const int k = k0 + s0 + hw.lane;
+        const float v = values[hw.j * S + s0 + hw.lane];
+        float prev = __shfl_up(v, 1, kRayRun);
+        if (hw.lane == 0) prev = last;
+        const bool cross = k >= 1 && k < n && lfgc_iso_inside(prev, iso) != lfgc_iso_inside(v, iso);     // k < n: no padding row
+        const unsigned long long mask = hw.ballot(cross);
         if (mask) {                              // the same for all 32 lanes of the half
-            if (lane == __ffsll((long long)mask) - 1) {
+            if (hw.lane == LfgcHalfWave::first(mask)) {
                 const float tn = t_near[r], tf = t_far[r];
-                float a, b;
-                ray_segment(tn, tf, dt, k - 1, a, b);
-                const float t_lo = 0.5f * (a + b);
-                ray_segment(tn, tf, dt, k, a, b);
-                bracket[r] = make_float4(t_lo, 0.5f * (a + b), prev - iso, v - iso);
+                bracket[r] = make_float4(lfgc_ray_midpoint(tn, tf, dt, k - 1), lfgc_ray_midpoint(tn, tf, dt, k), prev - iso, v - iso);
                 state[r] = make_float4(v, 0.0f, 0.0f, 0.0f);
                 k_next[r] = k;
             }
             return;
         }
-        last = __shfl(v, kRun - 1, kRun);
+        last = __shfl(v, kRayRun - 1, kRayRun);
     }
-    if (lane == 0) {
+    if (hw.lane == 0) {
         state[r] = make_float4(last, 0.0f, 0.0f, 1.0f);
         k_next[r] = k0 + S;
     }
 }
 
 // thread = one bracketed ray of the list: fold the value at the bracket's midpoint in (if given), emit the next midpoint
-__global__ __launch_bounds__(kBlock) void ray_iso_refine_kernel(const int* __restrict__ list, long long n,
-                                                                const float* __restrict__ values, const float* __restrict__ origins,
-                                                                const float* __restrict__ dirs, float iso,
-                                                                float4* __restrict__ bracket, float* __restrict__ pos) {
-    const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kRayBlock) void ray_iso_refine_kernel(const int* __restrict__ list, long long n,
+                                                                   const float* __restrict__ values, const float* __restrict__ origins,
+                                                                   const float* __restrict__ dirs, float iso,
+                                                                   float4* __restrict__ bracket, float* __restrict__ pos) {
+    const long long j = (long long)blockIdx.x * kRayBlock + threadIdx.x;
     if (j >= n) return;
     const long long r = list[j];
     float4 br = bracket[r];
@@ -255,15 +239,15 @@ __global__ __launch_bounds__(kBlock) void ray_iso_refine_kernel(const int* __res
     }
     const float tm = 0.5f * (br.x + br.y);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) pos[j * 3 + c] = origins[r * 3 + c] + tm * dirs[r * 3 + c];
+    for (int c = 0; c < 3; ++c) pos[j * 3 + c] = lfgc_ray_point(origins, dirs, r, c, tm);
 }
 
 // thread = one bracketed ray of the list: one secant step inside the final bracket
-__global__ __launch_bounds__(kBlock) void ray_iso_finish_kernel(const int* __restrict__ list, long long n,
-                                                                const float* __restrict__ origins, const float* __restrict__ dirs,
-                                                                const float4* __restrict__ bracket, float* __restrict__ t_hit,
-                                                                float* __restrict__ pos) {
-    const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kRayBlock) void ray_iso_finish_kernel(const int* __restrict__ list, long long n,
+                                                                   const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                                   const float4* __restrict__ bracket, float* __restrict__ t_hit,
+                                                                   float* __restrict__ pos) {
+    const long long j = (long long)blockIdx.x * kRayBlock + threadIdx.x;
     if (j >= n) return;
     const long long r = list[j];
     const float4 br = bracket[r];
@@ -273,10 +257,8 @@ __global__ __launch_bounds__(kBlock) void ray_iso_finish_kernel(const int* __res
     t = fminf(fmaxf(t, br.x), br.y);
     t_hit[j] = t;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) pos[j * 3 + c] = origins[r * 3 + c] + t * dirs[r * 3 + c];
+    for (int c = 0; c < 3; ++c) pos[j * 3 + c] = lfgc_ray_point(origins, dirs, r, c, t);
 }
-
-inline bool finite_f(float v) { return v - v == 0.0f; }
 
 }  // namespace
 
@@ -284,14 +266,15 @@ extern "C" int lfgc_ray_clip_f32(const float* origins, const float* dirs, int64_
                                  float t_min, float t_max, float dt, int max_steps, float* t_near, float* t_far, int32_t* n_steps,
                                  lfgc_stream_t stream) {
     if (!origins || !dirs || !box_min || !box_max || !t_near || !t_far || !n_steps) return LFGC_E_NULL;
-    if (n_rays < 1 || n_rays > 0x7fffffffLL || max_steps < 1 || !(dt > 0.0f) || !finite_f(dt) || !finite_f(t_min)) return LFGC_E_SHAPE;
+    if (n_rays < 1 || n_rays > 0x7fffffffLL || max_steps < 1 || !(dt > 0.0f) || !lfgc_finite(dt) || !lfgc_finite(t_min))
+        return LFGC_E_SHAPE;
     RayBox box;
     for (int a = 0; a < 3; ++a) {
         box.lo[a] = box_min[a];
         box.hi[a] = box_max[a];
         if (!(box.lo[a] <= box.hi[a])) return LFGC_E_SHAPE;
     }
-    hipLaunchKernelGGL(ray_clip_kernel, dim3((unsigned)((n_rays + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(ray_clip_kernel, dim3(lfgc_row_grid(n_rays)), dim3(kRayBlock), 0, (hipStream_t)stream,
                        origins, dirs, (long long)n_rays, box, t_min, t_max, dt, max_steps, t_near, t_far, n_steps);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
@@ -301,11 +284,11 @@ extern "C" int lfgc_ray_samples_f32(const int32_t* live, int64_t n_live, const f
                                     const float* t_far, const int32_t* n_steps, const int32_t* k_next, float dt, int S, float* pos,
                                     lfgc_stream_t stream) {
     if (!live || !origins || !dirs || !t_near || !t_far || !n_steps || !k_next || !pos) return LFGC_E_NULL;
-    if (n_live < 1 || n_live > 0x7fffffffLL || S < 32 || S % 32 != 0 || !(dt > 0.0f)) return LFGC_E_SHAPE;
+    if (lfgc_ray_list_check(n_live, S, dt) != LFGC_OK) return LFGC_E_SHAPE;
     const long long n_rows = (long long)n_live * S;
-    const long long nblocks = (n_rows + kBlock - 1) / kBlock;
-    if (nblocks > 0x7fffffffLL) return LFGC_E_UNSUPPORTED;
-    hipLaunchKernelGGL(ray_samples_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, n_rows, S, origins,
+    const unsigned nblocks = lfgc_row_grid(n_rows);
+    if (!nblocks) return LFGC_E_UNSUPPORTED;
+    hipLaunchKernelGGL(ray_samples_kernel, dim3(nblocks), dim3(kRayBlock), 0, (hipStream_t)stream, live, n_rows, S, origins,
                        dirs, t_near, t_far, n_steps, k_next, dt, pos);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
@@ -316,18 +299,12 @@ extern "C" int lfgc_ray_composite_f32(const int32_t* live, int64_t n_live, const
                                       int S, const float* tf_table, int K, float v_min, float tf_scale, float opacity_limit, float ka,
                                       float kd, float* state, lfgc_stream_t stream) {
     if (!live || !values || !dirs || !t_near || !t_far || !n_steps || !k_next || !tf_table || !state) return LFGC_E_NULL;
-    if (n_live < 1 || n_live > 0x7fffffffLL || S < 32 || S % 32 != 0 || K < 2 || !(dt > 0.0f)) return LFGC_E_SHAPE;
+    if (lfgc_ray_list_check(n_live, S, dt) != LFGC_OK || K < 2) return LFGC_E_SHAPE;
     if (((uintptr_t)tf_table | (uintptr_t)state) & 15) return LFGC_E_ALIGN;
-    const int per_block = kBlock / kRun;
-    const unsigned nblocks = (unsigned)((n_live + per_block - 1) / per_block);
-    const float4* tab = reinterpret_cast<const float4*>(tf_table);
-    float4* st = reinterpret_cast<float4*>(state);
-    if (grad) hipLaunchKernelGGL(ray_composite_kernel<true>, dim3(nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, (long long)n_live,
-                                 S, values, grad, dirs, t_near, t_far, n_steps, k_next, dt, tab, K, v_min, tf_scale, opacity_limit, ka,
-                                 kd, st);
-    else hipLaunchKernelGGL(ray_composite_kernel<false>, dim3(nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, (long long)n_live,
-                            S, values, grad, dirs, t_near, t_far, n_steps, k_next, dt, tab, K, v_min, tf_scale, opacity_limit, ka, kd,
-                            st);
+    hipLaunchKernelGGL(grad ? ray_composite_kernel<true> : ray_composite_kernel<false>, dim3(lfgc_half_wave_grid(n_live)),
+                       dim3(kRayBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values, grad, dirs, t_near, t_far, n_steps,
+                       k_next, dt, reinterpret_cast<const float4*>(tf_table), K, v_min, tf_scale, opacity_limit, ka, kd,
+                       reinterpret_cast<float4*>(state));
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }
@@ -349,12 +326,11 @@ extern "C" int lfgc_ray_iso_scan_f32(const int32_t* live, int64_t n_live, const 
                                      const int32_t* n_steps, int32_t* k_next, float dt, int S, float iso, float* state, float* bracket,
                                      lfgc_stream_t stream) {
     if (!live || !values || !t_near || !t_far || !n_steps || !k_next || !state || !bracket) return LFGC_E_NULL;
-    if (n_live < 1 || n_live > 0x7fffffffLL || S < 32 || S % 32 != 0 || !(dt > 0.0f) || !finite_f(iso)) return LFGC_E_SHAPE;
+    if (lfgc_ray_list_check(n_live, S, dt) != LFGC_OK || !lfgc_finite(iso)) return LFGC_E_SHAPE;
     if (((uintptr_t)state | (uintptr_t)bracket) & 15) return LFGC_E_ALIGN;
-    const int per_block = kBlock / kRun;
-    const unsigned nblocks = (unsigned)((n_live + per_block - 1) / per_block);
-    hipLaunchKernelGGL(ray_iso_scan_kernel, dim3(nblocks), dim3(kBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values,
-                       t_near, t_far, n_steps, k_next, dt, iso, reinterpret_cast<float4*>(state), reinterpret_cast<float4*>(bracket));
+    hipLaunchKernelGGL(ray_iso_scan_kernel, dim3(lfgc_half_wave_grid(n_live)), dim3(kRayBlock), 0, (hipStream_t)stream, live,
+                       (long long)n_live, S, values, t_near, t_far, n_steps, k_next, dt, iso, reinterpret_cast<float4*>(state),
+                       reinterpret_cast<float4*>(bracket));
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }
@@ -362,9 +338,9 @@ extern "C" int lfgc_ray_iso_scan_f32(const int32_t* live, int64_t n_live, const 
 extern "C" int lfgc_ray_iso_refine_f32(const int32_t* list, int64_t n, const float* values, const float* origins, const float* dirs,
                                        float iso, float* bracket, float* pos, lfgc_stream_t stream) {
     if (!list || !origins || !dirs || !bracket || !pos) return LFGC_E_NULL;
-    if (n < 1 || n > 0x7fffffffLL || !finite_f(iso)) return LFGC_E_SHAPE;
+    if (n < 1 || n > 0x7fffffffLL || !lfgc_finite(iso)) return LFGC_E_SHAPE;
     if ((uintptr_t)bracket & 15) return LFGC_E_ALIGN;
-    hipLaunchKernelGGL(ray_iso_refine_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, list,
+    hipLaunchKernelGGL(ray_iso_refine_kernel, dim3(lfgc_row_grid(n)), dim3(kRayBlock), 0, (hipStream_t)stream, list,
                        (long long)n, values, origins, dirs, iso, reinterpret_cast<float4*>(bracket), pos);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
@@ -375,7 +351,7 @@ extern "C" int lfgc_ray_iso_finish_f32(const int32_t* list, int64_t n, const flo
     if (!list || !origins || !dirs || !bracket || !t_hit || !pos) return LFGC_E_NULL;
     if (n < 1 || n > 0x7fffffffLL) return LFGC_E_SHAPE;
     if ((uintptr_t)bracket & 15) return LFGC_E_ALIGN;
-    hipLaunchKernelGGL(ray_iso_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, list,
+    hipLaunchKernelGGL(ray_iso_finish_kernel, dim3(lfgc_row_grid(n)), dim3(kRayBlock), 0, (hipStream_t)stream, list,
                        (long long)n, origins, dirs, reinterpret_cast<const float4*>(bracket), t_hit, pos);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;

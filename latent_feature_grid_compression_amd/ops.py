@@ -1245,6 +1245,22 @@ def _ray_i32(t: torch.Tensor, what: str) -> torch.Tensor:
     return t
 
 
+def _ray_f32x4(t: torch.Tensor, what: str, rows: Optional[int] = None) -> torch.Tensor:
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 4 or rows not in (None, t.shape[0]):
+        raise ValueError('%s must be a contiguous fp32 (R, 4) tensor' % what)
+    return t
+
+
+def _tf_table(tf_table: torch.Tensor, v_min: float, v_max: float) -> Tuple[int, float]:
+    """(K, tf_scale) of a (K, 4) table over [v_min, v_max]: row u = (v - v_min) * tf_scale holds value v."""
+    K = int(tf_table.shape[0])
+    if tf_table.dim() != 2 or tf_table.shape[1] != 4 or K < 2 or tf_table.dtype != torch.float32 or not tf_table.is_contiguous():
+        raise ValueError('tf_table must be a contiguous fp32 (K, 4) tensor with K >= 2')
+    if not float(v_max) > float(v_min):
+        raise ValueError('v_max must exceed v_min')
+    return K, (K - 1) / (float(v_max) - float(v_min))
+
+
 @_on_device
 def ray_clip(origins: torch.Tensor, dirs: torch.Tensor, box_min, box_max, dt: float, max_steps: int,
              t_min: float = 0.0, t_max: float = float('inf')) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1291,13 +1307,8 @@ def ray_composite(live: torch.Tensor, values: torch.Tensor, grad: Optional[torch
     _require_hip(live, values, grad, dirs, t_near, t_far, n_steps, k_next, tf_table, state)
     live = _ray_i32(live, 'live')
     n_rows = live.numel() * int(S)
-    K = int(tf_table.shape[0])
-    if tf_table.dim() != 2 or tf_table.shape[1] != 4 or K < 2 or tf_table.dtype != torch.float32 or not tf_table.is_contiguous():
-        raise ValueError('tf_table must be a contiguous fp32 (K, 4) tensor with K >= 2')
-    if state.dtype != torch.float32 or not state.is_contiguous() or state.dim() != 2 or state.shape[1] != 4:
-        raise ValueError('state must be a contiguous fp32 (R, 4) tensor')
-    if not float(v_max) > float(v_min):
-        raise ValueError('v_max must exceed v_min')
+    K, tf_scale = _tf_table(tf_table, v_min, v_max)
+    state = _ray_f32x4(state, 'state')
     values = _f32c(values).reshape(-1)
     if values.numel() != n_rows:
         raise ValueError('%d values for %d rays of %d samples' % (values.numel(), live.numel(), S))
@@ -1307,7 +1318,6 @@ def ray_composite(live: torch.Tensor, values: torch.Tensor, grad: Optional[torch
             raise ValueError('grad must be (%d, 3), got %s' % (n_rows, tuple(grad.shape)))
     if not live.numel():
         return
-    tf_scale = (K - 1) / (float(v_max) - float(v_min))
     check(_lib.load().lfgc_ray_composite_f32(live.data_ptr(), live.numel(), values.data_ptr(), _ptr(grad), _f32c(dirs).data_ptr(),
                                              _f32c(t_near).data_ptr(), _f32c(t_far).data_ptr(), _ray_i32(n_steps, 'n_steps').data_ptr(),
                                              _ray_i32(k_next, 'k_next').data_ptr(), float(dt), int(S), tf_table.data_ptr(), K,
@@ -1322,8 +1332,7 @@ def ray_compact(prev: Optional[torch.Tensor], n_steps: torch.Tensor, k_next: tor
     (1 - T < opacity_limit), in order (int32).  Synchronises once to learn their number."""
     _require_hip(prev, n_steps, k_next, state)
     n_steps, k_next = _ray_i32(n_steps, 'n_steps'), _ray_i32(k_next, 'k_next')
-    if state.dtype != torch.float32 or not state.is_contiguous() or tuple(state.shape) != (n_steps.numel(), 4):
-        raise ValueError('state must be a contiguous fp32 (R, 4) tensor')
+    state = _ray_f32x4(state, 'state', rows=n_steps.numel())
     n = n_steps.numel() if prev is None else _ray_i32(prev, 'prev').numel()
     out = torch.empty(n, dtype=torch.int32, device=n_steps.device)
     if n == 0:
@@ -1337,12 +1346,6 @@ def ray_compact(prev: Optional[torch.Tensor], n_steps: torch.Tensor, k_next: tor
 
 
 # ---- first-hit isosurface ray casting: scan, bisection and hit point around the same forward kernel --
-
-def _ray_f32x4(t: torch.Tensor, what: str) -> torch.Tensor:
-    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 4:
-        raise ValueError('%s must be a contiguous fp32 (R, 4) tensor' % what)
-    return t
-
 
 def _iso_value(iso) -> float:
     iso = float(iso)
@@ -1453,18 +1456,13 @@ def brick_occupancy(minmax: torch.Tensor, tf_table: torch.Tensor, v_min: float, 
     """uint8 table, one entry per brick of minmax (..., 2): 0 where the extinction of tf_table (K, 4) is zero on all of
     [min - margin, max + margin], else 1 (lfgc_brick_occupancy_f32).  v_min, v_max as ops.ray_composite takes them."""
     _require_hip(minmax, tf_table)
-    K = int(tf_table.shape[0])
-    if tf_table.dim() != 2 or tf_table.shape[1] != 4 or K < 2 or tf_table.dtype != torch.float32 or not tf_table.is_contiguous():
-        raise ValueError('tf_table must be a contiguous fp32 (K, 4) tensor with K >= 2')
+    K, tf_scale = _tf_table(tf_table, v_min, v_max)
     if minmax.dtype != torch.float32 or not minmax.is_contiguous() or minmax.dim() < 2 or minmax.shape[-1] != 2:
         raise ValueError('minmax must be a contiguous fp32 (..., 2) tensor')
-    if not float(v_max) > float(v_min):
-        raise ValueError('v_max must exceed v_min')
     if not float(margin) >= 0.0:
         raise ValueError('margin must be >= 0')
     occ = torch.empty(minmax.shape[:-1], dtype=torch.uint8, device=minmax.device)
     if occ.numel():
-        tf_scale = (K - 1) / (float(v_max) - float(v_min))
         check(_lib.load().lfgc_brick_occupancy_f32(minmax.data_ptr(), occ.numel(), tf_table.data_ptr(), K, float(v_min), tf_scale,
                                                    float(margin), occ.data_ptr(), _stream(minmax)), 'lfgc_brick_occupancy_f32')
     return occ

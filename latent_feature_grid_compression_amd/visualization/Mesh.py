@@ -20,7 +20,6 @@ is no CPU form of the extraction: CPU tensors raise LfgcError.
 """
 from __future__ import annotations
 
-import math
 from typing import Callable, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -46,12 +45,7 @@ class IsoMesh(NamedTuple):
 
 
 def _check(iso, refine_steps, res, max_slab_voxels):
-    iso = float(iso)
-    if not math.isfinite(iso):
-        raise ValueError('iso must be finite')
-    n_refine = int(refine_steps)
-    if n_refine != refine_steps or not 0 <= n_refine <= 64:
-        raise ValueError('refine_steps must be an integer in [0, 64]')
+    iso, n_refine = Render._iso_args(iso, refine_steps)
     res = tuple(int(v) for v in res)
     if len(res) != 3 or min(res) < 2:
         raise ValueError('the lattice needs three extents of at least 2, got %s' % (res,))
@@ -109,13 +103,8 @@ def isosurface_mesh(value_slab_fn: Callable, point_fn: Callable, res: Sequence[i
             if normals:
                 parts['normals'].append(torch.empty((0, 3), dtype=torch.float32, device=dev))
         elif normals:
-            out = point_fn(pos, gradient=True)
-            if not isinstance(out, (tuple, list)) or len(out) != 2 or out[1] is None:
-                raise ValueError('normals=True needs point_fn(pos, gradient=True) to return (values, gradients)')
-            g = out[1].reshape(-1, 3).to(torch.float32)
-            gn = g.norm(dim=1, keepdim=True)
-            parts['normals'].append(torch.where(gn > 0, -g / gn, torch.zeros_like(g)))
-            out = out[0]
+            out, g = Render._values_and_gradients(point_fn(pos, gradient=True), 'point_fn')
+            parts['normals'].append(Render._unit(-g))           # -g / |g|, +0 for a zero gradient
         else:
             out = point_fn(pos)
         parts['values'].append(out.reshape(-1).to(torch.float32))

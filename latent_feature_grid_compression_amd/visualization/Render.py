@@ -319,14 +319,8 @@ def render_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor, dir
     if kwargs.get('shading'):
         raise ValueError('render_from_volume has no gradients: shading is not available')
     scales = _scales_of(dataset)
-    if step is None:
-        step = 1.0 / float(dataset.max_dim)
-    volume = ops._f32c(volume.detach())
-    mn, mx, res = dataset.min_idx.tolist(), dataset.max_idx.tolist(), dataset.vol_res.tolist()
-
-    def value_fn(pos):
-        return ops.gt_interp(index_positions(dataset, pos), volume, mn, mx, res)
-    return render(value_fn, origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
+    step = _default_step(dataset, step)
+    return render(volume_value_fn(dataset, volume), origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
 
 
 # ---- empty-space skipping: value ranges of bricks of the field -------------------------------------------------------------
@@ -336,7 +330,7 @@ VOLUME_SKIP_MARGIN = 1e-5     # the three nested fp32 lerps of ops.gt_interp lea
 # 1.6e-3 with random weights, 0.13 after 113 train steps on the smooth volume.  A guard against an unmeasured model, wide
 # enough to leave little to skip; measure brick_range_excess for the model at hand and pass skip_margin to do better.
 NET_SKIP_MARGIN = 0.3
-_SKIP_GUARD = 0.0625          # include/lfgc.h, lfgc_ray_skip_f32: 1/16 cell around a sample's cell coordinate
+_SKIP_GUARD = 0.0625          # LFGC_RAY_SKIP_GUARD of include/lfgc.h (tests/test_render_skip_host.py compares the two)
 
 
 class BrickRanges:
@@ -479,6 +473,26 @@ def image_psnr(a: torch.Tensor, b: torch.Tensor, peak: float = 1.0) -> float:
 
 # ---- first-hit isosurface ray casting -------------------------------------------------------------------------------------
 
+def _iso_args(iso, refine_steps) -> Tuple[float, int]:
+    iso = ops._iso_value(iso)
+    n_refine = int(refine_steps)
+    if n_refine != refine_steps or not 0 <= n_refine <= 64:
+        raise ValueError('refine_steps must be an integer in [0, 64]')
+    return iso, n_refine
+
+
+def _values_and_gradients(out, who: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(values (n,), gradients (n, 3)) fp32 of what ``who``(pos, gradient=True) returned."""
+    if not isinstance(out, (tuple, list)) or len(out) != 2 or out[1] is None:
+        raise ValueError('normals=True needs %s(pos, gradient=True) to return (values, gradients)' % who)
+    return out[0].reshape(-1).to(torch.float32), out[1].reshape(-1, 3).to(torch.float32)
+
+
+def _unit(g: torch.Tensor) -> torch.Tensor:                       # g / |g| per row, zero where the gradient is zero
+    gn = g.norm(dim=1, keepdim=True)
+    return torch.where(gn > 0, g / gn, torch.zeros_like(g))
+
+
 class IsoHits(NamedTuple):
     """Result of ``isosurface``, one row per ray."""
     hit: torch.Tensor          # (R,) bool
@@ -514,12 +528,7 @@ def isosurface(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, is
 
     ``stats``: a dict that receives 'live' (marching rays per block), 'samples' (rows evaluated in the march), 'blocks',
     'bracketed' (rays with a hit) and 'refine_samples' (rows evaluated for the bisection and at the hit points)."""
-    iso = float(iso)
-    if not math.isfinite(iso):
-        raise ValueError('iso must be finite')
-    n_refine = int(refine_steps)
-    if n_refine != refine_steps or not 0 <= n_refine <= 64:
-        raise ValueError('refine_steps must be an integer in [0, 64]')
+    iso, n_refine = _iso_args(iso, refine_steps)
     S = int(block_steps)
 
     def scan(rays, part, pos):
@@ -544,15 +553,10 @@ def isosurface(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, is
         n_refined += (n_refine + 1) * part.numel()
         t[idx], position[idx] = t_hit, p_hit
         if normals:
-            out = value_fn(p_hit, gradient=True)
-            if not isinstance(out, (tuple, list)) or len(out) != 2 or out[1] is None:
-                raise ValueError('normals=True needs value_fn(pos, gradient=True) to return (values, gradients)')
-            g = out[1].reshape(-1, 3).to(torch.float32)
-            gn = g.norm(dim=1, keepdim=True)
-            unit = torch.where(gn > 0, g / gn, torch.zeros_like(g))
+            value[idx], g = _values_and_gradients(value_fn(p_hit, gradient=True), 'value_fn')
+            unit = _unit(g)
             away = (unit * dirs[idx]).sum(1, keepdim=True) > 0
             normal[idx] = torch.where(away, -unit, unit)
-            value[idx] = out[0].reshape(-1).to(torch.float32)
         else:
             value[idx] = value_fn(p_hit).reshape(-1).to(torch.float32)
     inf = torch.full_like(t, float('inf'))

@@ -18,10 +18,26 @@ def inside(v, iso):
         return (np.asarray(v, F) - F(iso)).astype(F) >= 0
 
 
-def t_mid(tn, tf, k, dt):
-    """t_m(k) = 0.5f*(a+b) of segment k: where lfgc_ray_samples_f32 puts sample k."""
-    a, b = RR.segments(np.asarray(tn, F), np.asarray(tf, F), np.asarray(k), dt)
-    return (F(0.5) * (a + b).astype(F)).astype(F)
+t_mid = RR.t_mid
+
+
+def same(a, b):
+    """np.array_equal that lets a NaN equal a NaN (the scan test carries NaN values on purpose)."""
+    return np.array_equal(a, b, equal_nan=True)
+
+
+def quad_torch(pos, gradient=False):
+    """0.5 - ((x x + y y) + z z), one rounded fp32 operation per torch call: the test function of the ray caster and the mesh."""
+    import torch
+    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+    v = torch.full_like(x, 0.5) - ((x * x + y * y) + z * z)
+    return (v, -2.0 * pos) if gradient else v
+
+
+def quad_numpy(p):
+    p = np.asarray(p, F)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return (F(0.5) - ((x * x + y * y).astype(F) + z * z).astype(F)).astype(F)
 
 
 def new_state(n_rays):

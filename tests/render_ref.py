@@ -49,13 +49,25 @@ def segments(tn, tf, k, dt):
     return a, b
 
 
+def t_mid(tn, tf, k, dt):
+    """t_m(k) = 0.5f*(a+b) of segment k (float32): where lfgc_ray_samples_f32 puts sample k."""
+    a, b = segments(np.asarray(tn, F), np.asarray(tf, F), np.asarray(k), dt)
+    return (F(0.5) * (a + b).astype(F)).astype(F)
+
+
+def tf_coordinate(v, K, v_min, v_max):
+    """u(v) = fminf(fmaxf((v - v_min) * tf_scale, 0), K - 1) in float32, tf_scale the float ops.ray_composite passes."""
+    tf_scale = F((K - 1) / (float(v_max) - float(v_min)))
+    with np.errstate(all='ignore'):
+        return np.fmin(np.fmax(((np.asarray(v, F) - F(v_min)).astype(F) * tf_scale).astype(F), F(0)), F(K - 1)).astype(F)
+
+
 def samples(live, origins, dirs, tn, tf, n_steps, k_next, dt, S):
     o, d = np.asarray(origins, F), np.asarray(dirs, F)
     r = np.repeat(np.asarray(live, np.int64), S)
     s = np.tile(np.arange(S, dtype=np.int64), len(live))
     k = np.maximum(np.minimum(k_next[r].astype(np.int64) + s, n_steps[r].astype(np.int64) - 1), 0)
-    a, b = segments(tn[r], tf[r], k, dt)
-    tm = (F(0.5) * (a + b).astype(F)).astype(F)
+    tm = t_mid(tn[r], tf[r], k, dt)
     p = (o[r] + (tm[:, None] * d[r]).astype(F)).astype(F)
     return p, k
 

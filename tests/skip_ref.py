@@ -12,7 +12,7 @@ import numpy as np
 import render_ref as RR
 
 F = np.float32
-GUARD = F(0.0625)
+GUARD = F(0.0625)                  # LFGC_RAY_SKIP_GUARD of include/lfgc.h (test_render_skip_host.py compares the two)
 
 
 def brick_counts(cells, B):
@@ -33,11 +33,7 @@ def brick_minmax(vol, B):
     return out
 
 
-def tf_coordinate(v, K, v_min, v_max):
-    """u(v) = fminf(fmaxf((v - v_min) * tf_scale, 0), K - 1) in float32, tf_scale the float ops.ray_composite passes."""
-    tf_scale = F((K - 1) / (float(v_max) - float(v_min)))
-    with np.errstate(all='ignore'):
-        return np.fmin(np.fmax(((np.asarray(v, F) - F(v_min)).astype(F) * tf_scale).astype(F), F(0)), F(K - 1)).astype(F)
+tf_coordinate = RR.tf_coordinate
 
 
 def occupancy(minmax, table, v_min, v_max, margin):
@@ -81,8 +77,7 @@ def skip(rays, origins, dirs, tn, tf, n_steps, k_next, dt, S, box_min, box_max, 
         n = int(n_steps[r])
         while k_next[r] < n:
             k = np.arange(k_next[r], min(k_next[r] + S, n), dtype=np.int64)
-            a, b = RR.segments(tn[r], tf[r], k, dt)
-            tm = (F(0.5) * (a + b).astype(F)).astype(F)
+            tm = RR.t_mid(tn[r], tf[r], k, dt)
             p = (o[r][None, :] + (tm[:, None] * d[r][None, :]).astype(F)).astype(F)
             if flat[touched(p, box_min, box_max, cells, B)].any():
                 break

@@ -12,27 +12,9 @@ import iso_ref as IR
 import render_ref as RR
 from test_hip_forward import build_synth, dev  # noqa: F401
 from test_gradient_gpu import _oracle, TOL
+from test_render_gpu import _ops, _render, _t
 
 pytestmark = pytest.mark.gpu
-
-
-def _ops():
-    from latent_feature_grid_compression_amd import ops
-    return ops
-
-
-def _render():
-    from latent_feature_grid_compression_amd.visualization import Render
-    return Render
-
-
-def _t(a, dev_):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev_)
-
-
-def _same(a, b):
-    """np.array_equal that lets a NaN equal a NaN (the scan test carries NaN values on purpose)."""
-    return np.array_equal(a, b, equal_nan=True)
 
 
 # ---- 1. scan, bit for bit ---------------------------------------------------------------------------------------------------
@@ -88,8 +70,8 @@ def test_scan_equals_the_restatement(dev, S, n_list):
     R_ = len(case['n_steps'])
     for got, want in zip(lists, r_lists):
         assert np.array_equal(got, want)                        # the compaction keeps exactly the marching rays, in order
-    assert _same(state[:R_], r_state)                           # carry and finished flag
-    assert _same(bracket[:R_], r_bracket)
+    assert IR.same(state[:R_], r_state)                           # carry and finished flag
+    assert IR.same(bracket[:R_], r_bracket)
     assert np.array_equal(k_next[:R_], r_k)
     hit = state[:R_, 3] == 0
     assert np.array_equal(k_next[:R_][rays][hit[rays]], case['expect'][rays][hit[rays]])
@@ -110,24 +92,12 @@ def test_a_sub_list_scans_to_the_same_rays(dev, S):
     sub = np.ascontiguousarray(case['live'][1::3])
     part = _device_chain(case, sub, dev)
     for a, b in zip(full[:3], part[:3]):
-        assert _same(a[sub], b[sub])
+        assert IR.same(a[sub], b[sub])
 
 
 # ---- 2. refine and finish, bit for bit, through the loop -----------------------------------------------------------------------
 
 _QUAD_ISO = -0.3          # |p|^2 = 0.8: a sphere that holds most of the box -- rays enter it, start inside it and leave it
-
-
-def _quad_torch(pos, gradient=False):
-    """0.5 - ((x x + y y) + z z), one rounded fp32 operation per torch call."""
-    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
-    return torch.full_like(x, 0.5) - ((x * x + y * y) + z * z)
-
-
-def _quad_numpy(p):
-    p = np.asarray(p, np.float32)
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    return (np.float32(0.5) - ((x * x + y * y).astype(np.float32) + z * z).astype(np.float32)).astype(np.float32)
 
 
 def _directed_ray_set(dev_):
@@ -143,16 +113,16 @@ def test_refine_and_finish_equal_the_restatement(dev, refine_steps):
     Rn = _render()
     o, d, dn = _directed_ray_set(dev)
     stats = {}
-    res = Rn.isosurface(_quad_torch, o, d, _QUAD_ISO, RR.DT, RR.BOX[0], RR.BOX[1], refine_steps=refine_steps, normals=False,
+    res = Rn.isosurface(IR.quad_torch, o, d, _QUAD_ISO, RR.DT, RR.BOX[0], RR.BOX[1], refine_steps=refine_steps, normals=False,
                         stats=stats)
-    ref = IR.march(_quad_numpy, o.cpu().numpy(), dn.cpu().numpy(), _QUAD_ISO, RR.DT, RR.BOX, refine_steps)
+    ref = IR.march(IR.quad_numpy, o.cpu().numpy(), dn.cpu().numpy(), _QUAD_ISO, RR.DT, RR.BOX, refine_steps)
     assert ref['hit'].sum() > 150 and (~ref['hit']).sum() > 150 and (ref['k'] > 32).sum() > 10      # also in the second block
     assert stats['bracketed'] == ref['hit'].sum() and stats['blocks'] >= 2
     assert np.array_equal(res.hit.cpu().numpy(), ref['hit'])
     for name in ('t_lo', 't_hi', 't', 'position'):
         assert np.array_equal(getattr(res, name).cpu().numpy(), ref[name]), name
     h = ref['hit']
-    assert np.array_equal(res.value.cpu().numpy()[h], _quad_numpy(ref['position'][h]))
+    assert np.array_equal(res.value.cpu().numpy()[h], IR.quad_numpy(ref['position'][h]))
     assert not res.normal.any() and not res.value[~res.hit].any() and not res.position[~res.hit].any()
     width = ref['t_hi'][h].astype(np.float64) - ref['t_lo'][h]
     assert (width <= RR.DT * 2.0 ** -refine_steps + 2 * np.spacing(ref['t_hi'][h])).all()

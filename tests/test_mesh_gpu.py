@@ -8,31 +8,20 @@ import numpy as np
 import pytest
 import torch
 
+import iso_ref as IR
 import mesh_ref as MR
 from test_hip_forward import build_synth, dev  # noqa: F401
 from test_gradient_gpu import TOL
+from test_render_gpu import _ops, _t
 
 pytestmark = pytest.mark.gpu
 
 _ROWS = 5                  # sentinel rows after every output
 
 
-def _ops():
-    from latent_feature_grid_compression_amd import ops
-    return ops
-
-
 def _mesh():
     from latent_feature_grid_compression_amd.visualization import Mesh
     return Mesh
-
-
-def _t(a, dev_):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev_)
-
-
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
 
 
 # ---- 1. count and emit, bit for bit ------------------------------------------------------------------------------------------
@@ -82,7 +71,7 @@ def test_count_and_emit_equal_the_restatement(dev, shape):
         assert (V, T) == (want_V, want_T), (x0, x1, xe)
         r_o, r_d, r_br, r_tr = MR.emit(vals, x1 - x0, iso, xs, tabs[1], tabs[2], base)
         assert np.array_equal(o, r_o) and np.array_equal(d, r_d), (x0, x1, xe)
-        assert _same(br, r_br), (x0, x1, xe)
+        assert IR.same(br, r_br), (x0, x1, xe)
         assert np.array_equal(tr, r_tr), (x0, x1, xe)
 
 
@@ -105,7 +94,7 @@ def test_count_and_emit_across_the_scans_carry(dev, n_owner):
     assert (V, T) == (want_V, want_T)
     r_o, r_d, r_br, r_tr = MR.emit(vals, n_owner, iso, *tabs, 7)
     assert np.array_equal(o, r_o) and np.array_equal(d, r_d)
-    assert _same(br, r_br)
+    assert IR.same(br, r_br)
     assert np.array_equal(tr, r_tr)
 
 
@@ -123,7 +112,7 @@ def test_two_runs_give_the_same_bits(dev):
     v, tabs, iso = MR.random_case((33, 9, 34), 102)
     a = _emit_with_sentinels(v, 33, iso, tabs, 0, dev)
     b = _emit_with_sentinels(v, 33, iso, tabs, 0, dev)
-    assert a[:2] == b[:2] and all(_same(x, y) for x, y in zip(a[2:], b[2:]))
+    assert a[:2] == b[:2] and all(IR.same(x, y) for x, y in zip(a[2:], b[2:]))
 
 
 # ---- 2. the loop on analytic value functions -----------------------------------------------------------------------------------
@@ -132,25 +121,12 @@ _QUAD_ISO = -0.3
 _QUAD_RES = (13, 12, 11)
 
 
-def _quad_torch(pos, gradient=False):
-    """0.5 - ((x x + y y) + z z), one rounded fp32 operation per torch call (the ray caster's test function)."""
-    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
-    v = torch.full_like(x, 0.5) - ((x * x + y * y) + z * z)
-    return (v, -2.0 * pos) if gradient else v
-
-
-def _quad_numpy(p):
-    p = np.asarray(p, np.float32)
-    x, y, z = p[:, 0], p[:, 1], p[:, 2]
-    return (np.float32(0.5) - ((x * x + y * y).astype(np.float32) + z * z).astype(np.float32)).astype(np.float32)
-
-
 def _quad_case(dev_):
     """Lattice of linspace(-0.8, 0.95): the sphere |p|^2 = 0.8 leaves it through the three low faces and closes inside the
     three high ones.  Returns (numpy tables, lattice values, slab function, device tables)."""
     tabs = [np.linspace(-0.8, 0.95, n).astype(np.float32) for n in _QUAD_RES]
     P = np.stack(np.meshgrid(*tabs, indexing='ij'), -1).reshape(-1, 3)
-    lat = _quad_numpy(P).reshape(_QUAD_RES)
+    lat = IR.quad_numpy(P).reshape(_QUAD_RES)
     lat_d = _t(lat, dev_)
     return tabs, lat, (lambda b, e: lat_d[b:e]), tuple(_t(t, dev_) for t in tabs)
 
@@ -159,13 +135,13 @@ def _quad_case(dev_):
 def test_the_loop_equals_the_restatement_whatever_the_slabs(dev, refine_steps):
     Mesh = _mesh()
     tabs, lat, slab_fn, tabs_d = _quad_case(dev)
-    ref = MR.mesh(lat, *tabs, _QUAD_ISO, refine_steps, _quad_numpy)
+    ref = MR.mesh(lat, *tabs, _QUAD_ISO, refine_steps, IR.quad_numpy)
     assert len(ref['vertices']) > 300 and len(ref['triangles']) > 600
     plane = _QUAD_RES[1] * _QUAD_RES[2]
     meshes = []
     for owner, n_slabs in ((None, 1), (1, 11), (2, 6), (5, 3)):
         stats = {}
-        m = Mesh.isosurface_mesh(slab_fn, _quad_torch, _QUAD_RES, tabs_d, _QUAD_ISO, refine_steps=refine_steps,
+        m = Mesh.isosurface_mesh(slab_fn, IR.quad_torch, _QUAD_RES, tabs_d, _QUAD_ISO, refine_steps=refine_steps,
                                  max_slab_voxels=(1 << 24) if owner is None else (owner + 2) * plane, stats=stats)
         assert stats['slabs'] == n_slabs == len(MR.slabs(_QUAD_RES[0], owner))
         meshes.append(m)
@@ -185,9 +161,9 @@ def test_the_loop_equals_the_restatement_whatever_the_slabs(dev, refine_steps):
     assert float((base.normals.double() - p / p.norm(dim=1, keepdim=True)).abs().max()) <= 1e-6
     agree, _ = MR.winding_agreement(base.vertices.cpu().numpy(), ref['triangles'], base.normals.cpu().numpy())
     assert agree == 1.0
-    none = Mesh.isosurface_mesh(slab_fn, _quad_torch, _QUAD_RES, tabs_d, _QUAD_ISO, refine_steps=refine_steps, normals=False)
+    none = Mesh.isosurface_mesh(slab_fn, IR.quad_torch, _QUAD_RES, tabs_d, _QUAD_ISO, refine_steps=refine_steps, normals=False)
     assert none.normals is None and torch.equal(none.vertices, base.vertices) and torch.equal(none.values, base.values)
-    empty = Mesh.isosurface_mesh(slab_fn, _quad_torch, _QUAD_RES, tabs_d, 0.75, refine_steps=refine_steps)      # above the maximum
+    empty = Mesh.isosurface_mesh(slab_fn, IR.quad_torch, _QUAD_RES, tabs_d, 0.75, refine_steps=refine_steps)      # above the maximum
     assert empty.vertices.shape == (0, 3) and empty.triangles.shape == (0, 3) and empty.normals.shape == (0, 3)
 
 

@@ -9,24 +9,11 @@ import torch
 import render_ref as RR
 import skip_ref as SR
 from test_hip_forward import build_synth, dev  # noqa: F401
+from test_render_gpu import _ops, _render, _t
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-
-
-def _ops():
-    from latent_feature_grid_compression_amd import ops
-    return ops
-
-
-def _render():
-    from latent_feature_grid_compression_amd.visualization import Render
-    return Render
-
-
-def _t(a, dev_):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev_)
 
 
 # ---- 1. brick ranges --------------------------------------------------------------------------------------------------------
