@@ -683,6 +683,41 @@ int lfgc_ray_composite_f32(const int32_t* live, int64_t n_live, const float* val
                            int S, const float* tf_table, int K, float v_min, float tf_scale, float opacity_limit, float ka,
                            float kd, float* state, lfgc_stream_t stream);
 
+/* lfgc_ray_composite_f32 under a 2-D transfer function over the value and the gradient magnitude: the same lists, the same
+ * state, segment length, alpha, shading, contribution rule, scan and sums -- the lookup is the only difference.
+ *   grad (n_live*S, 3) REQUIRED, in the units the table's g axis is in (lfgc_input_gradient_f32: per unit of normalised
+ *   position);  tf_table (Kv,Kg,4) row-major, entry tab[i*Kg + j] = r, g, b, extinction (16-byte aligned), Kv >= 2, Kg >= 2,
+ *   Kv*Kg <= 2^22, read through the caches;  tf_scale = (Kv-1)/(v_max-v_min);  g_scale = (Kg-1)/g_max, finite and > 0: row j of
+ *   the g axis sits at |g| = j*g_max/(Kg-1), the first at 0;  shade: 0 = no shading (shade = 1), 1 = the headlight with ka, kd.
+ * Per sample k < n_steps, fp32, one rounding per operation, in this order:
+ *   u  = fminf(fmaxf((v-v_min)*tf_scale, 0), Kv-1);  i = min((int)u, Kv-2);  f = u - i;
+ *   gn = sqrtf((gx*gx + gy*gy) + gz*gz)                                   -- the |g| of the shading
+ *   w  = fminf(fmaxf((gn-0)*g_scale, 0), Kg-1);      j = min((int)w, Kg-2);  h = w - j;
+ *   lo = tab[i][j]   + f*(tab[i+1][j]   - tab[i][j]);
+ *   hi = tab[i][j+1] + f*(tab[i+1][j+1] - tab[i][j+1]);
+ *   rgba = lo + h*(hi - lo);
+ * then as lfgc_ray_composite_f32.  A NaN value or gradient lands in row 0 of its axis (fmaxf), an infinite |g| in the last.
+ * A table that does not depend on j gives lo == hi and with it the bits of lfgc_ray_composite_f32 on its (Kv,4) column.
+ * Refused: LFGC_E_NULL for a missing pointer (grad included), LFGC_E_SHAPE for Kv < 2, Kg < 2, Kv*Kg > 2^22, a g_scale that
+ * is not finite and positive, shade outside {0, 1} and the list errors of lfgc_ray_composite_f32. */
+int lfgc_ray_composite2d_f32(const int32_t* live, int64_t n_live, const float* values, const float* grad, const float* dirs,
+                             const float* t_near, const float* t_far, const int32_t* n_steps, int32_t* k_next, float dt,
+                             int S, const float* tf_table, int Kv, int Kg, float v_min, float tf_scale, float g_scale,
+                             int shade, float opacity_limit, float ka, float kd, float* state, lfgc_stream_t stream);
+
+/* Joint histogram of value and gradient magnitude, the tool such a table is designed with:  counts[i*Bg + j] += the number
+ * of the n samples whose cell is (i, j), where (i, j) is the cell lfgc_ray_composite2d_f32 interpolates in for a table of
+ * (Bv+1, Bg+1) rows, by the same fp32 operations:  u = fminf(fmaxf((v-v_min)*v_scale, 0), Bv), i = min((int)u, Bv-1);
+ * gn as above, w = fminf(fmaxf(gn*g_scale, 0), Bg), j = min((int)w, Bg-1).  Values outside the range and |g| above g_max fall
+ * into the end bins, a NaN into bin 0 of its axis.
+ *   values device (n); grad device (n,3); v_scale = Bv/(v_max-v_min); g_scale = Bg/g_max, both finite and > 0;
+ *   counts device int64 (Bv,Bg), 8-byte aligned, ACCUMULATED into: the caller zeroes it once.
+ * One LDS histogram of 32-bit counters per workgroup (Bv*Bg <= 16384, else LFGC_E_UNSUPPORTED), at most 2^31 + 256 rows per
+ * workgroup, flushed with 64-bit integer atomics for the non-zero bins: the sums are integers, so the counts depend neither
+ * on scheduling nor on how the samples are cut into calls.  n == 0 returns LFGC_OK at once. */
+int lfgc_joint_histogram_f32(const float* values, const float* grad, int64_t n, int Bv, int Bg, float v_min, float v_scale,
+                             float g_scale, int64_t* counts, lfgc_stream_t stream);
+
 /* live_out[0..*count) = the rays r of prev[0..n_prev) (prev == NULL: r = 0..n_prev-1) with k_next[r] < n_steps[r] and
  * 1 - T[r] < opacity_limit, in the order of prev (ascending ids stay ascending: neighbouring pixels stay neighbours, and
  * the list does not depend on scheduling).  count: device int64.  live_out must not alias prev. */

@@ -45,6 +45,43 @@ __device__ __forceinline__ float lfgc_tf_coordinate(float v, float v_min, float 
     return fminf(fmaxf((v - v_min) * tf_scale, 0.0f), u_max);
 }
 
+// the cell i = min((int)u, K - 2) of such a coordinate in a table of K rows and the fraction f = u - i inside it
+__device__ __forceinline__ void lfgc_tf_cell(float u, int K, int& i, float& f) {
+    i = (int)u;
+    if (i > K - 2) i = K - 2;
+    f = u - (float)i;
+}
+__device__ __forceinline__ float4 lfgc_tf_lerp(const float4& c0, const float4& c1, float f) {
+    return make_float4(c0.x + f * (c1.x - c0.x), c0.y + f * (c1.y - c0.y), c0.z + f * (c1.z - c0.z), c0.w + f * (c1.w - c0.w));
+}
+// rgba of value v in a 1-D table of K rows
+__device__ __forceinline__ float4 lfgc_tf_lookup(const float4* __restrict__ tab, int K, float v, float v_min, float tf_scale) {
+    int i;
+    float f;
+    lfgc_tf_cell(lfgc_tf_coordinate(v, v_min, tf_scale, (float)(K - 1)), K, i, f);
+    return lfgc_tf_lerp(tab[i], tab[i + 1], f);
+}
+// the cell (i, j) and the fractions (f, h) of value v and gradient magnitude gn in a row-major (Kv, Kg) table whose g axis
+// starts at 0: a NaN of either lands in row 0 of its axis (fmaxf)
+__device__ __forceinline__ void lfgc_tf_cell2d(int Kv, int Kg, float v, float gn, float v_min, float tf_scale, float g_scale,
+                                               int& i, float& f, int& j, float& h) {
+    lfgc_tf_cell(lfgc_tf_coordinate(v, v_min, tf_scale, (float)(Kv - 1)), Kv, i, f);
+    lfgc_tf_cell(lfgc_tf_coordinate(gn, 0.0f, g_scale, (float)(Kg - 1)), Kg, j, h);
+}
+// rgba of (v, gn) in such a table, entry tab[i * Kg + j]: along the value in both g rows, then along g
+__device__ __forceinline__ float4 lfgc_tf_lookup2d(const float4* __restrict__ tab, int Kv, int Kg, float v, float gn, float v_min,
+                                                   float tf_scale, float g_scale) {
+    int i, j;
+    float f, h;
+    lfgc_tf_cell2d(Kv, Kg, v, gn, v_min, tf_scale, g_scale, i, f, j, h);
+    const float4* row = tab + (long long)i * Kg + j;
+    const float4 lo = lfgc_tf_lerp(row[0], row[Kg], f);
+    const float4 hi = lfgc_tf_lerp(row[1], row[Kg + 1], f);
+    return lfgc_tf_lerp(lo, hi, h);
+}
+// |g| as the shading and the tables form it
+__device__ __forceinline__ float lfgc_grad_norm(float gx, float gy, float gz) { return sqrtf(gx * gx + gy * gy + gz * gz); }
+
 // ---- host side of the entries ---------------------------------------------------------------------------------------------
 inline bool lfgc_finite(float v) { return v - v == 0.0f; }
 

@@ -5,6 +5,7 @@
 //                            tile of the forward kernel is 32 consecutive steps of ONE ray
 //   lfgc_ray_composite_f32   transfer function, headlight shading and front-to-back compositing of those S samples
 //                            into the per-ray state (premultiplied r, g, b and the transmittance T)
+//   lfgc_ray_composite2d_f32 the same under a 2-D table over value and gradient magnitude
 //   lfgc_ray_compact         order-preserving list of the rays that still have steps left and are not yet opaque
 //   lfgc_ray_iso_scan_f32    first-hit isosurface: the first sign change of v - iso among those S samples -> a bracket
 //   lfgc_ray_iso_refine_f32  one bisection step of every bracket, and the position of the next trial
@@ -81,15 +82,16 @@ __global__ __launch_bounds__(kRayBlock) void ray_samples_kernel(const int* __res
 // (1 - alpha) factors and a butterfly sum of the contributions.  T never increases, so the samples that contribute are a
 // prefix of the run: T after the run is T before the first lane that does not contribute.  The lanes a ray's samples sit
 // on do not depend on the list the ray is in, so neither does a single bit of its result.
-template <bool SHADE>
+// TF2D: the table is (K, Kg) over value and gradient magnitude (lfgc_tf_lookup2d) -- the lookup is the only difference.
+template <bool SHADE, bool TF2D>
 __global__ __launch_bounds__(kRayBlock) void ray_composite_kernel(const int* __restrict__ live, long long n_live, int S,
                                                                   const float* __restrict__ values, const float* __restrict__ grad,
                                                                   const float* __restrict__ dirs, const float* __restrict__ t_near,
                                                                   const float* __restrict__ t_far, const int* __restrict__ n_steps,
                                                                   int* __restrict__ k_next, float dt,
-                                                                  const float4* __restrict__ tab, int K, float v_min, float tf_scale,
-                                                                  float opacity_limit, float ka, float kd,
-                                                                  float4* __restrict__ state) {
+                                                                  const float4* __restrict__ tab, int K, int Kg, float v_min,
+                                                                  float tf_scale, float g_scale, float opacity_limit, float ka,
+                                                                  float kd, float4* __restrict__ state) {
     const LfgcHalfWave hw;
     if (hw.j >= n_live) return;                  // a whole half wave leaves: the shuffles below stay inside one half
     const long long r = live[hw.j];
@@ -99,7 +101,6 @@ __global__ __launch_bounds__(kRayBlock) void ray_composite_kernel(const int* __r
     if (SHADE) { dx = dirs[r * 3 + 0]; dy = dirs[r * 3 + 1]; dz = dirs[r * 3 + 2]; }
     const float4 st = state[r];
     float cr = st.x, cg = st.y, cb = st.z, T = st.w;
-    const float u_max = (float)(K - 1);
     for (int s0 = 0; s0 < S; s0 += kRayRun) {
         const long long row = hw.j * S + s0 + hw.lane;
         const int k = k0 + s0 + hw.lane;
@@ -108,23 +109,20 @@ __global__ __launch_bounds__(kRayBlock) void ray_composite_kernel(const int* __r
             float a, b;
             lfgc_ray_segment(tn, tf, dt, k, a, b);
             const float len = fmaxf(b - a, 0.0f);        // a step count rounded up: the last segment starts an ulp past t_far
-            const float u = lfgc_tf_coordinate(values[row], v_min, tf_scale, u_max);
-            int i = (int)u;
-            if (i > K - 2) i = K - 2;
-            const float f = u - (float)i;
-            const float4 c0 = tab[i], c1 = tab[i + 1];
-            const float sigma = c0.w + f * (c1.w - c0.w);
-            alpha = 1.0f - expf(-sigma * len);
-            float shade = 1.0f;
-            if (SHADE) {
-                const float gx = grad[row * 3 + 0], gy = grad[row * 3 + 1], gz = grad[row * 3 + 2];
-                const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
-                shade = gn > 0.0f ? ka + kd * fabsf(gx * dx + gy * dy + gz * dz) / gn : ka + kd;
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f, gn = 0.0f;
+            if (SHADE || TF2D) {
+                gx = grad[row * 3 + 0]; gy = grad[row * 3 + 1]; gz = grad[row * 3 + 2];
+                gn = lfgc_grad_norm(gx, gy, gz);
             }
+            const float4 rgba = TF2D ? lfgc_tf_lookup2d(tab, K, Kg, values[row], gn, v_min, tf_scale, g_scale)
+                                     : lfgc_tf_lookup(tab, K, values[row], v_min, tf_scale);
+            alpha = 1.0f - expf(-rgba.w * len);
+            float shade = 1.0f;
+            if (SHADE) shade = gn > 0.0f ? ka + kd * fabsf(gx * dx + gy * dy + gz * dz) / gn : ka + kd;
             const float w = alpha * shade;
-            er = w * (c0.x + f * (c1.x - c0.x));
-            eg = w * (c0.y + f * (c1.y - c0.y));
-            eb = w * (c0.z + f * (c1.z - c0.z));
+            er = w * rgba.x;
+            eg = w * rgba.y;
+            eb = w * rgba.z;
         }
         float incl = 1.0f - alpha;               // inclusive product of the factors of lanes 0..lane
 #pragma unroll
@@ -301,10 +299,27 @@ extern "C" int lfgc_ray_composite_f32(const int32_t* live, int64_t n_live, const
     if (!live || !values || !dirs || !t_near || !t_far || !n_steps || !k_next || !tf_table || !state) return LFGC_E_NULL;
     if (lfgc_ray_list_check(n_live, S, dt) != LFGC_OK || K < 2) return LFGC_E_SHAPE;
     if (((uintptr_t)tf_table | (uintptr_t)state) & 15) return LFGC_E_ALIGN;
-    hipLaunchKernelGGL(grad ? ray_composite_kernel<true> : ray_composite_kernel<false>, dim3(lfgc_half_wave_grid(n_live)),
-                       dim3(kRayBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values, grad, dirs, t_near, t_far, n_steps,
-                       k_next, dt, reinterpret_cast<const float4*>(tf_table), K, v_min, tf_scale, opacity_limit, ka, kd,
-                       reinterpret_cast<float4*>(state));
+    hipLaunchKernelGGL((grad ? ray_composite_kernel<true, false> : ray_composite_kernel<false, false>),
+                       dim3(lfgc_half_wave_grid(n_live)), dim3(kRayBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values,
+                       grad, dirs, t_near, t_far, n_steps, k_next, dt, reinterpret_cast<const float4*>(tf_table), K, 0, v_min,
+                       tf_scale, 0.0f, opacity_limit, ka, kd, reinterpret_cast<float4*>(state));
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_ray_composite2d_f32(const int32_t* live, int64_t n_live, const float* values, const float* grad, const float* dirs,
+                                        const float* t_near, const float* t_far, const int32_t* n_steps, int32_t* k_next, float dt,
+                                        int S, const float* tf_table, int Kv, int Kg, float v_min, float tf_scale, float g_scale,
+                                        int shade, float opacity_limit, float ka, float kd, float* state, lfgc_stream_t stream) {
+    if (!live || !values || !grad || !dirs || !t_near || !t_far || !n_steps || !k_next || !tf_table || !state) return LFGC_E_NULL;
+    if (lfgc_ray_list_check(n_live, S, dt) != LFGC_OK || Kv < 2 || Kg < 2 || (long long)Kv * Kg > (1LL << 22) ||
+        !(g_scale > 0.0f) || !lfgc_finite(g_scale) || (shade != 0 && shade != 1))
+        return LFGC_E_SHAPE;
+    if (((uintptr_t)tf_table | (uintptr_t)state) & 15) return LFGC_E_ALIGN;
+    hipLaunchKernelGGL((shade ? ray_composite_kernel<true, true> : ray_composite_kernel<false, true>),
+                       dim3(lfgc_half_wave_grid(n_live)), dim3(kRayBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values,
+                       grad, dirs, t_near, t_far, n_steps, k_next, dt, reinterpret_cast<const float4*>(tf_table), Kv, Kg, v_min,
+                       tf_scale, g_scale, opacity_limit, ka, kd, reinterpret_cast<float4*>(state));
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }

@@ -1325,6 +1325,85 @@ def ray_composite(live: torch.Tensor, values: torch.Tensor, grad: Optional[torch
                                              _stream(live)), 'lfgc_ray_composite_f32')
 
 
+def _tf_table2d(tf_table: torch.Tensor, v_min: float, v_max: float, g_max: float) -> Tuple[int, int, float, float]:
+    """(Kv, Kg, tf_scale, g_scale) of a (Kv, Kg, 4) table over [v_min, v_max] x [0, g_max]."""
+    if (tf_table.dim() != 3 or tf_table.shape[2] != 4 or tf_table.shape[0] < 2 or tf_table.shape[1] < 2
+            or tf_table.dtype != torch.float32 or not tf_table.is_contiguous()):
+        raise ValueError('tf_table must be a contiguous fp32 (Kv, Kg, 4) tensor with Kv >= 2 and Kg >= 2')
+    Kv, Kg = int(tf_table.shape[0]), int(tf_table.shape[1])
+    if Kv * Kg > 1 << 22:
+        raise ValueError('tf_table has %d x %d entries, more than 2^22' % (Kv, Kg))
+    if not float(v_max) > float(v_min):
+        raise ValueError('v_max must exceed v_min')
+    if not 0.0 < float(g_max) < float('inf'):
+        raise ValueError('g_max must be positive and finite')
+    return Kv, Kg, (Kv - 1) / (float(v_max) - float(v_min)), (Kg - 1) / float(g_max)
+
+
+@_on_device
+def ray_composite2d(live: torch.Tensor, values: torch.Tensor, grad: torch.Tensor, dirs: torch.Tensor, t_near: torch.Tensor,
+                    t_far: torch.Tensor, n_steps: torch.Tensor, k_next: torch.Tensor, dt: float, S: int, tf_table: torch.Tensor,
+                    v_min: float, v_max: float, g_max: float, opacity_limit: float, state: torch.Tensor, shade: bool = False,
+                    ka: float = 0.3, kd: float = 0.7) -> None:
+    """``ray_composite`` under a 2-D table over value and gradient magnitude: lfgc_ray_composite2d_f32.  grad
+    (len(live)*S, 3) is required, in the units of ``g_max``; tf_table (Kv, Kg, 4) covers [v_min, v_max] x [0, g_max];
+    ``shade`` adds the headlight with ka, kd."""
+    _require_hip(live, values, grad, dirs, t_near, t_far, n_steps, k_next, tf_table, state)
+    live = _ray_i32(live, 'live')
+    n_rows = live.numel() * int(S)
+    Kv, Kg, tf_scale, g_scale = _tf_table2d(tf_table, v_min, v_max, g_max)
+    state = _ray_f32x4(state, 'state')
+    values = _f32c(values).reshape(-1)
+    if values.numel() != n_rows:
+        raise ValueError('%d values for %d rays of %d samples' % (values.numel(), live.numel(), S))
+    if grad is None:
+        raise ValueError('a 2-D transfer function needs the gradients: grad is None')
+    grad = _f32c(grad)
+    if tuple(grad.shape) != (n_rows, 3):
+        raise ValueError('grad must be (%d, 3), got %s' % (n_rows, tuple(grad.shape)))
+    if not live.numel():
+        return
+    check(_lib.load().lfgc_ray_composite2d_f32(live.data_ptr(), live.numel(), values.data_ptr(), grad.data_ptr(),
+                                               _f32c(dirs).data_ptr(), _f32c(t_near).data_ptr(), _f32c(t_far).data_ptr(),
+                                               _ray_i32(n_steps, 'n_steps').data_ptr(), _ray_i32(k_next, 'k_next').data_ptr(),
+                                               float(dt), int(S), tf_table.data_ptr(), Kv, Kg, float(v_min), tf_scale, g_scale,
+                                               1 if shade else 0, float(opacity_limit), float(ka), float(kd), state.data_ptr(),
+                                               _stream(live)), 'lfgc_ray_composite2d_f32')
+
+
+HISTOGRAM_MAX_BINS = 16384     # Bv * Bg of lfgc_joint_histogram_f32: one 64 KB LDS histogram per workgroup
+
+
+@_on_device
+def joint_histogram(values: torch.Tensor, grad: torch.Tensor, bins, v_min: float, v_max: float, g_max: float,
+                    counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """counts (Bv, Bg) int64 += the joint histogram of values (n,) and |grad (n, 3)| over [v_min, v_max] x [0, g_max]:
+    lfgc_joint_histogram_f32.  Bin (i, j) is the cell ``ray_composite2d`` interpolates in for a table of (Bv + 1, Bg + 1)
+    rows; what lies outside the range falls into the end bins.  ``counts`` None starts from zero; the sums are integers,
+    so neither scheduling nor the cut of the samples into calls shows."""
+    _require_hip(values, grad, counts)
+    Bv, Bg = (int(b) for b in bins)
+    if Bv < 1 or Bg < 1 or Bv * Bg > HISTOGRAM_MAX_BINS:
+        raise ValueError('bins must be (Bv, Bg) with Bv, Bg >= 1 and Bv * Bg <= %d, got %s' % (HISTOGRAM_MAX_BINS, (Bv, Bg)))
+    if not float(v_max) > float(v_min):
+        raise ValueError('v_max must exceed v_min')
+    if not 0.0 < float(g_max) < float('inf'):
+        raise ValueError('g_max must be positive and finite')
+    values = _f32c(values).reshape(-1)
+    grad = _f32c(grad)
+    if tuple(grad.shape) != (values.numel(), 3):
+        raise ValueError('grad must be (%d, 3), got %s' % (values.numel(), tuple(grad.shape)))
+    if counts is None:
+        counts = torch.zeros((Bv, Bg), dtype=torch.int64, device=values.device)
+    elif counts.dtype != torch.int64 or not counts.is_contiguous() or tuple(counts.shape) != (Bv, Bg):
+        raise ValueError('counts must be a contiguous int64 %s tensor' % ((Bv, Bg),))
+    if values.numel():
+        check(_lib.load().lfgc_joint_histogram_f32(values.data_ptr(), grad.data_ptr(), values.numel(), Bv, Bg, float(v_min),
+                                                   Bv / (float(v_max) - float(v_min)), Bg / float(g_max), counts.data_ptr(),
+                                                   _stream(values)), 'lfgc_joint_histogram_f32')
+    return counts
+
+
 @_on_device
 def ray_compact(prev: Optional[torch.Tensor], n_steps: torch.Tensor, k_next: torch.Tensor, state: torch.Tensor,
                 opacity_limit: float) -> torch.Tensor:

@@ -18,6 +18,10 @@ Empty-space skipping: ``render_from_net(..., skip=BrickRanges.from_net(dataset, 
 blocks of ``block_steps`` steps that lie in bricks of the volume where the transfer function is transparent over the
 brick's value range (ops.ray_skip after the clip and after each compositing); the model is not evaluated there.
 
+A ``TransferFunction2D`` over value and gradient magnitude goes wherever a ``TransferFunction`` goes in ``render``,
+``render_from_net``, ``render_from_volume`` and ``BrickRanges.occupancy`` (ops.ray_composite2d: every sample then needs its
+gradient); ``joint_histogram_from_net`` / ``joint_histogram_from_volume`` count the volume over the same two axes.
+
 First-hit isosurfaces use the same loop with ops.ray_iso_scan in the place of the compositing:
 
     hits = isosurface_from_net(dataset, net, origins, dirs, iso=0.2)                     # IsoHits: hit, t, position, normal, value
@@ -27,6 +31,7 @@ First-hit isosurfaces use the same loop with ops.ray_iso_scan in the place of th
 """
 from __future__ import annotations
 
+import functools
 import math
 from types import SimpleNamespace
 from typing import Callable, NamedTuple, Optional, Sequence, Tuple
@@ -121,6 +126,64 @@ class TransferFunction:
         return t
 
 
+class TransferFunction2D:
+    """Bilinear table over the value range [v_min, v_max] and the gradient magnitude [0, g_max]: (Kv, Kg, 4) entries of
+    (r, g, b, extinction per unit normalised length), Kv, Kg >= 2; row i of the value axis sits at
+    v_min + i (v_max - v_min) / (Kv - 1), row j of the gradient axis at j g_max / (Kg - 1); what lies outside takes the
+    end rows.  The gradient is the one ``net.value_and_gradient`` returns: per unit of normalised position.  Material
+    boundaries have a large |gradient|, homogeneous regions a small one: a table that is transparent at small |gradient|
+    shows the boundaries alone."""
+
+    def __init__(self, table, v_min: float = -1.0, v_max: float = 1.0, g_max: float = 1.0):
+        table = torch.as_tensor(table, dtype=torch.float32).detach()
+        if table.dim() != 3 or table.shape[2] != 4 or table.shape[0] < 2 or table.shape[1] < 2:
+            raise ValueError('2-D transfer function table must be (Kv, Kg, 4) with Kv, Kg >= 2, got %s' % (tuple(table.shape),))
+        if table.shape[0] * table.shape[1] > 1 << 22:
+            raise ValueError('2-D transfer function table must not have more than 2^22 entries')
+        if not bool(torch.isfinite(table).all()):
+            raise ValueError('transfer function table must be finite')
+        if bool((table[..., 3] < 0).any()):
+            raise ValueError('extinction (column 3) must be >= 0')
+        if not float(v_max) > float(v_min):
+            raise ValueError('v_max must exceed v_min')
+        if not 0.0 < float(g_max) < float('inf'):
+            raise ValueError('g_max must be positive and finite')
+        self.table = table.contiguous()
+        self.v_min, self.v_max, self.g_max = float(v_min), float(v_max), float(g_max)
+        self._on = {}
+        self._projection = None
+
+    on = TransferFunction.on
+
+    def value_projection(self) -> TransferFunction:
+        """The 1-D table over the value alone that is at least as opaque as this one at any gradient: Kv rows, the
+        extinction of a row is the largest of its Kg entries (its colour their mean).  Where it is transparent, so is this
+        table for every gradient -- what ``BrickRanges.occupancy`` needs.  Cached."""
+        if self._projection is None:
+            rows = torch.cat([self.table[..., :3].mean(1), self.table[..., 3].amax(1, keepdim=True)], 1)
+            self._projection = TransferFunction(rows, self.v_min, self.v_max)
+        return self._projection
+
+    @classmethod
+    def from_ramp(cls, tf: TransferFunction, g_lo: float, g_hi: float, Kg: int = 64, g_max: Optional[float] = None) -> 'TransferFunction2D':
+        """Boundary emphasis: the colours of the 1-D ``tf`` at every gradient, its extinction times a linear ramp in the
+        gradient magnitude that is 0 up to ``g_lo`` and 1 from ``g_hi`` on.  ``Kg`` rows over [0, g_max] (default
+        g_max = g_hi)."""
+        g_lo, g_hi = float(g_lo), float(g_hi)
+        g_max = g_hi if g_max is None else float(g_max)
+        if not 0.0 <= g_lo < g_hi or g_hi == float('inf'):
+            raise ValueError('the ramp needs 0 <= g_lo < g_hi < inf')
+        if int(Kg) != Kg or int(Kg) < 2:
+            raise ValueError('Kg must be an integer >= 2')
+        if not 0.0 < g_max < float('inf'):
+            raise ValueError('g_max must be positive and finite')
+        g = torch.arange(int(Kg), dtype=torch.float64) * (g_max / (int(Kg) - 1))
+        ramp = ((g - g_lo) / (g_hi - g_lo)).clamp(0.0, 1.0)
+        table = tf.table.to(torch.float64).unsqueeze(1).repeat(1, int(Kg), 1)
+        table[..., 3] *= ramp.view(1, -1)
+        return cls(table.to(torch.float32), tf.v_min, tf.v_max, g_max)
+
+
 # ---- the marching loop --------------------------------------------------------------------------------------------------
 
 def max_steps_for(box_min, box_max, step: float) -> int:
@@ -207,6 +270,10 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
     last segment is cut at the box, so the image is continuous in ``step``.  ``opacity_limit``: a ray stops contributing
     once its opacity reaches it.  ``dirs`` are normalised here.
 
+    ``tf`` may be a ``TransferFunction2D`` over value and gradient magnitude.  ``value_fn`` must then return (values,
+    gradients) whether or not ``shading`` is set, the gradients per unit of normalised position (the units of ``tf.g_max``);
+    ``shading='headlight'`` combines with it and uses the same gradients.
+
     Loop: clip -> compact the hits -> read the count; while rays are live: for chunks of the live list with
     chunk * block_steps <= max_samples_per_launch: samples -> value_fn -> composite; then compact and read the count.
     That 8-byte read-back per block of ``block_steps`` steps is the only synchronisation; a ray's arithmetic does not
@@ -219,9 +286,16 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
     if not 0.0 < float(opacity_limit) <= 1.0:
         raise ValueError('opacity_limit must lie in (0, 1]')
     S, table = int(block_steps), tf.on(origins.device)
+    two_d = isinstance(tf, TransferFunction2D)
 
     def composite(rays, part, pos):
         out = value_fn(pos)
+        if two_d:
+            if not isinstance(out, (tuple, list)) or len(out) != 2 or out[1] is None:
+                raise ValueError('a 2-D transfer function needs value_fn to return (values, gradients), with or without shading')
+            ops.ray_composite2d(part, out[0], out[1], rays.dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S,
+                                table, tf.v_min, tf.v_max, tf.g_max, opacity_limit, rays.state, bool(shading), ka, kd)
+            return
         values, grad = out if shading else (out, None)
         if shading and grad is None:
             raise ValueError("shading='headlight' needs value_fn to return (values, gradients)")
@@ -260,7 +334,10 @@ def render_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: torch.T
 
     ``skip=BrickRanges.from_net(dataset, net)`` (``render``) skips the blocks that lie in bricks ``tf`` is transparent
     in, gradient evaluations included; ``skip_margin`` defaults to NET_SKIP_MARGIN.  Ranges taken before the model's
-    parameters were last updated raise ValueError."""
+    parameters were last updated raise ValueError.
+
+    A ``TransferFunction2D`` evaluates ``net.value_and_gradient`` for every sample, shaded or not, under the same
+    eval-mode rule."""
     ops._require_hip(origins, dirs)
     scales = _scales_of(dataset_or_scales)
     step = _default_step(dataset_or_scales, step)
@@ -269,8 +346,11 @@ def render_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: torch.T
     shading = bool(kwargs.get('shading'))
     if shading and net.training:
         raise ValueError("shading='headlight' evaluates net.value_and_gradient in eval mode: call net.eval() first")
-    net_fn = _net_value_fn(net, values=not shading)
-    return render(lambda pos: net_fn(pos, gradient=shading), origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
+    gradient = shading or isinstance(tf, TransferFunction2D)
+    if gradient and net.training:
+        raise ValueError('a 2-D transfer function evaluates net.value_and_gradient in eval mode: call net.eval() first')
+    net_fn = _net_value_fn(net, values=not gradient)
+    return render(lambda pos: net_fn(pos, gradient=gradient), origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
 
 
 def _default_step(dataset_or_scales, step):
@@ -314,13 +394,18 @@ def render_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor, dir
     """The same loop over the ground truth: samples are mapped back to index units (``index_positions``) and read with the
     trilinear sampler ops.gt_interp.  Same rays, same transfer function, same step as ``render_from_net`` ->
     ``image_psnr`` of the two is the image-space quality of the compression.  Unshaded only.
-    ``skip=BrickRanges.from_volume(dataset, volume)`` skips empty space; the image stays the same bit for bit."""
+    ``skip=BrickRanges.from_volume(dataset, volume)`` skips empty space; the image stays the same bit for bit.
+    A ``TransferFunction2D`` takes its gradients from ``volume_value_fn(dataset, volume)(pos, gradient=True)``: central
+    differences of the sampler at +- half a voxel, six more samples per sample."""
     ops._require_hip(origins, dirs, volume)
     if kwargs.get('shading'):
         raise ValueError('render_from_volume has no gradients: shading is not available')
     scales = _scales_of(dataset)
     step = _default_step(dataset, step)
-    return render(volume_value_fn(dataset, volume), origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
+    value_fn = volume_value_fn(dataset, volume)
+    if isinstance(tf, TransferFunction2D):
+        value_fn = functools.partial(value_fn, gradient=True)
+    return render(value_fn, origins, dirs, tf, step, [-s for s in scales], scales, **kwargs)
 
 
 # ---- empty-space skipping: value ranges of bricks of the field -------------------------------------------------------------
@@ -401,13 +486,20 @@ class BrickRanges:
 
     def occupancy(self, tf: TransferFunction, margin: Optional[float] = None, device=None) -> torch.Tensor:
         """uint8 (nbx, nby, nbz) on the device: 0 where ``tf`` is transparent over the brick's range widened by ``margin``
-        (default ``default_margin``), else 1 (ops.brick_occupancy).  Cached per (tf, margin)."""
+        (default ``default_margin``), else 1 (ops.brick_occupancy).  Cached per (tf, margin).
+
+        A ``TransferFunction2D`` is tested through its ``value_projection()``: a brick is empty iff every entry that any
+        value in its widened range and ANY gradient can interpolate between has extinction 0.  The 2-D lookup then
+        yields an extinction of exactly 0 (0 + f (0 - 0) twice, then 0 + h (0 - 0)), so alpha is exactly 0 and the skipped
+        image equals the unskipped one bit for bit.  The test is conservative in the gradient axis: the bricks bound the
+        value only, so a table that is transparent for small gradients alone skips nothing."""
         margin = self.default_margin if margin is None else float(margin)
         if device is not None and torch.device(device).type == 'cuda' and self.minmax.device != _with_index(device):
             raise ValueError('the ranges live on %s, the rays on %s' % (self.minmax.device, device))
         occ = self._occ.get((tf, margin))
         if occ is None:
-            occ = self._occ[(tf, margin)] = ops.brick_occupancy(self.minmax, tf.on(self.minmax.device), tf.v_min, tf.v_max, margin)
+            tf1 = tf.value_projection() if isinstance(tf, TransferFunction2D) else tf
+            occ = self._occ[(tf, margin)] = ops.brick_occupancy(self.minmax, tf1.on(self.minmax.device), tf1.v_min, tf1.v_max, margin)
         return occ
 
     def check_box(self, box_min, box_max) -> None:
@@ -469,6 +561,66 @@ def image_psnr(a: torch.Tensor, b: torch.Tensor, peak: float = 1.0) -> float:
         raise ValueError('images differ in shape: %s and %s' % (tuple(a.shape), tuple(b.shape)))
     mse = float(((a.double() - b.double()) ** 2).mean())
     return float('inf') if mse == 0.0 else 10.0 * math.log10(peak * peak / mse)
+
+
+# ---- joint histograms of value and gradient magnitude: what a 2-D transfer function is designed on -------------------------
+
+def _joint_histogram(chunks: Callable, bins, v_range, g_max: Optional[float], device) -> Tuple[torch.Tensor, float]:
+    """``chunks()`` yields (values (n,), gradients (n, 3)) over the lattice; one pass for g_max where it is None, one to bin."""
+    v_min, v_max = (float(v) for v in v_range)
+    if g_max is None:
+        top = torch.zeros((), dtype=torch.float32, device=device)
+        for _, g in chunks():
+            top = torch.maximum(top, g.norm(dim=1).max())
+        g_max = float(top)
+        if not 0.0 < g_max < float('inf'):
+            raise ValueError('the largest gradient magnitude is %r: pass g_max' % g_max)
+    counts = torch.zeros(tuple(int(b) for b in bins), dtype=torch.int64, device=device)
+    for v, g in chunks():
+        ops.joint_histogram(v, g, bins, v_min, v_max, g_max, counts)
+    return counts, float(g_max)
+
+
+def joint_histogram_from_net(dataset, net, bins=(64, 64), v_range=(-1.0, 1.0), g_max: Optional[float] = None,
+                             max_stash_bytes: int = 1 << 30) -> Tuple[torch.Tensor, float]:
+    """(counts int64 (Bv, Bg) on the device, g_max): how many points of the volume lattice have their value in bin i of
+    ``v_range`` and their gradient magnitude in bin j of [0, g_max] -- the bins are the cells of a ``TransferFunction2D`` of
+    (Bv + 1, Bg + 1) rows over the same ranges, as the renderer finds them (ops.joint_histogram).  The pair is what
+    ``net.value_and_gradient`` returns in eval mode at the positions of ops.lattice_slab_positions: the clamped value and
+    the gradient of the unclamped output per unit of normalised position.  Covers the lattice in the row chunks of
+    ``gradient_field_from_net``, so neither field is ever resident, and the counts do not depend on ``max_stash_bytes``.
+    ``g_max=None`` takes the largest magnitude in a first pass over the volume."""
+    from .OutputToVTK import _row_chunks
+    if net.training:
+        raise ValueError('the histogram bins net.value_and_gradient in eval mode: call net.eval() first')
+    res = dataset.vol_res_touple
+    dev = next(net.parameters()).device
+    scales = dataset.scales.tolist()
+
+    def chunks():
+        for b, e in _row_chunks(net, res[0], res[1] * res[2], max_stash_bytes):
+            v, g = net.value_and_gradient(ops.lattice_slab_positions(res, b, e, 32, scales, dev), max_stash_bytes)
+            yield v.view(-1), g
+    return _joint_histogram(chunks, bins, v_range, g_max, dev)
+
+
+def joint_histogram_from_volume(dataset, volume: torch.Tensor, bins=(64, 64), v_range=(-1.0, 1.0), g_max: Optional[float] = None,
+                                max_slab_voxels: int = 1 << 22) -> Tuple[torch.Tensor, float]:
+    """The same of the ground truth: the volume's own values and OutputToVTK.gradient_ground_truth (central differences of
+    the trilinear sampler, per unit of normalised position), x-slabs of at most ``max_slab_voxels`` points at a time."""
+    from .OutputToVTK import gradient_ground_truth
+    ops._require_hip(volume)
+    volume = ops._f32c(volume.detach())
+    res = dataset.vol_res_touple
+    if tuple(volume.shape) != tuple(res):
+        raise ValueError('volume %s does not have the shape of the dataset %s' % (tuple(volume.shape), tuple(res)))
+    planes = max(1, int(max_slab_voxels) // (res[1] * res[2]))
+
+    def chunks():
+        for b in range(0, res[0], planes):
+            e = min(b + planes, res[0])
+            yield volume[b:e].reshape(-1), gradient_ground_truth(dataset, volume, b, e)
+    return _joint_histogram(chunks, bins, v_range, g_max, volume.device)
 
 
 # ---- first-hit isosurface ray casting -------------------------------------------------------------------------------------

@@ -12,6 +12,11 @@ blocks, live rays per block, ms per frame of both, GPU time of the skip kernel, 
 Render.brick_range_excess of this model and of cfg 3 after a short training run on bench.py's smooth volume -- the two
 measurements Render.NET_SKIP_MARGIN is derived from (twice the larger, rounded up to one significant digit).
 
+With --tf2d (or --modes tf2d alone) the headlight frame is rendered under the 1-D table, under the same table repeated
+along a gradient axis and under TransferFunction2D.from_ramp of it (ramp between the quartiles of the model's |gradient|),
+alternating in the same run, the ramp frame also with empty-space skipping; before that Render.joint_histogram_from_net of
+the model at 256^3 is split into gradient evaluation and binning, and the binning kernel is timed alone.
+
 Prints, per mode: ms per frame (wall clock around whole frames, synchronised), samples evaluated and samples/s, the
 live-ray count per block of 32 steps, the share of GPU time in the ray kernels against the network evaluation (HIP events
 around every launch of one extra, instrumented frame), and the rate of ops.forward_raw alone on the same positions in the
@@ -35,7 +40,7 @@ def main() -> None:
     ap.add_argument('--precision', default='f16x2')
     ap.add_argument('--opacity-limit', type=float, default=0.999)
     ap.add_argument('--iso', type=float, default=None, help='also time an isosurface frame at this isovalue')
-    ap.add_argument('--modes', default='', help='comma-separated subset of unshaded,headlight,isosurface to time (default: all)')
+    ap.add_argument('--modes', default='', help='comma-separated subset of unshaded,headlight,isosurface to time (default: all); tf2d: the --tf2d report')
     ap.add_argument('--zero-below', type=float, default=0.5,
                     help='share of the value range, from its lower end, over which the table has no extinction (the scene: 0.5)')
     ap.add_argument('--skip', action='store_true', help='also compare the unshaded frame with and without empty-space skipping')
@@ -44,6 +49,9 @@ def main() -> None:
                     help="--skip: margin of the brick ranges; default Render.NET_SKIP_MARGIN, 'auto' = the margin derived in this run")
     ap.add_argument('--skip-trained-steps', type=int, default=113,
                     help='--skip: train steps of the second model brick_range_excess is measured on (0: leave it out)')
+    ap.add_argument('--tf2d', action='store_true',
+                    help='also time the headlight frame under TransferFunction2D.from_ramp of the table, and the joint histogram')
+    ap.add_argument('--tf2d-kg', type=int, default=64, help='--tf2d: rows of the gradient axis')
     args = ap.parse_args()
 
     import numpy as np
@@ -176,6 +184,8 @@ def main() -> None:
         torch.cuda.empty_cache()
     if args.skip:
         summary['skip'] = skip_report(args, m, ds, tf, o, d, step, box, plain)
+    if args.tf2d or 'tf2d' in args.modes.split(','):
+        summary['tf2d'] = tf2d_report(args, m, ds, tf, o, d, step, box, shaded)
     print(json.dumps(summary), flush=True)
 
 
@@ -272,6 +282,126 @@ def skip_report(args, m, ds, tf, o, d, step, box, plain) -> dict:
     print('[skip] ms per frame over %d alternating frames: without %s; with %s' % (args.frames, fmt(ms[False]), fmt(ms[True])))
     print('[skip] GPU time of the skip kernel: %.2f ms in %d launches; the two frames differ by max abs %.3e, PSNR %.1f dB'
           % (skip_ms, len(spans), diff, out['psnr_dB']), flush=True)
+    return out
+
+
+def tf2d_report(args, m, ds, tf, o, d, step, box, shaded) -> dict:
+    """--tf2d (or --modes tf2d): the headlight frame under the 1-D table, under the same table repeated along the gradient
+    axis (the same image: the lookup's cost alone) and under TransferFunction2D.from_ramp of it (extinction ramped from
+    the lower to the upper quartile of the model's |gradient|), alternating in one run; the ramp frame with and without
+    empty-space skipping; and Render.joint_histogram_from_net of the model, split into gradient evaluation and binning."""
+    import statistics
+    import torch
+    from latent_feature_grid_compression_amd import ops
+    from latent_feature_grid_compression_amd.visualization import Render
+    dev = o.device
+    n_vox = int(ds.n_voxels)
+    # ---- the joint histogram: one untimed pass for g_max and the warm-up, then the timed binning pass
+    _, g_max = Render.joint_histogram_from_net(ds, m, bins=(64, 64))
+    spans, saved = [], ops.joint_histogram
+
+    def timed_hist(*a, **k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = saved(*a, **k)
+        e1.record()
+        spans.append((e0, e1))
+        return r
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    try:
+        ops.joint_histogram = timed_hist
+        e0.record()
+        counts, _ = Render.joint_histogram_from_net(ds, m, bins=(64, 64), g_max=g_max)
+        e1.record()
+    finally:
+        ops.joint_histogram = saved
+    torch.cuda.synchronize()
+    total_ms = e0.elapsed_time(e1)
+    bin_ms = float(sum(a.elapsed_time(b) for a, b in spans))
+    assert int(counts.sum()) == n_vox
+    by_g = counts.sum(0).double().cumsum(0) / n_vox                  # the marginal of |gradient|: its quartiles
+    edge = lambda q: float((int((by_g < q).sum()) + 1) * g_max / counts.shape[1])      # noqa: E731
+    g_lo, g_hi = edge(0.25), edge(0.75)
+    hist = {'voxels': n_vox, 'g_max': g_max, 'g_lo': g_lo, 'g_hi': g_hi, 'total_ms': total_ms, 'binning_ms': bin_ms,
+            'launches': len(spans), 'binning_GBps': 16.0 * n_vox / bin_ms / 1e6}
+    print('[tf2d] joint histogram of %d voxels, 64 x 64 bins: %.2f ms on the GPU, of which binning %.3f ms in %d launches = '
+          '%.0f GB/s at 16 B per sample (%.1f %% of 8 TB/s); |gradient| max %.3f, quartiles %.3f and %.3f'
+          % (n_vox, total_ms, bin_ms, len(spans), hist['binning_GBps'], hist['binning_GBps'] / 80.0, g_max, g_lo, g_hi))
+    # the binning kernel alone, one launch over 2^24 samples: spread over all bins, and all in one bin (LDS atomics collide)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    n_syn = 1 << 24
+    syn = {'spread': (2.0 * torch.rand(n_syn, generator=gen, device=dev) - 1.0, 0.3 * torch.randn((n_syn, 3), generator=gen, device=dev)),
+           'one_bin': (torch.zeros(n_syn, device=dev), torch.zeros((n_syn, 3), device=dev))}
+    for name, (sv, sg) in syn.items():
+        acc = ops.joint_histogram(sv, sg, (64, 64), -1.0, 1.0, 1.0)                        # warm-up
+        best = float('inf')
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.joint_histogram(sv, sg, (64, 64), -1.0, 1.0, 1.0, acc)
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1))
+        hist['one_launch_%s_ms' % name], hist['one_launch_%s_GBps' % name] = best, 16.0 * n_syn / best / 1e6
+        print('[tf2d] binning alone, one launch of 2^24 samples, %s: %.3f ms = %.0f GB/s (%.1f %% of 8 TB/s)'
+              % (name, best, hist['one_launch_%s_GBps' % name], hist['one_launch_%s_GBps' % name] / 80.0))
+    del syn, sv, sg
+    torch.cuda.empty_cache()
+    # ---- frames
+    flat =Render.TransferFunction2D(tf.table.unsqueeze(1).repeat(1, args.tf2d_kg, 1), tf.v_min, tf.v_max, g_max)
+    ramp = Render.TransferFunction2D.from_ramp(tf, g_lo, g_hi, args.tf2d_kg, g_max)
+    ranges = Render.BrickRanges.from_net(ds, m, brick=args.brick)
+    margin = ranges.default_margin if args.skip_margin in (None, 'auto') else float(args.skip_margin)
+    kinds = {'headlight': (tf, None), 'tf2d_flat': (flat, None), 'tf2d': (ramp, None), 'tf2d_skip': (ramp, ranges)}
+
+    def frame(kind, stats=None):
+        table, skip = kinds[kind]
+        return Render.render(shaded, o, d, table, step, box[0], box[1], opacity_limit=args.opacity_limit, shading='headlight',
+                             stats=stats, skip=skip, skip_margin=margin if skip is not None else None)
+    st = {k: {} for k in kinds}
+    img = {k: frame(k, st[k]) for k in kinds}                                              # warm-up, stats and the images
+    torch.cuda.synchronize()
+    ms = {k: [] for k in kinds}
+    for _ in range(args.frames):                                                           # alternating, same process
+        for k in kinds:
+            t0 = time.perf_counter()
+            frame(k)
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    comp = {}
+    for k, name in (('headlight', 'ray_composite'), ('tf2d_flat', 'ray_composite2d'), ('tf2d', 'ray_composite2d')):
+        spans, saved = [], getattr(ops, name)
+
+        def timed(*a, _f=saved, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _f(*a, **kw)
+            e1.record()
+            spans.append((e0, e1))
+        try:
+            setattr(ops, name, timed)
+            frame(k)
+        finally:
+            setattr(ops, name, saved)
+        torch.cuda.synchronize()
+        comp[k] = float(sum(a.elapsed_time(b) for a, b in spans))
+    fmt = lambda v: 'min %.1f median %.1f max %.1f' % (min(v), statistics.median(v), max(v))      # noqa: E731
+    out = {'kg': args.tf2d_kg, 'histogram': hist, 'frame_ms': ms, 'samples': {k: st[k]['samples'] for k in kinds},
+           'composite_kernel_ms': comp, 'skipped_blocks': st['tf2d_skip']['skipped_blocks'], 'skip_margin': margin,
+           'flat_equals_headlight': bool(torch.equal(img['tf2d_flat'], img['headlight'])),
+           'skip_max_abs': float((img['tf2d_skip'] - img['tf2d']).abs().max()),
+           'mean_opacity': {k: float(img[k][:, 3].mean()) for k in kinds}}
+    for k in kinds:
+        print('[tf2d] %-10s ms per frame over %d alternating frames: %s; %d samples, mean opacity %.3f'
+              % (k, args.frames, fmt(ms[k]), st[k]['samples'], out['mean_opacity'][k]))
+    print('[tf2d] spread of the headlight frames: %.1f ms; median tf2d_flat - headlight %.1f ms; the flat 2-D image equals the '
+          'headlight image: %s' % (max(ms['headlight']) - min(ms['headlight']),
+                                   statistics.median(ms['tf2d_flat']) - statistics.median(ms['headlight']), out['flat_equals_headlight']))
+    print('[tf2d] GPU time of the composite kernel over a frame: %s'
+          % ', '.join('%s %.2f ms' % (k, v) for k, v in comp.items()))
+    print('[tf2d] skipping under the ramp table (margin %g): %d blocks skipped, samples %d -> %d, images differ by max abs %.3e'
+          % (margin, out['skipped_blocks'], st['tf2d']['samples'], st['tf2d_skip']['samples'], out['skip_max_abs']), flush=True)
     return out
 
 
