@@ -1,6 +1,8 @@
-// lfgc_backward.hip -- C-ABI entry for the backward of the fused path: checks, workspace carving, dispatch.
+// lfgc_backward.hip -- C-ABI entry for the backward of the fused path: checks, workspace carving, dispatch; and the
+// backward's kernels that are no templates (the fixed-point scatter's passes, the slab reduction), compiled here once.
 #include <cstdlib>
 #include "lfgc_backward.h"
+#include "lfgc_f16split.h"       // u32x4
 
 typedef int LfgcBwdDispatch(int MT, const LfgcBwdArgs& a, const LfgcWgradArgs& w, int waves, int precision, int lds_bytes,
                             int grid_data, int grid_w, hipStream_t stream, const LfgcDetScatter* det);
@@ -13,6 +15,115 @@ static unsigned long long* g_bwd_stamps = nullptr;
 // Diagnostics builds only (tools/phase_stamps.py bwd): device buffer of 20 counters per wave slot of the data kernel.
 extern "C" void lfgc_debug_set_bwd_stamp_buffer(void* p) { g_bwd_stamps = reinterpret_cast<unsigned long long*>(p); }
 #endif
+
+// ---- the fixed-point scatter's passes around lfgc_bwd_scatter_det_kernel (lfgc_backward.h has the scheme) ----------------
+static __global__ __launch_bounds__(256) void lfgc_det_zero_kernel(long long* __restrict__ acc, long long cells,
+                                                                 unsigned* __restrict__ maxw) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;            // cells is a multiple of 8
+    if (i < cells) *reinterpret_cast<u32x4*>(acc + i) = u32x4{0u, 0u, 0u, 0u};
+    if (blockIdx.x == 0 && threadIdx.x == 0) *maxw = 0u;
+}
+
+static __global__ __launch_bounds__(256) void lfgc_det_max_kernel(const float* __restrict__ dfeat, long long count,
+                                                                unsigned* __restrict__ maxw) {
+    unsigned m = 0u;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        const unsigned b = __float_as_uint(dfeat[i]) & 0x7fffffffu;
+        m = b > m ? b : m;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)m, off);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(maxw, m);
+}
+
+int lfgc_launch_det_max(const float* dfeat, long long count, unsigned* maxw, hipStream_t stream) {
+    const long long mblocks = (count + 255) / 256;
+    hipLaunchKernelGGL(lfgc_det_max_kernel, dim3((unsigned)(mblocks < 2048 ? mblocks : 2048)), dim3(256), 0, stream, dfeat, count, maxw);
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+static __global__ __launch_bounds__(256) void lfgc_det_finish_kernel(const long long* __restrict__ acc,
+                                                                   const unsigned* __restrict__ maxw, long long n,
+                                                                   float* __restrict__ d_grid, long long cells) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;            // cells is a multiple of 8
+    if (i >= cells) return;
+    const unsigned mb = *maxw;
+    f32x4 o;
+    if (mb >= kLfgcDetNonFinite) {
+        o.x = o.y = o.z = o.w = __uint_as_float(0x7fc00000u);
+    } else {
+        const double q = lfgc_det_pow2(lfgc_det_qexp(mb, n));                      // max == 0: acc is all zero
+        o.x = (float)((double)acc[i] * q); o.y = (float)((double)acc[i + 1] * q);
+        o.z = (float)((double)acc[i + 2] * q); o.w = (float)((double)acc[i + 3] * q);
+    }
+    *reinterpret_cast<f32x4*>(d_grid + i) = o;
+}
+
+// ---- the slab reduction (kernel 3 of lfgc_backward.h) ----------------------------------------------------------------------
+struct LfgcReduceArgs {
+    const float* slabs;
+    int nslabs, slab_floats;
+    float* dw[LFGC_MAX_LAYERS + 1];
+    float* db[LFGC_MAX_LAYERS + 1];
+    LfgcPlan plan;
+    int col_of_src[64];        // layer 0: packed column that holds original column c
+};
+
+// d_weights / d_biases in nn.Linear layout = sum over workgroup slabs.  A block owns 64 consecutive output
+// elements; its 4 waves each sum a quarter of the slabs (coalesced 256-B rows), the quarters are combined in a
+// fixed order through LDS, so the result is bitwise repeatable.
+static __global__ __launch_bounds__(256) void lfgc_bwd_reduce_kernel(const LfgcReduceArgs a) {
+    const LfgcPlan& p = a.plan;
+    const int K0 = p.E + p.C;
+    const int n0 = p.H * K0 + p.H;                     // layer 0: weights then bias
+    const int n1 = p.H * p.H + p.H;
+    const int total = n0 + (p.L - 1) * n1 + p.H + 1;
+    __shared__ float part[4][64];
+    const int o = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int idx = blockIdx.x * 64 + o;
+    int src = 0;
+    float* dst = nullptr;
+    if (idx < total) {
+        if (idx < n0) {
+            if (idx < p.H * K0) {
+                const int row = idx / K0, c = idx % K0;
+                src = row * p.K0R + a.col_of_src[c];
+                dst = a.dw[0] + idx;
+            } else {
+                const int r = idx - p.H * K0;
+                src = p.HP * p.K0R + r;
+                dst = a.db[0] + r;
+            }
+        } else if (idx < n0 + (p.L - 1) * n1) {
+            const int l = 1 + (idx - n0) / n1, oo = (idx - n0) % n1;
+            const int base = lfgc_slab_layer_off(p, l);
+            if (oo < p.H * p.H) {
+                src = base + (oo / p.H) * p.HP + (oo % p.H);
+                dst = a.dw[l] + oo;
+            } else {
+                src = base + p.HP * p.HP + (oo - p.H * p.H);
+                dst = a.db[l] + (oo - p.H * p.H);
+            }
+        } else {
+            const int oo = idx - n0 - (p.L - 1) * n1;
+            const int base = lfgc_slab_layer_off(p, p.L);
+            if (oo < p.H) { src = base + oo; dst = a.dw[p.L] + oo; }
+            else { src = base + p.HP; dst = a.db[p.L]; }
+        }
+    }
+    float s = 0.0f;
+    if (idx < total) {
+        const float* sp = a.slabs + src;
+        for (int g = q; g < a.nslabs; g += 4) s += sp[(long long)g * a.slab_floats];
+    }
+    part[q][o] = s;
+    __syncthreads();
+    if (q == 0 && idx < total) *dst = ((part[0][o] + part[1][o]) + part[2][o]) + part[3][o];
+}
 
 namespace {
 #ifndef LFGC_MAX_SLABS
@@ -72,12 +183,33 @@ long long carve_floats(const Carve& c) { return c.dstash_floats + c.slab_floats_
 // lfgc_backward_det_f32's tail behind carve_floats(), 16-byte aligned: int64 accumulator (D,H,W,Cs) | max word (16 bytes)
 long long det_offset_bytes(const Carve& c) { return (carve_floats(c) * 4 + 15) / 16 * 16; }
 long long det_cells(const LfgcPlan& p, int D, int H, int W) { return (long long)D * H * W * p.CH; }
+
+// What the backward entries and lfgc_input_gradient_f32 share: their checks, in the order each of them makes them
+// (`own_null`: one of the entry's own mandatory pointers is null; `own_addrs`: the OR of the entry's own addresses that have
+// to be 16-byte aligned), then the plan and every LfgcBwdArgs field that does not depend on the entry.  The rest starts out
+// zero: the training build's scratch pointers, stamps, and nbatches (bwd_select's, once an entry knows that n > 0).
+int bwd_begin(const lfgc_mlp_desc* desc, const lfgc_positions* positions, const float* grid_cl, int D, int H, int W,
+              const float* packed, int precision, const float* stash, const float* d_out, float* d_pos,
+              bool own_null, uintptr_t own_addrs, LfgcPlan& p, LfgcBwdArgs& a) {
+    if (!desc || !positions || !grid_cl || !packed || !stash || own_null) return LFGC_E_NULL;
+    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
+    if (!lfgc_precision_supported(precision)) return LFGC_E_UNSUPPORTED;
+    if (!positions->pos) return LFGC_E_NULL;            // the backward runs on explicit positions only
+    if (positions->n < 0 || D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
+    if ((((uintptr_t)grid_cl) | ((uintptr_t)packed) | ((uintptr_t)stash) | own_addrs) & 15) return LFGC_E_ALIGN;
+    p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
+    a = LfgcBwdArgs{};
+    a.pos = positions->pos; a.n = positions->n;
+    a.grid = grid_cl; a.D = D; a.H = H; a.W = W; a.Cs = p.CH;
+    a.packed = packed; a.L = p.L; a.stash = stash; a.d_out = d_out; a.d_pos = d_pos;
+    return LFGC_OK;
+}
 }  // namespace
 
 extern "C" int lfgc_backward_plan(const lfgc_mlp_desc* desc, int64_t n_samples, int precision, lfgc_backward_plan_info* out) {
     if (!desc || !out) return LFGC_E_NULL;
     if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
-    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
+    if (!lfgc_precision_supported(precision)) return LFGC_E_UNSUPPORTED;
     if (n_samples < 0) return LFGC_E_SHAPE;
     const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
     *out = bwd_select(p, carve(p, n_samples), n_samples);
@@ -107,16 +239,12 @@ static int backward_impl(bool det, const lfgc_mlp_desc* desc, const lfgc_positio
                          const float* packed, int precision, const float* stash, const float* d_out,
                          float* d_grid_cl, float* const* d_weights, float* const* d_biases, float* d_pos,
                          void* workspace, int64_t workspace_bytes, lfgc_stream_t stream) {
-    if (!desc || !positions || !grid_cl || !packed || !stash || !d_out || !d_grid_cl || !d_weights || !d_biases)
-        return LFGC_E_NULL;
-    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
-    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
-    if (!positions->pos) return LFGC_E_NULL;            // backward runs on explicit positions only
-    if (positions->n < 0 || D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
-    if ((((uintptr_t)grid_cl) | ((uintptr_t)packed) | ((uintptr_t)stash) | ((uintptr_t)d_grid_cl) | ((uintptr_t)workspace)) & 15)
-        return LFGC_E_ALIGN;
-    const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
-    const long long n = positions->n;
+    LfgcPlan p;
+    LfgcBwdArgs a;
+    const int rc0 = bwd_begin(desc, positions, grid_cl, D, H, W, packed, precision, stash, d_out, d_pos,
+                              !d_out || !d_grid_cl || !d_weights || !d_biases, ((uintptr_t)d_grid_cl) | ((uintptr_t)workspace), p, a);
+    if (rc0 != LFGC_OK) return rc0;
+    const long long n = a.n;
     hipStream_t st = (hipStream_t)stream;
     for (int l = 0; l <= p.L; ++l)
         if (!d_weights[l] || !d_biases[l]) return LFGC_E_NULL;
@@ -140,12 +268,7 @@ static int backward_impl(bool det, const lfgc_mlp_desc* desc, const lfgc_positio
     float* dscale = slabs + c.slab_floats_total;
     float* dfeat = dscale + c.dscale_floats;
 
-    LfgcBwdArgs a;
-    a.pos = positions->pos; a.n = n;
-    a.grid = grid_cl; a.D = D; a.H = H; a.W = W; a.Cs = p.CH;
-    a.packed = packed; a.L = p.L; a.stash = stash; a.d_out = d_out;
-    a.dstash = dstash; a.dscale = dscale; a.d_grid = d_grid_cl; a.d_pos = d_pos;
-    a.stamps = nullptr;
+    a.dstash = dstash; a.dscale = dscale; a.d_grid = d_grid_cl;
 #ifdef LFGC_STAMPS
     a.stamps = g_bwd_stamps;
 #endif
@@ -153,7 +276,7 @@ static int backward_impl(bool det, const lfgc_mlp_desc* desc, const lfgc_positio
     LfgcWgradArgs w;
     w.stash = stash; w.dstash = dstash; w.d_out = d_out; w.n = n; w.ntiles = c.ntiles; w.L = p.L;
     w.slabs = slabs; w.slab_floats = lfgc_slab_floats(p);
-    w.dscale = precision == LFGC_PRECISION_F32 ? nullptr : dscale;     // f16 builds: f16-split contraction (lfgc_backward.h)
+    w.dscale = precision == LFGC_PRECISION_F32 ? nullptr : dscale;     // f16 builds: f16-split contraction (lfgc_bwd_weight.h)
 
     const lfgc_backward_plan_info b = bwd_select(p, c, n);
     w.roles = b.roles;
@@ -230,24 +353,13 @@ extern "C" int lfgc_input_gradient_f32(const lfgc_mlp_desc* desc, const lfgc_pos
                                        const float* grid_cl, int D, int H, int W,
                                        const float* packed, int precision, const float* stash, const float* d_out,
                                        float* d_pos, lfgc_stream_t stream) {
-    if (!desc || !positions || !grid_cl || !packed || !stash || !d_pos) return LFGC_E_NULL;
-    if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
-    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
-    if (!positions->pos) return LFGC_E_NULL;            // explicit positions only, like the backward
-    if (positions->n < 0 || D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
-    if ((((uintptr_t)grid_cl) | ((uintptr_t)packed) | ((uintptr_t)stash)) & 15) return LFGC_E_ALIGN;
-    const long long n = positions->n;
-    if (n == 0) return LFGC_OK;
-    const LfgcPlan p = lfgc_make_plan(desc->grid_channels, desc->hidden, desc->num_layers, desc->n_freqs);
-    const lfgc_backward_plan_info b = bwd_select(p, carve(p, n), n);
-
+    LfgcPlan p;
     LfgcBwdArgs a;
-    a.pos = positions->pos; a.n = n;
-    a.grid = grid_cl; a.D = D; a.H = H; a.W = W; a.Cs = p.CH;
-    a.packed = packed; a.L = p.L; a.stash = stash; a.d_out = d_out;
-    a.dstash = nullptr; a.dscale = nullptr; a.d_grid = nullptr; a.dfeat = nullptr; a.d_pos = d_pos;
+    const int rc = bwd_begin(desc, positions, grid_cl, D, H, W, packed, precision, stash, d_out, d_pos, !d_pos, 0, p, a);
+    if (rc != LFGC_OK) return rc;
+    if (a.n == 0) return LFGC_OK;
+    const lfgc_backward_plan_info b = bwd_select(p, carve(p, a.n), a.n);
     a.nbatches = b.nbatches;
-    a.stamps = nullptr;
     return kIgrad[p.CH / 8 - 1](p.MT, a, b.waves, precision, b.lds_bytes, (int)b.grid, (hipStream_t)stream);
 }
 

@@ -1,5 +1,5 @@
 // backward-kernel instantiations for grid channel stride 24
-#include "lfgc_backward.h"
+#include "lfgc_bwd_weight.h"
 int lfgc_bwd_dispatch_ch24(int MT, const LfgcBwdArgs& a, const LfgcWgradArgs& w, int waves, int h16, int lds_bytes, int grid_data, int grid_w,
                               hipStream_t stream, const LfgcDetScatter* det) {
     switch (MT) {

@@ -56,7 +56,7 @@ int fwd_check_shape(const lfgc_mlp_desc* desc, int D, int H, int W, int precisio
     if (!lfgc_mlp_supported(desc)) return LFGC_E_UNSUPPORTED;
     if (D < 1 || H < 1 || W < 1) return LFGC_E_SHAPE;
     if ((long long)D * H * W * lfgc_roundup(desc->grid_channels, 8) >= (1LL << 30)) return LFGC_E_UNSUPPORTED;   // 32-bit byte offsets
-    if (precision != LFGC_PRECISION_F32 && precision != LFGC_PRECISION_F16X2 && precision != LFGC_PRECISION_F16) return LFGC_E_UNSUPPORTED;
+    if (!lfgc_precision_supported(precision)) return LFGC_E_UNSUPPORTED;
     return LFGC_OK;
 }
 

@@ -371,6 +371,11 @@ __device__ __forceinline__ float lfgc_freq(int k) {
     return (float)(2 << k) * 3.14159274101257324f;     // exact power of two times fp32(pi): one rounding, exact here
 }
 
+// The precision codes the forward and backward entries take (include/lfgc.h); any other is LFGC_E_UNSUPPORTED.
+static inline bool lfgc_precision_supported(int precision) {
+    return precision == LFGC_PRECISION_F32 || precision == LFGC_PRECISION_F16X2 || precision == LFGC_PRECISION_F16;
+}
+
 // Per-device host-side caches (CU count, one-time kernel attributes) are keyed by the current HIP device: a process may
 // drive several devices (the caller selects the device of its tensors before calling in; ops.py does).
 #define LFGC_MAX_DEVICES 16

@@ -1,5 +1,5 @@
 // input-gradient (INPUT_ONLY) instantiations of the backward data kernel for grid channel stride 8
-#include "lfgc_backward.h"
+#include "lfgc_bwd_data.h"
 int lfgc_igrad_dispatch_ch8(int MT, const LfgcBwdArgs& a, int waves, int h16, int lds_bytes, int grid_data, hipStream_t stream) {
     switch (MT) {
         case 1: return lfgc_launch_bwd_data_any<8, 1, 2, true>(a, waves, h16, lds_bytes, grid_data, stream);

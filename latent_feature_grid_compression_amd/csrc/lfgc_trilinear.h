@@ -1,7 +1,7 @@
 // lfgc_trilinear.h -- the one definition of grid_sample's trilinear cell (ATen GridSampler.h, align_corners=False, zero
 // padding), per axis.  Every kernel that samples the feature grid or scatters into it takes its geometry from here:
 // LfgcSampler::issue and LfgcColumnSampler::stage_a (lfgc_forward.h), lfgc_bwd_data_kernel and the deferred scatter
-// (lfgc_backward.h).  Forward and backward agree bit for bit because they run these operations in this order.
+// (lfgc_bwd_data.h).  Forward and backward agree bit for bit because they run these operations in this order.
 // What stays with the caller, because it fixes the caller's rounding and instruction stream: how offsets are formed
 // (32-bit byte offsets in the forward, long long float offsets in the backward), whether weights are zeroed per axis
 // (forward) or per corner (backward), the corner order dz = c >> 2, dy = (c >> 1) & 1, dx = c & 1 and the product
