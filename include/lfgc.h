@@ -705,6 +705,50 @@ int lfgc_ray_composite2d_f32(const int32_t* live, int64_t n_live, const float* v
                              int S, const float* tf_table, int Kv, int Kg, float v_min, float tf_scale, float g_scale,
                              int shade, float opacity_limit, float ka, float kd, float* state, lfgc_stream_t stream);
 
+/* lfgc_ray_composite_f32 with pre-integrated classification (Engel, Kraus and Ertl 2001, in the integral-table form): what
+ * is composited is not the segment around a sample under the table's value AT the sample, but the SLAB between two
+ * consecutive samples under the table's mean over the value range the slab spans.  For a field that is linear between
+ * samples the opacity is exact at any step.  Same lists, state, samples (lfgc_ray_samples_f32), shading, contribution
+ * rule, scan and sums; fp32, one rounding per operation, in the stated order, unless said otherwise.
+ *   pre device double (K,4), 16-byte aligned, K <= 2^22; tab and pre are read through the caches;
+ *   carry_v device float (R), carry_k device int32 (R), initialised to -1 by the caller: the carry below.
+ * Bracket.  Cell c of the 1-D table lies between rows c and c+1; along the cell fraction x in [0,1] both tau (column 3)
+ * and the colour are linear.  For 0 <= x0 <= x1 <= 1, B(c; x0, x1) is the mean over [x0, x1] of (tau r, tau g, tau b, tau):
+ * with t0 = tab[c], d = tab[c+1] - tab[c], s = x0 + x1, q = (x0*x0 + x0*x1) + x1*x1:
+ *   B.w   = t0.w + (0.5f*d.w)*s
+ *   B.rgb = (t0.w*t0.rgb + (0.5f*(t0.w*d.rgb + d.w*t0.rgb))*s) + (d.w*d.rgb)*(q/3)
+ * (the integral over [x0, x1] is (x1-x0)*B; no cancellation where x0 is close to x1; at x0 == x1 the pointwise lookup).
+ * pre[0] = 0, pre[i] = the sum over c < i of B(c; 0, 1), computed and stored in float64.
+ * Slab mean of two table coordinates u_a, u_b (u as lfgc_ray_composite_f32 forms it; a NaN value lands in row 0): cell and
+ * fraction of fminf(u_a,u_b) -> (i_lo, f_lo), of fmaxf(u_a,u_b) -> (i_hi, f_hi), i = min((int)u, K-2), f = u - i.
+ *   i_lo == i_hi:  M = B(i_lo; f_lo, f_hi), tau_bar = M.w;
+ *   otherwise:     M = ((1-f_lo)*B(i_lo; f_lo, 1) + (float)(pre[i_hi] - pre[i_lo+1])) + f_hi*B(i_hi; 0, f_hi), the difference
+ *                  of the two rows taken in float64 and rounded once;  L = ((1-f_lo) + (float)(i_hi-i_lo-1)) + f_hi  (> 0:
+ *                  f_lo < 1 whenever the cells differ);  tau_bar = M.w / L;
+ *   c_bar = M.rgb / M.w where M.w > 0, else 0: the extinction-weighted mean colour.
+ * A slab of length len has alpha = 1 - expf(-tau_bar*len) and the colour c_bar; it enters the ray as a sample does:
+ * rgb += T*(alpha*shade)*c_bar, then T *= 1 - alpha.
+ * Slabs of a ray.  Sample k < n_steps sits at t_m(k), the midpoint of its segment [a_k, b_k], and owns one slab:
+ *   joined -- k > 0 and sample k-1 of the ray was composited (by this call or, through the carry, the one before):
+ *             [t_m(k-1), t_m(k)], values (v_{k-1}, v_k), len = fmaxf(t_m(k) - t_m(k-1), 0);
+ *   else the opening half slab [a_k, t_m(k)], values (v_k, v_k), len = fmaxf(t_m(k) - a_k, 0): k == 0 (a_0 = t_near) and
+ *             the first sample after lfgc_ray_skip_f32 moved k_next.
+ * Sample n_steps-1 also owns the closing half slab [t_m(k), b_k] (b_k = t_far), values (v_k, v_k),
+ * len = fmaxf(b_k - t_m(k), 0), folded into the same lane after its own slab (alpha1, c1), with the sample's shade:
+ *   e = (alpha1*shade)*c1 + (((1-alpha1)*alpha2)*shade)*c2, factor (1-alpha1)*(1-alpha2).
+ * The slabs of a ray tile [t_near, t_far], so the image is continuous in dt.  shade is that of sample k.  A sample
+ * contributes, its closing half included, iff 1 - T_before < opacity_limit.
+ * Carry.  After a call carry_v[ray], carry_k[ray] hold the value and the step of the ray's last row with k < n_steps
+ * (untouched where the call has none); on entry the carry is valid iff k_next[ray] > 0 and carry_k[ray] == k_next[ray] - 1.
+ * Whoever moves k_next in between (lfgc_ray_skip_f32) thereby makes it stale and needs to do nothing else.
+ * Refused before any launch: LFGC_E_NULL for a missing pointer except grad, LFGC_E_SHAPE for K < 2, K > 2^22 and the list
+ * errors of lfgc_ray_composite_f32, LFGC_E_ALIGN for a tf_table, pre or state that is not 16-byte aligned. */
+int lfgc_ray_composite_preint_f32(const int32_t* live, int64_t n_live, const float* values, const float* grad,
+                                  const float* dirs, const float* t_near, const float* t_far, const int32_t* n_steps,
+                                  int32_t* k_next, float dt, int S, const float* tf_table, int K, float v_min, float tf_scale,
+                                  float opacity_limit, float ka, float kd, float* state, const double* pre, float* carry_v,
+                                  int32_t* carry_k, lfgc_stream_t stream);
+
 /* Joint histogram of value and gradient magnitude, the tool such a table is designed with:  counts[i*Bg + j] += the number
  * of the n samples whose cell is (i, j), where (i, j) is the cell lfgc_ray_composite2d_f32 interpolates in for a table of
  * (Bv+1, Bg+1) rows, by the same fp32 operations:  u = fminf(fmaxf((v-v_min)*v_scale, 0), Bv), i = min((int)u, Bv-1);

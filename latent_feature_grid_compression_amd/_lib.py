@@ -158,6 +158,8 @@ SIGNATURES = {
                                [c_void_p, c_void_p]),
     'lfgc_ray_composite2d_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 7 + [c_float, c_int, c_void_p, c_int, c_int] +
                                  [c_float] * 3 + [c_int] + [c_float] * 3 + [c_void_p, c_void_p]),
+    'lfgc_ray_composite_preint_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 7 + [c_float, c_int, c_void_p, c_int] +
+                                      [c_float] * 5 + [c_void_p] * 5),
     'lfgc_joint_histogram_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p]),
     'lfgc_ray_compact_workspace_bytes': (c_int64, [c_int64]),
     'lfgc_ray_compact': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64,

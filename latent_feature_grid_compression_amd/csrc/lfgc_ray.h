@@ -61,6 +61,55 @@ __device__ __forceinline__ float4 lfgc_tf_lookup(const float4* __restrict__ tab,
     lfgc_tf_cell(lfgc_tf_coordinate(v, v_min, tf_scale, (float)(K - 1)), K, i, f);
     return lfgc_tf_lerp(tab[i], tab[i + 1], f);
 }
+// ---- pre-integrated classification (include/lfgc.h: lfgc_ray_composite_preint_f32) -----------------------------------------
+// the bracket B(c; x0, x1) of the cell between rows t0 and t1, 0 <= x0 <= x1 <= 1: the mean over the cell fractions
+// [x0, x1] of (tau r, tau g, tau b, tau), tau and the colour both linear in the fraction.  No cancellation where x0 is
+// close to x1; at x0 == x1 the pointwise lookup
+__device__ __forceinline__ float4 lfgc_tf_bracket(const float4& t0, const float4& t1, float x0, float x1) {
+    const float s = x0 + x1;
+    const float q3 = ((x0 * x0 + x0 * x1) + x1 * x1) / 3.0f;
+    const float dx = t1.x - t0.x, dy = t1.y - t0.y, dz = t1.z - t0.z, dw = t1.w - t0.w;
+    return make_float4((t0.w * t0.x + (0.5f * (t0.w * dx + dw * t0.x)) * s) + (dw * dx) * q3,
+                       (t0.w * t0.y + (0.5f * (t0.w * dy + dw * t0.y)) * s) + (dw * dy) * q3,
+                       (t0.w * t0.z + (0.5f * (t0.w * dz + dw * t0.z)) * s) + (dw * dz) * q3,
+                       t0.w + (0.5f * dw) * s);
+}
+// the slab between the table coordinates u_a and u_b (either order): its extinction-weighted mean colour in x, y, z and
+// its mean extinction in w.  pre (K, 4) float64: row i = the sum of B(c; 0, 1) over the cells c < i
+__device__ __forceinline__ float4 lfgc_tf_slab_mean(const float4* __restrict__ tab, const double* __restrict__ pre, int K,
+                                                    float u_a, float u_b) {
+    int i_lo, i_hi;
+    float f_lo, f_hi;
+    lfgc_tf_cell(fminf(u_a, u_b), K, i_lo, f_lo);
+    lfgc_tf_cell(fmaxf(u_a, u_b), K, i_hi, f_hi);
+    float4 m;
+    float tau;
+    if (i_lo == i_hi) {
+        m = lfgc_tf_bracket(tab[i_lo], tab[i_lo + 1], f_lo, f_hi);
+        tau = m.w;
+    } else {                                     // the rest of the low cell, the whole cells between, the start of the high cell
+        const float w_lo = 1.0f - f_lo;          // > 0: f_lo == 1 only in the last cell, and then both are in it
+        const float4 lo = lfgc_tf_bracket(tab[i_lo], tab[i_lo + 1], f_lo, 1.0f);
+        const float4 hi = lfgc_tf_bracket(tab[i_hi], tab[i_hi + 1], 0.0f, f_hi);
+        const double* p1 = pre + 4 * (long long)i_hi;
+        const double* p0 = pre + 4 * (long long)(i_lo + 1);
+        m = make_float4((w_lo * lo.x + (float)(p1[0] - p0[0])) + f_hi * hi.x, (w_lo * lo.y + (float)(p1[1] - p0[1])) + f_hi * hi.y,
+                        (w_lo * lo.z + (float)(p1[2] - p0[2])) + f_hi * hi.z, (w_lo * lo.w + (float)(p1[3] - p0[3])) + f_hi * hi.w);
+        tau = m.w / ((w_lo + (float)(i_hi - i_lo - 1)) + f_hi);
+    }
+    const bool lit = m.w > 0.0f;
+    return make_float4(lit ? m.x / m.w : 0.0f, lit ? m.y / m.w : 0.0f, lit ? m.z / m.w : 0.0f, tau);
+}
+// the lengths of the slabs sample k owns: its own, [t_m(k-1), t_m(k)] where it is joined to a composited sample k - 1 and
+// else the opening half [a_k, t_m(k)], and the closing half [t_m(k), b_k] (which counts for the ray's last sample alone)
+__device__ __forceinline__ void lfgc_ray_slab(float tn, float tf, float dt, int k, bool joined, float& len, float& len_close) {
+    float a, b;
+    lfgc_ray_segment(tn, tf, dt, k, a, b);
+    const float tm = 0.5f * (a + b);
+    len = fmaxf(tm - (joined ? lfgc_ray_midpoint(tn, tf, dt, k - 1) : a), 0.0f);
+    len_close = fmaxf(b - tm, 0.0f);
+}
+
 // the cell (i, j) and the fractions (f, h) of value v and gradient magnitude gn in a row-major (Kv, Kg) table whose g axis
 // starts at 0: a NaN of either lands in row 0 of its axis (fmaxf)
 __device__ __forceinline__ void lfgc_tf_cell2d(int Kv, int Kg, float v, float gn, float v_min, float tf_scale, float g_scale,

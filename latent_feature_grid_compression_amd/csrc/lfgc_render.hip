@@ -6,6 +6,7 @@
 //   lfgc_ray_composite_f32   transfer function, headlight shading and front-to-back compositing of those S samples
 //                            into the per-ray state (premultiplied r, g, b and the transmittance T)
 //   lfgc_ray_composite2d_f32 the same under a 2-D table over value and gradient magnitude
+//   lfgc_ray_composite_preint_f32  the same with pre-integrated classification: slabs between consecutive samples
 //   lfgc_ray_compact         order-preserving list of the rays that still have steps left and are not yet opaque
 //   lfgc_ray_iso_scan_f32    first-hit isosurface: the first sign change of v - iso among those S samples -> a bracket
 //   lfgc_ray_iso_refine_f32  one bisection step of every bracket, and the position of the next trial
@@ -149,6 +150,107 @@ __global__ __launch_bounds__(kRayBlock) void ray_composite_kernel(const int* __r
         const float t_cut = __shfl(t_before, first_out & (kRayRun - 1), kRayRun);
         T = out_mask ? t_cut : t_all;
         cr += sr; cg += sg; cb += sb;
+    }
+    if (hw.lane == 0) {
+        state[r] = make_float4(cr, cg, cb, T);
+        k_next[r] = k0 + S;
+    }
+}
+
+// ---- composite, pre-integrated ----------------------------------------------------------------------------------------
+// The same half wave, runs, product scan, cut and butterfly sum as ray_composite_kernel; what a lane folds is the SLAB
+// between its sample and the one before it (lfgc_tf_slab_mean over the two table coordinates) instead of its segment.
+// Lane l sees its predecessor's value through a shuffle, lane 0 takes the previous run's lane 31 or the carry
+// (carry_v, carry_k: the ray's last value and its step; valid iff carry_k == k_next - 1), as ray_iso_scan_kernel does.
+// A sample without a composited predecessor opens with the half slab from its segment's front; the ray's last sample
+// also folds the closing half slab to t_far into its own lane.  No LDS.
+template <bool SHADE>
+__global__ __launch_bounds__(kRayBlock) void ray_composite_preint_kernel(const int* __restrict__ live, long long n_live, int S,
+                                                                         const float* __restrict__ values, const float* __restrict__ grad,
+                                                                         const float* __restrict__ dirs, const float* __restrict__ t_near,
+                                                                         const float* __restrict__ t_far, const int* __restrict__ n_steps,
+                                                                         int* __restrict__ k_next, float dt,
+                                                                         const float4* __restrict__ tab, const double* __restrict__ pre,
+                                                                         int K, float v_min, float tf_scale, float opacity_limit,
+                                                                         float ka, float kd, float4* __restrict__ state,
+                                                                         float* __restrict__ carry_v, int* __restrict__ carry_k) {
+    const LfgcHalfWave hw;
+    if (hw.j >= n_live) return;                  // a whole half wave leaves: the shuffles below stay inside one half
+    const long long r = live[hw.j];
+    const float tn = t_near[r], tf = t_far[r];
+    const int n = n_steps[r], k0 = k_next[r];
+    float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+    if (SHADE) { dx = dirs[r * 3 + 0]; dy = dirs[r * 3 + 1]; dz = dirs[r * 3 + 2]; }
+    const float4 st = state[r];
+    float cr = st.x, cg = st.y, cb = st.z, T = st.w;
+    float last = carry_v[r];
+    bool has_last = k0 > 0 && carry_k[r] == k0 - 1;      // a jump of the skip kernel moved k_next: the carry is stale
+    const float u_max = (float)(K - 1);
+    for (int s0 = 0; s0 < S; s0 += kRayRun) {
+        const long long row = hw.j * S + s0 + hw.lane;
+        const int k = k0 + s0 + hw.lane;
+        const float v = values[row];
+        float prev = __shfl_up(v, 1, kRayRun);
+        if (hw.lane == 0) prev = last;
+        float factor = 1.0f, er = 0.0f, eg = 0.0f, eb = 0.0f;
+        if (k < n) {
+            const bool joined = hw.lane > 0 || has_last;
+            float len, len_close;
+            lfgc_ray_slab(tn, tf, dt, k, joined, len, len_close);
+            const float u = lfgc_tf_coordinate(v, v_min, tf_scale, u_max);
+            const float4 m = lfgc_tf_slab_mean(tab, pre, K, joined ? lfgc_tf_coordinate(prev, v_min, tf_scale, u_max) : u, u);
+            const float alpha = 1.0f - expf(-m.w * len);
+            float shade = 1.0f;
+            if (SHADE) {
+                const float gx = grad[row * 3 + 0], gy = grad[row * 3 + 1], gz = grad[row * 3 + 2];
+                const float gn = lfgc_grad_norm(gx, gy, gz);
+                shade = gn > 0.0f ? ka + kd * fabsf(gx * dx + gy * dy + gz * dz) / gn : ka + kd;
+            }
+            const float w = alpha * shade;
+            er = w * m.x;
+            eg = w * m.y;
+            eb = w * m.z;
+            factor = 1.0f - alpha;
+            if (k == n - 1) {                    // the closing half slab behind the ray's last sample, in the same lane
+                const float4 c = lfgc_tf_slab_mean(tab, pre, K, u, u);
+                const float alpha2 = 1.0f - expf(-c.w * len_close);
+                const float w2 = (factor * alpha2) * shade;
+                er += w2 * c.x;
+                eg += w2 * c.y;
+                eb += w2 * c.z;
+                factor *= 1.0f - alpha2;
+            }
+            if (k == n - 1 || s0 + hw.lane == S - 1) {   // the ray's last row of this call with k < n: one lane
+                carry_v[r] = v;
+                carry_k[r] = k;
+            }
+        }
+        float incl = factor;                     // inclusive product of the factors of lanes 0..lane
+#pragma unroll
+        for (int off = 1; off < kRayRun; off <<= 1) {
+            const float t = __shfl_up(incl, off, kRayRun);
+            if (hw.lane >= off) incl *= t;
+        }
+        float excl = __shfl_up(incl, 1, kRayRun);
+        if (hw.lane == 0) excl = 1.0f;
+        const float t_before = T * excl;
+        // the cut at the first lane that is out, as in ray_composite_kernel
+        const unsigned long long out_mask = hw.ballot(!(1.0f - t_before < opacity_limit));
+        const int first_out = LfgcHalfWave::first(out_mask);
+        const bool in = hw.lane < first_out;
+        float sr = in ? t_before * er : 0.0f, sg = in ? t_before * eg : 0.0f, sb = in ? t_before * eb : 0.0f;
+#pragma unroll
+        for (int off = kRayRun / 2; off > 0; off >>= 1) {
+            sr += __shfl_xor(sr, off, kRayRun);
+            sg += __shfl_xor(sg, off, kRayRun);
+            sb += __shfl_xor(sb, off, kRayRun);
+        }
+        const float t_all = T * __shfl(incl, kRayRun - 1, kRayRun);
+        const float t_cut = __shfl(t_before, first_out & (kRayRun - 1), kRayRun);
+        T = out_mask ? t_cut : t_all;
+        cr += sr; cg += sg; cb += sb;
+        last = __shfl(v, kRayRun - 1, kRayRun);
+        has_last = true;
     }
     if (hw.lane == 0) {
         state[r] = make_float4(cr, cg, cb, T);
@@ -320,6 +422,23 @@ extern "C" int lfgc_ray_composite2d_f32(const int32_t* live, int64_t n_live, con
                        dim3(lfgc_half_wave_grid(n_live)), dim3(kRayBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values,
                        grad, dirs, t_near, t_far, n_steps, k_next, dt, reinterpret_cast<const float4*>(tf_table), Kv, Kg, v_min,
                        tf_scale, g_scale, opacity_limit, ka, kd, reinterpret_cast<float4*>(state));
+    LFGC_HIP_CHECK_LAUNCH();
+    return LFGC_OK;
+}
+
+extern "C" int lfgc_ray_composite_preint_f32(const int32_t* live, int64_t n_live, const float* values, const float* grad,
+                                             const float* dirs, const float* t_near, const float* t_far, const int32_t* n_steps,
+                                             int32_t* k_next, float dt, int S, const float* tf_table, int K, float v_min,
+                                             float tf_scale, float opacity_limit, float ka, float kd, float* state,
+                                             const double* pre, float* carry_v, int32_t* carry_k, lfgc_stream_t stream) {
+    if (!live || !values || !dirs || !t_near || !t_far || !n_steps || !k_next || !tf_table || !state || !pre || !carry_v || !carry_k)
+        return LFGC_E_NULL;
+    if (lfgc_ray_list_check(n_live, S, dt) != LFGC_OK || K < 2 || K > (1 << 22)) return LFGC_E_SHAPE;
+    if (((uintptr_t)tf_table | (uintptr_t)pre | (uintptr_t)state) & 15) return LFGC_E_ALIGN;
+    hipLaunchKernelGGL((grad ? ray_composite_preint_kernel<true> : ray_composite_preint_kernel<false>),
+                       dim3(lfgc_half_wave_grid(n_live)), dim3(kRayBlock), 0, (hipStream_t)stream, live, (long long)n_live, S, values,
+                       grad, dirs, t_near, t_far, n_steps, k_next, dt, reinterpret_cast<const float4*>(tf_table), pre, K, v_min,
+                       tf_scale, opacity_limit, ka, kd, reinterpret_cast<float4*>(state), carry_v, carry_k);
     LFGC_HIP_CHECK_LAUNCH();
     return LFGC_OK;
 }

@@ -1325,6 +1325,46 @@ def ray_composite(live: torch.Tensor, values: torch.Tensor, grad: Optional[torch
                                              _stream(live)), 'lfgc_ray_composite_f32')
 
 
+@_on_device
+def ray_composite_preint(live: torch.Tensor, values: torch.Tensor, grad: Optional[torch.Tensor], dirs: torch.Tensor,
+                         t_near: torch.Tensor, t_far: torch.Tensor, n_steps: torch.Tensor, k_next: torch.Tensor, dt: float, S: int,
+                         tf_table: torch.Tensor, pre: torch.Tensor, v_min: float, v_max: float, opacity_limit: float,
+                         state: torch.Tensor, carry_v: torch.Tensor, carry_k: torch.Tensor, ka: float = 0.3,
+                         kd: float = 0.7) -> None:
+    """``ray_composite`` with pre-integrated classification: every sample composites the slab between itself and the
+    sample before it under the table's mean over the slab's value range (lfgc_ray_composite_preint_f32).  pre (K, 4)
+    float64 is the integral table of tf_table (Render.TransferFunction.integral_on); carry_v (R,) fp32 and carry_k (R,)
+    int32, -1 before a ray's first call, hand a ray's last value from call to call and are updated in place."""
+    _require_hip(live, values, grad, dirs, t_near, t_far, n_steps, k_next, tf_table, pre, state, carry_v, carry_k)
+    live = _ray_i32(live, 'live')
+    n_rows = live.numel() * int(S)
+    K, tf_scale = _tf_table(tf_table, v_min, v_max)
+    if pre.dtype != torch.float64 or not pre.is_contiguous() or tuple(pre.shape) != (K, 4):
+        raise ValueError('pre must be a contiguous float64 (%d, 4) tensor, the integral of tf_table' % K)
+    state = _ray_f32x4(state, 'state')
+    R = state.shape[0]
+    if carry_v.dtype != torch.float32 or not carry_v.is_contiguous() or tuple(carry_v.shape) != (R,):
+        raise ValueError('carry_v must be a contiguous fp32 (R,) tensor')
+    if tuple(_ray_i32(carry_k, 'carry_k').shape) != (R,):
+        raise ValueError('carry_k must be (R,)')
+    values = _f32c(values).reshape(-1)
+    if values.numel() != n_rows:
+        raise ValueError('%d values for %d rays of %d samples' % (values.numel(), live.numel(), S))
+    if grad is not None:
+        grad = _f32c(grad)
+        if tuple(grad.shape) != (n_rows, 3):
+            raise ValueError('grad must be (%d, 3), got %s' % (n_rows, tuple(grad.shape)))
+    if not live.numel():
+        return
+    check(_lib.load().lfgc_ray_composite_preint_f32(live.data_ptr(), live.numel(), values.data_ptr(), _ptr(grad),
+                                                    _f32c(dirs).data_ptr(), _f32c(t_near).data_ptr(), _f32c(t_far).data_ptr(),
+                                                    _ray_i32(n_steps, 'n_steps').data_ptr(), _ray_i32(k_next, 'k_next').data_ptr(),
+                                                    float(dt), int(S), tf_table.data_ptr(), K, float(v_min), tf_scale,
+                                                    float(opacity_limit), float(ka), float(kd), state.data_ptr(), pre.data_ptr(),
+                                                    carry_v.data_ptr(), carry_k.data_ptr(), _stream(live)),
+          'lfgc_ray_composite_preint_f32')
+
+
 def _tf_table2d(tf_table: torch.Tensor, v_min: float, v_max: float, g_max: float) -> Tuple[int, int, float, float]:
     """(Kv, Kg, tf_scale, g_scale) of a (Kv, Kg, 4) table over [v_min, v_max] x [0, g_max]."""
     if (tf_table.dim() != 3 or tf_table.shape[2] != 4 or tf_table.shape[0] < 2 or tf_table.shape[1] < 2

@@ -116,6 +116,8 @@ class TransferFunction:
         self.table = table.contiguous()
         self.v_min, self.v_max = float(v_min), float(v_max)
         self._on = {}
+        self._integral = None
+        self._integral_on = {}
 
     def on(self, device) -> torch.Tensor:
         """The table on ``device`` (cached)."""
@@ -123,6 +125,27 @@ class TransferFunction:
         t = self._on.get(device)
         if t is None:
             t = self._on[device] = self.table.to(device).contiguous()
+        return t
+
+    def integral(self) -> torch.Tensor:
+        """The float64 (K, 4) integral table of ``render(..., preintegrated=True)`` on the CPU (cached): row i is the sum
+        over the cells c < i of the cell's mean of (tau r, tau g, tau b, tau), tau = the extinction and both tau and the
+        colour linear across a cell (include/lfgc.h: lfgc_ray_composite_preint_f32).  Row 0 is zero; the differences of
+        column 3 are the trapezoid areas of the extinction in units of one cell."""
+        if self._integral is None:
+            t = self.table.to(torch.float64)
+            t0, d = t[:-1], t[1:] - t[:-1]
+            w0, dw = t0[:, 3:4], d[:, 3:4]
+            cell = torch.cat([w0 * t0[:, :3] + 0.5 * (w0 * d[:, :3] + dw * t0[:, :3]) + (dw * d[:, :3]) / 3.0, w0 + 0.5 * dw], 1)
+            self._integral = torch.cat([torch.zeros((1, 4), dtype=torch.float64), torch.cumsum(cell, 0)], 0).contiguous()
+        return self._integral
+
+    def integral_on(self, device) -> torch.Tensor:
+        """``integral()`` on ``device`` (cached)."""
+        device = torch.device(device)
+        t = self._integral_on.get(device)
+        if t is None:
+            t = self._integral_on[device] = self.integral().to(device).contiguous()
         return t
 
 
@@ -257,7 +280,7 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
            block_steps: int = 32, opacity_limit: float = 0.999, shading: Optional[str] = None,
            max_samples_per_launch: int = 1 << 22, ka: float = 0.3, kd: float = 0.7, t_min: float = 0.0,
            t_max: float = float('inf'), stats: Optional[dict] = None, skip: Optional['BrickRanges'] = None,
-           skip_margin: Optional[float] = None) -> torch.Tensor:
+           skip_margin: Optional[float] = None, preintegrated: bool = False) -> torch.Tensor:
     """(R, 4): premultiplied r, g, b and the opacity 1 - T of every ray (``background`` puts it over a colour).
 
     ``skip``: ``BrickRanges`` of the field ``value_fn`` evaluates, over the same box.  A ray then jumps over every block of
@@ -274,12 +297,25 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
     gradients) whether or not ``shading`` is set, the gradients per unit of normalised position (the units of ``tf.g_max``);
     ``shading='headlight'`` combines with it and uses the same gradients.
 
+    ``preintegrated=True`` composites with pre-integrated classification (ops.ray_composite_preint): a sample stands for
+    the slab between itself and the sample before it, under the mean of ``tf`` over the value range the slab spans
+    (``tf.integral()``), not for its segment under ``tf`` at its own value.  Where the field is linear between samples
+    the opacity does not depend on ``step``, so thin features of ``tf`` survive a large step; self-attenuation inside a
+    slab is not modelled.  The samples, and with them the calls of ``value_fn``, are the same.  1-D tables only: a
+    ``TransferFunction2D`` raises ValueError.  With ``skip`` the occupancy table is the same (a brick is empty iff ``tf``
+    is transparent over its widened range, which is also what a slab inside it integrates to), but the image is NOT
+    promised to equal the unskipped one bit for bit: the slab that straddles a jump is replaced by an opening half slab
+    behind it and the last sample before the jump gets no trailing half, so a ray may differ by its number of jumps times
+    1 - exp(-tau_max * step).  The default, False, changes nothing.
+
     Loop: clip -> compact the hits -> read the count; while rays are live: for chunks of the live list with
     chunk * block_steps <= max_samples_per_launch: samples -> value_fn -> composite; then compact and read the count.
     That 8-byte read-back per block of ``block_steps`` steps is the only synchronisation; a ray's arithmetic does not
     depend on the chunk or list it sits in, so the image does not depend on ``max_samples_per_launch``.
 
     ``stats``: a dict that receives 'live' (live rays per block), 'samples' (rows evaluated) and 'blocks'."""
+    if preintegrated and isinstance(tf, TransferFunction2D):
+        raise ValueError('preintegrated=True needs a 1-D TransferFunction: pre-integration over two axes is not available')
     ops._require_hip(origins, dirs)
     if shading not in (None, 'headlight'):
         raise ValueError("shading must be None or 'headlight'")
@@ -287,6 +323,7 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
         raise ValueError('opacity_limit must lie in (0, 1]')
     S, table = int(block_steps), tf.on(origins.device)
     two_d = isinstance(tf, TransferFunction2D)
+    pre = tf.integral_on(origins.device) if preintegrated else None
 
     def composite(rays, part, pos):
         out = value_fn(pos)
@@ -299,6 +336,13 @@ def render(value_fn: Callable, origins: torch.Tensor, dirs: torch.Tensor, tf: Tr
         values, grad = out if shading else (out, None)
         if shading and grad is None:
             raise ValueError("shading='headlight' needs value_fn to return (values, gradients)")
+        if preintegrated:
+            if not hasattr(rays, 'carry_v'):                     # a ray's last value and its step, beside the state
+                rays.carry_v = torch.zeros(rays.state.shape[0], dtype=torch.float32, device=rays.state.device)
+                rays.carry_k = torch.full((rays.state.shape[0],), -1, dtype=torch.int32, device=rays.state.device)
+            ops.ray_composite_preint(part, values, grad, rays.dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S,
+                                     table, pre, tf.v_min, tf.v_max, opacity_limit, rays.state, rays.carry_v, rays.carry_k, ka, kd)
+            return
         ops.ray_composite(part, values, grad, rays.dirs, rays.t_near, rays.t_far, rays.n_steps, rays.k_next, step, S, table,
                           tf.v_min, tf.v_max, opacity_limit, rays.state, ka, kd)
     table_of = None
@@ -337,7 +381,11 @@ def render_from_net(dataset_or_scales, net, origins: torch.Tensor, dirs: torch.T
     parameters were last updated raise ValueError.
 
     A ``TransferFunction2D`` evaluates ``net.value_and_gradient`` for every sample, shaded or not, under the same
-    eval-mode rule."""
+    eval-mode rule.
+
+    ``preintegrated=True`` (``render``) composites slabs between consecutive samples under the integral of a 1-D ``tf``:
+    the same evaluations of the model, an opacity that does not depend on ``step`` where the model is linear between
+    samples.  With ``skip`` the image may differ from the unskipped one at the jumps (``render``)."""
     ops._require_hip(origins, dirs)
     scales = _scales_of(dataset_or_scales)
     step = _default_step(dataset_or_scales, step)
@@ -396,7 +444,9 @@ def render_from_volume(dataset, volume: torch.Tensor, origins: torch.Tensor, dir
     ``image_psnr`` of the two is the image-space quality of the compression.  Unshaded only.
     ``skip=BrickRanges.from_volume(dataset, volume)`` skips empty space; the image stays the same bit for bit.
     A ``TransferFunction2D`` takes its gradients from ``volume_value_fn(dataset, volume)(pos, gradient=True)``: central
-    differences of the sampler at +- half a voxel, six more samples per sample."""
+    differences of the sampler at +- half a voxel, six more samples per sample.
+    ``preintegrated=True`` (``render``) composites slabs between consecutive samples under the integral of a 1-D ``tf``;
+    with ``skip`` the image is then no longer the unskipped one bit for bit, only within the bound ``render`` states."""
     ops._require_hip(origins, dirs, volume)
     if kwargs.get('shading'):
         raise ValueError('render_from_volume has no gradients: shading is not available')

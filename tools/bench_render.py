@@ -17,6 +17,13 @@ along a gradient axis and under TransferFunction2D.from_ramp of it (ramp between
 alternating in the same run, the ramp frame also with empty-space skipping; before that Render.joint_histogram_from_net of
 the model at 256^3 is split into gradient evaluation and binning, and the binning kernel is timed alone.
 
+With --preint (or --modes preint alone) the unshaded and the headlight frame are rendered under the midpoint rule and with
+pre-integrated classification (render(..., preintegrated=True)) at steps h, 2h, 4h and 8h, h the default half voxel, the
+two rules alternating in the same run: ms per frame, samples, GPU time of each rule's composite kernel and image_psnr
+against ONE reference image, the midpoint rule at h/4; then the largest step at which the pre-integrated frame still has
+the PSNR of the midpoint frame at h.  The same follows for cfg 3 after --skip-trained-steps train steps on bench.py's
+smooth volume (0: left out).
+
 Prints, per mode: ms per frame (wall clock around whole frames, synchronised), samples evaluated and samples/s, the
 live-ray count per block of 32 steps, the share of GPU time in the ray kernels against the network evaluation (HIP events
 around every launch of one extra, instrumented frame), and the rate of ops.forward_raw alone on the same positions in the
@@ -52,6 +59,8 @@ def main() -> None:
     ap.add_argument('--tf2d', action='store_true',
                     help='also time the headlight frame under TransferFunction2D.from_ramp of the table, and the joint histogram')
     ap.add_argument('--tf2d-kg', type=int, default=64, help='--tf2d: rows of the gradient axis')
+    ap.add_argument('--preint', action='store_true',
+                    help='also compare the midpoint rule and pre-integrated classification at steps h, 2h, 4h and 8h')
     args = ap.parse_args()
 
     import numpy as np
@@ -186,6 +195,8 @@ def main() -> None:
         summary['skip'] = skip_report(args, m, ds, tf, o, d, step, box, plain)
     if args.tf2d or 'tf2d' in args.modes.split(','):
         summary['tf2d'] = tf2d_report(args, m, ds, tf, o, d, step, box, shaded)
+    if args.preint or 'preint' in args.modes.split(','):
+        summary['preint'] = preint_report(args, m, ds, tf, o, d)
     print(json.dumps(summary), flush=True)
 
 
@@ -403,6 +414,91 @@ def tf2d_report(args, m, ds, tf, o, d, step, box, shaded) -> dict:
     print('[tf2d] skipping under the ramp table (margin %g): %d blocks skipped, samples %d -> %d, images differ by max abs %.3e'
           % (margin, out['skipped_blocks'], st['tf2d']['samples'], st['tf2d_skip']['samples'], out['skip_max_abs']), flush=True)
     return out
+
+
+def preint_report(args, m, ds, tf, o, d) -> dict:
+    """--preint (or --modes preint): the midpoint rule against pre-integrated classification over the step, on this model
+    and on cfg 3 after a short training run on the smooth volume; the reference image of either is the midpoint rule at a
+    quarter of the default step."""
+    import statistics
+    import torch
+    import bench
+    from latent_feature_grid_compression_amd import ops
+    from latent_feature_grid_compression_amd.visualization import Render
+    mults = (1, 2, 4, 8)
+    kinds = [(mult, pre) for mult in mults for pre in (False, True)]
+    fmt = lambda v: 'min %.1f median %.1f max %.1f' % (min(v), statistics.median(v), max(v))      # noqa: E731
+
+    def table_of(name, model, dataset):
+        h = 1.0 / float(dataset.max_dim)
+        scales = dataset.scales.tolist()
+        lo, hi = [-s for s in scales], scales
+        out = {'h': h}
+        for mode in ('unshaded', 'headlight'):
+            shading = None if mode == 'unshaded' else 'headlight'
+
+            def frame(mult, pre, stats=None):
+                return Render.render_from_net(dataset, model, o, d, tf, step=h * mult, opacity_limit=args.opacity_limit,
+                                              shading=shading, stats=stats, preintegrated=pre)
+            ref = frame(0.25, False)
+            st = {k: {} for k in kinds}
+            img = {k: frame(*k, st[k]) for k in kinds}                                     # warm-up, stats and the images
+            torch.cuda.synchronize()
+            ms = {k: [] for k in kinds}
+            for _ in range(args.frames):                                                   # alternating, same process
+                for k in kinds:
+                    t0 = time.perf_counter()
+                    frame(*k)
+                    torch.cuda.synchronize()
+                    ms[k].append((time.perf_counter() - t0) * 1e3)
+            rows = []
+            for k in kinds:
+                name_op = 'ray_composite_preint' if k[1] else 'ray_composite'
+                spans, saved = [], getattr(ops, name_op)
+
+                def timed(*a, _f=saved, **kw):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    _f(*a, **kw)
+                    e1.record()
+                    spans.append((e0, e1))
+                try:
+                    setattr(ops, name_op, timed)
+                    frame(*k)
+                finally:
+                    setattr(ops, name_op, saved)
+                torch.cuda.synchronize()
+                rows.append({'step_over_h': k[0], 'preintegrated': k[1], 'frame_ms': ms[k], 'samples': st[k]['samples'],
+                             'composite_kernel_ms': float(sum(a.elapsed_time(b) for a, b in spans)),
+                             'psnr_dB': Render.image_psnr(img[k], ref), 'mean_opacity': float(img[k][:, 3].mean())})
+            at_h = next(r for r in rows if r['step_over_h'] == 1 and not r['preintegrated'])
+            match = [r for r in rows if r['preintegrated'] and r['psnr_dB'] >= at_h['psnr_dB']]
+            best = max(match, key=lambda r: r['step_over_h']) if match else None
+            out[mode] = {'rows': rows, 'midpoint_at_h_psnr_dB': at_h['psnr_dB'],
+                         'largest_matching_step_over_h': best['step_over_h'] if best else None,
+                         'frame_ms_there': statistics.median(best['frame_ms']) if best else None}
+            for r in rows:
+                print('[preint] %s %-9s step %dh %-14s %s ms; %d samples; composite kernel %.2f ms; PSNR %.2f dB against the '
+                      'midpoint rule at h/4; mean opacity %.3f'
+                      % (name, mode, r['step_over_h'], 'pre-integrated' if r['preintegrated'] else 'midpoint', fmt(r['frame_ms']),
+                         r['samples'], r['composite_kernel_ms'], r['psnr_dB'], r['mean_opacity']))
+            print('[preint] %s %s: the midpoint rule at h has %.2f dB; the largest step at which the pre-integrated frame still has '
+                  'that: %s' % (name, mode, at_h['psnr_dB'], 'none' if best is None else '%dh, %.1f ms per frame (midpoint at h: %.1f)'
+                                % (best['step_over_h'], out[mode]['frame_ms_there'], statistics.median(at_h['frame_ms']))),
+                  flush=True)
+            del img, ref
+            torch.cuda.empty_cache()
+        return out
+
+    report = {'steps_over_h': list(mults), 'reference': 'midpoint rule at h/4', 'random': table_of('random', m, ds)}
+    if args.skip_trained_steps > 0:
+        ctx = bench.cfg3_train_setup(o.device, args.precision)
+        for _ in range(args.skip_trained_steps):
+            ctx['step']()
+        tm = ctx['model'].eval()
+        tm.precision = args.precision
+        report['trained'] = dict(table_of('trained', tm, ctx['ds']), steps=args.skip_trained_steps)
+    return report
 
 
 if __name__ == '__main__':
