@@ -336,6 +336,49 @@ int lfgc_codec_pack_labels(const void* labels, int label_bytes, int64_t n, int b
 int lfgc_codec_dequant_f32(const uint8_t* packed, int64_t packed_bytes, int bits, int64_t n, const float* centres,
                            float* out, lfgc_stream_t stream);
 
+/* Lossless entropy stage of the codec (the reference has none): byte-symbol rANS with a static order-0
+ * model, interleaved over the 64 lanes of a wave.  Frequencies sum to M = 4096; the state x is 32 bits in [2^16, 2^32);
+ * renormalisation moves one 16-bit word; the initial encoder state is 2^16.
+ *   STREAM, little-endian:   u32 n | u16 R | u16 0 | u16 f[256] | u32 words[nc]   then per chunk   u32 state[64], u16 word[words[c]]
+ *   with nc = ceil(n / 64R): 520 + 260 nc bytes of overhead.  A chunk is 64 R symbols, one wave; lane l codes the chunk
+ *   positions 64 r + l, r = 0..R-1; a position at or beyond n is inactive in that round (no coding, no renormalisation).
+ *   DECODER, r = 0..R-1, each active lane:  slot = x & 4095;  s = the symbol with cum[s] <= slot < cum[s] + f[s];
+ *   x = f[s] (x >> 12) + slot - cum[s];  if x < 2^16: x = (x << 16) | next word -- the lanes that read in one round take
+ *   consecutive words of the chunk in ascending lane order.  After the last round every state is 2^16 and the cursor stands at
+ *   the end of the chunk's words.
+ *   ENCODER, the inverse, r = R-1..0, each active lane:  if (x >> 20) >= f[s]: emit x & 0xFFFF, x >>= 16  (this form: f may be
+ *   4096);  x = ((x / f[s]) << 12) + x mod f[s] + cum[s].  The words of round r lie in ascending lane order after those of the
+ *   rounds below r.
+ *   NORMALISATION of 256 counts h, n = sum h:  f[s] = 0 where h[s] = 0, else max(1, floor(4096 h[s] / n));  d = 4096 - sum f;
+ *   walk the symbols cyclically by descending h (ties: ascending symbol), adding 1 to each visited symbol with h > 0 while
+ *   d > 0, taking 1 from each visited symbol with f > 1 while d < 0, until d = 0;  cum[s] = sum of f below s.
+ * 1 <= n < 2^32 and 1 <= rounds <= 65535, else LFGC_E_SHAPE.  Workspace from the caller (lfgc_codec_rans_workspace_bytes: 0
+ * for arguments the entries refuse), 8-byte aligned; nothing allocated, no synchronisation, integer arithmetic only. */
+
+/* counts[s] += the number of bytes of sym[0..n) equal to s (256 int64, 8-byte aligned, zeroed by the caller).  One LDS
+ * histogram per wave flushed with integer atomics: deterministic. */
+int lfgc_codec_histogram_u8(const uint8_t* sym, int64_t n, int64_t* counts, lfgc_stream_t stream);
+/* HOST function (no device work): freq[256] from counts[256] by the rule above; counts >= 0 with 0 < sum <= 2^50. */
+int lfgc_codec_rans_normalize_host(const int64_t* counts, uint16_t* freq);
+int64_t lfgc_codec_rans_workspace_bytes(int64_t n, int rounds);
+/* First pass: codes sym[0..n) with the device table freq[256] and keeps only the words per chunk, then scans them; the
+ * workspace holds both for the second pass and *total_words (device int64) their sum: the stream has
+ * 520 + 260 nc + 2 * total_words bytes. */
+int lfgc_codec_rans_encode_count(const uint8_t* sym, int64_t n, int rounds, const uint16_t* freq, int64_t* total_words,
+                                 void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+/* Second pass, same arguments and the same workspace: codes again and writes the whole stream into out (2-byte aligned,
+ * out_bytes >= 520 + 260 nc else LFGC_E_WORKSPACE), every chunk at its final place, the chunk's words filled from the end
+ * backwards.  One writer per address, no atomics; a store is made only inside the chunk's own range and the buffer. */
+int lfgc_codec_rans_encode_write(const uint8_t* sym, int64_t n, int rounds, const uint16_t* freq, uint8_t* out,
+                                 int64_t out_bytes, void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+/* out[0..n) = the symbols of the stream in[0..in_bytes) (4-byte aligned; n and rounds as its header says, which the caller
+ * has read and checked: in_bytes >= 520 + 260 nc else LFGC_E_SHAPE).  Every word index is clamped to the chunk's own words
+ * and every chunk to the buffer before a load, so no stream makes the kernel read outside in[0..in_bytes).  *status (device
+ * int32, zeroed by the caller) |= 1 a lane wanted a word beyond its chunk, 2 a final state is not 2^16, 4 a chunk's cursor
+ * did not end at its end, 8 a chunk does not lie inside the buffer. */
+int lfgc_codec_rans_decode(const uint8_t* in, int64_t in_bytes, int64_t n, int rounds, uint8_t* out, int32_t* status,
+                           void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused sample + Fourier-embed + MLP decoder
  * ---------------------------------------------------------------------------------------------- */

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint16, c_uint32, c_uint64, c_void_p
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('LFGC_LIB_PATH') or os.path.join(PKG_DIR, 'liblfgc.so')   # override: diagnostics builds only
@@ -108,6 +108,12 @@ SIGNATURES = {
     'lfgc_codec_labels_u16_f32': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     'lfgc_codec_pack_labels': (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     'lfgc_codec_dequant_f32':(c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    'lfgc_codec_histogram_u8': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    'lfgc_codec_rans_normalize_host': (c_int, [POINTER(c_int64), POINTER(c_uint16)]),
+    'lfgc_codec_rans_workspace_bytes': (c_int64, [c_int64, c_int]),
+    'lfgc_codec_rans_encode_count': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'lfgc_codec_rans_encode_write': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    'lfgc_codec_rans_decode': (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     'lfgc_mlp_supported': (c_int, [POINTER(MlpDesc)]),
     'lfgc_grid_channel_stride': (c_int, [c_int]),
     'lfgc_packed_bytes': (c_int64, [POINTER(MlpDesc)]),

@@ -6,6 +6,10 @@ The reference's codec does its per-coefficient work in Python (mask string conca
 per pruned coefficient :302-305, scikit-learn k-means on the host) and is unusable beyond toy sizes; here that work runs
 on the GPU through the C-ABI (``lfgc_codec_*``: bit mask, order-preserving compaction / expansion, 1-D k-means, label
 dequantisation) and only the file layout itself (header, layer fields, byte streams) is host code below.
+
+``store_model_parameters(..., entropy=True)`` is this package's own extension: a lossless rANS stage over the labels and the
+mask (``lfgc_codec_rans_*``), flagged in the header so that the reference's reader refuses such a file
+instead of misreading it.  Without it the files are the reference's.
 """
 from __future__ import annotations
 
@@ -98,30 +102,60 @@ def _f32_bytes(t) -> bytes:
     return np.ascontiguousarray(t.detach().cpu().numpy().reshape(-1).astype('<f4')).tobytes()
 
 
-def _quantised_block(values: torch.Tensor, bits: int) -> bytes:
+_ENTROPY_FLAG = 0x80      # header byte 5 of an entropy-mode file is bits | 0x80: older readers refuse it as a width
+
+
+def _coded(plain: bytes, streams) -> bytes:
+    """[u8 mode][payload] of an entropy-mode file: mode 1 and the rANS streams where they are strictly smaller than the plain
+    bytes, else mode 0 and the plain bytes -- a field never grows by more than this one byte."""
+    if sum(s.numel() for s in streams) < len(plain):
+        return b'\x01' + b''.join(s.cpu().numpy().tobytes() for s in streams)
+    return b'\x00' + plain
+
+
+def _label_streams(labels: torch.Tensor, bits: int):
+    """One rANS stream over the labels as bytes, or above 8 bits two: the plane label & 0xFF, then label >> 8."""
+    if bits <= 8:
+        return [ops.codec_rans_encode(labels)]
+    wide = labels.to(torch.int32)
+    return [ops.codec_rans_encode((wide & 0xFF).to(torch.uint8)), ops.codec_rans_encode((wide >> 8).to(torch.uint8))]
+
+
+def _quantised_block(values: torch.Tensor, bits: int, entropy: bool = False) -> bytes:
     """[2^bits fp32 centres][labels, `bits` each, MSB first][bits % 8: the last label as uint32] (reference
     write_tensor_quantized :170-182).  At 8 bits the uint8 label array is the stream; at any other width
-    lfgc_codec_pack_labels packs it, a partial last byte LEFT-aligned (include/lfgc.h) -- what the readers slice."""
+    lfgc_codec_pack_labels packs it, a partial last byte LEFT-aligned (include/lfgc.h) -- what the readers slice.
+    ``entropy``: [centres][u8 mode] and then that same remainder (mode 0) or the labels' rANS streams (mode 1)."""
     centres, labels = ops.codec_kmeans(values, 1 << bits)
     if bits == 8:
-        return _f32_bytes(centres) + labels.cpu().numpy().tobytes()
-    block = _f32_bytes(centres) + ops.codec_pack_labels(labels, bits).cpu().numpy().tobytes()
-    if bits % 8 != 0:
-        block += struct.pack('<I', int(labels[-1:].cpu().numpy()[0]))
-    return block
+        rest = labels.cpu().numpy().tobytes()
+    else:
+        rest = ops.codec_pack_labels(labels, bits).cpu().numpy().tobytes()
+        if bits % 8 != 0:
+            rest += struct.pack('<I', int(labels[-1:].cpu().numpy()[0]))
+    if not entropy:
+        return _f32_bytes(centres) + rest
+    return _f32_bytes(centres) + _coded(rest, _label_streams(labels, bits))
 
 
-def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION):
+def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION, entropy=False):
     """Write ``filename`` (header, first / final layer in fp32, hidden layers and the non-zero wavelet coefficients as
     ``bit_precision``-bit codebook indices, 1 to 16) and ``filename + "_mask.bnr"`` (bit mask of the non-zero
-    coefficients): reference :120-223, whose ``bit_precision = 8`` (:141) is the default here."""
+    coefficients): reference :120-223, whose ``bit_precision = 8`` (:141) is the default here.
+
+    ``entropy=True`` adds the lossless rANS stage: header byte 5 becomes ``bits | 0x80``, every quantised
+    block is ``[centres][u8 mode]`` + the plain remainder (mode 0) or the labels' rANS streams (mode 1), and the mask file is
+    ``[u8 mode]`` + the plain mask or its rANS stream; mode 1 only where it is strictly smaller.  ``restore_model`` reads
+    either kind.  The default writes the same bytes as before."""
     bits = _check_bit_precision(bit_precision)
+    entropy = bool(entropy)
     if len(model.shape_array) == 0:
         raise ValueError('a model without wavelet levels has no grid_size to put in the header (reference :131)')
     grids = [_device_flat(g) for g in model.feature_grid]
     nonzero = [ops.codec_compact(g) for g in grids]
     header = struct.pack('9B', model.num_layer, model.hidden_width, model.input_channel, model.d_in, model.output_channel,
-                         bits, int(model.shape_array[-1][0]), len(grids), int(model.feature_grid[0].shape[0]))
+                         bits | (_ENTROPY_FLAG if entropy else 0), int(model.shape_array[-1][0]), len(grids),
+                         int(model.feature_grid[0].shape[0]))
     weights, biases = get_net_weights_biases(model)
     with open(filename, 'wb') as f:
         f.write(header)
@@ -132,7 +166,7 @@ def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION):
         f.write(_f32_bytes(weights[0]))
         f.write(_f32_bytes(biases[0]))
         for w, b in zip(weights[1:-1], biases[1:-1]):
-            f.write(_quantised_block(_device_flat(w), bits))
+            f.write(_quantised_block(_device_flat(w), bits, entropy))
             f.write(_f32_bytes(b))
         f.write(_f32_bytes(weights[-1]))
         f.write(_f32_bytes(biases[-1]))
@@ -140,23 +174,29 @@ def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION):
             if nz.numel() == 0:
                 raise ValueError('a coefficient tensor without any non-zero entry cannot be quantised (the reference '
                                  'fails in KMeans here as well)')
-            f.write(_quantised_block(nz, bits))
+            f.write(_quantised_block(nz, bits, entropy))
     mask = ops.codec_mask(torch.cat(grids))           # one bit stream over all tensors, like the reference's mask_string
+    plain_mask = mask.cpu().numpy().tobytes()
     with open(filename + '_mask.bnr', 'wb') as f:
-        f.write(mask.cpu().numpy().tobytes())
+        f.write(_coded(plain_mask, [ops.codec_rans_encode(mask)]) if entropy else plain_mask)
 
 
 def restore_model(filename, wavelet_filter='db2'):
     """Rebuild the model a parameter file + mask file describe (reference :226-332).  Like the reference the network is
     re-created with 'fourier' embedding (2 frequencies) and no drop layers; unlike it the model is returned on the GPU
     (it cannot run anywhere else).  The format has no field for the wavelet basis: ``wavelet_filter`` (passed on to
-    ``setup_model``) names the one the stored model was built with, db2 like the reference by default."""
+    ``setup_model``) names the one the stored model was built with, db2 like the reference by default.
+
+    An entropy-mode pair (``store_model_parameters(..., entropy=True)``) is recognised by header byte 5 (``bits | 0x80``).
+    Both kinds are read and checked on the host in full -- ``ValueError`` for a truncated file, a stream header that does
+    not add up, or a frequency on a label the codebook does not have -- before the first device call."""
     with open(filename, 'rb') as f:
         raw = f.read()
     with open(filename + '_mask.bnr', 'rb') as f:
         mask_raw = f.read()
     pos = 0
 
+    # ---- 1. the whole file pair is read and checked on the host, before anything touches the GPU --------------------
     def take(fmt):
         nonlocal pos
         size = struct.calcsize(fmt)
@@ -167,12 +207,13 @@ def restore_model(filename, wavelet_filter='db2'):
         return vals
 
     n_layers, layer_width, input_dim, input_channel, output_dim, bits, grid_size, n_grids, feature_size = take('9B')
+    entropy = bool(bits & _ENTROPY_FLAG)
+    bits &= ~_ENTROPY_FLAG
     if not 1 <= bits <= 16:
         raise ValueError('%s: bit precision %d not supported' % (filename, bits))
     n_clusters = int(math.pow(2, bits))
     grid_sizes = [take('<I')[0] for _ in range(n_grids)]
     zeros = [take('<I')[0] for _ in range(n_grids)]
-    dev = torch.device('cuda')
 
     def floats(n):
         nonlocal pos
@@ -182,37 +223,98 @@ def restore_model(filename, wavelet_filter='db2'):
         pos += 4 * n
         return torch.from_numpy(a.astype(np.float32))
 
-    def quantised(n):
-        nonlocal pos
-        centres = floats(n_clusters).to(dev)
-        nbytes = (n * bits) // 8 + (1 if (n * bits) % 8 else 0)
-        if pos + nbytes > len(raw):
-            raise ValueError('%s: truncated parameter file' % filename)
-        packed = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8, count=nbytes, offset=pos).copy()).to(dev)
-        pos += nbytes
-        out = ops.codec_dequant(packed, bits, n, centres) if n else torch.empty(0, device=dev)
-        if bits % 8 != 0:                       # the writer repeats the last label as a uint32 (:184-186, :265-267)
-            last = take('<I')[0]
-            if n:
-                out[-1] = centres[last]
-        return out
+    def rans_stream(buf, at, n, n_symbols, what, exact=False):
+        """(bytes, header) of the rANS stream at buf[at:] that must hold n symbols below n_symbols."""
+        try:
+            info = ops.codec_rans_header(buf, at, exact=exact)
+        except ValueError as e:
+            raise ValueError('%s: %s' % (what, e)) from None
+        if info.n != n:
+            raise ValueError('%s: a stream of %d symbols where %d are expected' % (what, info.n, n))
+        if info.freq[n_symbols:].any():          # a decoded label can then never index past the codebook
+            raise ValueError('%s: the model gives a frequency to a symbol of %d or above' % (what, n_symbols))
+        return np.frombuffer(buf, dtype=np.uint8, count=info.nbytes, offset=at), info
 
-    net_weights = [floats(input_dim * layer_width).to(dev)]
-    net_biases = [floats(layer_width).to(dev)]
+    def quantised(n):
+        """Host description of one block: the centres, and the packed labels (+ the uint32 last label) or the rANS planes."""
+        nonlocal pos
+        block = {'n': n, 'centres': floats(n_clusters), 'last': None, 'packed': None, 'planes': None}
+        mode = take('B')[0] if entropy else 0
+        if mode == 0:
+            nbytes = (n * bits) // 8 + (1 if (n * bits) % 8 else 0)
+            if pos + nbytes > len(raw):
+                raise ValueError('%s: truncated parameter file' % filename)
+            block['packed'] = np.frombuffer(raw, dtype=np.uint8, count=nbytes, offset=pos)
+            pos += nbytes
+            if bits % 8 != 0:                   # the writer repeats the last label as a uint32 (:184-186, :265-267)
+                block['last'] = take('<I')[0]
+        elif mode == 1:
+            block['planes'] = []
+            for limit in ([1 << bits] if bits <= 8 else [256, 1 << (bits - 8)]):
+                data, info = rans_stream(raw, pos, n, limit, filename)
+                pos += info.nbytes
+                block['planes'].append((data, info))
+        else:
+            raise ValueError('%s: block mode %d not supported' % (filename, mode))
+        return block
+
+    net_weights = [floats(input_dim * layer_width)]
+    net_biases = [floats(layer_width)]
     for _ in range(n_layers - 1):
         net_weights.append(quantised(layer_width * layer_width))
-        net_biases.append(floats(layer_width).to(dev))
-    net_weights.append(floats(output_dim * layer_width).to(dev))
-    net_biases.append(floats(output_dim).to(dev))
+        net_biases.append(floats(layer_width))
+    net_weights.append(floats(output_dim * layer_width))
+    net_biases.append(floats(output_dim))
+    grid_blocks = [quantised(nz) for nz in grid_sizes]
 
     total = sum(grid_sizes) + sum(zeros)
-    if len(mask_raw) * 8 < total:
-        raise ValueError('%s_mask.bnr: %d bits needed, %d present' % (filename, total, len(mask_raw) * 8))
-    mask = torch.from_numpy(np.frombuffer(mask_raw, dtype=np.uint8).copy()).to(dev)
+    mask_stream = None
+    if not entropy:
+        mask_bytes = len(mask_raw)
+    elif len(mask_raw) < 1 or mask_raw[0] > 1:
+        raise ValueError('%s_mask.bnr: %s' % (filename, 'mode %d not supported' % mask_raw[0] if mask_raw else 'empty'))
+    elif mask_raw[0] == 0:
+        mask_raw = mask_raw[1:]
+        mask_bytes = len(mask_raw)
+    else:
+        mask_stream = rans_stream(mask_raw, 1, (total + 7) // 8, 256, filename + '_mask.bnr', exact=True)
+        mask_bytes = mask_stream[1].n
+    if mask_bytes * 8 < total:
+        raise ValueError('%s_mask.bnr: %d bits needed, %d present' % (filename, total, mask_bytes * 8))
+
+    # ---- 2. the per-coefficient work, on the GPU -------------------------------------------------------------------------
+    dev = torch.device('cuda')
+
+    def upload(a):
+        return torch.from_numpy(np.array(a)).to(dev)
+
+    def dequantised(block):
+        n, centres = block['n'], block['centres'].to(dev)
+        if n == 0:
+            return torch.empty(0, device=dev)
+        if block['planes'] is None:
+            out = ops.codec_dequant(upload(block['packed']), bits, n, centres)
+            if block['last'] is not None:
+                out[-1] = centres[block['last']]
+            return out
+        # labels held as bytes are a bits = 8 stream, two planes interleaved high byte first a bits = 16 stream; the
+        # codebook is padded to that width (the frequency check above keeps every label below 2^bits)
+        planes = [ops.codec_rans_decode_parsed(upload(data), info) for data, info in block['planes']]
+        width = 8 * len(planes)
+        packed = planes[0] if len(planes) == 1 else torch.stack([planes[1], planes[0]], dim=1).reshape(-1)
+        padded = torch.zeros(1 << width, dtype=torch.float32, device=dev)
+        padded[:n_clusters] = centres
+        return ops.codec_dequant(packed, width, n, padded)
+
+    net_weights = [w.to(dev) if torch.is_tensor(w) else dequantised(w) for w in net_weights]
+    net_biases = [b.to(dev) for b in net_biases]
+    if mask_stream is None:
+        mask = upload(np.frombuffer(mask_raw, dtype=np.uint8))
+    else:
+        mask = ops.codec_rans_decode_parsed(upload(mask_stream[0]), mask_stream[1])
     grid_params, bit_offset = [], 0
-    for nz, z in zip(grid_sizes, zeros):
-        values = quantised(nz)
-        grid_params.append(ops.codec_expand(mask, bit_offset, nz + z, values))
+    for block, nz, z in zip(grid_blocks, grid_sizes, zeros):
+        grid_params.append(ops.codec_expand(mask, bit_offset, nz + z, dequantised(block)))
         bit_offset += nz + z
 
     model = setup_model(input_channel=input_channel, hidden_channel=layer_width, out_channel=output_dim,

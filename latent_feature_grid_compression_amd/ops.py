@@ -6,6 +6,7 @@ import contextlib
 import ctypes
 import functools
 import os
+import struct
 import threading
 import weakref
 from types import SimpleNamespace
@@ -1098,6 +1099,136 @@ def codec_dequant(packed: torch.Tensor, bits: int, n: int, centres: torch.Tensor
     check(_lib.load().lfgc_codec_dequant_f32(packed.contiguous().data_ptr(), packed.numel(), int(bits), int(n),
                                              centres.data_ptr(), out.data_ptr(), _stream(packed)), 'lfgc_codec_dequant_f32')
     return out
+
+
+# ---- entropy stage of the codec: 64-lane interleaved rANS (include/lfgc.h) ---------------------------------
+
+RANS_ROUNDS = 512                 # rounds per chunk the file writer uses: chunks of 32 768 symbols
+RANS_HEADER_BYTES = 8 + 2 * 256   # u32 n | u16 R | u16 0 | u16 f[256]
+
+
+def codec_rans_header(buf, offset: int = 0, length: Optional[int] = None, exact: bool = False) -> SimpleNamespace:
+    """Read and check the header of the rANS stream at buf[offset:] on the HOST (buf: bytes-like; nothing touches the GPU):
+    n, rounds, freq (256 int64), words (nc int64), nbytes = 520 + 260 nc + 2 sum(words).  `length` is the number of bytes the
+    stream may take from `offset` (default: the rest of buf; buf itself only has to hold the header and the word counts);
+    `exact` wants nbytes == length.  ValueError for a truncated stream, rounds < 1, sum f != 4096 or word counts that do
+    not fit the length."""
+    view = memoryview(buf).cast('B')
+    have = len(view) - int(offset)
+    length = have if length is None else int(length)
+    if offset < 0 or min(have, length) < RANS_HEADER_BYTES:
+        raise ValueError('truncated rANS stream: no room for its %d-byte header' % RANS_HEADER_BYTES)
+    n, rounds, zero = struct.unpack_from('<IHH', view, offset)
+    freq = np.frombuffer(view, '<u2', 256, offset + 8).astype(np.int64)
+    if rounds < 1 or zero != 0:
+        raise ValueError('rANS stream header: rounds per chunk %d, reserved field %d' % (rounds, zero))
+    if int(freq.sum()) != 4096:
+        raise ValueError('rANS stream header: the frequencies sum to %d, not 4096' % int(freq.sum()))
+    nc = -(-n // (64 * rounds))
+    if min(have, length) < RANS_HEADER_BYTES + 4 * nc:
+        raise ValueError('truncated rANS stream: %d chunks of %d symbols need %d bytes of word counts' % (nc, 64 * rounds, 4 * nc))
+    words = np.frombuffer(view, '<u4', nc, offset + RANS_HEADER_BYTES).astype(np.int64)
+    nbytes = RANS_HEADER_BYTES + 260 * nc + 2 * int(words.sum())
+    if nbytes > length or (exact and nbytes != length):
+        raise ValueError('rANS stream: header, %d chunks and %d words make %d bytes, %d are there'
+                         % (nc, int(words.sum()), nbytes, length))
+    return SimpleNamespace(n=n, rounds=rounds, freq=freq, words=words, nbytes=nbytes)
+
+
+def rans_normalize(counts) -> np.ndarray:
+    """256 uint16 frequencies summing to 4096 from 256 symbol counts (host C++, lfgc_codec_rans_normalize_host)."""
+    counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int64)
+    if counts.size != 256:
+        raise ValueError('the model is over byte symbols: 256 counts, got %d' % counts.size)
+    freq = np.zeros(256, dtype=np.uint16)
+    check(_lib.load().lfgc_codec_rans_normalize_host(counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                     freq.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))),
+          'lfgc_codec_rans_normalize_host')
+    return freq
+
+
+def _flat_u8(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype != torch.uint8:
+        raise ValueError('%s must be a uint8 tensor' % what)
+    return t.detach().contiguous().reshape(-1)
+
+
+@_on_device
+def codec_histogram_u8(sym: torch.Tensor) -> torch.Tensor:
+    """(256,) int64 on the device: how often each byte value occurs in the uint8 tensor."""
+    sym = _flat_u8(sym, 'symbols')
+    _require_hip(sym)
+    counts = torch.zeros(256, dtype=torch.int64, device=sym.device)
+    check(_lib.load().lfgc_codec_histogram_u8(sym.data_ptr(), sym.numel(), counts.data_ptr(), _stream(sym)),
+          'lfgc_codec_histogram_u8')
+    return counts
+
+
+def _rans_workspace(n: int, rounds: int, device) -> torch.Tensor:
+    nbytes = int(_lib.load().lfgc_codec_rans_workspace_bytes(int(n), int(rounds)))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+@_on_device
+def codec_rans_encode(sym_u8: torch.Tensor, rounds: int = RANS_ROUNDS) -> torch.Tensor:
+    """The whole rANS stream (device uint8) of a device uint8 tensor of 1 to 2^32 - 1 symbols, `rounds` (1 to 65 535) rounds
+    per chunk.  Synchronises twice: the counts go to the host for the normalisation, and the number of words sizes the
+    stream."""
+    sym = _flat_u8(sym_u8, 'symbols')
+    _require_hip(sym)
+    n, rounds = sym.numel(), int(rounds)
+    if not 1 <= n < 1 << 32 or not 1 <= rounds <= 0xFFFF:
+        raise ValueError('rANS codes 1 to 2^32 - 1 symbols in chunks of 1 to 65535 rounds, got n = %d, rounds = %d' % (n, rounds))
+    lib = _lib.load()
+    freq = torch.from_numpy(rans_normalize(codec_histogram_u8(sym).cpu().numpy()).view(np.int16)).to(sym.device)
+    ws = _rans_workspace(n, rounds, sym.device)
+    total = torch.zeros(1, dtype=torch.int64, device=sym.device)
+    check(lib.lfgc_codec_rans_encode_count(sym.data_ptr(), n, rounds, freq.data_ptr(), total.data_ptr(), ws.data_ptr(),
+                                           ws.numel() * 8, _stream(sym)), 'lfgc_codec_rans_encode_count')
+    nc = -(-n // (64 * rounds))
+    out = torch.empty(RANS_HEADER_BYTES + 260 * nc + 2 * int(total.item()), dtype=torch.uint8, device=sym.device)
+    check(lib.lfgc_codec_rans_encode_write(sym.data_ptr(), n, rounds, freq.data_ptr(), out.data_ptr(), out.numel(),
+                                           ws.data_ptr(), ws.numel() * 8, _stream(sym)), 'lfgc_codec_rans_encode_write')
+    return out
+
+
+def codec_rans_decode_parsed(stream: torch.Tensor, info: SimpleNamespace) -> torch.Tensor:
+    """The kernel side of codec_rans_decode for a device stream whose header `info` the host has checked."""
+    out = torch.empty(info.n, dtype=torch.uint8, device=stream.device)
+    if info.n == 0:
+        return out
+    if stream.data_ptr() % 4:
+        stream = stream.clone()
+    status = torch.zeros(1, dtype=torch.int32, device=stream.device)
+    ws = _rans_workspace(info.n, info.rounds, stream.device)
+    check(_lib.load().lfgc_codec_rans_decode(stream.data_ptr(), stream.numel(), info.n, info.rounds, out.data_ptr(),
+                                             status.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(stream)),
+          'lfgc_codec_rans_decode')
+    code = int(status.item())
+    if code:
+        raise ValueError('malformed rANS stream (status %d: 1 = a lane wanted a word beyond its chunk, 2 = a final state is not '
+                         '2^16, 4 = a chunk\'s words were not used up, 8 = a chunk lies outside the stream)' % code)
+    return out
+
+
+@_on_device
+def codec_rans_decode(stream_u8: torch.Tensor) -> torch.Tensor:
+    """The symbols (device uint8) of a whole rANS stream held in a uint8 tensor.  The header is read and checked on the host
+    first (codec_rans_header, exact length); ValueError for a header that fails and for a stream the kernel reports as
+    malformed.  Synchronises to read the header and the status word."""
+    stream = _flat_u8(stream_u8, 'the stream')
+    if stream.is_cuda:                      # the header and the word counts are all the host needs
+        head = stream[:RANS_HEADER_BYTES].cpu().numpy().tobytes()
+        if len(head) == RANS_HEADER_BYTES:
+            n, rounds = int(np.frombuffer(head, '<u4', 1)[0]), int(np.frombuffer(head, '<u2', 1, 4)[0])
+            if rounds >= 1:
+                nc = -(-n // (64 * rounds))
+                head += stream[RANS_HEADER_BYTES:RANS_HEADER_BYTES + 4 * nc].cpu().numpy().tobytes()
+    else:
+        head = stream.numpy().tobytes()
+    info = codec_rans_header(head, 0, stream.numel(), exact=True)
+    _require_hip(stream)
+    return codec_rans_decode_parsed(stream, info)
 
 
 # ---- ground truth / statistics -------------------------------------------------------------------------

@@ -1,0 +1,361 @@
+"""CPU tests for the codec's entropy stage: the numpy reference coder (tests/rans_ref.py) against the
+known answers of the format and against itself, the host normalisation entry against the reference's, the header checks of
+``ops`` and ``restore_model`` (all made before anything touches the GPU), the C entries' argument checks, and the default
+``entropy=False`` still writing a plain file."""
+import ctypes
+import os
+import re
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+import rans_ref as A
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_NULL, E_SHAPE, E_ALIGN, E_WORKSPACE = -1, -2, -4, -5
+ONE = ctypes.c_void_p(16)                 # any non-NULL aligned address: nothing is launched, nothing dereferenced on these paths
+SIZES = [1, 63, 64, 65, 127, 129, 1000, 4097]
+ROUNDS = [1, 2, 3, 16]
+NEW_SYMBOLS = ['lfgc_codec_histogram_u8', 'lfgc_codec_rans_normalize_host', 'lfgc_codec_rans_workspace_bytes',
+               'lfgc_codec_rans_encode_count', 'lfgc_codec_rans_encode_write', 'lfgc_codec_rans_decode']
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from latent_feature_grid_compression_amd import _lib
+    return _lib.load()
+
+
+# ---- 1. the reference coder -------------------------------------------------------------------------------------------------
+
+def test_reference_known_answer_a():
+    sym = np.asarray([0, 0, 1, 0, 2, 0, 0, 1, 0, 0], np.uint8)
+    f, states, words = A.encode_parts(sym, 1)
+    assert list(f[:3]) == [2868, 819, 409] and not f[3:].any()
+    assert [len(w) for w in words] == [0]
+    want = {0: 0x16988, 1: 0x50B44, 2: 0xA0EC7}
+    assert list(states[0][:10]) == [want[int(s)] for s in sym]
+    assert np.all(states[0][10:] == 0x10000)
+    stream = A.encode(sym, 1)
+    assert len(stream) == 780
+    assert np.array_equal(A.decode(stream), sym)
+
+
+def case_b_symbols():
+    i = np.arange(3000)
+    return (((i * i) % 7) % 3 + 250 * (i % 97 == 0)).astype(np.uint8)
+
+
+def test_reference_known_answer_b():
+    sym = case_b_symbols()
+    counts = np.bincount(sym, minlength=256)
+    present = [0, 1, 2, 250, 251, 252]
+    assert list(counts[present]) == [424, 1696, 849, 5, 18, 8] and counts.sum() == 3000
+    f, states, words = A.encode_parts(sym, 16)
+    assert list(f[present]) == [579, 2316, 1160, 6, 25, 10] and f.sum() == 4096
+    assert [len(w) for w in words] == [64, 64, 64]
+    assert list(states[0][:4]) == [0x36B34FD9, 0x23E413, 0x1909F37A, 0x8D6E62]
+    assert list(words[0][:6]) == [0x758D, 0x17AC, 0xC796, 0x17AC, 0x758D, 0xC796]
+    assert list(states[2][:4]) == [0x280CC3, 0x1424F9, 0x1403E3, 0x5271E5] and states[2][63] == 0xB1D54
+    assert list(words[2][-3:]) == [0xACD3, 0xD280, 0x755E]
+    stream = A.encode(sym, 16)
+    assert len(stream) == 520 + 260 * 3 + 2 * 192
+    assert np.array_equal(A.decode(stream), sym)
+
+
+def test_reference_known_answer_c():
+    sym = np.full(300, 7, np.uint8)
+    f, states, words = A.encode_parts(sym, 2)
+    assert f[7] == 4096 and f.sum() == 4096
+    assert [len(w) for w in words] == [0, 0, 0]
+    assert np.all(states == 0x10000)
+    assert np.array_equal(A.decode(A.encode(sym, 2)), sym)
+
+
+def distribution(kind, n, rng):
+    """The input distributions of the GPU tests (tests/test_codec_entropy_gpu.py imports this)."""
+    if kind == 'single':
+        return np.full(n, 7, np.uint8)
+    if kind == 'mask10':                                    # bytes of a bit mask with 10 % of the bits set
+        return np.packbits(rng.random(8 * n) < 0.1)
+    if kind == 'skewed256':                                 # all 256 symbols where n allows, one at 99 %
+        s = np.where(rng.random(n) < 0.99, 17, rng.integers(0, 256, n)).astype(np.uint8)
+        s[:min(n, 256)] = np.arange(min(n, 256))
+        return s
+    assert kind == 'uniform'
+    return rng.integers(0, 256, n).astype(np.uint8)
+
+
+KINDS = ['single', 'mask10', 'skewed256', 'uniform']
+
+
+@pytest.mark.parametrize('R', ROUNDS)
+def test_reference_round_trips(R):
+    rng = np.random.default_rng(40 + R)
+    for n in SIZES:
+        for kind in KINDS:
+            sym = distribution(kind, n, rng)
+            stream = A.encode(sym, R)
+            info = A.stream_info(stream, exact=True)
+            assert info['n'] == n and info['R'] == R and info['words'].size == -(-n // (64 * R))
+            assert np.array_equal(A.decode(stream), sym), (n, R, kind)
+
+
+def test_reference_decoder_detects_a_flipped_bit():
+    """The malformed stream of the GPU test: the reference's own decoder has to refuse it."""
+    stream, _ = flipped_stream()
+    with pytest.raises(ValueError, match='malformed'):
+        A.decode(stream)
+
+
+def flipped_stream():
+    """(a mask10 stream of 5000 symbols, R = 16, with bit 3 of word 11 of chunk 2 flipped; the symbols).  Header, word counts
+    and length stay consistent, so only decoding can tell."""
+    sym = distribution('mask10', 5000, np.random.default_rng(7))
+    stream = bytearray(A.encode(sym, 16))
+    info = A.stream_info(bytes(stream), exact=True)
+    assert info['words'].size == 5 and info['words'][2] > 11
+    at = A.HEADER + 4 * 5 + 3 * 256 + 2 * int(info['words'][:2].sum()) + 2 * 11
+    stream[at] ^= 1 << 3
+    return bytes(stream), sym
+
+
+# ---- 2. normalisation: the host entry against the reference ----------------------------------------------------------------------
+
+def histograms():
+    single = np.zeros(256, np.int64); single[200] = 12345
+    two = np.zeros(256, np.int64); two[3], two[250] = 1, 10 ** 9
+    skewed = np.full(256, 40, np.int64); skewed[17] = 99 * 255 * 40          # 99 %: 255 clamps to 1, then a negative d
+    uniform = np.full(256, 1000, np.int64)
+    ties = np.zeros(256, np.int64); ties[[5, 9, 100]] = 7                     # 4096 / 3: the remainder goes by ascending symbol
+    return {'single': single, 'two 1:1e9': two, 'all 256, one at 99 %': skewed, 'uniform': uniform, 'ties': ties}
+
+
+@pytest.mark.parametrize('name', list(histograms()))
+def test_host_normalisation_equals_the_reference(lib, name):
+    from latent_feature_grid_compression_amd import ops
+    h = histograms()[name]
+    want = A.normalise(h)
+    assert want.sum() == 4096 and np.all((want > 0) == (h > 0))
+    got = ops.rans_normalize(h)
+    assert got.dtype == np.uint16 and np.array_equal(got.astype(np.int64), want), name
+    if name == 'all 256, one at 99 %':
+        assert 255 + int(h[17]) * 4096 // int(h.sum()) > 4096                  # the case it is there for: d < 0
+    if name == 'single':
+        assert got[200] == 4096
+
+
+def test_host_normalisation_argument_errors(lib):
+    i64, u16 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint16)
+    f = np.zeros(256, np.uint16)
+    for bad in (np.zeros(256, np.int64), np.where(np.arange(256) == 4, -1, 5).astype(np.int64)):
+        assert lib.lfgc_codec_rans_normalize_host(bad.ctypes.data_as(i64), f.ctypes.data_as(u16)) == E_SHAPE
+    assert lib.lfgc_codec_rans_normalize_host(None, f.ctypes.data_as(u16)) == E_NULL
+
+
+# ---- 3. header checks, on the host ---------------------------------------------------------------------------------------------------
+
+def tampered(kind):
+    stream = bytearray(A.encode(case_b_symbols(), 16))
+    if kind == 'truncated':
+        return bytes(stream[:-2])
+    if kind == 'truncated header':
+        return bytes(stream[:300])
+    if kind == 'sum f':
+        stream[8:10] = struct.pack('<H', 580)                                  # f[0] 579 -> 580
+    elif kind == 'word count':
+        stream[A.HEADER + 4:A.HEADER + 8] = struct.pack('<I', 65)              # words[1] 64 -> 65
+    elif kind == 'rounds':
+        stream[4:6] = struct.pack('<H', 0)
+    elif kind == 'chunk count':
+        stream[4:6] = struct.pack('<H', 8)                                     # R 16 -> 8: 6 chunks where the counts are 3
+    return bytes(stream)
+
+
+@pytest.mark.parametrize('kind', ['truncated', 'truncated header', 'sum f', 'word count', 'rounds', 'chunk count'])
+def test_stream_header_is_refused_on_the_host(kind):
+    from latent_feature_grid_compression_amd import ops
+    bad = tampered(kind)
+    with pytest.raises(ValueError):
+        ops.codec_rans_header(bad, exact=True)
+    with pytest.raises(ValueError):                                            # a ValueError, not the no-GPU LfgcError: checked first
+        ops.codec_rans_decode(torch.frombuffer(bytearray(bad), dtype=torch.uint8))
+    with pytest.raises(ValueError):
+        A.stream_info(bad, exact=True)
+
+
+def test_stream_header_accepts_a_valid_stream_and_only_then_asks_for_the_gpu():
+    from latent_feature_grid_compression_amd import _lib, ops
+    good = A.encode(case_b_symbols(), 16)
+    info = ops.codec_rans_header(good, exact=True)
+    assert (info.n, info.rounds, info.nbytes) == (3000, 16, len(good)) and list(info.words) == [64, 64, 64]
+    assert np.array_equal(info.freq, A.stream_info(good)['f'])
+    info = ops.codec_rans_header(b'xyz' + good + b'more', 3)                   # inside a longer buffer
+    assert info.nbytes == len(good)
+    with pytest.raises(ValueError):
+        ops.codec_rans_header(b'xyz' + good + b'more', 3, exact=True)
+    with pytest.raises(_lib.LfgcError):
+        ops.codec_rans_decode(torch.frombuffer(bytearray(good), dtype=torch.uint8))
+    with pytest.raises(_lib.LfgcError):
+        ops.codec_rans_encode(torch.zeros(100, dtype=torch.uint8))
+    with pytest.raises(_lib.LfgcError):
+        ops.codec_histogram_u8(torch.zeros(100, dtype=torch.uint8))
+    with pytest.raises(ValueError):
+        ops.codec_rans_encode(torch.zeros(100))                                # not bytes
+
+
+# ---- 4. restore_model's checks, on files the reference writer made ----------------------------------------------------------------------
+
+BITS, WIDTH, C = 4, 64, 2
+TOTAL = 65536                                                                  # coefficients: an 8 KB mask
+STREAM_AT = 9 + 8 + 4 * ((15 + C) * WIDTH + WIDTH) + 4 * (1 << BITS) + 1       # the hidden block's stream in the file
+
+
+def reference_files(label_offset=0):
+    """An entropy-mode pair with every field in mode 1: one hidden block of 4096 skewed labels, one coefficient tensor with
+    5 % kept.  `label_offset` moves the hidden block's labels out of the codebook."""
+    rng = np.random.default_rng(21)
+    mask = rng.random(TOTAL) < 0.05
+    nz = int(mask.sum())
+    header = dict(n_layers=2, layer_width=WIDTH, input_dim=15 + C, input_channel=3, output_dim=1, bit_precision=BITS,
+                  grid_size=16, n_grids=1, feature_size=C, grid_sizes=[nz], zeros=[TOTAL - nz])
+    weights = [rng.standard_normal((15 + C) * WIDTH).astype(np.float32), None, rng.standard_normal(WIDTH).astype(np.float32)]
+    biases = [rng.standard_normal(WIDTH).astype(np.float32)] * 2 + [np.zeros(1, np.float32)]
+
+    def labels(n):
+        return np.minimum((rng.random(n) ** 10 * 16).astype(np.int64), 15)
+
+    blocks = [{'centres': np.arange(16, dtype=np.float32), 'labels': labels(WIDTH * WIDTH) + label_offset},
+              {'centres': np.arange(16, dtype=np.float32) - 8, 'labels': labels(nz)}]
+    param, mask_file, modes = A.write_files(header, weights, biases, blocks, mask)
+    assert modes == [1, 1, 1]
+    return param, mask_file
+
+
+def restore(tmp_path, param, mask_file):
+    from latent_feature_grid_compression_amd.model.model_utils import restore_model
+    path = str(tmp_path / 'model')
+    open(path, 'wb').write(param)
+    open(path + '_mask.bnr', 'wb').write(mask_file)
+    return restore_model(path)
+
+
+def test_reference_files_parse_back():
+    param, mask_file = reference_files()
+    got = A.parse_files(param, mask_file)
+    assert got['modes'] == [1, 1, 1] and got['header']['bit_precision'] == BITS
+    assert A.stream_info(param, STREAM_AT)['n'] == WIDTH * WIDTH               # STREAM_AT is where the tests below cut
+
+
+@pytest.mark.parametrize('kind', ['truncated', 'sum f', 'word count', 'impossible label', 'mask word count', 'mask truncated',
+                                  'block mode', 'mask mode'])
+def test_restore_model_refuses_a_bad_entropy_file_before_any_device_use(tmp_path, monkeypatch, kind):
+    """ValueError from the host pass.  torch.Tensor.to would be the first device use: it is made to fail the test."""
+    param, mask_file = reference_files(label_offset=16 if kind == 'impossible label' else 0)
+    param, mask_file = bytearray(param), bytearray(mask_file)
+    if kind == 'truncated':
+        param = param[:STREAM_AT + 700]
+    elif kind == 'sum f':
+        f0 = struct.unpack_from('<H', param, STREAM_AT + 8)[0]
+        struct.pack_into('<H', param, STREAM_AT + 8, f0 + 1)
+    elif kind == 'word count':
+        struct.pack_into('<I', param, STREAM_AT + A.HEADER, 1 << 30)
+    elif kind == 'mask word count':
+        w0 = struct.unpack_from('<I', mask_file, 1 + A.HEADER)[0]
+        struct.pack_into('<I', mask_file, 1 + A.HEADER, w0 + 1)
+    elif kind == 'mask truncated':
+        mask_file = mask_file[:-2]
+    elif kind == 'block mode':
+        param[STREAM_AT - 1] = 2
+    elif kind == 'mask mode':
+        mask_file[0] = 2
+
+    def no_device(*a, **k):
+        raise AssertionError('restore_model reached the device before refusing the file')
+    monkeypatch.setattr(torch.Tensor, 'to', no_device)
+    monkeypatch.setattr(torch.Tensor, 'cuda', no_device)
+    with pytest.raises(ValueError):
+        restore(tmp_path, bytes(param), bytes(mask_file))
+
+
+def test_previous_readers_refuse_the_flag_as_a_width():
+    """What the reader did before the flag existed, and the reference's: byte 5 is the width, and 0x84 is no width."""
+    param, _ = reference_files()
+    assert param[5] == BITS | 0x80 and not 1 <= param[5] <= 16
+
+
+# ---- 5. the default still writes a plain file ------------------------------------------------------------------------------------------------
+
+def test_entropy_false_reaches_the_plain_writer(tmp_path, monkeypatch):
+    """Host stand-ins for the device steps (non-zero selection, mask bits, the block writer) record how the writer calls them."""
+    from latent_feature_grid_compression_amd.model import model_utils as MU
+    m = MU.setup_model(3, 16, 1, 3, 'fourier', 2, '', 0.1, 0.9, 'db2', 3, 15, '')          # on the CPU
+    seen = []
+
+    def fake_block(values, bits, entropy=False):
+        seen.append(entropy)
+        return b'B' * 5
+
+    monkeypatch.setattr(MU, '_device_flat', lambda t: t.detach().float().reshape(-1))
+    monkeypatch.setattr(MU, '_quantised_block', fake_block)
+    monkeypatch.setattr(MU.ops, 'codec_compact', lambda g: g[g != 0])
+    monkeypatch.setattr(MU.ops, 'codec_mask', lambda g: torch.from_numpy(np.packbits((g != 0).numpy())))
+    monkeypatch.setattr(MU.ops, 'codec_rans_encode', lambda s: torch.zeros(1, dtype=torch.uint8))
+    n_blocks = 2 + len(m.feature_grid)
+    for kwargs in ({}, {'entropy': False}):
+        seen.clear()
+        path = str(tmp_path / ('plain%d' % len(kwargs)))
+        MU.store_model_parameters(m, path, 8, **kwargs)
+        assert seen == [False] * n_blocks
+        assert open(path, 'rb').read()[5] == 8
+        total = sum(p.numel() for p in m.feature_grid)
+        assert len(open(path + '_mask.bnr', 'rb').read()) == (total + 7) // 8      # no mode byte
+    seen.clear()
+    path = str(tmp_path / 'entropy')
+    MU.store_model_parameters(m, path, 8, entropy=True)
+    assert seen == [True] * n_blocks
+    assert open(path, 'rb').read()[5] == 8 | 0x80
+    assert open(path + '_mask.bnr', 'rb').read()[0] == 1                           # the 1-byte stand-in stream is smaller
+
+
+# ---- 6. the library -----------------------------------------------------------------------------------------------------------------------------
+
+def test_new_symbols_are_declared_bound_and_exported(lib):
+    from latent_feature_grid_compression_amd import _lib, ops
+    header = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'lfgc.h')).read(), flags=re.S)
+    declared = set(re.findall(r'\b(lfgc_[a-z0-9_]+)\s*\(', header))
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NEW_SYMBOLS:
+        assert name in declared and name in _lib.SIGNATURES and hasattr(raw, name), name
+    for fn in ('codec_histogram_u8', 'codec_rans_encode', 'codec_rans_decode', 'codec_rans_header', 'rans_normalize'):
+        assert callable(getattr(ops, fn))
+    assert 'lfgc_codec_rans' in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+
+
+def test_entries_validate_their_arguments_on_the_host(lib):
+    """include/lfgc.h's return codes, decided before anything is launched: no device is touched and no pointer read."""
+    ws = lib.lfgc_codec_rans_workspace_bytes(200000, 512)
+    assert ws >= 7 * 4 + 8 * 8                                                 # 7 chunks: counts + offsets
+    for n, R in ((0, 512), (1 << 32, 512), (10, 0), (10, 65536)):
+        assert lib.lfgc_codec_rans_workspace_bytes(n, R) == 0
+        assert lib.lfgc_codec_rans_encode_count(ONE, n, R, ONE, ONE, ONE, 1 << 20, None) == E_SHAPE
+        assert lib.lfgc_codec_rans_encode_write(ONE, n, R, ONE, ONE, 1 << 20, ONE, 1 << 20, None) == E_SHAPE
+        assert lib.lfgc_codec_rans_decode(ONE, 1 << 20, n, R, ONE, ONE, ONE, 1 << 20, None) == E_SHAPE
+    assert lib.lfgc_codec_rans_encode_count(None, 10, 1, ONE, ONE, ONE, 1 << 20, None) == E_NULL
+    assert lib.lfgc_codec_rans_encode_count(ONE, 10, 1, None, ONE, ONE, 1 << 20, None) == E_NULL
+    assert lib.lfgc_codec_rans_encode_count(ONE, 10, 1, ONE, None, ONE, 1 << 20, None) == E_NULL
+    assert lib.lfgc_codec_rans_encode_count(ONE, 10, 1, ONE, ONE, None, 1 << 20, None) == E_NULL
+    assert lib.lfgc_codec_rans_encode_count(ONE, 200000, 512, ONE, ONE, ONE, ws - 1, None) == E_WORKSPACE
+    assert lib.lfgc_codec_rans_encode_write(ONE, 10, 1, ONE, None, 1 << 20, ONE, 1 << 20, None) == E_NULL
+    assert lib.lfgc_codec_rans_encode_write(ONE, 10, 1, ONE, ctypes.c_void_p(17), 1 << 20, ONE, 1 << 20, None) == E_ALIGN
+    assert lib.lfgc_codec_rans_encode_write(ONE, 200000, 512, ONE, ONE, 520 + 260 * 7 - 1, ONE, 1 << 20, None) == E_WORKSPACE
+    assert lib.lfgc_codec_rans_decode(None, 1 << 20, 10, 1, ONE, ONE, ONE, 1 << 20, None) == E_NULL
+    assert lib.lfgc_codec_rans_decode(ONE, 1 << 20, 10, 1, ONE, None, ONE, 1 << 20, None) == E_NULL
+    assert lib.lfgc_codec_rans_decode(ctypes.c_void_p(18), 1 << 20, 10, 1, ONE, ONE, ONE, 1 << 20, None) == E_ALIGN
+    assert lib.lfgc_codec_rans_decode(ONE, 520 + 260 * 7 - 1, 200000, 512, ONE, ONE, ONE, 1 << 20, None) == E_SHAPE
+    assert lib.lfgc_codec_histogram_u8(None, 10, ONE, None) == E_NULL
+    assert lib.lfgc_codec_histogram_u8(ONE, -1, ONE, None) == E_SHAPE
+    assert lib.lfgc_codec_histogram_u8(ONE, 10, ctypes.c_void_p(20), None) == E_ALIGN
+    assert lib.lfgc_codec_histogram_u8(ONE, 0, ONE, None) == 0                 # nothing to count, nothing launched
