@@ -280,7 +280,9 @@ int lfgc_codec_compact_f32(const float* x, int64_t n, float* out, int64_t* count
                            int64_t workspace_bytes, lfgc_stream_t stream);
 
 /* out[i] = mask bit (bit_offset + i) ? values[rank of that bit among the set bits of [bit_offset, bit_offset + i)] : 0
- * (restore_model's zero re-insertion, model_utils.py:297-306, there one np.insert per pruned element). */
+ * (restore_model's zero re-insertion, model_utils.py:297-306, there one np.insert per pruned element).  The number of set
+ * bits of the range, the selection's scanned total, is left in the workspace as the int64 at index ceil(n / 2048), behind
+ * the workgroup offsets: a caller that has to verify it reads it there. */
 int lfgc_codec_expand_f32(const uint8_t* mask, int64_t bit_offset, int64_t n, const float* values, float* out,
                           void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
 
@@ -378,6 +380,33 @@ int lfgc_codec_rans_encode_write(const uint8_t* sym, int64_t n, int rounds, cons
  * did not end at its end, 8 a chunk does not lie inside the buffer. */
 int lfgc_codec_rans_decode(const uint8_t* in, int64_t in_bytes, int64_t n, int rounds, uint8_t* out, int32_t* status,
                            void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+
+/* The pruning mask once per CELL (mode 2 of the mask file; the reference has none).  A coefficient
+ * tensor is viewed as x[c][j], c < C channels, j < S cells, in its flat order (x[c * S + j]); every drop layer multiplies it
+ * by one factor per cell, so a pruned model's zero pattern is the same in all C channels.  The mask is then two streams: the
+ * SUPPORT, one bit per cell (any channel non-zero), and the RESIDUAL, the mask bits of the support cells only, channel-major
+ * over the compacted tensor V[c][r] = x[c][j_r] (j_r = the r-th support cell, ascending).  "Non-zero" is the rule of the
+ * mask entry above: v != 0.0f, so -0.0 is zero and NaN is non-zero.  C >= 1, S >= 1 and C * S within int64, else
+ * LFGC_E_SHAPE.  The two selections take the workspace of lfgc_codec_select_workspace_bytes for S elements, 8-byte
+ * aligned.  Integer and copy work only; nothing allocated, no synchronisation, one writer per output address, no atomics. */
+
+/* flags[j] = 1 where any channel of cell j is non-zero, else 0 (S bytes).  The one pass that reads the whole tensor: lanes
+ * run over consecutive cells, 16-byte loads where S % 4 == 0, x is 16-byte and flags 4-byte aligned. */
+int lfgc_codec_support_f32(const float* x, int C, int64_t S, uint8_t* flags, lfgc_stream_t stream);
+/* bits[0 .. (n+7)/8): bit i (MSB first) = flags[i] != 0, tail bits zero.  The caller concatenates the flags of all tensors
+ * first, so the stream needs no bit offsets on the write side. */
+int lfgc_codec_pack_flags_u8(const uint8_t* flags, int64_t n, uint8_t* bits, lfgc_stream_t stream);
+/* V[c * K + r] = x[c * S + j_r] over the K cells with flags[j] != 0, in ascending order; *count (device int64) = K.  V needs
+ * room for C * K floats (C * S when K is not known beforehand).  The existing mask entry over V gives the residual bits, the
+ * existing compaction over V the non-zero values of x in their flat order. */
+int lfgc_codec_compact_support_f32(const float* x, int C, int64_t S, const uint8_t* flags, float* V, int64_t* count,
+                                   void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+/* The inverse: out[c * S + j] = support bit (bit_offset + j) ? V[c * K + rank of that bit among the set bits of
+ * [bit_offset, bit_offset + j)] : 0, every element of out written.  0 <= K <= S comes from the file: every index into V is
+ * clamped to C * K - 1 before the load (K = 0: nothing is loaded), so no file makes the kernel read outside V[0, C * K);
+ * *status (device int32, zeroed by the caller) |= 1 where the S support bits hold a number of set bits other than K. */
+int lfgc_codec_expand_support_f32(const uint8_t* support, int64_t bit_offset, int C, int64_t S, const float* V, int64_t K,
+                                  float* out, int32_t* status, void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused sample + Fourier-embed + MLP decoder

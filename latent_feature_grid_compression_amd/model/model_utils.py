@@ -9,7 +9,8 @@ dequantisation) and only the file layout itself (header, layer fields, byte stre
 
 ``store_model_parameters(..., entropy=True)`` is this package's own extension: a lossless rANS stage over the labels and the
 mask (``lfgc_codec_rans_*``), flagged in the header so that the reference's reader refuses such a file
-instead of misreading it.  Without it the files are the reference's.
+instead of misreading it.  Without it the files are the reference's.  ``channel_mask=True`` on top of it lets the mask file
+store the pruning pattern once per cell instead of once per coefficient (``lfgc_codec_support_f32`` and its companions).
 """
 from __future__ import annotations
 
@@ -138,7 +139,24 @@ def _quantised_block(values: torch.Tensor, bits: int, entropy: bool = False) -> 
     return _f32_bytes(centres) + _coded(rest, _label_streams(labels, bits))
 
 
-def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION, entropy=False):
+_CHANNEL_MASK_MODE = 2    # first byte of a mask file that holds the mask once per cell: support + residual
+
+
+def _channel_mask_file(grids, channels: int) -> bytes:
+    """Mode 2 of the mask file: ``[u8 2][u32 K per tensor][field support][field residual]``.  A tensor is
+    viewed as (channels, S cells); the support has one bit per cell (any channel non-zero), the residual the mask bits of the
+    K support cells only, channel-major; a field is ``_coded`` over its MSB-first bytes."""
+    flags = [ops.codec_support(g, channels) for g in grids]
+    cells = [ops.codec_compact_support(g, channels, f) for g, f in zip(grids, flags)]
+    support = ops.codec_pack_flags(torch.cat(flags))
+    residual = ops.codec_mask(torch.cat([v.reshape(-1) for v in cells]))
+    out = bytes([_CHANNEL_MASK_MODE]) + b''.join(struct.pack('<I', v.shape[1]) for v in cells)
+    for field in (support, residual):
+        out += _coded(field.cpu().numpy().tobytes(), [ops.codec_rans_encode(field)])
+    return out
+
+
+def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION, entropy=False, channel_mask=False):
     """Write ``filename`` (header, first / final layer in fp32, hidden layers and the non-zero wavelet coefficients as
     ``bit_precision``-bit codebook indices, 1 to 16) and ``filename + "_mask.bnr"`` (bit mask of the non-zero
     coefficients): reference :120-223, whose ``bit_precision = 8`` (:141) is the default here.
@@ -146,9 +164,18 @@ def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION, entrop
     ``entropy=True`` adds the lossless rANS stage: header byte 5 becomes ``bits | 0x80``, every quantised
     block is ``[centres][u8 mode]`` + the plain remainder (mode 0) or the labels' rANS streams (mode 1), and the mask file is
     ``[u8 mode]`` + the plain mask or its rANS stream; mode 1 only where it is strictly smaller.  ``restore_model`` reads
-    either kind.  The default writes the same bytes as before."""
+    either kind.  The default writes the same bytes as before.
+
+    ``channel_mask=True`` (needs ``entropy=True``: the plain mask file has no mode byte) lets the mask file take a third
+    mode, the mask once per cell: every drop layer prunes whole cells, so the zero pattern of a pruned model repeats in all
+    channels, and mode 2 stores one support bit per cell plus the mask bits of the support cells only.  The writer forms
+    modes 0, 1 and 2 and keeps the strictly smallest (ties: the lower mode), so a dense or per-coefficient-pruned model
+    keeps the ``entropy=True`` file; the parameter file is the ``entropy=True`` one, byte for byte.  ``restore_model``
+    recognises the mode from the mask file's first byte."""
     bits = _check_bit_precision(bit_precision)
-    entropy = bool(entropy)
+    entropy, channel_mask = bool(entropy), bool(channel_mask)
+    if channel_mask and not entropy:
+        raise ValueError('channel_mask=True needs entropy=True: the plain mask file has no mode byte')
     if len(model.shape_array) == 0:
         raise ValueError('a model without wavelet levels has no grid_size to put in the header (reference :131)')
     grids = [_device_flat(g) for g in model.feature_grid]
@@ -177,8 +204,14 @@ def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION, entrop
             f.write(_quantised_block(nz, bits, entropy))
     mask = ops.codec_mask(torch.cat(grids))           # one bit stream over all tensors, like the reference's mask_string
     plain_mask = mask.cpu().numpy().tobytes()
+    mask_file = _coded(plain_mask, [ops.codec_rans_encode(mask)]) if entropy else plain_mask
+    channels = int(model.feature_grid[0].shape[0])
+    if channel_mask and all(g.numel() % channels == 0 for g in grids):
+        per_cell = _channel_mask_file(grids, channels)
+        if len(per_cell) < len(mask_file):
+            mask_file = per_cell
     with open(filename + '_mask.bnr', 'wb') as f:
-        f.write(_coded(plain_mask, [ops.codec_rans_encode(mask)]) if entropy else plain_mask)
+        f.write(mask_file)
 
 
 def restore_model(filename, wavelet_filter='db2'):
@@ -189,7 +222,13 @@ def restore_model(filename, wavelet_filter='db2'):
 
     An entropy-mode pair (``store_model_parameters(..., entropy=True)``) is recognised by header byte 5 (``bits | 0x80``).
     Both kinds are read and checked on the host in full -- ``ValueError`` for a truncated file, a stream header that does
-    not add up, or a frequency on a label the codebook does not have -- before the first device call."""
+    not add up, or a frequency on a label the codebook does not have -- before the first device call.
+
+    A mask file in mode 2 (``channel_mask=True``: the mask once per cell) is recognised by its first byte.
+    Its host checks: truncation, trailing bytes, a field mode above 1, tensors that are no whole number of cells, more
+    support cells than cells, more non-zero coefficients than the support cells hold, a stream of another length than its
+    field.  The two counts only the device can check -- set support bits and set residual bits per tensor -- raise
+    ``ValueError`` after the expansion, which is made safe against either being wrong."""
     with open(filename, 'rb') as f:
         raw = f.read()
     with open(filename + '_mask.bnr', 'rb') as f:
@@ -267,12 +306,51 @@ def restore_model(filename, wavelet_filter='db2'):
     net_biases.append(floats(output_dim))
     grid_blocks = [quantised(nz) for nz in grid_sizes]
 
+    def per_cell_mask():
+        """Host description of a mode-2 mask file: (cells S_t, support cells K_t, [(bytes, stream header or None) of the
+        support and of the residual field])."""
+        what = filename + '_mask.bnr'
+        if feature_size < 1 or any((nz + z) % feature_size for nz, z in zip(grid_sizes, zeros)):
+            raise ValueError('%s: a tensor is no whole number of cells of %d channels' % (what, feature_size))
+        cells = [(nz + z) // feature_size for nz, z in zip(grid_sizes, zeros)]
+        at = 1 + 4 * n_grids
+        if len(mask_raw) < at:
+            raise ValueError('%s: truncated mask file' % what)
+        kept = list(struct.unpack_from('<%dI' % n_grids, mask_raw, 1))
+        for t, (nz, S, K) in enumerate(zip(grid_sizes, cells, kept)):
+            if K > S or nz > feature_size * K:
+                raise ValueError('%s: tensor %d has %d cells and %d non-zero coefficients, the file names %d support cells'
+                                 % (what, t, S, nz, K))
+        fields = []
+        for nbits in (sum(cells), feature_size * sum(kept)):
+            nbytes = (nbits + 7) // 8
+            if at >= len(mask_raw):
+                raise ValueError('%s: truncated mask file' % what)
+            mode = mask_raw[at]
+            at += 1
+            if mode == 0:
+                if at + nbytes > len(mask_raw):
+                    raise ValueError('%s: truncated mask file' % what)
+                fields.append((np.frombuffer(mask_raw[at:at + nbytes], dtype=np.uint8), None))
+                at += nbytes
+            elif mode == 1:
+                fields.append(rans_stream(mask_raw, at, nbytes, 256, what))
+                at += fields[-1][1].nbytes
+            else:
+                raise ValueError('%s: field mode %d not supported' % (what, mode))
+        if at != len(mask_raw):
+            raise ValueError('%s: %d trailing bytes' % (what, len(mask_raw) - at))
+        return cells, kept, fields
+
     total = sum(grid_sizes) + sum(zeros)
-    mask_stream = None
+    mask_stream = per_cell = None
     if not entropy:
         mask_bytes = len(mask_raw)
-    elif len(mask_raw) < 1 or mask_raw[0] > 1:
+    elif len(mask_raw) < 1 or mask_raw[0] > _CHANNEL_MASK_MODE:
         raise ValueError('%s_mask.bnr: %s' % (filename, 'mode %d not supported' % mask_raw[0] if mask_raw else 'empty'))
+    elif mask_raw[0] == _CHANNEL_MASK_MODE:
+        per_cell = per_cell_mask()
+        mask_bytes = (total + 7) // 8            # the flat mask is never materialised
     elif mask_raw[0] == 0:
         mask_raw = mask_raw[1:]
         mask_bytes = len(mask_raw)
@@ -308,14 +386,42 @@ def restore_model(filename, wavelet_filter='db2'):
 
     net_weights = [w.to(dev) if torch.is_tensor(w) else dequantised(w) for w in net_weights]
     net_biases = [b.to(dev) for b in net_biases]
-    if mask_stream is None:
-        mask = upload(np.frombuffer(mask_raw, dtype=np.uint8))
-    else:
-        mask = ops.codec_rans_decode_parsed(upload(mask_stream[0]), mask_stream[1])
     grid_params, bit_offset = [], 0
-    for block, nz, z in zip(grid_blocks, grid_sizes, zeros):
-        grid_params.append(ops.codec_expand(mask, bit_offset, nz + z, dequantised(block)))
-        bit_offset += nz + z
+    if per_cell is not None:
+        # mode 2: the values go to the set residual bits of the tensor's support cells, the cells to the set support bits.
+        # The values are padded to the residual range's length, so no residual makes the expansion read past them; the
+        # two counts the host could not check -- set residual bits = non-zero coefficients, set support bits = K -- come
+        # back from the device once, after the last tensor.
+        cells, kept, fields = per_cell
+        support, residual = [upload(data) if info is None else ops.codec_rans_decode_parsed(upload(data), info)
+                             for data, info in fields]
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        found, cell_offset = [], 0
+        for block, nz, S, K in zip(grid_blocks, grid_sizes, cells, kept):
+            n = feature_size * K
+            values = torch.zeros(n, dtype=torch.float32, device=dev)
+            if n:
+                values[:nz] = dequantised(block)
+                values, count = ops.codec_expand(residual, bit_offset, n, values, counted=True)
+                found.append(count)
+            else:
+                found.append(torch.zeros((), dtype=torch.int64, device=dev))
+            grid_params.append(ops.codec_expand_support(support, cell_offset, feature_size, S, values, K, status))
+            cell_offset += S
+            bit_offset += n
+        found = torch.stack(found).cpu().tolist()
+        if int(status.item()) or found != grid_sizes:
+            raise ValueError('%s_mask.bnr: the support or the residual does not hold the number of set bits the files name '
+                             '(support cells %s, status %d; non-zero coefficients %s, set residual bits %s)'
+                             % (filename, kept, int(status.item()), grid_sizes, found))
+    else:
+        if mask_stream is None:
+            mask = upload(np.frombuffer(mask_raw, dtype=np.uint8))
+        else:
+            mask = ops.codec_rans_decode_parsed(upload(mask_stream[0]), mask_stream[1])
+        for block, nz, z in zip(grid_blocks, grid_sizes, zeros):
+            grid_params.append(ops.codec_expand(mask, bit_offset, nz + z, dequantised(block)))
+            bit_offset += nz + z
 
     model = setup_model(input_channel=input_channel, hidden_channel=layer_width, out_channel=output_dim,
                         num_layer=n_layers, embedding_type='fourier', n_embedding_freq=2, drop_type='',

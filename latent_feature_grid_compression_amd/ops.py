@@ -982,9 +982,19 @@ def codec_compact(x: torch.Tensor) -> torch.Tensor:
     return out[:int(count.item())]
 
 
+_SELECT_PER_BLOCK = 2048          # kSelectPerBlock of csrc/lfgc_select.h: elements per workgroup of a selection
+
+
 @_on_device
-def codec_expand(mask: torch.Tensor, bit_offset: int, n: int, values: torch.Tensor) -> torch.Tensor:
-    """(n,) fp32: values scattered to the set bits [bit_offset, bit_offset + n) of the MSB-first mask, zeros elsewhere."""
+def codec_expand(mask: torch.Tensor, bit_offset: int, n: int, values: torch.Tensor, counted: bool = False):
+    """(n,) fp32: values scattered to the set bits [bit_offset, bit_offset + n) of the MSB-first mask, zeros elsewhere.
+    ``counted``: (that, the number of set bits in the range as a 0-d device int64 -- the selection's scanned total, which
+    stays in its workspace behind the block offsets; no synchronisation)."""
+    out, ws = _codec_expand(mask, bit_offset, n, values)
+    return (out, ws[-(-int(n) // _SELECT_PER_BLOCK)]) if counted else out
+
+
+def _codec_expand(mask, bit_offset, n, values):
     _require_hip(mask, values)
     if mask.dtype != torch.uint8 or (int(bit_offset) + int(n) + 7) // 8 > mask.numel():
         raise ValueError('mask too short for %d bits at offset %d' % (n, bit_offset))
@@ -995,6 +1005,88 @@ def codec_expand(mask: torch.Tensor, bit_offset: int, n: int, values: torch.Tens
     ws = _select_workspace(n, mask.device)
     check(_lib.load().lfgc_codec_expand_f32(mask.contiguous().data_ptr(), int(bit_offset), int(n), values.data_ptr(),
                                             out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(mask)), 'lfgc_codec_expand_f32')
+    return out, ws
+
+
+# ---- the mask once per cell: support + residual (mode 2 of the mask file; csrc/lfgc_chanmask.hip) --------------
+
+def _cells(x: torch.Tensor, C: int) -> Tuple[torch.Tensor, int, int]:
+    C = int(C)
+    if C < 1 or x.numel() < 1 or x.numel() % C:
+        raise ValueError('a tensor of %d coefficients is no whole number (at least one) of cells of %d channels' % (x.numel(), C))
+    return _flat_f32(x), C, x.numel() // C
+
+
+@_on_device
+def codec_support(x: torch.Tensor, C: int) -> torch.Tensor:
+    """uint8 (S,): 1 where any of the C channels of cell j is non-zero, x viewed as (C, S) in its flat order."""
+    x, C, S = _cells(x, C)
+    flags = torch.empty(S, dtype=torch.uint8, device=x.device)
+    check(_lib.load().lfgc_codec_support_f32(x.data_ptr(), C, S, flags.data_ptr(), _stream(x)), 'lfgc_codec_support_f32')
+    return flags
+
+
+@_on_device
+def codec_pack_flags(flags: torch.Tensor) -> torch.Tensor:
+    """uint8 (ceil(n/8),): bit i (MSB first) = flags.flat[i] != 0 of a uint8 tensor, tail bits zero."""
+    flags = _flat_u8(flags, 'flags')
+    _require_hip(flags)
+    if flags.numel() < 1:
+        raise ValueError('flag packing needs at least one flag')
+    bits = torch.empty((flags.numel() + 7) // 8, dtype=torch.uint8, device=flags.device)
+    check(_lib.load().lfgc_codec_pack_flags_u8(flags.data_ptr(), flags.numel(), bits.data_ptr(), _stream(flags)),
+          'lfgc_codec_pack_flags_u8')
+    return bits
+
+
+@_on_device
+def codec_compact_support(x: torch.Tensor, C: int, flags: torch.Tensor) -> torch.Tensor:
+    """(C, K) fp32: the cells of x (viewed as (C, S)) whose flag is set, in order.  Synchronises once to learn K."""
+    x, C, S = _cells(x, C)
+    flags = _flat_u8(flags, 'flags')
+    _require_hip(flags)
+    if flags.numel() != S:
+        raise ValueError('%d flags for %d cells' % (flags.numel(), S))
+    V = torch.empty(C * S, dtype=torch.float32, device=x.device)
+    count = torch.zeros(1, dtype=torch.int64, device=x.device)
+    ws = _select_workspace(S, x.device)
+    check(_lib.load().lfgc_codec_compact_support_f32(x.data_ptr(), C, S, flags.data_ptr(), V.data_ptr(), count.data_ptr(),
+                                                     ws.data_ptr(), ws.numel() * 8, _stream(x)), 'lfgc_codec_compact_support_f32')
+    K = int(count.item())
+    return V[:C * K].view(C, K)
+
+
+@_on_device
+def codec_expand_support(support: torch.Tensor, bit_offset: int, C: int, S: int, V: torch.Tensor, K: int,
+                         status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(C * S,) fp32: cell j of every channel c is V[c * K + rank] where bit (bit_offset + j) of the MSB-first support stream
+    is set, zero elsewhere.  K is the caller's word for the number of set bits: the kernel clamps every index into V to
+    C * K - 1 and sets bit 0 of ``status`` (device int32, one element, accumulated over calls, no synchronisation) where the
+    support holds another number.  Without ``status`` the wrapper checks it itself, synchronising, and raises ValueError."""
+    _require_hip(support, V, status)
+    bit_offset, C, S, K = int(bit_offset), int(C), int(S), int(K)
+    if C < 1 or S < 1 or bit_offset < 0 or not 0 <= K <= S:
+        raise ValueError('expansion needs C >= 1, S >= 1, a bit offset >= 0 and 0 <= K <= S, got C = %d, S = %d, offset %d, '
+                         'K = %d' % (C, S, bit_offset, K))
+    if support.dtype != torch.uint8 or (bit_offset + S + 7) // 8 > support.numel():
+        raise ValueError('support too short for %d bits at offset %d' % (S, bit_offset))
+    V = _f32c(V).reshape(-1)
+    if V.numel() < C * K:
+        raise ValueError('%d values where C * K = %d are needed' % (V.numel(), C * K))
+    if V.numel() == 0:
+        V = torch.zeros(1, dtype=torch.float32, device=support.device)
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=support.device)
+    elif status.dtype != torch.int32 or status.numel() != 1 or not status.is_contiguous():
+        raise ValueError('status must be one int32')
+    out = torch.empty(C * S, dtype=torch.float32, device=support.device)
+    ws = _select_workspace(S, support.device)
+    check(_lib.load().lfgc_codec_expand_support_f32(support.contiguous().data_ptr(), bit_offset, C, S, V.data_ptr(), K,
+                                                    out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                                    _stream(support)), 'lfgc_codec_expand_support_f32')
+    if own and int(status.item()):
+        raise ValueError('the support holds a number of set bits other than K = %d' % K)
     return out
 
 
