@@ -409,6 +409,43 @@ int lfgc_codec_expand_support_f32(const uint8_t* support, int64_t bit_offset, in
                                   float* out, int32_t* status, void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Error-bounded residual layer (the reference has none): what turns "the model's prediction p of a
+ * voxel" into "a value within eps of the ground truth g".  Host side (file layout, rANS over the symbols, slab loop):
+ * latent_feature_grid_compression_amd/model/residual_codec.py.  With eps a positive normal fp32 number, step = eps + eps and
+ * inv = 1.0f / step formed on the host (LFGC_E_SHAPE unless all three are positive, normal and finite), per voxel, every
+ * operation ONE fp32 rounding, never an fma:
+ *     t = (g - p) * inv;   q = rintf(t)   (ties to even);   escape unless |q| <= 127   (NaN and Inf land here);
+ *     r = p + (float)(int)q * step;       escape unless |(double)g - (double)r| <= (double)eps;
+ *     symbol = (q << 1) ^ (q >> 31) in 0..254, or 255 for an escape.
+ * A voxel with a symbol below 255 decodes to r, an escape to the bits of g (NaN payloads included), kept in lattice order.
+ * The second test is the guarantee itself: the rounding of r breaks the bound for some voxels at small eps, and the test
+ * makes those escape.  It holds for the decoder only if its p has the encoder's bits, so both sides form
+ *     checksum = sum_i (uint64)bits(p_i) * (2 i + 1)  mod 2^64        (i = index in the array; integer adds, order-free)
+ * and the caller compares them.  n >= 1; pred, gt, out, outliers 4-byte, checksum, counts and workspaces 8-byte aligned
+ * (LFGC_E_ALIGN).  Nothing allocated, no synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* sym[i] = the symbol of voxel i; *checksum (device uint64, zeroed by the caller) += the checksum of pred.  One streaming
+ * pass of 9 bytes per voxel: 4 voxels per lane (16-byte loads, one 4-byte store) where pred and gt are 16-byte and sym
+ * 4-byte aligned, the n % 4 tail and any other alignment one voxel per lane. */
+int lfgc_residual_quantize_f32(const float* pred, const float* gt, int64_t n, float eps, uint8_t* sym, uint64_t* checksum,
+                               lfgc_stream_t stream);
+/* Workspace of the two selections below (lfgc_codec_select_workspace_bytes' rule). */
+int64_t lfgc_residual_workspace_bytes(int64_t n);
+/* outliers[0..*count) = gt[i] of the voxels with sym[i] == 255, in order, bit for bit; count: device int64.  outliers needs
+ * room for n floats where the count is not known beforehand. */
+int lfgc_residual_outliers_f32(const uint8_t* sym, const float* gt, int64_t n, float* outliers, int64_t* count, void* workspace,
+                               int64_t workspace_bytes, lfgc_stream_t stream);
+/* out[i] = sym[i] == 255 ? outliers[rank of i among the escapes] : r(pred[i], sym[i]), every i < n written; out may be pred.
+ * 0 <= K <= n is the caller's word for the number of outliers it holds (from the file; outliers may be NULL for K = 0): an
+ * escape of rank >= K reads nothing, writes 0 and sets bit 1 of *status; bit 0 is set where the escapes found are not K
+ * (*status: device int32, zeroed by the caller; *n_escape: device int64, the number found).  *checksum (zeroed by the
+ * caller) += the checksum of pred, taken by a pass of its own before anything is written. */
+int lfgc_residual_apply_f32(const float* pred, const uint8_t* sym, int64_t n, float eps, const float* outliers, int64_t K,
+                            float* out, uint64_t* checksum, int64_t* n_escape, int32_t* status, void* workspace,
+                            int64_t workspace_bytes, lfgc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused sample + Fourier-embed + MLP decoder
  * ---------------------------------------------------------------------------------------------- */
 

@@ -119,6 +119,11 @@ SIGNATURES = {
     'lfgc_codec_compact_support_f32': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     'lfgc_codec_expand_support_f32': (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                               c_int64, c_void_p]),
+    'lfgc_residual_quantize_f32': (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    'lfgc_residual_workspace_bytes': (c_int64, [c_int64]),
+    'lfgc_residual_outliers_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    'lfgc_residual_apply_f32': (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int64, c_void_p]),
     'lfgc_mlp_supported': (c_int, [POINTER(MlpDesc)]),
     'lfgc_grid_channel_stride': (c_int, [c_int]),
     'lfgc_packed_bytes': (c_int64, [POINTER(MlpDesc)]),

@@ -445,3 +445,7 @@ def restore_model(filename, wavelet_filter='db2'):
             p.data = net_biases[bdx].view(p.data.shape)
             bdx += 1
     return model
+
+
+# the error-bounded residual layer over a stored model is exported from here as well
+from .residual_codec import PredictionMismatch, parse_residual_file, restore_volume, store_residuals  # noqa: E402,F401

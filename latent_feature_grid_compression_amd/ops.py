@@ -1323,6 +1323,114 @@ def codec_rans_decode(stream_u8: torch.Tensor) -> torch.Tensor:
     return codec_rans_decode_parsed(stream, info)
 
 
+# ---- error-bounded residual layer (include/lfgc.h; csrc/lfgc_residual.hip) ----------------------------------
+
+RESIDUAL_ESCAPE = 255             # the symbol of a voxel stored verbatim
+
+
+def residual_eps(max_error) -> float:
+    """float32(max_error) as a Python float.  ValueError unless it, step = eps + eps and 1 / step are positive, normal, finite
+    fp32 numbers -- the rule of the C entries, applied on the host."""
+    try:
+        with np.errstate(all='ignore'):
+            eps = np.float32(max_error)
+            step = np.float32(eps + eps)
+            inv = np.float32(1.0) / step if step != 0 else np.float32(np.inf)
+    except (TypeError, ValueError):
+        raise ValueError('max_error must be a number, got %r' % (max_error,)) from None
+    tiny = np.finfo(np.float32).tiny
+    if eps.shape != () or not all(np.isfinite(v) and v >= tiny for v in (eps, step, inv)):
+        raise ValueError('max_error, twice it and the reciprocal of that must be positive normal fp32 numbers, got %r' % (max_error,))
+    return float(eps)
+
+
+def _residual_f32(t, what: str, n: Optional[int] = None) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous float32 tensor' % what)
+    if n is not None and t.numel() != n:
+        raise ValueError('%s has %d elements where %d are needed' % (what, t.numel(), n))
+    return t.detach().reshape(-1)
+
+
+def _residual_word(t, dtype, what: str, device) -> torch.Tensor:
+    """A one-element accumulator of the entries (checksum, status): the caller's, or a zeroed one."""
+    if t is None:
+        return torch.zeros(1, dtype=dtype, device=device)
+    if not torch.is_tensor(t) or t.dtype != dtype or t.numel() != 1 or not t.is_contiguous():
+        raise ValueError('%s must be one %s' % (what, str(dtype).replace('torch.', '')))
+    return t
+
+
+@_on_device
+def residual_quantize(pred: torch.Tensor, gt: torch.Tensor, max_error, sym: Optional[torch.Tensor] = None,
+                      checksum: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(symbols uint8 (n,), checksum int64 (1,)) of a prediction against its ground truth under the bound ``max_error``: 0 to
+    254 = the zigzag of the residual in steps of twice the bound, 255 = the voxel is stored verbatim.  The checksum of
+    ``pred`` (the uint64 of include/lfgc.h held in an int64) is ADDED to ``checksum`` where one is given.  No synchronisation."""
+    eps = residual_eps(max_error)
+    p = _residual_f32(pred, 'pred')
+    g = _residual_f32(gt, 'gt', p.numel())
+    _require_hip(p, g, sym, checksum)
+    if p.numel() < 1:
+        raise ValueError('the residual layer needs at least one voxel')
+    if sym is None:
+        sym = torch.empty(p.numel(), dtype=torch.uint8, device=p.device)
+    elif sym.dtype != torch.uint8 or sym.numel() != p.numel() or not sym.is_contiguous():
+        raise ValueError('sym must be a contiguous uint8 tensor of %d elements' % p.numel())
+    checksum = _residual_word(checksum, torch.int64, 'checksum', p.device)
+    check(_lib.load().lfgc_residual_quantize_f32(p.data_ptr(), g.data_ptr(), p.numel(), eps, sym.data_ptr(), checksum.data_ptr(),
+                                                 _stream(p)), 'lfgc_residual_quantize_f32')
+    return sym.reshape(-1), checksum
+
+
+@_on_device
+def residual_outliers(sym: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
+    """The ground truth of the voxels whose symbol is 255, in order, bit for bit (1-D fp32).  Synchronises once to learn
+    their number."""
+    sym = _flat_u8(sym, 'sym')
+    g = _residual_f32(gt, 'gt', sym.numel())
+    _require_hip(sym, g)
+    if sym.numel() < 1:
+        raise ValueError('the residual layer needs at least one voxel')
+    out = torch.empty(sym.numel(), dtype=torch.float32, device=sym.device)
+    count = torch.zeros(1, dtype=torch.int64, device=sym.device)
+    ws = _select_workspace(sym.numel(), sym.device, 'lfgc_residual_workspace_bytes')
+    check(_lib.load().lfgc_residual_outliers_f32(sym.data_ptr(), g.data_ptr(), sym.numel(), out.data_ptr(), count.data_ptr(),
+                                                 ws.data_ptr(), ws.numel() * 8, _stream(sym)), 'lfgc_residual_outliers_f32')
+    return out[:int(count.item())]
+
+
+@_on_device
+def residual_apply(pred: torch.Tensor, sym: torch.Tensor, max_error, outliers: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   checksum: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """(out, checksum int64 (1,), n_escape int64 (1,), status int32 (1,)): the volume restored from a prediction, its symbols
+    and the K = ``outliers.numel()`` voxels stored verbatim.  ``out`` may be ``pred`` (default: a new tensor of its shape).
+    The kernel never reads past the K outliers: an escape beyond them becomes 0 and sets bit 1 of ``status``, and bit 0 is
+    set where the symbols hold another number of escapes than K (``n_escape``: how many).  ``checksum`` and ``status`` are
+    accumulated into where given.  No synchronisation: the caller reads the three words when it wants them."""
+    eps = residual_eps(max_error)
+    p = _residual_f32(pred, 'pred')
+    sym = _flat_u8(sym, 'sym')
+    if sym.numel() != p.numel():
+        raise ValueError('%d symbols for %d voxels' % (sym.numel(), p.numel()))
+    if p.numel() < 1:
+        raise ValueError('the residual layer needs at least one voxel')
+    v = _residual_f32(outliers, 'outliers')
+    if v.numel() > p.numel():
+        raise ValueError('%d outliers for %d voxels' % (v.numel(), p.numel()))
+    _require_hip(p, sym, v, out, checksum, status)
+    o = torch.empty_like(pred) if out is None else out
+    _residual_f32(o, 'out', p.numel())
+    checksum = _residual_word(checksum, torch.int64, 'checksum', p.device)
+    status = _residual_word(status, torch.int32, 'status', p.device)
+    n_escape = torch.zeros(1, dtype=torch.int64, device=p.device)
+    ws = _select_workspace(p.numel(), p.device, 'lfgc_residual_workspace_bytes')
+    check(_lib.load().lfgc_residual_apply_f32(p.data_ptr(), sym.data_ptr(), p.numel(), eps, v.data_ptr() if v.numel() else None,
+                                              v.numel(), o.data_ptr(), checksum.data_ptr(), n_escape.data_ptr(), status.data_ptr(),
+                                              ws.data_ptr(), ws.numel() * 8, _stream(p)), 'lfgc_residual_apply_f32')
+    return o, checksum, n_escape, status
+
+
 # ---- ground truth / statistics -------------------------------------------------------------------------
 
 def _float3(v):
