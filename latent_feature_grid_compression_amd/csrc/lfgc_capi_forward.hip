@@ -64,6 +64,12 @@ int fwd_env_waves(int resident, int waves) {            // diagnostics: LFGC_FWD
     if (const char* e = getenv("LFGC_FWD_WAVES")) { if (!resident && (e[0] == '4' || e[0] == '8')) return e[0] - '0'; }
     return waves;
 }
+// diagnostics: LFGC_FWD_RUNTIME_DEPTH=1 runs the any-depth f16 kernels on 4-layer nets too -- the baseline arm of same-tree
+// A/Bs (tools/ab_forward.py) and the reference of tests/test_fwd_static_depth_gpu.py
+int fwd_env_runtime_depth() {
+    const char* e = getenv("LFGC_FWD_RUNTIME_DEPTH");
+    return (e && e[0] == '1') ? 1 : 0;
+}
 
 long long fwd_lds_bytes(const LfgcPlan& p, bool h16, bool resident, long long table_floats, int nzc) {
     return 4 * (h16 ? lfgc_fwd16_lds_floats(p, resident, table_floats, nzc) : lfgc_fwd_lds_floats(p, resident, table_floats));
@@ -177,6 +183,7 @@ extern "C" int lfgc_forward_f32(const lfgc_mlp_desc* desc, const lfgc_positions*
     const bool h16 = precision != LFGC_PRECISION_F32;
     a.single = precision == LFGC_PRECISION_F16 ? 1 : 0;
     a.status = nullptr; a.redo_if = nullptr; a.stamps = nullptr;
+    a.runtime_depth = fwd_env_runtime_depth();
 #ifdef LFGC_STAMPS
     a.stamps = g_stamps;
 #endif

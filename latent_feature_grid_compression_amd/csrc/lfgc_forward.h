@@ -50,8 +50,12 @@ struct LfgcFwdArgs {
     // lattice mode, f16 builds: "z-run" tiles (LfgcColumnSampler): a wave's 32 samples are 32 consecutive z of ONE (x, y)
     // row of the slab; tiles_per_row = ceil(res2 / 32), ntiles = rows * tiles_per_row, nzc = z cells a tile's column holds
     int zrun, nzc, tiles_per_row;
+    // f16 builds, read by the launcher only: 1 = the any-depth kernel even where a depth-specialised one exists
+    // (diagnostics: LFGC_FWD_RUNTIME_DEPTH).  It sits in what was padding before `ntiles`: no other member moves.
+    int runtime_depth;
     long long ntiles;
 };
+static_assert(sizeof(LfgcFwdArgs) == 184 && offsetof(LfgcFwdArgs, ntiles) == 176, "kernel-argument layout");
 
 // Lattice coordinate of voxel v along one axis, formed like field_from_net does per tile
 // (visualization/OutputToVTK.py:23-37) + torch.linspace's CPU formula (start + step*i below the

@@ -365,8 +365,15 @@ constexpr bool lfgc_fwd16_offsets_are_the_plans(int L) {
 }
 
 // ZRUN (lattice mode only, never with STASH): z-run tiles and the column sampler (LfgcColumnSampler, lfgc_forward.h).
-template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH, bool SPLIT, bool ZRUN>
+// LD: the net's depth as a compile-time value, or 0 for any depth (a.L).  With a run-time depth the tile body is a loop
+// over ping-pong layer pairs with three alternative endings, and at every join the compiler moves the activation
+// ping-pong, the carry accumulator and the operand queue between register sets (about 100 v_mov per tile of a 4-layer
+// net, all outside the MFMAs' shadow); the ring slot, the next block and its DMA plan are run-time scalar work beside
+// every barrier.  LD = 4 (the depth of every BASELINE net; the launcher selects it, inference kernels only) writes the
+// four layers out straight-line and folds those to constants: the same instructions in the same order otherwise.
+template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH, bool SPLIT, bool ZRUN, int LD>
 __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwdArgs a) {
+    static_assert(LD == 0 || (LD == 4 && !STASH), "depth-specialised bodies exist for 4-layer inference only");
     using SHAPE = LfgcShape<CH, MT, NF>;
     constexpr LfgcPlan P = SHAPE::P;
     constexpr int HP = P.HP, KS0 = P.KS0;        // KS0: fp32 inputs per lane (stash layout of the exact build)
@@ -400,7 +407,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);      // the same number, known to be wave-uniform
     const int j = lane & 31;
     const int hh = lane >> 5;
-    const int L = a.L;
+    const int L = LD ? LD : a.L;
     const int off_final = blk0 + (L - 1) * blk1;
     const int off_h = off_final + HP + 4 + tblk0 + (L - 1) * tblk1;
     const float* hblk = a.packed + off_h + 32 + LFGC_MAX_LAYERS * HP + HP;
@@ -483,7 +490,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
         // opaque per batch: otherwise the address arithmetic of every piece of every block is hoisted out of this loop
         // into ~60 SGPRs that do not exist (spilled to VGPR lanes, v_readlane in the gaps)
         asm volatile("" : "+s"(dma.wave));
-        auto acquire = [&](int l) -> const float* {
+        auto acquire = [&](int l) __attribute__((always_inline)) -> const float* {
             if (!STREAM) return s_w + (l == 0 ? 0 : blkh0 + (l - 1) * blkh1);
             LFGC_STAMP(2 + 2 * (l < 6 ? l : 6));           // the layer before this acquire (or the input phase for l = 0 -> slot 1 below)
 #if LFGC_ABLATE & 8                                        // diagnostics: no weight streaming, no barriers (wrong results)
@@ -500,14 +507,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
             LFGC_STAMP(1);                                  // wait for my DMA pieces
             __syncthreads();
             LFGC_STAMP(3 + 2 * (l < 5 ? l : 5));            // barrier before layer l
-            const float* blk = s_w + (step & 1) * BLKMAX;
+            // ring parity: layer l of a net of even compile-time depth always finds its block in slot l & 1
+            static_assert(LD % 2 == 0, "the ring parity is kept per tile");
+            const unsigned par = LD ? (unsigned)l : step;
+            const float* blk = s_w + (par & 1) * BLKMAX;
             // the next block (the layer after this one, or layer 0 of the next batch) goes into the other ring slot -- every
             // wave is past the barrier, so nobody reads it any more -- piece by piece under this layer's MFMAs
             // (after the last batch the slot is filled once more for nobody: an unconditional stream keeps the gaps
             // free of branches)
             const int ln = (l + 1 == L) ? 0 : l + 1;
             dma.src = hblk + (ln == 0 ? 0 : blkh0 + (long long)(ln - 1) * blkh1);
-            dma.dst = s_w + ((step + 1) & 1) * BLKMAX;
+            dma.dst = s_w + ((par + 1) & 1) * BLKMAX;
             dma.nvec = (ln == 0 ? blkh0 : blkh1) / 4;
             lfgc_dma_plan_block(dma);
             ++step;
@@ -562,8 +572,18 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
                 lfgc_layer_fwd16<KS16_0, MT, SH0, STASH, false, SPLIT, false, NP1, blkh1 / 4, WAVES>(blk, X0hi, X0lo, ca, s_scale[8], s_bias, Ahi, Alo, ca,
                                                                              s_final, ydot, tmax, stash_of(0), j, hh, lane, dma);
         }
-        // hidden layers 1 .. L-2 in ping-pong pairs, then the last one with the head folded in
-        {
+        if constexpr (LD == 4) {     // straight-line: A -> B, B -> A, the last layer and the head from A
+            const float* blk = acquire(1);
+            lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[9], s_bias + HP, Bhi, Blo, cb,
+                                                                        s_final, ydot, tmax, stash_of(1), j, hh, lane, dma);
+            blk = acquire(2);
+            lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, false, SPLIT, true, NP1, blkh1 / 4, WAVES>(blk, Bhi, Blo, cb, s_scale[10], s_bias + 2 * HP, Ahi, Alo, ca,
+                                                                        s_final, ydot, tmax, stash_of(2), j, hh, lane, dma);
+            blk = acquire(3);
+            lfgc_layer_fwd16<KS16_1, MT, SH1, STASH, true, SPLIT, true, NP0, blkh0 / 4, WAVES>(blk, Ahi, Alo, ca, s_scale[11], s_bias + 3 * HP, Bhi, Blo, cb,
+                                                                       s_final, ydot, tmax, stash_of(3), j, hh, lane, dma);
+        } else {
+            // hidden layers 1 .. L-2 in ping-pong pairs, then the last one with the head folded in
             int l = 1;
             for (; l + 2 < L; l += 2) {
                 const float* blk = acquire(l);
@@ -613,10 +633,21 @@ __global__ __launch_bounds__(WAVES * 64, 2) void lfgc_fwd16_kernel(const LfgcFwd
 #endif
 }
 
+template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH, bool SPLIT, bool ZRUN, int LD>
+static int lfgc_launch_fwd16_ld(const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream) {
+    return lfgc_launch<lfgc_fwd16_kernel<CH, MT, NF, WAVES, STREAM, STASH, SPLIT, ZRUN, LD>>(dim3(grid), dim3(WAVES * 64), lds_bytes,
+                                                                                             stream, a);
+}
+
+// Inference on a 4-layer net runs the depth-specialised body (LD = 4) unless the caller asks for the any-depth one
+// (a.runtime_depth); every other depth, and every kernel that writes a stash, runs LD = 0.
 template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH, bool SPLIT, bool ZRUN>
 static int lfgc_launch_fwd16_cfg(const LfgcFwdArgs& a, int lds_bytes, int grid, hipStream_t stream) {
-    return lfgc_launch<lfgc_fwd16_kernel<CH, MT, NF, WAVES, STREAM, STASH, SPLIT, ZRUN>>(dim3(grid), dim3(WAVES * 64), lds_bytes,
-                                                                                         stream, a);
+    if constexpr (!STASH) {
+        if (a.L == 4 && !a.runtime_depth)
+            return lfgc_launch_fwd16_ld<CH, MT, NF, WAVES, STREAM, STASH, SPLIT, ZRUN, 4>(a, lds_bytes, grid, stream);
+    }
+    return lfgc_launch_fwd16_ld<CH, MT, NF, WAVES, STREAM, STASH, SPLIT, ZRUN, 0>(a, lds_bytes, grid, stream);
 }
 
 template <int CH, int MT, int NF, int WAVES, bool STREAM, bool STASH>
