@@ -82,8 +82,12 @@ int lfgc_grid_layout_f32(const float* src, float* dst, int C, int64_t voxels, in
  * :69-73; the permute is this library's, the reference samples the channel-first grid).
  *   out_cl / d_out_cl  device (t0,t1,t2, channel_stride), channel_stride = lfgc_grid_channel_stride(C); pad channels
  *                      are written as 0 / ignored
- *   taps               REQUIRED (separable bank, see above).  Returns LFGC_E_UNSUPPORTED for taps == NULL, C > 32 or
- *                      arrays of 2^30 bytes and more: the caller then composes the two channel-first entry points. */
+ *   taps               REQUIRED (separable bank, see above).  Returns LFGC_E_UNSUPPORTED for taps == NULL or arrays of
+ *                      2^30 bytes and more: the caller then composes the two channel-first entry points.
+ *   C                  any C >= 1: channel groups of 32, 16 or 8 (lfgc_idwt_level_cl_plan below) cover every stride
+ *                      that is a multiple of 8.  C > 32 is taken by this plain pair only (tests/test_wavelet_cl_paths_gpu.py
+ *                      runs C = 40 and 48); the drop pair below refuses it, and nobody has timed such a level against the
+ *                      two-kernel form. */
 int lfgc_idwt_level_cl_f32(const float* lll, const float* hf, const float* taps, float* out_cl,
                            int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream);
 int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* taps, float* d_lll, float* d_hf,
@@ -667,6 +671,37 @@ int lfgc_idwt_level_plan(int filter_len, int has_taps, int has_drop, int C, int 
 int lfgc_idwt_level_bwd_plan(int filter_len, int has_taps, int has_drop, int C, int d0, int d1, int d2, int t0, int t1, int t2,
                              lfgc_wavelet_plan_info* out);
 int lfgc_dwt_level_plan(int filter_len, int has_taps, int C, int n0, int n1, int n2, lfgc_wavelet_plan_info* out);
+
+/* The same for the channel-last last level: which instantiation of its two kernels (csrc/lfgc_wavelet_cl.hip)
+ * lfgc_idwt_level_cl_drop_len_f32 (synthesis) and lfgc_idwt_level_cl_drop_bwd_det_len_f32 (adjoint), and every entry
+ * that forwards to them, launch for a shape.  One selection function per direction fills this struct and the launcher
+ * consumes it.  A work item is (cells consecutive cells of the flattened (y,x) plane) x (cw channels) x (zchunk z steps);
+ * items = ptiles * ngroups * nchunks, dealt to 8 queues of ceil(items / 8) workgroups: blocks = 8 ceil(items / 8). */
+typedef struct lfgc_wavelet_cl_plan_info {
+    int32_t cw;              /* channels per workgroup: 8, 16 (synthesis also 32)                                */
+    int32_t cells;           /* plane cells per workgroup: 32 (adjoint: 32 or 64)                                */
+    int32_t nt;              /* synthesis: 1 = streaming stores, else 0                                          */
+    int32_t drop;            /* 1: the DROP build (factors or penalty gradients folded in)                       */
+    int32_t zchunk;          /* z steps per work item (synthesis: of d0 + L/2 - 1 cell slices; adjoint: of d0)   */
+    int32_t nchunks;         /* ceil(steps / zchunk)                                                             */
+    int32_t ptiles;          /* ceil(plane cells / cells); synthesis plane (d1 + L/2 - 1)(d2 + L/2 - 1), adjoint d1 d2 */
+    int32_t ngroups;         /* channel_stride / cw                                                              */
+    int32_t threads;         /* 32 cw                                                                            */
+    int32_t lds_bytes;       /* dynamic LDS of the launch (at most 80 KB)                                        */
+    int32_t blocks;          /* workgroups                                                                       */
+} lfgc_wavelet_cl_plan_info;
+
+/* filter_len, C, channel_stride and extents as for the entry itself (taps given); has_drop: any of mul_lll / mul_hf given
+ * (the adjoint: or penalty_grads[0] / [1]).  The z chunking minimises a cost that depends on the device's CU count:
+ * num_cus > 0 is used as given, which makes the query pure host arithmetic with no device behind it; num_cus <= 0 means
+ * the current device's count, which is what a launch uses.  The diagnostics switches LFGC_CL_CW, LFGC_CL_NT,
+ * LFGC_CL_ADJ_NG and LFGC_CL_NCHUNKS are honoured as by a launch.  Returns the LFGC_E_* the launch would return for
+ * the same shape arguments (LFGC_E_NULL only for out == NULL; C > 32 with has_drop: LFGC_E_UNSUPPORTED, which the drop
+ * entries return for C > 32 whatever operands they are given); *out is filled on LFGC_OK only. */
+int lfgc_idwt_level_cl_plan(int filter_len, int has_drop, int C, int channel_stride, int d0, int d1, int d2,
+                            int t0, int t1, int t2, int num_cus, lfgc_wavelet_cl_plan_info* out);
+int lfgc_idwt_level_cl_bwd_plan(int filter_len, int has_drop, int C, int channel_stride, int d0, int d1, int d2,
+                                int t0, int t1, int t2, int num_cus, lfgc_wavelet_cl_plan_info* out);
 
 /* The reduced-precision pair under the names SURVEY section 8(b) gives it (BASELINE config 3, "bf16 train step"; the
  * reference itself has no reduced-precision path): exactly lfgc_forward_f32 / lfgc_backward_f32 with precision =

@@ -47,6 +47,11 @@ class WaveletPlanInfo(Structure):
                 ('lds_bytes', c_int32), ('grid', c_uint32 * 3)]
 
 
+class WaveletClPlanInfo(Structure):
+    _fields_ = [(k, c_int32) for k in ('cw', 'cells', 'nt', 'drop', 'zchunk', 'nchunks', 'ptiles', 'ngroups', 'threads',
+                                       'lds_bytes', 'blocks')]
+
+
 WAVELET_KERNELS = ('tiled_dense', 'tiled_separable', 'sliding_window', 'analysis_dense', 'analysis_separable')
 
 
@@ -149,6 +154,8 @@ SIGNATURES = {
     'lfgc_idwt_level_plan': (c_int, [c_int] * 10 + [POINTER(WaveletPlanInfo)]),
     'lfgc_idwt_level_bwd_plan': (c_int, [c_int] * 10 + [POINTER(WaveletPlanInfo)]),
     'lfgc_dwt_level_plan': (c_int, [c_int] * 6 + [POINTER(WaveletPlanInfo)]),
+    'lfgc_idwt_level_cl_plan': (c_int, [c_int] * 11 + [POINTER(WaveletClPlanInfo)]),
+    'lfgc_idwt_level_cl_bwd_plan': (c_int, [c_int] * 11 + [POINTER(WaveletClPlanInfo)]),
     'lfgc_forward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'lfgc_backward_bf16': (c_int, [POINTER(MlpDesc), POINTER(Positions), c_void_p, c_int, c_int, c_int,

@@ -614,10 +614,10 @@ __global__ __launch_bounds__(32 * CW) void analysis_cl_kernel(const AnalysisClAr
 }
 
 // z chunk length: few enough workgroups per slot that no round is mostly idle, long enough that the warm-up plane of a
-// chunk (read and contracted, nothing emitted) stays a small share.
-int pick_zchunk(long long columns, int nz, int slots_per_cu) {
+// chunk (read and contracted, nothing emitted) stays a small share.  num_cus: the CU count the cost is formed with.
+int pick_zchunk(long long columns, int nz, int slots_per_cu, int num_cus) {
     if (const char* e = getenv("LFGC_CL_NCHUNKS")) { const int nc = atoi(e); if (nc >= 1 && nc <= nz) return (nz + nc - 1) / nc; }   // diagnostics
-    const int slots = slots_per_cu * lfgc_num_cus();
+    const int slots = slots_per_cu * num_cus;
     long long best_cost = -1;
     int best = nz;
     for (int nchunks = 1; nchunks <= nz; ++nchunks) {
@@ -630,12 +630,25 @@ int pick_zchunk(long long columns, int nz, int slots_per_cu) {
     return best;
 }
 
+// Launch shape of both kernels once cw, cells, drop and lds_bytes are chosen: plane tiles x channel groups x z chunks of
+// `nz` steps, as 8 XCD queues of ceil(total / 8) workgroups (cl_work_item).  slots_per_cu: resident workgroups per CU.
+int fill_cl_launch(long long ptiles, int channel_stride, int nz, int slots_per_cu, int num_cus, lfgc_wavelet_cl_plan_info* p) {
+    p->ngroups = channel_stride / p->cw;
+    if (ptiles * p->ngroups > 0x0fffffffLL) return LFGC_E_UNSUPPORTED;
+    p->ptiles = (int)ptiles;
+    p->threads = p->cw * kCells;
+    p->zchunk = pick_zchunk(ptiles * p->ngroups, nz, slots_per_cu, num_cus > 0 ? num_cus : lfgc_num_cus());
+    p->nchunks = (nz + p->zchunk - 1) / p->zchunk;
+    const long long total = (long long)p->ptiles * p->ngroups * p->nchunks;
+    const long long blocks = (total + 7) / 8 * 8;
+    if (blocks > 0x7fffffffLL || p->lds_bytes > 80 * 1024) return LFGC_E_UNSUPPORTED;
+    p->blocks = (int)blocks;
+    return LFGC_OK;
+}
+
 template <auto Kern, typename A>
-int launch_cl(int threads, const A& a, int lds_bytes, hipStream_t stream) {
-    const long long total = (long long)a.ptiles * a.ngroups * a.nchunks;
-    const long long blocks = (total + 7) / 8 * 8;      // cl_work_item: 8 XCD queues of ceil(total / 8)
-    if (blocks > 0x7fffffffLL || lds_bytes > 80 * 1024) return LFGC_E_UNSUPPORTED;
-    return lfgc_launch<Kern>(dim3((unsigned)blocks), dim3(threads), lds_bytes, stream, a);
+int launch_cl(const A& a, const lfgc_wavelet_cl_plan_info& p, hipStream_t stream) {
+    return lfgc_launch<Kern>(dim3((unsigned)p.blocks), dim3((unsigned)p.threads), p.lds_bytes, stream, a);
 }
 
 // drop-layer operands of the two directions (all NULL / NaN: the plain level)
@@ -646,10 +659,8 @@ struct ClDropBwd {
     int gstride;           // AnalysisClArgs::dmul_gstride
 };
 
-int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, const float* taps, int L, int C, int cs,
-             int d0, int d1, int d2, int t0, int t1, int t2) {
-    if (!p0 || !p1 || !p2 || !p3) return LFGC_E_NULL;
-    if (!taps) return LFGC_E_UNSUPPORTED;              // dense stencil: channel-first kernels + lfgc_grid_layout_f32
+// Shape checks of both directions (the pointer checks are the entries' own).
+int check_cl_shape(int L, int C, int cs, int d0, int d1, int d2, int t0, int t1, int t2) {
     if (L != 2 && L != 4) return LFGC_E_UNSUPPORTED;   // 6- and 8-tap: channel-first kernels + lfgc_grid_layout_f32
     if (C < 1 || d0 < 1 || d1 < 1 || d2 < 1 || t0 < 1 || t1 < 1 || t2 < 1) return LFGC_E_SHAPE;
     if (t0 > 2 * d0 + L - 2 || t1 > 2 * d1 + L - 2 || t2 > 2 * d2 + L - 2) return LFGC_E_SHAPE;
@@ -659,19 +670,48 @@ int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, con
     return LFGC_OK;
 }
 
-// Launch of the selected synthesis shape; DROP picks the instantiation, everything else is decided by idwt_cl below.
+int check_cl(const void* p0, const void* p1, const void* p2, const void* p3, const float* taps, int L, int C, int cs,
+             int d0, int d1, int d2, int t0, int t1, int t2) {
+    if (!p0 || !p1 || !p2 || !p3) return LFGC_E_NULL;
+    if (!taps) return LFGC_E_UNSUPPORTED;              // dense stencil: channel-first kernels + lfgc_grid_layout_f32
+    return check_cl_shape(L, C, cs, d0, d1, d2, t0, t1, t2);
+}
+
+// THE launch selection of the synthesis: idwt_cl launches what *p says and lfgc_idwt_level_cl_plan reports it.
+int idwt_cl_select(int K, bool drop, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2, int num_cus,
+                   lfgc_wavelet_cl_plan_info* p) {
+    *p = lfgc_wavelet_cl_plan_info{};
+    p->drop = drop;
+    p->cells = kCells;
+    // 32 channels on a large plane: one workgroup of 16 waves writes whole 128-byte lines (d = 65: 197 vs 203 us); on a
+    // small one two 8-wave groups balance better (d = 33: 26.5 vs 28.7 us).  24 channels: three groups of 8.
+    const long long ptiles = ((long long)(d1 + K - 1) * (d2 + K - 1) + kCells - 1) / kCells;
+    int cw = channel_stride == 32 ? (ptiles >= 96 ? 32 : 16) : channel_stride == 16 ? 16 : 8;
+    if (const char* e = getenv("LFGC_CL_CW")) { const int v = atoi(e); if ((v == 8 || v == 16 || v == 32) && channel_stride % v == 0) cw = v; }   // diagnostics
+    p->cw = cw;
+    p->lds_bytes = 2 * 8 * kCells * (cw + 1) * 4 + (drop ? 2 * 8 * K * K * kCells * 4 : 0);    // DROP: + the factor table
+    bool nt = cw == 32 && (long long)t0 * t1 * t2 * channel_stride * 4 > (48LL << 20); // see cl_store
+    if (const char* e = getenv("LFGC_CL_NT")) nt = e[0] == '1';                         // diagnostics
+    p->nt = nt;
+    // workgroups per CU: 96 VGPRs, 4 waves per SIMD.  DROP: 101 to 110 VGPRs (Haar: 40), still 4 waves per SIMD, and the
+    // 8 KB factor table leaves the LDS count as it is (75.8 KB x 1, 43 KB x 2, 26.4 KB x 4 of 160 KB)
+    return fill_cl_launch(ptiles, channel_stride, d0 + K - 1, cw == 32 ? 1 : cw == 16 ? 2 : 4, num_cus, p);
+}
+
+// Launch of the selected synthesis shape; DROP picks the instantiation, everything else was decided by idwt_cl_select.
 template <int K, bool DROP>
-int idwt_cl_launch(const IdwtClArgs<K>& a, int cw, bool nt, int lds, hipStream_t st) {
-    if (cw == 32) {
+int idwt_cl_launch(const IdwtClArgs<K>& a, const lfgc_wavelet_cl_plan_info& p, hipStream_t st) {
+    const bool nt = p.nt != 0;
+    if (p.cw == 32) {
         // 67.6 KB of LDS, above the 64 KB default limit: the first use raises BOTH store-policy builds, so that a first
         // launch of the other one inside a later graph capture makes no attribute call
-        int rc = lfgc_raise_lds_limit<idwt_cl_kernel<32, kCells, true, K, DROP>>(lds);
-        if (rc == LFGC_OK) rc = lfgc_raise_lds_limit<idwt_cl_kernel<32, kCells, false, K, DROP>>(lds);
+        int rc = lfgc_raise_lds_limit<idwt_cl_kernel<32, kCells, true, K, DROP>>(p.lds_bytes);
+        if (rc == LFGC_OK) rc = lfgc_raise_lds_limit<idwt_cl_kernel<32, kCells, false, K, DROP>>(p.lds_bytes);
         if (rc != LFGC_OK) return rc;
-        return nt ? launch_cl<idwt_cl_kernel<32, kCells, true, K, DROP>>(1024, a, lds, st) : launch_cl<idwt_cl_kernel<32, kCells, false, K, DROP>>(1024, a, lds, st);
+        return nt ? launch_cl<idwt_cl_kernel<32, kCells, true, K, DROP>>(a, p, st) : launch_cl<idwt_cl_kernel<32, kCells, false, K, DROP>>(a, p, st);
     }
-    if (cw == 16) return nt ? launch_cl<idwt_cl_kernel<16, kCells, true, K, DROP>>(512, a, lds, st) : launch_cl<idwt_cl_kernel<16, kCells, false, K, DROP>>(512, a, lds, st);
-    return nt ? launch_cl<idwt_cl_kernel<8, kCells, true, K, DROP>>(256, a, lds, st) : launch_cl<idwt_cl_kernel<8, kCells, false, K, DROP>>(256, a, lds, st);
+    if (p.cw == 16) return nt ? launch_cl<idwt_cl_kernel<16, kCells, true, K, DROP>>(a, p, st) : launch_cl<idwt_cl_kernel<16, kCells, false, K, DROP>>(a, p, st);
+    return nt ? launch_cl<idwt_cl_kernel<8, kCells, true, K, DROP>>(a, p, st) : launch_cl<idwt_cl_kernel<8, kCells, false, K, DROP>>(a, p, st);
 }
 
 template <int K>
@@ -683,30 +723,40 @@ int idwt_cl(const float* lll, const float* hf, const ClDropFwd& dr, const float*
     a.o0 = (2 * d0 + 2 * K - 2 - t0) / 2; a.o1 = (2 * d1 + 2 * K - 2 - t1) / 2; a.o2 = (2 * d2 + 2 * K - 2 - t2) / 2;
     for (int i = 0; i < 4 * K; ++i) a.taps[i] = taps[i];
     a.mul_l = dr.mul_l; a.mul_h = dr.mul_h; a.thr_l = dr.thr_l; a.thr_h = dr.thr_h;
-    const bool drop = dr.mul_l || dr.mul_h;
-    // 32 channels on a large plane: one workgroup of 16 waves writes whole 128-byte lines (d = 65: 197 vs 203 us); on a
-    // small one two 8-wave groups balance better (d = 33: 26.5 vs 28.7 us).  24 channels: three groups of 8.
-    const long long ptiles = ((long long)(d1 + K - 1) * (d2 + K - 1) + kCells - 1) / kCells;
-    int cw = channel_stride == 32 ? (ptiles >= 96 ? 32 : 16) : channel_stride == 16 ? 16 : 8;
-    if (const char* e = getenv("LFGC_CL_CW")) { const int v = atoi(e); if ((v == 8 || v == 16 || v == 32) && channel_stride % v == 0) cw = v; }   // diagnostics
-    a.ngroups = channel_stride / cw;
-    if (ptiles * a.ngroups > 0x0fffffffLL) return LFGC_E_UNSUPPORTED;
-    a.ptiles = (int)ptiles;
-    const int lds = 2 * 8 * kCells * (cw + 1) * 4 + (drop ? 2 * 8 * K * K * kCells * 4 : 0);    // DROP: + the factor table
-    // workgroups per CU: 96 VGPRs, 4 waves per SIMD.  DROP: 101 to 110 VGPRs (Haar: 40), still 4 waves per SIMD, and the
-    // 8 KB factor table leaves the LDS count as it is (75.8 KB x 1, 43 KB x 2, 26.4 KB x 4 of 160 KB)
-    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0 + K - 1, cw == 32 ? 1 : cw == 16 ? 2 : 4);
-    a.nchunks = (d0 + K - 1 + a.zchunk - 1) / a.zchunk;
-    bool nt = cw == 32 && (long long)t0 * t1 * t2 * channel_stride * 4 > (48LL << 20); // see cl_store
-    if (const char* e = getenv("LFGC_CL_NT")) nt = e[0] == '1';                         // diagnostics
-    return drop ? idwt_cl_launch<K, true>(a, cw, nt, lds, st) : idwt_cl_launch<K, false>(a, cw, nt, lds, st);
+    lfgc_wavelet_cl_plan_info p;
+    const int rc = idwt_cl_select(K, dr.mul_l || dr.mul_h, channel_stride, d0, d1, d2, t0, t1, t2, 0, &p);
+    if (rc != LFGC_OK) return rc;
+    a.zchunk = p.zchunk; a.ptiles = p.ptiles; a.ngroups = p.ngroups; a.nchunks = p.nchunks;
+    return p.drop ? idwt_cl_launch<K, true>(a, p, st) : idwt_cl_launch<K, false>(a, p, st);
+}
+
+// THE launch selection of the adjoint: idwt_cl_bwd launches what *p says and lfgc_idwt_level_cl_bwd_plan reports it.
+int idwt_cl_bwd_select(int K, bool drop, int channel_stride, int d0, int d1, int d2, int num_cus, lfgc_wavelet_cl_plan_info* p) {
+    *p = lfgc_wavelet_cl_plan_info{};
+    p->drop = drop;
+    const int cw = channel_stride % 16 == 0 ? 16 : 8;
+    // cells per workgroup: 64 on a large plane (256-byte runs per (channel, band): one whole line + two shared ones per
+    // store instead of two shared ones: 188 -> 176 us at d = 65; 128 cells: no further gain), 32 on a small one (d = 33:
+    // 23.6 vs 24.2 us, more workgroups)
+    int ng = (long long)d1 * d2 >= 3072 ? 2 : 1;
+    if (const char* e = getenv("LFGC_CL_ADJ_NG")) { const int v = atoi(e); if (v == 1 || v == 2) ng = v; }   // diagnostics
+    p->cw = cw;
+    p->cells = kCells * ng;
+    const long long ptiles = ((long long)d1 * d2 + kCells * ng - 1) / (kCells * ng);
+    // LDS 33 KB x ng per 16 channels; <= 6 waves per SIMD.  DROP has the same tile; db2 with 32-cell tiles runs at 90
+    // instead of 76 VGPRs, i.e. 5 waves per SIMD = 20 per CU: two 8-wave or five 4-wave workgroups (64-cell tiles: 109
+    // to 111 VGPRs, 4 waves per SIMD as before; Haar: at most 46)
+    int slots = cw == 16 ? (ng == 2 ? 2 : 3) : (ng == 2 ? 4 : 6);
+    if (drop && K == 2 && ng == 1) slots = cw == 16 ? 2 : 5;
+    p->lds_bytes = 2 * cw * (8 * kCells * ng + 1) * 4;
+    return fill_cl_launch(ptiles, channel_stride, d0, slots, num_cus, p);
 }
 
 template <int K, bool DROP>
-int idwt_cl_bwd_launch(const AnalysisClArgs<K>& a, int cw, int ng, int lds, hipStream_t st) {
-    if (ng == 2) return cw == 16 ? launch_cl<analysis_cl_kernel<16, 2, K, DROP>>(512, a, lds, st)      // 65.7 KB of LDS
-                                 : launch_cl<analysis_cl_kernel<8, 2, K, DROP>>(256, a, lds, st);
-    return cw == 16 ? launch_cl<analysis_cl_kernel<16, 1, K, DROP>>(512, a, lds, st) : launch_cl<analysis_cl_kernel<8, 1, K, DROP>>(256, a, lds, st);
+int idwt_cl_bwd_launch(const AnalysisClArgs<K>& a, const lfgc_wavelet_cl_plan_info& p, hipStream_t st) {
+    if (p.cells == 2 * kCells) return p.cw == 16 ? launch_cl<analysis_cl_kernel<16, 2, K, DROP>>(a, p, st)      // 65.7 KB of LDS
+                                                 : launch_cl<analysis_cl_kernel<8, 2, K, DROP>>(a, p, st);
+    return p.cw == 16 ? launch_cl<analysis_cl_kernel<16, 1, K, DROP>>(a, p, st) : launch_cl<analysis_cl_kernel<8, 1, K, DROP>>(a, p, st);
 }
 
 template <int K>
@@ -721,30 +771,15 @@ int idwt_cl_bwd(const float* d_out_cl, const float* taps, const ClDropBwd& dr, f
     a.lll = dr.lll; a.hf = dr.hf; a.mul_l = dr.mul_l; a.mul_h = dr.mul_h; a.d_mul_l = dr.d_mul_l; a.d_mul_h = dr.d_mul_h;
     a.g_l2_l = dr.pg[0]; a.g_l2_h = dr.pg[1]; a.g_l1_l = dr.pg[2]; a.g_l1_h = dr.pg[3];
     a.dmul_gstride = dr.gstride;
-    const bool drop = dr.mul_l || dr.mul_h || dr.pg[0] || dr.pg[1];
-    const int cw = channel_stride % 16 == 0 ? 16 : 8;
-    // cells per workgroup: 64 on a large plane (256-byte runs per (channel, band): one whole line + two shared ones per
-    // store instead of two shared ones: 188 -> 176 us at d = 65; 128 cells: no further gain), 32 on a small one (d = 33:
-    // 23.6 vs 24.2 us, more workgroups)
-    int ng = (long long)d1 * d2 >= 3072 ? 2 : 1;
-    if (const char* e = getenv("LFGC_CL_ADJ_NG")) { const int v = atoi(e); if (v == 1 || v == 2) ng = v; }   // diagnostics
-    const long long ptiles = ((long long)d1 * d2 + kCells * ng - 1) / (kCells * ng);
-    a.ngroups = channel_stride / cw;
-    if (ptiles * a.ngroups > 0x0fffffffLL) return LFGC_E_UNSUPPORTED;
-    a.ptiles = (int)ptiles;
-    // LDS 33 KB x ng per 16 channels; <= 6 waves per SIMD.  DROP has the same tile; db2 with 32-cell tiles runs at 90
-    // instead of 76 VGPRs, i.e. 5 waves per SIMD = 20 per CU: two 8-wave or five 4-wave workgroups (64-cell tiles: 109
-    // to 111 VGPRs, 4 waves per SIMD as before; Haar: at most 46)
-    int slots = cw == 16 ? (ng == 2 ? 2 : 3) : (ng == 2 ? 4 : 6);
-    if (drop && K == 2 && ng == 1) slots = cw == 16 ? 2 : 5;
-    a.zchunk = pick_zchunk(ptiles * a.ngroups, d0, slots);
-    a.nchunks = (d0 + a.zchunk - 1) / a.zchunk;
-    const int lds = 2 * cw * (8 * kCells * ng + 1) * 4;
-    return drop ? idwt_cl_bwd_launch<K, true>(a, cw, ng, lds, st) : idwt_cl_bwd_launch<K, false>(a, cw, ng, lds, st);
+    lfgc_wavelet_cl_plan_info p;
+    const int rc = idwt_cl_bwd_select(K, dr.mul_l || dr.mul_h || dr.pg[0] || dr.pg[1], channel_stride, d0, d1, d2, 0, &p);
+    if (rc != LFGC_OK) return rc;
+    a.zchunk = p.zchunk; a.ptiles = p.ptiles; a.ngroups = p.ngroups; a.nchunks = p.nchunks;
+    return p.drop ? idwt_cl_bwd_launch<K, true>(a, p, st) : idwt_cl_bwd_launch<K, false>(a, p, st);
 }
 
 // The two entries behind the C ABI: argument checks, then the one dispatch on the filter length.  wide_ok: the plain pair
-// does not refuse C > 32, the drop pair does (open points).
+// takes C > 32 (include/lfgc.h; tests/test_wavelet_cl_paths_gpu.py runs C = 40 and 48), the drop pair refuses it.
 int idwt_cl_entry(bool wide_ok, const float* lll, const float* hf, const float* mul_lll, float thr_lll, const float* mul_hf,
                   float thr_hf, const float* taps, int filter_len, float* out_cl, int C, int channel_stride,
                   int d0, int d1, int d2, int t0, int t1, int t2, lfgc_stream_t stream) {
@@ -828,4 +863,30 @@ extern "C" int lfgc_idwt_level_cl_bwd_f32(const float* d_out_cl, const float* ta
                                           int C, int channel_stride, int d0, int d1, int d2, int t0, int t1, int t2,
                                           lfgc_stream_t stream) {
     return lfgc_idwt_level_cl_bwd_len_f32(d_out_cl, taps, 4, d_lll, d_hf, C, channel_stride, d0, d1, d2, t0, t1, t2, stream);
+}
+
+// ---- read-only plan queries (include/lfgc.h): the selections above, nothing launched --------------------------------
+
+extern "C" int lfgc_idwt_level_cl_plan(int filter_len, int has_drop, int C, int channel_stride, int d0, int d1, int d2,
+                                       int t0, int t1, int t2, int num_cus, lfgc_wavelet_cl_plan_info* out) {
+    if (!out) return LFGC_E_NULL;
+    const int rc = check_cl_shape(filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    if (C > 32 && has_drop) return LFGC_E_UNSUPPORTED;
+    lfgc_wavelet_cl_plan_info p;
+    const int rs = idwt_cl_select(filter_len / 2, has_drop != 0, channel_stride, d0, d1, d2, t0, t1, t2, num_cus, &p);
+    if (rs == LFGC_OK) *out = p;
+    return rs;
+}
+
+extern "C" int lfgc_idwt_level_cl_bwd_plan(int filter_len, int has_drop, int C, int channel_stride, int d0, int d1, int d2,
+                                           int t0, int t1, int t2, int num_cus, lfgc_wavelet_cl_plan_info* out) {
+    if (!out) return LFGC_E_NULL;
+    const int rc = check_cl_shape(filter_len, C, channel_stride, d0, d1, d2, t0, t1, t2);
+    if (rc != LFGC_OK) return rc;
+    if (C > 32 && has_drop) return LFGC_E_UNSUPPORTED;
+    lfgc_wavelet_cl_plan_info p;
+    const int rs = idwt_cl_bwd_select(filter_len / 2, has_drop != 0, channel_stride, d0, d1, d2, num_cus, &p);
+    if (rs == LFGC_OK) *out = p;
+    return rs;
 }

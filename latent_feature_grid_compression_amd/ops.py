@@ -298,10 +298,11 @@ def _adjoint(d_out, C, filter_rev, lll, hf, mul_l, mul_h, want_dml, want_dmh, d,
     d_mh = want_dmh if torch.is_tensor(want_dmh) else (
         torch.zeros(shapes['mul_h'], dtype=torch.float32, device=dev) if want_dmh else None)
     pen, _keep = (None, None) if penalty_ptrs is None else _lib.ptr_array([int(v) for v in penalty_ptrs])
-    # slices of the deterministic mode: the channel-last adjoint runs channel groups of 16 where they divide the stride
-    nslices = (cs // 16 if cs % 16 == 0 else cs // 8) if use_cl else C
-    stride, sl, sh = 0, d_ml, d_mh
-    if deterministic and nslices > 1 and (d_ml is not None or d_mh is not None):
+    # slices of the deterministic mode: the channel groups the channel-last adjoint's own selection runs
+    nslices, stride, sl, sh = 1, 0, d_ml, d_mh
+    if deterministic and (d_ml is not None or d_mh is not None):
+        nslices = _cl_adjoint_groups(L, C, d, (t0, t1, t2)) if use_cl else C
+    if nslices > 1:
         stride = int(np.prod(shapes['mul_h' if d_mh is not None else 'mul_l']))
         sl = torch.zeros((nslices, stride), dtype=torch.float32, device=dev) if d_ml is not None else None
         sh = torch.zeros((nslices, stride), dtype=torch.float32, device=dev) if d_mh is not None else None
@@ -460,6 +461,36 @@ def idwt_level_bwd_plan(filter_len: int, C: int, d: Sequence[int], t: Sequence[i
 def dwt_level_plan(filter_len: int, C: int, n: Sequence[int], has_taps: bool = True) -> SimpleNamespace:
     """lfgc_dwt_level_plan: the same for dwt_level of a (C, n0,n1,n2) input."""
     return _wavelet_plan('lfgc_dwt_level_plan', filter_len, has_taps, C, *n)
+
+
+def _wavelet_cl_plan(entry: str, filter_len, has_drop, C, d, t, num_cus) -> SimpleNamespace:
+    info = _lib.WaveletClPlanInfo()
+    check(getattr(_lib.load(), entry)(int(filter_len), int(bool(has_drop)), int(C), grid_channel_stride(C),
+                                      *[int(v) for v in d], *[int(v) for v in t], int(num_cus), ctypes.byref(info)), entry)
+    p = SimpleNamespace(**{k: int(getattr(info, k)) for k, _ in info._fields_})
+    p.nt, p.drop = bool(p.nt), bool(p.drop)
+    return p
+
+
+def idwt_level_cl_plan(filter_len: int, C: int, d: Sequence[int], t: Sequence[int], has_drop: bool = False,
+                       num_cus: int = 0) -> SimpleNamespace:
+    """lfgc_idwt_level_cl_plan: the launch idwt_level_cl / idwt_level_cl_drop (has_drop) would make for a level d -> t of
+    C channels, nothing enqueued.  num_cus > 0: the z chunking for a device of that many CUs (no device needed); 0: the
+    current device's.  Fields: cw, cells, nt, drop, zchunk, nchunks, ptiles, ngroups, threads, lds_bytes, blocks."""
+    return _wavelet_cl_plan('lfgc_idwt_level_cl_plan', filter_len, has_drop, C, d, t, num_cus)
+
+
+def idwt_level_cl_bwd_plan(filter_len: int, C: int, d: Sequence[int], t: Sequence[int], has_drop: bool = False,
+                           num_cus: int = 0) -> SimpleNamespace:
+    """lfgc_idwt_level_cl_bwd_plan: the same for idwt_level_cl_bwd / idwt_level_cl_drop_bwd (has_drop: factors or L2
+    penalties)."""
+    return _wavelet_cl_plan('lfgc_idwt_level_cl_bwd_plan', filter_len, has_drop, C, d, t, num_cus)
+
+
+def _cl_adjoint_groups(L: int, C: int, d: Sequence[int], t: Sequence[int]) -> int:
+    """Channel groups of the channel-last adjoint = slices of its deterministic mode: the launch's own selection (it does
+    not depend on the CU count or on the DROP build)."""
+    return idwt_level_cl_bwd_plan(L, C, d, t, num_cus=1).ngroups
 
 
 @_on_device

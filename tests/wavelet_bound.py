@@ -1,5 +1,6 @@
-"""Componentwise error bound for the channel-first wavelet level kernels, shared by tests/test_wavelet_paths_gpu.py (the
-kernels against the fp64 oracle) and tests/test_wavelet_paths_host.py (which pins this checker on the CPU).
+"""Componentwise error bound for the wavelet level kernels, shared by tests/test_wavelet_paths_gpu.py and
+tests/test_wavelet_cl_paths_gpu.py (the channel-first and the channel-last kernels against the fp64 oracle) and by
+tests/test_wavelet_paths_host.py and tests/test_wavelet_cl_plans_host.py (which pin this checker on the CPU).
 
 Every element must satisfy   |got - ref64| <= c * 2^-24 * mag   where ref64 is the oracle (oracle/ref_torch.py) run in
 float64 on the fp32 inputs and the fp32 filter buffer, and mag is the SAME linear map applied to absolute values: the
@@ -165,11 +166,13 @@ def _fma(a, b, t):
     return (a.astype(np.float64) * np.float64(b) + t.astype(np.float64)).astype(np.float32)
 
 
-def _contract(lo, hi, bank, K, leak=None, tap_shift=False):
+def _contract(lo, hi, bank, K, leak=None, tap_shift=False, seam=0):
     """One axis (the last of lo / hi) of the synthesis: out[2 jj + p] = chain over e, s of in_s[jj - e] * bank[s][p + 2 e],
     jj in [0, d + K - 1), in the kernel's order (neighbour e outer, band s inner), cells outside [0, d) reading zero.
     leak: an array of lo's shape without the last axis, read at cell index d instead of zero -- (lo_leak, hi_leak).
-    tap_shift: the high band's first tap of parity 0 is read one index too far (Haar's two low taps are equal)."""
+    tap_shift: the high band's first tap of parity 0 is read one index too far (Haar's two low taps are equal).
+    seam: chunks of `seam` cells that start without their warm-up cells -- cell jj of a chunk beginning at b > 0 loses the
+    terms of the cells jj - e < b."""
     d = lo.shape[-1]
     n = d + K - 1
     pad = [(0, 0)] * (lo.ndim - 1) + [(K - 1, K - 1)]
@@ -177,22 +180,28 @@ def _contract(lo, hi, bank, K, leak=None, tap_shift=False):
     if leak is not None and K > 1:
         for s in range(2):
             P[s][..., K - 1 + d] = leak[s]
+    jj = np.arange(n)
+    begin = (jj // seam) * seam if seam else np.zeros(n, np.int64)
     out = np.zeros(lo.shape[:-1] + (2 * n,), np.float32)
     for p in range(2):
         t = np.zeros(lo.shape[:-1] + (n,), np.float32)
         for e in range(K):
+            keep = ((jj - e >= begin) | (begin == 0)).astype(np.float32)     # all ones without a seam
             for s in range(2):
                 tap = p + 2 * e + (1 if (tap_shift and p == 0 and e == 0 and s == 1) else 0)
-                t = _fma(P[s][..., K - 1 - e:K - 1 - e + n], bank[s][tap], t)
+                t = _fma(P[s][..., K - 1 - e:K - 1 - e + n] * keep, bank[s][tap], t)
         out[..., p::2] = t
     return out
 
 
-def separable_level_fp32(lll, hf, bank, t, bug=None):
+def separable_level_fp32(lll, hf, bank, t, bug=None, zchunk=0):
     """The kernel's arithmetic in numpy fp32: contract x, then y, then z with 2K-term fmaf chains, then crop to t.
     lll (C,d0,d1,d2), hf (C,7,d0,d1,d2) fp32, bank (2,L) fp32 (ops._factor_bank).
     bug = 'select': the x-range select of the neighbour at x = d2 is dropped, so that cell reads what lies behind it in
-    the staged plane -- the next row's first cell (zeros behind the last row); 'tap': one tap index shifted by one."""
+    the staged plane -- the next row's first cell (zeros behind the last row); 'tap': one tap index shifted by one;
+    'seam': the z walk of the channel-last kernels (csrc/lfgc_wavelet_cl.hip) in chunks of `zchunk` cell slices, each
+    chunk after the first starting WITHOUT its warm-up planes: the cell slices jz_begin .. jz_begin + K - 2 lose what the
+    coefficient planes jz_begin - 1 .. jz_begin - (K - 1) carry into them."""
     bank = np.asarray(bank, np.float32)
     K = bank.shape[1] // 2
     C = lll.shape[0]
@@ -207,7 +216,140 @@ def separable_level_fp32(lll, hf, bank, t, bug=None):
     X = np.moveaxis(X, -2, -1)                                                 # (C, sz, sy, z, X, y)
     Y = _contract(X[:, :, 0], X[:, :, 1], bank, K)                             # (C, sz, z, X, Y)
     Y = np.moveaxis(Y, -3, -1)                                                 # (C, sz, X, Y, z)
-    Z = _contract(Y[:, 0], Y[:, 1], bank, K)                                   # (C, X, Y, Z)
+    Z = _contract(Y[:, 0], Y[:, 1], bank, K, seam=(zchunk if bug == 'seam' else 0))   # (C, X, Y, Z)
     full = np.transpose(Z, (0, 3, 2, 1))                                       # (C, Z, Y, X)
     off = [(full.shape[1 + a] - t[a]) // 2 for a in range(3)]
     return np.ascontiguousarray(full[:, off[0]:off[0] + t[0], off[1]:off[1] + t[1], off[2]:off[2] + t[2]])
+
+
+# ---- channel-last last level (csrc/lfgc_wavelet_cl.hip): the launch rules restated, the cases, their references ----------
+# Shared by tests/test_wavelet_cl_plans_host.py (the plan queries against these rules, no device) and
+# tests/test_wavelet_cl_paths_gpu.py (every case asserts its plan, then runs it against level_reference).
+
+CL_CELLS = 32
+CL_LDS_CAP = 80 * 1024
+CL_KNOBS = {'cw': 'LFGC_CL_CW', 'nt': 'LFGC_CL_NT', 'ng': 'LFGC_CL_ADJ_NG', 'nchunks': 'LFGC_CL_NCHUNKS'}
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def cl_pick_zchunk(columns, nz, slots_per_cu, num_cus, nchunks=None):
+    """z steps per work item.  The rule as the source states it: few enough workgroups per slot that no round is mostly
+    idle, long enough that the warm-up plane of a chunk stays a small share -- the chunk count in 1..nz whose
+    rounds * (zchunk + 1) is smallest, the first one on a tie; a forced count in 1..nz wins, any other is ignored."""
+    if nchunks is not None and 1 <= nchunks <= nz:
+        return _ceil(nz, nchunks)
+    slots = slots_per_cu * num_cus
+    best_cost, best = None, nz
+    for n in range(1, nz + 1):
+        zc = _ceil(nz, n)
+        cost = _ceil(columns * _ceil(nz, zc), slots) * (zc + 1)
+        if best_cost is None or cost < best_cost:
+            best_cost, best = cost, zc
+    return best
+
+
+def cl_expected_plan(adjoint, L, C, d, t, drop, num_cus, cw=None, nt=None, ng=None, nchunks=None):
+    """The launch of the channel-last level as the source comments and DESIGN section 3.2.1 give it; cw / nt / ng / nchunks:
+    the diagnostics knobs' values (None: not set).  Returns a dict of the fields of lfgc_wavelet_cl_plan_info."""
+    K = L // 2
+    cs = _ceil(C, 8) * 8
+    if not adjoint:
+        ptiles = _ceil((d[1] + K - 1) * (d[2] + K - 1), CL_CELLS)
+        w = (32 if ptiles >= 96 else 16) if cs == 32 else 16 if cs == 16 else 8
+        if cw in (8, 16, 32) and cs % cw == 0:
+            w = cw
+        cells = CL_CELLS
+        lds = 2 * 8 * CL_CELLS * (w + 1) * 4 + (2 * 8 * K * K * CL_CELLS * 4 if drop else 0)
+        stream = w == 32 and t[0] * t[1] * t[2] * cs * 4 > 48 << 20
+        if nt is not None:
+            stream = str(nt)[0] == '1'
+        slots = {32: 1, 16: 2, 8: 4}[w]
+        nz = d[0] + K - 1
+    else:
+        w = 16 if cs % 16 == 0 else 8
+        g = 2 if d[1] * d[2] >= 3072 else 1
+        if ng in (1, 2):
+            g = ng
+        cells = CL_CELLS * g
+        ptiles = _ceil(d[1] * d[2], cells)
+        lds = 2 * w * (8 * cells + 1) * 4
+        stream = False
+        slots = (2 if g == 2 else 3) if w == 16 else (4 if g == 2 else 6)
+        if drop and K == 2 and g == 1:
+            slots = 2 if w == 16 else 5
+        nz = d[0]
+    ngroups = cs // w
+    zchunk = cl_pick_zchunk(ptiles * ngroups, nz, slots, num_cus, nchunks)
+    n = _ceil(nz, zchunk)
+    return dict(cw=w, cells=cells, nt=stream, drop=bool(drop), zchunk=zchunk, nchunks=n, ptiles=ptiles, ngroups=ngroups,
+                threads=32 * w, lds_bytes=lds, blocks=_ceil(ptiles * ngroups * n, 8) * 8)
+
+
+def cl_target(L, d):
+    """Targets of the channel-last cases: db2 cropped by one on one axis (which one rotates with the shape), Haar
+    min(that, 2 d) = its full level."""
+    t = [2 * v + 2 for v in d]
+    t[sum(d) % 3] -= 1
+    return tuple(t) if L == 4 else tuple(min(tv, 2 * dv) for tv, dv in zip(t, d))
+
+
+# (name, C, d, knobs, synthesis CW, adjoint CW, adjoint cell groups NG): the smallest shapes that reach each path
+CL_ROWS = [
+    ('cw32_ng2', 32, (2, 56, 56), {}, 32, 16, 2),              # ptiles 102 (db2) / 98 (Haar); d1 d2 = 3136 >= 3072
+    ('cw16_stride32', 30, (5, 9, 12), {}, 16, 16, 1),
+    ('cw16_stride16', 13, (5, 12, 7), {}, 16, 16, 1),
+    ('cw8_one_group', 5, (6, 7, 9), {}, 8, 8, 1),
+    ('cw8_three_groups', 22, (4, 35, 6), {}, 8, 8, 1),
+    ('cw8_forced_stride32', 30, (5, 9, 12), {'cw': 8}, 8, 16, 1),
+    ('cw32_forced_small_plane', 30, (5, 9, 12), {'cw': 32}, 32, 16, 1),
+    ('one_cell_one_plane', 3, (1, 1, 1), {}, 8, 8, 1),
+    ('adj_cw8_ng2', 8, (2, 56, 56), {}, 8, 8, 2),
+    ('adj_ng2_forced_ragged_cw16', 30, (5, 9, 12), {'ng': 2}, 16, 16, 2),      # 108 cells: second group of tile 2 ragged
+    ('adj_ng2_forced_ragged_cw8', 5, (5, 9, 12), {'ng': 2}, 8, 8, 2),
+    ('adj_ng2_forced_empty_group', 13, (3, 7, 10), {'ng': 2}, 16, 16, 2),      # 70 cells: tile 2's second group empty
+]
+CL_ROW = {r[0]: r for r in CL_ROWS}
+CL_MASKED_ROWS = ('cw32_ng2', 'cw16_stride32', 'cw16_stride16', 'adj_ng2_forced_ragged_cw16', 'adj_ng2_forced_empty_group')
+CL_PENALTY = [0.7, -1.3, 0.4, 2.1]
+CL_WIDE = [(40, (5, 6, 7)), (48, (5, 6, 7))]       # C > 32 through the plain pair's C ABI
+# z chunks: nz = 7 steps forced into 1, 2, 3 and 7 chunks of 7 / 4+3 / 3+3+1 / 1 each
+CL_NCHUNKS = (1, 2, 3, 7)
+CL_CHUNK_ROWS = [('cw16_stride16', 13, (12, 7)), ('cw8_one_group', 5, (7, 9))]
+
+
+def cl_chunk_shape(L, plane, adjoint):
+    """d with 7 z steps: the synthesis walks d0 + K - 1 cell slices, the adjoint d0 planes."""
+    return ((7 if adjoint else 8 - L // 2),) + tuple(plane)
+
+
+_CL_REFS = {}
+
+
+def cl_case(L, C, d, variant='plain', pen=None, adjoint=True):
+    """Inputs and fp64 reference of one channel-last case, computed once per process: standard-normal coefficients and
+    gradient, factors uniform in [-1, 1].  variant: 'plain', 'drop' (both factors, product rule), 'masked' (both factors,
+    threshold 0.5).  Returns a SimpleNamespace: lll, hf, g, ml, mh, thr, t, ref (name -> (ref64, mag)).  Every magnitude
+    is asserted positive: no element of any tensor is outside the componentwise bound."""
+    from types import SimpleNamespace
+    key = (L, C, tuple(d), variant, None if pen is None else tuple(pen), adjoint)
+    if key in _CL_REFS:
+        return _CL_REFS[key]
+    t = cl_target(L, d)
+    _, frev = filters(L)
+    rng = np.random.default_rng([L, C, *d, ('plain', 'drop', 'masked').index(variant)])
+    f = lambda draw, *s: torch.from_numpy(draw(s).astype(np.float32))
+    normal, unif = rng.standard_normal, (lambda s: rng.uniform(-1.0, 1.0, s))
+    lll, hf, g = f(normal, C, *d), f(normal, C, 7, *d), f(normal, C, *t)
+    ml = mh = thr = None
+    if variant != 'plain':
+        ml, mh = f(unif, *d), f(unif, 7, *d)
+        thr = 0.5 if variant == 'masked' else None
+    ref = level_reference(lll, hf, frev, t, ml, thr, mh, thr, g if adjoint else None, pen)
+    for name, (r, mag) in ref.items():
+        assert (mag > 0).all(), (key, name)
+    case = SimpleNamespace(L=L, C=C, d=tuple(d), t=t, frev=frev, lll=lll, hf=hf, g=g, ml=ml, mh=mh, thr=thr, pen=pen, ref=ref)
+    _CL_REFS[key] = case
+    return case
