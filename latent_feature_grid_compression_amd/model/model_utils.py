@@ -14,17 +14,17 @@ store the pruning pattern once per cell instead of once per coefficient (``lfgc_
 """
 from __future__ import annotations
 
-import math
 import os
 import re
 import struct
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from .. import ops
-
 from ..wavelet_transform.Torch_Wavelet_Transform import WaveletFilter3d
+from .codec_container import Reader, read_field, write_field
 from .Feature_Embedding import FourierEmbedding
 from .Feature_Grid_Model import Feature_Grid_Model
 from .Smallify_Dropout import SmallifyDropout
@@ -106,14 +106,6 @@ def _f32_bytes(t) -> bytes:
 _ENTROPY_FLAG = 0x80      # header byte 5 of an entropy-mode file is bits | 0x80: older readers refuse it as a width
 
 
-def _coded(plain: bytes, streams) -> bytes:
-    """[u8 mode][payload] of an entropy-mode file: mode 1 and the rANS streams where they are strictly smaller than the plain
-    bytes, else mode 0 and the plain bytes -- a field never grows by more than this one byte."""
-    if sum(s.numel() for s in streams) < len(plain):
-        return b'\x01' + b''.join(s.cpu().numpy().tobytes() for s in streams)
-    return b'\x00' + plain
-
-
 def _label_streams(labels: torch.Tensor, bits: int):
     """One rANS stream over the labels as bytes, or above 8 bits two: the plane label & 0xFF, then label >> 8."""
     if bits <= 8:
@@ -136,7 +128,7 @@ def _quantised_block(values: torch.Tensor, bits: int, entropy: bool = False) -> 
             rest += struct.pack('<I', int(labels[-1:].cpu().numpy()[0]))
     if not entropy:
         return _f32_bytes(centres) + rest
-    return _f32_bytes(centres) + _coded(rest, _label_streams(labels, bits))
+    return _f32_bytes(centres) + write_field(rest, _label_streams(labels, bits))
 
 
 _CHANNEL_MASK_MODE = 2    # first byte of a mask file that holds the mask once per cell: support + residual
@@ -145,14 +137,14 @@ _CHANNEL_MASK_MODE = 2    # first byte of a mask file that holds the mask once p
 def _channel_mask_file(grids, channels: int) -> bytes:
     """Mode 2 of the mask file: ``[u8 2][u32 K per tensor][field support][field residual]``.  A tensor is
     viewed as (channels, S cells); the support has one bit per cell (any channel non-zero), the residual the mask bits of the
-    K support cells only, channel-major; a field is ``_coded`` over its MSB-first bytes."""
+    K support cells only, channel-major; a field is ``write_field`` over its MSB-first bytes."""
     flags = [ops.codec_support(g, channels) for g in grids]
     cells = [ops.codec_compact_support(g, channels, f) for g, f in zip(grids, flags)]
     support = ops.codec_pack_flags(torch.cat(flags))
     residual = ops.codec_mask(torch.cat([v.reshape(-1) for v in cells]))
     out = bytes([_CHANNEL_MASK_MODE]) + b''.join(struct.pack('<I', v.shape[1]) for v in cells)
     for field in (support, residual):
-        out += _coded(field.cpu().numpy().tobytes(), [ops.codec_rans_encode(field)])
+        out += write_field(field.cpu().numpy().tobytes(), [ops.codec_rans_encode(field)])
     return out
 
 
@@ -204,7 +196,7 @@ def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION, entrop
             f.write(_quantised_block(nz, bits, entropy))
     mask = ops.codec_mask(torch.cat(grids))           # one bit stream over all tensors, like the reference's mask_string
     plain_mask = mask.cpu().numpy().tobytes()
-    mask_file = _coded(plain_mask, [ops.codec_rans_encode(mask)]) if entropy else plain_mask
+    mask_file = write_field(plain_mask, [ops.codec_rans_encode(mask)]) if entropy else plain_mask
     channels = int(model.feature_grid[0].shape[0])
     if channel_mask and all(g.numel() % channels == 0 for g in grids):
         per_cell = _channel_mask_file(grids, channels)
@@ -214,221 +206,173 @@ def store_model_parameters(model, filename, bit_precision=_BIT_PRECISION, entrop
         f.write(mask_file)
 
 
+def _parse_block(r: Reader, n: int, bits: int, entropy: bool) -> SimpleNamespace:
+    """One quantised block of ``n`` labels: ``n, centres, mode`` and, mode 0, ``packed`` labels + ``last`` (the uint32 the
+    writer repeats the last label in when bits % 8 != 0, reference :184-186, :265-267; else None) or, mode 1, ``planes``:
+    (bytes, stream header) of the labels' low bytes and, above 8 bits, of their high bytes."""
+    block = SimpleNamespace(n=n, centres=r.array('<f4', 1 << bits), packed=None, last=None, planes=None)
+    nbytes, tail = (n * bits + 7) // 8, 4 if bits % 8 else 0
+    streams = [(n, 1 << bits)] if bits <= 8 else [(n, 256), (n, 1 << (bits - 8))]
+    block.mode, payload = read_field(r, nbytes + tail, streams, coded=entropy)
+    if block.mode == 0:
+        block.packed = payload[:nbytes]
+        block.last = struct.unpack_from('<I', payload, nbytes)[0] if tail else None
+    else:
+        block.planes = payload
+    return block
+
+
+def _parse_mask(d: SimpleNamespace, mask_raw, what: str) -> SimpleNamespace:
+    """``fields`` as ``read_field`` returns them, and ``cells``, ``kept``.  The flat mask (the plain file, or one field over
+    all coefficients) has one field and None for the rest; a file that starts with byte 2 holds the mask once per cell:
+    cells S_t and support cells K_t per tensor, then the support and the residual field."""
+    r, total = Reader(mask_raw, what), sum(d.grid_sizes) + sum(d.zeros)
+    if not d.entropy or bytes(r.view[:1]) != bytes([_CHANNEL_MASK_MODE]):
+        field = read_field(r, None, [((total + 7) // 8, 256)], coded=d.entropy, exact=True)
+        if field[0] == 0 and 8 * len(field[1]) < total:      # a longer plain mask is accepted, as by the reference
+            raise ValueError('%s: %d bits needed, %d present' % (what, total, 8 * len(field[1])))
+        return SimpleNamespace(fields=[field], cells=None, kept=None)
+    C = d.feature_size
+    if C < 1 or any((nz + z) % C for nz, z in zip(d.grid_sizes, d.zeros)):
+        raise ValueError('%s: a tensor is no whole number of cells of %d channels' % (what, C))
+    cells = [(nz + z) // C for nz, z in zip(d.grid_sizes, d.zeros)]
+    kept = list(r.take('<B%dI' % d.n_grids)[1:])
+    for t, (nz, S, K) in enumerate(zip(d.grid_sizes, cells, kept)):
+        if K > S or nz > C * K:
+            raise ValueError('%s: tensor %d has %d cells and %d non-zero coefficients, the file names %d support cells'
+                             % (what, t, S, nz, K))
+    fields = [read_field(r, (nbits + 7) // 8, [((nbits + 7) // 8, 256)]) for nbits in (sum(cells), C * sum(kept))]
+    r.end()
+    return SimpleNamespace(fields=fields, cells=cells, kept=kept)
+
+
+def parse_model_files(raw, mask_raw, name: str = '') -> SimpleNamespace:
+    """Host description of a parameter file and its mask file (bytes-like; ``name``: the parameter file's, for messages);
+    nothing touches the GPU and no payload is copied.  ``n_layers, layer_width, input_dim, input_channel, output_dim, bits,
+    entropy`` (header byte 5 split into the width and its 0x80 flag), ``grid_size, n_grids, feature_size``, ``grid_sizes``,
+    ``zeros``; ``weights`` and ``biases`` per layer, fp32 arrays except the hidden weights, which like ``grid_blocks`` are
+    blocks (``_parse_block``); ``mask`` (``_parse_mask``).  ValueError for a truncated file, a width outside 1..16, a field
+    mode above 1, a stream header that does not add up, holds another number of symbols than its field or gives a
+    frequency to a label the codebook does not have, a flat mask with too few bits or a stream that does not end with the
+    file; in a per-cell mask file also trailing bytes, tensors that are no whole number of cells, more support cells than
+    cells, and more non-zero coefficients than the support cells hold."""
+    r = Reader(raw, name or 'parameter file')
+    d = SimpleNamespace()
+    d.n_layers, d.layer_width, d.input_dim, d.input_channel, d.output_dim, bits, d.grid_size, d.n_grids, d.feature_size = \
+        r.take('9B')
+    d.entropy, d.bits = bool(bits & _ENTROPY_FLAG), bits & ~_ENTROPY_FLAG
+    if not 1 <= d.bits <= 16:
+        raise ValueError('%s: bit precision %d not supported' % (r.what, d.bits))
+    d.grid_sizes = list(r.take('<%dI' % d.n_grids))
+    d.zeros = list(r.take('<%dI' % d.n_grids))
+    d.weights, d.biases = [r.array('<f4', d.input_dim * d.layer_width)], [r.array('<f4', d.layer_width)]
+    for _ in range(d.n_layers - 1):
+        d.weights.append(_parse_block(r, d.layer_width * d.layer_width, d.bits, d.entropy))
+        d.biases.append(r.array('<f4', d.layer_width))
+    d.weights.append(r.array('<f4', d.output_dim * d.layer_width))
+    d.biases.append(r.array('<f4', d.output_dim))
+    d.grid_blocks = [_parse_block(r, nz, d.bits, d.entropy) for nz in d.grid_sizes]     # bytes after them are not looked at
+    d.mask = _parse_mask(d, mask_raw, name + '_mask.bnr' if name else 'mask file')
+    return d
+
+
+def _upload(a, dev) -> torch.Tensor:
+    return torch.from_numpy(np.array(a)).to(dev)
+
+
+def _field_on_device(field, dev) -> torch.Tensor:
+    """The bytes of a one-stream field: uploaded as they are, or decoded."""
+    mode, payload = field
+    return _upload(payload, dev) if mode == 0 else ops.codec_rans_decode_parsed(_upload(payload[0][0], dev), payload[0][1])
+
+
+def _dequantised(block: SimpleNamespace, bits: int, dev) -> torch.Tensor:
+    n, centres = block.n, _upload(block.centres, dev)
+    if n == 0:
+        return torch.empty(0, device=dev)
+    if block.mode == 0:
+        out = ops.codec_dequant(_upload(block.packed, dev), bits, n, centres)
+        if block.last is not None:
+            out[-1] = centres[block.last]
+        return out
+    # labels held as bytes are a bits = 8 stream, two planes interleaved high byte first a bits = 16 stream; the codebook
+    # is padded to that width (the host's frequency check keeps every label below 2^bits)
+    planes = [ops.codec_rans_decode_parsed(_upload(data, dev), info) for data, info in block.planes]
+    width = 8 * len(planes)
+    packed = planes[0] if len(planes) == 1 else torch.stack([planes[1], planes[0]], dim=1).reshape(-1)
+    padded = torch.zeros(1 << width, dtype=torch.float32, device=dev)
+    padded[:1 << bits] = centres
+    return ops.codec_dequant(packed, width, n, padded)
+
+
+def _expand_flat(d: SimpleNamespace, dev) -> list:
+    """Every coefficient tensor, flat: its values at the set bits of the flat mask."""
+    mask, grids, bit_offset = _field_on_device(d.mask.fields[0], dev), [], 0
+    for block, nz, z in zip(d.grid_blocks, d.grid_sizes, d.zeros):
+        grids.append(ops.codec_expand(mask, bit_offset, nz + z, _dequantised(block, d.bits, dev)))
+        bit_offset += nz + z
+    return grids
+
+
+def _expand_per_cell(d: SimpleNamespace, what: str, dev) -> list:
+    """The same from a per-cell mask: the values go to the set residual bits of the tensor's support cells, the cells to
+    the set support bits.  The values are padded to the residual range's length, so no residual makes the expansion read
+    past them; the two counts the host could not check -- set residual bits = non-zero coefficients, set support bits = K
+    -- come back from the device once, after the last tensor."""
+    support, residual = [_field_on_device(f, dev) for f in d.mask.fields]
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    grids, found, cell_offset, bit_offset = [], [], 0, 0
+    for block, nz, S, K in zip(d.grid_blocks, d.grid_sizes, d.mask.cells, d.mask.kept):
+        n = d.feature_size * K
+        values = torch.zeros(n, dtype=torch.float32, device=dev)
+        if n:
+            values[:nz] = _dequantised(block, d.bits, dev)
+            values, count = ops.codec_expand(residual, bit_offset, n, values, counted=True)
+            found.append(count)
+        else:
+            found.append(torch.zeros((), dtype=torch.int64, device=dev))
+        grids.append(ops.codec_expand_support(support, cell_offset, d.feature_size, S, values, K, status))
+        cell_offset += S
+        bit_offset += n
+    found = torch.stack(found).cpu().tolist()
+    if int(status.item()) or found != d.grid_sizes:
+        raise ValueError('%s: the support or the residual does not hold the number of set bits the files name (support cells '
+                         '%s, status %d; non-zero coefficients %s, set residual bits %s)'
+                         % (what, d.mask.kept, int(status.item()), d.grid_sizes, found))
+    return grids
+
+
+def _decode_model_files(d: SimpleNamespace, name: str):
+    """(weights, biases, flat coefficient tensors) of a parsed pair, on the GPU: all the per-coefficient work."""
+    dev = torch.device('cuda')
+    weights = [_upload(w, dev) if isinstance(w, np.ndarray) else _dequantised(w, d.bits, dev) for w in d.weights]
+    biases = [_upload(b, dev) for b in d.biases]
+    grids = _expand_flat(d, dev) if d.mask.cells is None else _expand_per_cell(d, name + '_mask.bnr', dev)
+    return weights, biases, grids
+
+
 def restore_model(filename, wavelet_filter='db2'):
     """Rebuild the model a parameter file + mask file describe (reference :226-332).  Like the reference the network is
     re-created with 'fourier' embedding (2 frequencies) and no drop layers; unlike it the model is returned on the GPU
     (it cannot run anywhere else).  The format has no field for the wavelet basis: ``wavelet_filter`` (passed on to
     ``setup_model``) names the one the stored model was built with, db2 like the reference by default.
 
-    An entropy-mode pair (``store_model_parameters(..., entropy=True)``) is recognised by header byte 5 (``bits | 0x80``).
-    Both kinds are read and checked on the host in full -- ``ValueError`` for a truncated file, a stream header that does
-    not add up, or a frequency on a label the codebook does not have -- before the first device call.
-
-    A mask file in mode 2 (``channel_mask=True``: the mask once per cell) is recognised by its first byte.
-    Its host checks: truncation, trailing bytes, a field mode above 1, tensors that are no whole number of cells, more
-    support cells than cells, more non-zero coefficients than the support cells hold, a stream of another length than its
-    field.  The two counts only the device can check -- set support bits and set residual bits per tensor -- raise
-    ``ValueError`` after the expansion, which is made safe against either being wrong."""
+    Every kind of pair ``store_model_parameters`` writes is recognised from the files themselves, and read and checked on the
+    host in full (``parse_model_files``: ValueError) before the first device call.  The two counts of a per-cell mask that
+    only the device can check -- set support bits and set residual bits per tensor -- raise ``ValueError`` after the
+    expansion, which is made safe against either being wrong."""
     with open(filename, 'rb') as f:
         raw = f.read()
     with open(filename + '_mask.bnr', 'rb') as f:
         mask_raw = f.read()
-    pos = 0
-
-    # ---- 1. the whole file pair is read and checked on the host, before anything touches the GPU --------------------
-    def take(fmt):
-        nonlocal pos
-        size = struct.calcsize(fmt)
-        if pos + size > len(raw):
-            raise ValueError('%s: truncated parameter file' % filename)
-        vals = struct.unpack(fmt, raw[pos:pos + size])
-        pos += size
-        return vals
-
-    n_layers, layer_width, input_dim, input_channel, output_dim, bits, grid_size, n_grids, feature_size = take('9B')
-    entropy = bool(bits & _ENTROPY_FLAG)
-    bits &= ~_ENTROPY_FLAG
-    if not 1 <= bits <= 16:
-        raise ValueError('%s: bit precision %d not supported' % (filename, bits))
-    n_clusters = int(math.pow(2, bits))
-    grid_sizes = [take('<I')[0] for _ in range(n_grids)]
-    zeros = [take('<I')[0] for _ in range(n_grids)]
-
-    def floats(n):
-        nonlocal pos
-        if pos + 4 * n > len(raw):
-            raise ValueError('%s: truncated parameter file' % filename)
-        a = np.frombuffer(raw, dtype='<f4', count=n, offset=pos)
-        pos += 4 * n
-        return torch.from_numpy(a.astype(np.float32))
-
-    def rans_stream(buf, at, n, n_symbols, what, exact=False):
-        """(bytes, header) of the rANS stream at buf[at:] that must hold n symbols below n_symbols."""
-        try:
-            info = ops.codec_rans_header(buf, at, exact=exact)
-        except ValueError as e:
-            raise ValueError('%s: %s' % (what, e)) from None
-        if info.n != n:
-            raise ValueError('%s: a stream of %d symbols where %d are expected' % (what, info.n, n))
-        if info.freq[n_symbols:].any():          # a decoded label can then never index past the codebook
-            raise ValueError('%s: the model gives a frequency to a symbol of %d or above' % (what, n_symbols))
-        return np.frombuffer(buf, dtype=np.uint8, count=info.nbytes, offset=at), info
-
-    def quantised(n):
-        """Host description of one block: the centres, and the packed labels (+ the uint32 last label) or the rANS planes."""
-        nonlocal pos
-        block = {'n': n, 'centres': floats(n_clusters), 'last': None, 'packed': None, 'planes': None}
-        mode = take('B')[0] if entropy else 0
-        if mode == 0:
-            nbytes = (n * bits) // 8 + (1 if (n * bits) % 8 else 0)
-            if pos + nbytes > len(raw):
-                raise ValueError('%s: truncated parameter file' % filename)
-            block['packed'] = np.frombuffer(raw, dtype=np.uint8, count=nbytes, offset=pos)
-            pos += nbytes
-            if bits % 8 != 0:                   # the writer repeats the last label as a uint32 (:184-186, :265-267)
-                block['last'] = take('<I')[0]
-        elif mode == 1:
-            block['planes'] = []
-            for limit in ([1 << bits] if bits <= 8 else [256, 1 << (bits - 8)]):
-                data, info = rans_stream(raw, pos, n, limit, filename)
-                pos += info.nbytes
-                block['planes'].append((data, info))
-        else:
-            raise ValueError('%s: block mode %d not supported' % (filename, mode))
-        return block
-
-    net_weights = [floats(input_dim * layer_width)]
-    net_biases = [floats(layer_width)]
-    for _ in range(n_layers - 1):
-        net_weights.append(quantised(layer_width * layer_width))
-        net_biases.append(floats(layer_width))
-    net_weights.append(floats(output_dim * layer_width))
-    net_biases.append(floats(output_dim))
-    grid_blocks = [quantised(nz) for nz in grid_sizes]
-
-    def per_cell_mask():
-        """Host description of a mode-2 mask file: (cells S_t, support cells K_t, [(bytes, stream header or None) of the
-        support and of the residual field])."""
-        what = filename + '_mask.bnr'
-        if feature_size < 1 or any((nz + z) % feature_size for nz, z in zip(grid_sizes, zeros)):
-            raise ValueError('%s: a tensor is no whole number of cells of %d channels' % (what, feature_size))
-        cells = [(nz + z) // feature_size for nz, z in zip(grid_sizes, zeros)]
-        at = 1 + 4 * n_grids
-        if len(mask_raw) < at:
-            raise ValueError('%s: truncated mask file' % what)
-        kept = list(struct.unpack_from('<%dI' % n_grids, mask_raw, 1))
-        for t, (nz, S, K) in enumerate(zip(grid_sizes, cells, kept)):
-            if K > S or nz > feature_size * K:
-                raise ValueError('%s: tensor %d has %d cells and %d non-zero coefficients, the file names %d support cells'
-                                 % (what, t, S, nz, K))
-        fields = []
-        for nbits in (sum(cells), feature_size * sum(kept)):
-            nbytes = (nbits + 7) // 8
-            if at >= len(mask_raw):
-                raise ValueError('%s: truncated mask file' % what)
-            mode = mask_raw[at]
-            at += 1
-            if mode == 0:
-                if at + nbytes > len(mask_raw):
-                    raise ValueError('%s: truncated mask file' % what)
-                fields.append((np.frombuffer(mask_raw[at:at + nbytes], dtype=np.uint8), None))
-                at += nbytes
-            elif mode == 1:
-                fields.append(rans_stream(mask_raw, at, nbytes, 256, what))
-                at += fields[-1][1].nbytes
-            else:
-                raise ValueError('%s: field mode %d not supported' % (what, mode))
-        if at != len(mask_raw):
-            raise ValueError('%s: %d trailing bytes' % (what, len(mask_raw) - at))
-        return cells, kept, fields
-
-    total = sum(grid_sizes) + sum(zeros)
-    mask_stream = per_cell = None
-    if not entropy:
-        mask_bytes = len(mask_raw)
-    elif len(mask_raw) < 1 or mask_raw[0] > _CHANNEL_MASK_MODE:
-        raise ValueError('%s_mask.bnr: %s' % (filename, 'mode %d not supported' % mask_raw[0] if mask_raw else 'empty'))
-    elif mask_raw[0] == _CHANNEL_MASK_MODE:
-        per_cell = per_cell_mask()
-        mask_bytes = (total + 7) // 8            # the flat mask is never materialised
-    elif mask_raw[0] == 0:
-        mask_raw = mask_raw[1:]
-        mask_bytes = len(mask_raw)
-    else:
-        mask_stream = rans_stream(mask_raw, 1, (total + 7) // 8, 256, filename + '_mask.bnr', exact=True)
-        mask_bytes = mask_stream[1].n
-    if mask_bytes * 8 < total:
-        raise ValueError('%s_mask.bnr: %d bits needed, %d present' % (filename, total, mask_bytes * 8))
-
-    # ---- 2. the per-coefficient work, on the GPU -------------------------------------------------------------------------
-    dev = torch.device('cuda')
-
-    def upload(a):
-        return torch.from_numpy(np.array(a)).to(dev)
-
-    def dequantised(block):
-        n, centres = block['n'], block['centres'].to(dev)
-        if n == 0:
-            return torch.empty(0, device=dev)
-        if block['planes'] is None:
-            out = ops.codec_dequant(upload(block['packed']), bits, n, centres)
-            if block['last'] is not None:
-                out[-1] = centres[block['last']]
-            return out
-        # labels held as bytes are a bits = 8 stream, two planes interleaved high byte first a bits = 16 stream; the
-        # codebook is padded to that width (the frequency check above keeps every label below 2^bits)
-        planes = [ops.codec_rans_decode_parsed(upload(data), info) for data, info in block['planes']]
-        width = 8 * len(planes)
-        packed = planes[0] if len(planes) == 1 else torch.stack([planes[1], planes[0]], dim=1).reshape(-1)
-        padded = torch.zeros(1 << width, dtype=torch.float32, device=dev)
-        padded[:n_clusters] = centres
-        return ops.codec_dequant(packed, width, n, padded)
-
-    net_weights = [w.to(dev) if torch.is_tensor(w) else dequantised(w) for w in net_weights]
-    net_biases = [b.to(dev) for b in net_biases]
-    grid_params, bit_offset = [], 0
-    if per_cell is not None:
-        # mode 2: the values go to the set residual bits of the tensor's support cells, the cells to the set support bits.
-        # The values are padded to the residual range's length, so no residual makes the expansion read past them; the
-        # two counts the host could not check -- set residual bits = non-zero coefficients, set support bits = K -- come
-        # back from the device once, after the last tensor.
-        cells, kept, fields = per_cell
-        support, residual = [upload(data) if info is None else ops.codec_rans_decode_parsed(upload(data), info)
-                             for data, info in fields]
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        found, cell_offset = [], 0
-        for block, nz, S, K in zip(grid_blocks, grid_sizes, cells, kept):
-            n = feature_size * K
-            values = torch.zeros(n, dtype=torch.float32, device=dev)
-            if n:
-                values[:nz] = dequantised(block)
-                values, count = ops.codec_expand(residual, bit_offset, n, values, counted=True)
-                found.append(count)
-            else:
-                found.append(torch.zeros((), dtype=torch.int64, device=dev))
-            grid_params.append(ops.codec_expand_support(support, cell_offset, feature_size, S, values, K, status))
-            cell_offset += S
-            bit_offset += n
-        found = torch.stack(found).cpu().tolist()
-        if int(status.item()) or found != grid_sizes:
-            raise ValueError('%s_mask.bnr: the support or the residual does not hold the number of set bits the files name '
-                             '(support cells %s, status %d; non-zero coefficients %s, set residual bits %s)'
-                             % (filename, kept, int(status.item()), grid_sizes, found))
-    else:
-        if mask_stream is None:
-            mask = upload(np.frombuffer(mask_raw, dtype=np.uint8))
-        else:
-            mask = ops.codec_rans_decode_parsed(upload(mask_stream[0]), mask_stream[1])
-        for block, nz, z in zip(grid_blocks, grid_sizes, zeros):
-            grid_params.append(ops.codec_expand(mask, bit_offset, nz + z, dequantised(block)))
-            bit_offset += nz + z
-
-    model = setup_model(input_channel=input_channel, hidden_channel=layer_width, out_channel=output_dim,
-                        num_layer=n_layers, embedding_type='fourier', n_embedding_freq=2, drop_type='',
+    d = parse_model_files(raw, mask_raw, filename)
+    net_weights, net_biases, grid_params = _decode_model_files(d, filename)
+    model = setup_model(input_channel=d.input_channel, hidden_channel=d.layer_width, out_channel=d.output_dim,
+                        num_layer=d.n_layers, embedding_type='fourier', n_embedding_freq=2, drop_type='',
                         drop_momentum=0.025, drop_threshold=0.75, wavelet_filter=wavelet_filter,
-                        grid_features=feature_size, grid_size=grid_size, checkpoint_path='').to(dev)
+                        grid_features=d.feature_size, grid_size=d.grid_size, checkpoint_path='').to('cuda')
     built = [p.numel() for name, p in model.named_parameters() if re.match(r'.*grid.*', name, re.I)]
-    stored = [nz + z for nz, z in zip(grid_sizes, zeros)]
+    stored = [nz + z for nz, z in zip(d.grid_sizes, d.zeros)]
     if built != stored:
         raise ValueError('%s holds %d coefficient tensors of %s elements, a %r model of this shape has %d of %s: name the '
                          'stored model\'s basis with wavelet_filter=' % (filename, len(stored), stored, wavelet_filter,

@@ -10,9 +10,10 @@ File, little-endian::
     per x-slab of slab_planes planes (the last one shorter), in x order:
         u32 K | u64 checksum | u8 mode | payload | K x f32 outliers
 
-mode 0: the slab's symbol bytes; mode 1: their rANS stream (``ops.RANS_ROUNDS`` rounds per chunk), taken only where it is
-strictly shorter.  The arithmetic of symbols, outliers and checksum is the contract of include/lfgc.h; all per-voxel work is
-HIP (csrc/lfgc_residual.hip, csrc/lfgc_rans.hip), this module is the slab loop and the bytes."""
+``u8 mode | payload`` is the codec's field (codec_container.py) -- mode 0: the slab's symbol bytes; mode 1: their rANS
+stream (``ops.RANS_ROUNDS`` rounds per chunk), only where it is strictly shorter.  The arithmetic of symbols, outliers and
+checksum is the contract of include/lfgc.h; all per-voxel work is HIP (csrc/lfgc_residual.hip, csrc/lfgc_rans.hip), this
+module is the slab loop and the bytes."""
 from __future__ import annotations
 
 import struct
@@ -25,12 +26,12 @@ import torch
 
 from .. import ops
 from ..visualization.OutputToVTK import field_from_net_fused
+from .codec_container import Reader, read_field, write_field
 
 MAGIC = b'LFGR'
 VERSION = 1
-_HEADER = struct.Struct('<4s4B3IfII')
-_RECORD = struct.Struct('<IQB')                  # K, checksum, mode
-_RECORD_HEAD = struct.Struct('<IQ')              # what the writer puts before the mode byte of ``_coded``
+_HEADER = '<4s4B3IfII'
+_RECORD = '<IQ'                                  # K, checksum: what stands before a record's field
 _SLAB_VOXELS = 1 << 24                           # default slab: at most this many voxels (64 MiB of prediction)
 
 
@@ -66,10 +67,8 @@ def parse_residual_file(raw: bytes) -> SimpleNamespace:
     bad magic or version, a zero dimension, an eps that is no positive normal number, tiled_res or slab_planes < 1, a
     truncated record, an unknown mode, K above the slab's voxel count, a stream of another symbol count than the slab, and
     trailing bytes."""
-    view = memoryview(raw).cast('B')
-    if len(view) < _HEADER.size:
-        raise ValueError('truncated residual file: no room for its %d-byte header' % _HEADER.size)
-    magic, version, z0, z1, z2, X, Y, Z, eps, tiled_res, slab_planes = _HEADER.unpack_from(view, 0)
+    r = Reader(raw, 'residual file')
+    magic, version, z0, z1, z2, X, Y, Z, eps, tiled_res, slab_planes = r.take(_HEADER)
     if magic != MAGIC or version != VERSION or z0 or z1 or z2:
         raise ValueError('not a residual file of version %d (magic %r, version %d, reserved %d %d %d)'
                          % (VERSION, bytes(magic), version, z0, z1, z2))
@@ -81,34 +80,18 @@ def parse_residual_file(raw: bytes) -> SimpleNamespace:
         raise ValueError('residual file: the bound %r is no positive normal fp32 number' % (eps,)) from None
     if tiled_res < 1 or slab_planes < 1:
         raise ValueError('residual file: tiled_res %d, slab_planes %d' % (tiled_res, slab_planes))
-    records, at = [], _HEADER.size
+    records = []
     for x0, x1 in _slabs(X, slab_planes):
         n = (x1 - x0) * Y * Z
-        if len(view) - at < _RECORD.size:
-            raise ValueError('truncated residual file: the record of planes %d to %d is missing' % (x0, x1))
-        K, checksum, mode = _RECORD.unpack_from(view, at)
-        at += _RECORD.size
+        K, checksum = r.take(_RECORD)
         if K > n:
             raise ValueError('residual file: %d outliers in a slab of %d voxels' % (K, n))
-        if mode not in (0, 1):
-            raise ValueError('residual file: unknown mode %d of the record of planes %d to %d' % (mode, x0, x1))
-        room = len(view) - at - 4 * K
-        info = None
-        if mode == 1:
-            if room < 0:
-                raise ValueError('truncated residual file: the record of planes %d to %d' % (x0, x1))
-            info = ops.codec_rans_header(view, at, room)
-            if info.n != n:
-                raise ValueError('residual file: a stream of %d symbols for a slab of %d voxels' % (info.n, n))
-        nbytes = n if mode == 0 else info.nbytes
-        if room < nbytes:
-            raise ValueError('truncated residual file: the record of planes %d to %d needs %d bytes, %d are there'
-                             % (x0, x1, nbytes + 4 * K, room + 4 * K))
-        records.append(SimpleNamespace(x0=x0, x1=x1, n=n, K=K, checksum=checksum, mode=mode, payload=(at, nbytes), rans=info,
-                                       outliers=at + nbytes))
-        at += nbytes + 4 * K
-    if at != len(view):
-        raise ValueError('residual file: %d trailing bytes' % (len(view) - at))
+        mode, payload = read_field(r, n, [(n, 256)], length=r.room() - 1 - 4 * K)     # a stream leaves room for the outliers
+        data, info = (payload, None) if mode == 0 else payload[0]
+        records.append(SimpleNamespace(x0=x0, x1=x1, n=n, K=K, checksum=checksum, mode=mode, payload=(r.at - len(data), len(data)),
+                                       rans=info, outliers=r.at))
+        r.array('<f4', K)
+    r.end()
     return SimpleNamespace(X=X, Y=Y, Z=Z, eps=eps, tiled_res=tiled_res, slab_planes=slab_planes, records=records)
 
 
@@ -126,7 +109,6 @@ def store_residuals(dataset, model, gt_vol: torch.Tensor, filename, max_error, t
     voxels) one ``field_from_net_fused`` launch, the quantisation, the compaction of the outliers and the rANS coder; device
     memory stays bounded by the slab.  An absolute bound: for one relative to the value range, multiply by the range.
     Returns ``{'bytes', 'escapes', 'voxels', 'bits_per_voxel'}``."""
-    from .model_utils import _coded              # late: model_utils exports this module's functions
     eps = ops.residual_eps(max_error)
     tiled_res = _positive_int(tiled_res, 'tiled_res')
     res = tuple(int(v) for v in dataset.vol_res_touple)
@@ -137,15 +119,15 @@ def store_residuals(dataset, model, gt_vol: torch.Tensor, filename, max_error, t
         raise ValueError('a slab of %d planes has 2^32 voxels or more: the entropy coder takes fewer' % slab_planes)
     device = _device_of(model)
     gt_vol = gt_vol.detach().contiguous()
-    out = [_HEADER.pack(MAGIC, VERSION, 0, 0, 0, res[0], res[1], res[2], eps, tiled_res, slab_planes)]
+    out = [struct.pack(_HEADER, MAGIC, VERSION, 0, 0, 0, res[0], res[1], res[2], eps, tiled_res, slab_planes)]
     escapes = 0
     for x0, x1 in _slabs(res[0], slab_planes):
         gt = gt_vol[x0:x1].to(device)
         pred = field_from_net_fused(dataset, model, x0, x1, tiled_res)
         sym, checksum = ops.residual_quantize(pred, gt, eps)
         outliers = ops.residual_outliers(sym, gt)
-        out.append(_RECORD_HEAD.pack(outliers.numel(), int(checksum.item()) & 0xFFFFFFFFFFFFFFFF))
-        out.append(_coded(sym.cpu().numpy().tobytes(), [ops.codec_rans_encode(sym, ops.RANS_ROUNDS)]))
+        out.append(struct.pack(_RECORD, outliers.numel(), int(checksum.item()) & 0xFFFFFFFFFFFFFFFF))
+        out.append(write_field(sym.cpu().numpy().tobytes(), [ops.codec_rans_encode(sym, ops.RANS_ROUNDS)]))
         out.append(outliers.cpu().numpy().astype('<f4', copy=False).tobytes())
         escapes += outliers.numel()
     blob = b''.join(out)

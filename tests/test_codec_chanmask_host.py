@@ -171,9 +171,12 @@ def test_reference_mode2_files_parse_back_and_pass_the_host_checks(tmp_path, mon
         restore(tmp_path, param, mask_file)
 
 
-@pytest.mark.parametrize('kind', ['truncated', 'truncated counts', 'trailing bytes', 'support field mode', 'residual field mode',
-                                  'channels', 'K above S', 'K too small', 'symbol count', 'stream word count'])
-def test_restore_model_refuses_a_bad_mode2_pair_before_any_device_use(tmp_path, monkeypatch, kind):
+BAD_MODE2_KINDS = ['truncated', 'truncated counts', 'trailing bytes', 'support field mode', 'residual field mode', 'channels',
+                   'K above S', 'K too small', 'symbol count', 'stream word count']
+
+
+def bad_mode2_pair(kind):
+    """reference_files() with one thing wrong (tests/test_codec_container_host.py parses these directly)."""
     param, mask_file, nz, K = reference_files()
     param, mask_file = bytearray(param), bytearray(mask_file)
     support_at = 1 + 4                                                           # the support field's mode byte
@@ -202,10 +205,16 @@ def test_restore_model_refuses_a_bad_mode2_pair_before_any_device_use(tmp_path, 
     elif kind == 'stream word count':
         w0 = struct.unpack_from('<I', mask_file, support_at + 1 + A.HEADER)[0]
         struct.pack_into('<I', mask_file, support_at + 1 + A.HEADER, w0 + 1)
+    return bytes(param), bytes(mask_file)
+
+
+@pytest.mark.parametrize('kind', BAD_MODE2_KINDS)
+def test_restore_model_refuses_a_bad_mode2_pair_before_any_device_use(tmp_path, monkeypatch, kind):
+    param, mask_file = bad_mode2_pair(kind)
     monkeypatch.setattr(torch.Tensor, 'to', no_device)
     monkeypatch.setattr(torch.Tensor, 'cuda', no_device)
     with pytest.raises(ValueError):
-        restore(tmp_path, bytes(param), bytes(mask_file))
+        restore(tmp_path, param, mask_file)
 
 
 # ---- 5. the writer's argument check ------------------------------------------------------------------------------------------------------

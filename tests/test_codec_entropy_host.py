@@ -249,10 +249,12 @@ def test_reference_files_parse_back():
     assert A.stream_info(param, STREAM_AT)['n'] == WIDTH * WIDTH               # STREAM_AT is where the tests below cut
 
 
-@pytest.mark.parametrize('kind', ['truncated', 'sum f', 'word count', 'impossible label', 'mask word count', 'mask truncated',
-                                  'block mode', 'mask mode'])
-def test_restore_model_refuses_a_bad_entropy_file_before_any_device_use(tmp_path, monkeypatch, kind):
-    """ValueError from the host pass.  torch.Tensor.to would be the first device use: it is made to fail the test."""
+BAD_ENTROPY_KINDS = ['truncated', 'sum f', 'word count', 'impossible label', 'mask word count', 'mask truncated', 'block mode',
+                     'mask mode']
+
+
+def bad_entropy_pair(kind):
+    """reference_files() with one thing wrong (tests/test_codec_container_host.py parses these directly)."""
     param, mask_file = reference_files(label_offset=16 if kind == 'impossible label' else 0)
     param, mask_file = bytearray(param), bytearray(mask_file)
     if kind == 'truncated':
@@ -271,13 +273,20 @@ def test_restore_model_refuses_a_bad_entropy_file_before_any_device_use(tmp_path
         param[STREAM_AT - 1] = 2
     elif kind == 'mask mode':
         mask_file[0] = 2
+    return bytes(param), bytes(mask_file)
+
+
+@pytest.mark.parametrize('kind', BAD_ENTROPY_KINDS)
+def test_restore_model_refuses_a_bad_entropy_file_before_any_device_use(tmp_path, monkeypatch, kind):
+    """ValueError from the host pass.  torch.Tensor.to would be the first device use: it is made to fail the test."""
+    param, mask_file = bad_entropy_pair(kind)
 
     def no_device(*a, **k):
         raise AssertionError('restore_model reached the device before refusing the file')
     monkeypatch.setattr(torch.Tensor, 'to', no_device)
     monkeypatch.setattr(torch.Tensor, 'cuda', no_device)
     with pytest.raises(ValueError):
-        restore(tmp_path, bytes(param), bytes(mask_file))
+        restore(tmp_path, param, mask_file)
 
 
 def test_previous_readers_refuse_the_flag_as_a_width():
