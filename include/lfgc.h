@@ -233,7 +233,8 @@ int lfgc_drop_apply_bwd_f32(const float* d_out, const float* x, const float* mul
 
 /* SmallifySignVarianceTracker.sign_variance_pruning_onlyVar (model/Smallify_Dropout.py:106-112) on DEVICE state:
  * phi = sign(betas) - ema; ema += momentum*phi; emavar = (1 - momentum)*(emavar + momentum*phi^2), fp32, the
- * reference's operation order (bit-identical state; the reference moves betas to the CPU every step). */
+ * reference's operation order (bit-identical state; the reference moves betas to the CPU every step).  sign is
+ * torch.sign's (b > 0) - (b < 0): +0 for -0 and for a NaN beta of either sign, so a NaN beta reads as 0. */
 int lfgc_sign_variance_update_f32(const float* betas, float* ema, float* emavar, float momentum, int64_t n,
                                   lfgc_stream_t stream);
 /* The same step for all drop layers of a model in one launch: host arrays of n_layers (<= LFGC_PENALTY_MAX_TERMS)

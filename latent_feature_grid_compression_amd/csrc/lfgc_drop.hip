@@ -54,13 +54,15 @@ __global__ __launch_bounds__(256) void sum_slices_kernel(const float* __restrict
 }
 
 // phi = sign(beta) - EMA;  EMA += mom * phi;  EMAVar = (1 - mom) * (EMAVar + mom * phi^2)      -- the reference's fp32
-// operation order (Smallify_Dropout.py:108-112), so the state is bit-identical to its CPU tensors.
+// operation order (Smallify_Dropout.py:108-112), so the state is bit-identical to its CPU tensors for every beta:
+// sign is torch.sign's (b > 0) - (b < 0), which is +0 for -0 and for a NaN of either sign (a NaN beta does not
+// poison the tracker state).
 __global__ __launch_bounds__(256) void sign_variance_kernel(const float* __restrict__ betas, float* __restrict__ ema,
                                                             float* __restrict__ emavar, float mom, long long n) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float b = betas[i];
-    const float sgn = b != b ? b : (float)((b > 0.0f) - (b < 0.0f));
+    const float sgn = (float)((b > 0.0f) - (b < 0.0f));
     const float e = ema[i];
     const float phi = __fsub_rn(sgn, e);
     ema[i] = __fadd_rn(e, __fmul_rn(mom, phi));
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void sign_variance_multi_kernel(const TrackerA
     const long long i = (long long)(blockIdx.x - a.block_start[t]) * 256 + threadIdx.x;
     if (i >= a.n[t]) return;
     const float b = a.betas[t][i];
-    const float sgn = b != b ? b : (float)((b > 0.0f) - (b < 0.0f));
+    const float sgn = (float)((b > 0.0f) - (b < 0.0f));
     const float e = a.ema[t][i];
     const float phi = __fsub_rn(sgn, e);
     a.ema[t][i] = __fadd_rn(e, __fmul_rn(a.mom, phi));
@@ -176,8 +178,10 @@ __global__ __launch_bounds__(256) void penalty_grads_kernel(const PenaltyArgs a,
             ga[i] = g * (2.0f * v);
         } else {
             const double la = (double)term.b[i] - 2.0 * (double)v;
-            const double s = 1.0 / (1.0 + exp(-(kl_k2() + kl_k3() * la)));
-            const double d_la = -kl_k1() * kl_k3() * s * (1.0 - s) - 0.5 / (1.0 + exp(la));   // d/dla of -t1 + t2
+            // sigmoid'(x) = s (1 - s) = e / (1 + e)^2 with e = exp(-|x|): no 1 - s, which as a difference is good to 2^-53
+            // absolute only and costs the gradient its fp32 accuracy from la ~ 20 on (2.4e-6 relative at la = 24)
+            const double e = exp(-fabs(kl_k2() + kl_k3() * la));
+            const double d_la = -kl_k1() * kl_k3() * (e / ((1.0 + e) * (1.0 + e))) - 0.5 / (1.0 + exp(la));   // d/dla of -t1 + t2
             gb[i] = (float)((double)g * d_la);
             ga[i] = (float)((double)g * (-2.0 * d_la));
         }

@@ -1475,6 +1475,8 @@ def gt_interp(p: torch.Tensor, f: torch.Tensor, min_bb, max_bb, res) -> torch.Te
     _require_hip(p, f)
     p, f = _f32c(p), _f32c(f)
     out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
+    if p.shape[0] == 0:                 # an empty tensor has no address to hand down (the entry refuses NULL before it reads n)
+        return out
     X, Y, Z = f.shape
     check(lib.lfgc_gt_interp_f32(p.data_ptr(), f.data_ptr(), _float3(min_bb), _float3(max_bb), _float3(res), p.shape[0], X, Y, Z,
                                  out.data_ptr(), _stream(p)), 'lfgc_gt_interp_f32')
@@ -1528,6 +1530,8 @@ def lattice_positions(flat: torch.Tensor, res, min_idx, max_idx, scales) -> Tupl
     n = flat.numel()
     raw = torch.empty((n, 3), dtype=torch.float32, device=flat.device)
     norm = torch.empty((n, 3), dtype=torch.float32, device=flat.device)
+    if n == 0:
+        return raw, norm
     r3 = (ctypes.c_int32 * 3)(*[int(x) for x in res])
     check(_lib.load().lfgc_lattice_positions_f32(flat.data_ptr(), n, r3, _float3(min_idx), _float3(max_idx), _float3(scales),
                                                  raw.data_ptr(), norm.data_ptr(), _stream(flat)), 'lfgc_lattice_positions_f32')
@@ -1562,6 +1566,8 @@ def lattice_sample(state: torch.Tensor, n: int, seed: int, res, min_idx, max_idx
     raw = torch.empty((n, 3), dtype=torch.float32, device=state.device)
     norm = torch.empty((n, 3), dtype=torch.float32, device=state.device)
     flat = torch.empty(n, dtype=torch.int64, device=state.device) if want_flat else None
+    if n == 0:                          # no draw: the counter in `state` stays where it is, as the entry has it for n = 0
+        return (raw, norm, flat) if want_flat else (raw, norm)
     r3 = (ctypes.c_int32 * 3)(*[int(x) for x in res])
     check(_lib.load().lfgc_lattice_sample_f32(int(seed) & 0xFFFFFFFFFFFFFFFF, state.data_ptr(), n, r3, _float3(min_idx), _float3(max_idx),
                                               _float3(scales), raw.data_ptr(), norm.data_ptr(),
@@ -1594,6 +1600,8 @@ def deviation_partial(pred: torch.Tensor, gt: torch.Tensor, acc: Optional[torch.
     pred, gt = _f32c(pred).reshape(-1), _f32c(gt).reshape(-1)
     if acc is None:
         acc = torch.tensor([0.0, 0.0, float('inf'), float('-inf')], dtype=torch.float64, device=pred.device)
+    if pred.numel() == 0:
+        return acc
     check(lib.lfgc_deviation_partial_f32(pred.data_ptr(), gt.data_ptr(), pred.numel(), acc.data_ptr(), _stream(pred)),
           'lfgc_deviation_partial_f32')
     return acc
