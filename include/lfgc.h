@@ -1036,6 +1036,33 @@ int lfgc_ray_skip_f32(const int32_t* live, int64_t n_list, const float* origins,
                       const float* box_max, const int32_t* cells, int32_t B, const uint8_t* occ, int32_t* skipped,
                       lfgc_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Structural similarity (SSIM) of two fp32 arrays a, b of shape (n0, n1, n2), row-major, axis 0 slowest.
+ * Axis a has a window of w_a taps (1..16) with fp64 weights g_a[0..w_a) that the caller has normalised to sum 1, and a
+ * stride s_a >= 1.  Windows are valid-only: m_a = (n_a - w_a) / s_a + 1 of them, window (i0,i1,i2) covers
+ * i_a s_a <= idx_a < i_a s_a + w_a.  With W(t) = g0[t0] g1[t1] g2[t2] the moments mu_x, mu_y, E_xx, E_yy, E_xy are the
+ * W-weighted sums of x, y, x x, y y, x y in fp64 (x from a, y from b; a product of two fp32 values is exact in fp64), and
+ *   vx = k (E_xx - mu_x mu_x)   vy = k (E_yy - mu_y mu_y)   vxy = k (E_xy - mu_x mu_y)          k = cov_norm
+ *   SSIM = ((2 mu_x mu_y + c1)(2 vxy + c2)) / ((mu_x mu_x + mu_y mu_y + c1)(vx + vy + c2))
+ * The three second moments take the same operation sequence, so two buffers of equal contents give exactly 1.0 in every
+ * window.  A NaN stays in the windows that cover it.
+ *   plane_sums device double (m0): plane_sums[i0] = the sum of the SSIM of the windows (i0, ., .), added in an order that
+ *              depends on (n1, n2, w, s) only -- not on n0, not on the launch: a call on the sub-array a[x0:x1] gives the
+ *              planes it holds the same bits as a call on the whole array.  No floating-point atomics.
+ *   map        device double (m0, m1, m2) or NULL.
+ *   weights    host, w[0] + w[1] + w[2] finite values, axis 0 first; w, s host int[3].  c1, c2, cov_norm positive, finite.
+ *   workspace  lfgc_ssim_workspace_bytes(n0, n1, n2, w, s) bytes, 8-byte aligned: one double per workgroup.
+ * Decided before anything is launched: LFGC_E_NULL for a missing pointer other than map; LFGC_E_SHAPE for n_a < w_a,
+ * w_a < 1, s_a < 1, a non-finite weight or a c1, c2, cov_norm that is not positive and finite; LFGC_E_UNSUPPORTED for
+ * w_a > 16, n0 n1 n2 > 2^61 and more than 2^31 - 1 workgroups (m0 times the tiles of a plane, 8 x 32 windows each for
+ * overlapping windows); LFGC_E_WORKSPACE for a short workspace; LFGC_E_ALIGN for plane_sums, map or workspace not 8-byte
+ * aligned.  Nothing allocated, no synchronisation.  lfgc_ssim_workspace_bytes returns 0 for refused arguments.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t lfgc_ssim_workspace_bytes(int n0, int n1, int n2, const int* w, const int* s);
+int lfgc_ssim_planes_f32(const float* a, const float* b, int n0, int n1, int n2, const double* weights, const int* w,
+                         const int* s, double c1, double c2, double cov_norm, double* plane_sums, double* map,
+                         void* workspace, int64_t workspace_bytes, lfgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

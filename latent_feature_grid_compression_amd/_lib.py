@@ -198,6 +198,9 @@ SIGNATURES = {
     'lfgc_brick_occupancy_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_void_p]),
     'lfgc_ray_skip_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 6 + [c_float, c_int, POINTER(c_float), POINTER(c_float),
                                                                        POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p]),
+    'lfgc_ssim_workspace_bytes': (c_int64, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    'lfgc_ssim_planes_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), POINTER(c_int), POINTER(c_int),
+                                     c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

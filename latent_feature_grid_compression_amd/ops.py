@@ -2036,3 +2036,64 @@ def iso_mesh_emit(values: torch.Tensor, n_owner: int, iso: float, xs: torch.Tens
                                              _ptr(origins), _ptr(dirs), _ptr(bracket), _ptr(triangles), _stream(values)),
           'lfgc_iso_mesh_emit_f32')
     return origins, dirs, bracket, triangles
+
+
+# ---- structural similarity: plane sums of the SSIM of separable, valid-only windows --------------------
+
+SSIM_MAX_WINDOW = 16           # taps per axis of lfgc_ssim_planes_f32
+
+
+def ssim_window_counts(shape, lengths, strides) -> Tuple[int, int, int]:
+    """Windows per axis, (n - w) // s + 1.  ValueError, naming the axis, for a window longer than its extent, a window
+    outside 1..16 and a stride below 1."""
+    shape, lengths, strides = tuple(int(v) for v in shape), tuple(int(v) for v in lengths), tuple(int(v) for v in strides)
+    if len(shape) != 3 or len(lengths) != 3 or len(strides) != 3:
+        raise ValueError('SSIM takes 3-D arrays with one window and one stride per axis, got shape %s, windows %s, strides %s'
+                         % (shape, lengths, strides))
+    for axis, (n, w, s) in enumerate(zip(shape, lengths, strides)):
+        if not 1 <= w <= SSIM_MAX_WINDOW:
+            raise ValueError('the window of axis %d has %d taps: 1..%d are supported' % (axis, w, SSIM_MAX_WINDOW))
+        if s < 1:
+            raise ValueError('the stride of axis %d is %d: it must be at least 1' % (axis, s))
+        if w > n:
+            raise ValueError('the window of axis %d (%d taps) is longer than the extent %d' % (axis, w, n))
+    return tuple((n - w) // s + 1 for n, w, s in zip(shape, lengths, strides))
+
+
+@_on_device
+def ssim_plane_sums(a: torch.Tensor, b: torch.Tensor, windows, strides, c1: float, c2: float, cov_norm: float = 1.0,
+                    want_map: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(plane_sums (m0,) fp64, map (m0, m1, m2) fp64 or None) on the device: lfgc_ssim_planes_f32 of two (n0, n1, n2)
+    tensors.  ``windows`` holds the three axes' weights (each normalised to sum 1, 1..16 taps), ``strides`` three ints;
+    c1, c2 and cov_norm are those of the formula.  plane_sums[i0] adds the SSIM of the windows (i0, ., .) in an order
+    that does not depend on n0, so the planes of a sub-array a[x0:x1] come out with the bits they have in the whole."""
+    if a.shape != b.shape:
+        raise ValueError('the two arrays differ in shape: %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    weights = [np.ascontiguousarray(np.asarray(g, dtype=np.float64).reshape(-1)) for g in windows]
+    if len(weights) != 3:
+        raise ValueError('windows must hold the weights of the three axes, got %d entries' % len(weights))
+    lengths = [int(g.size) for g in weights]
+    m = ssim_window_counts(a.shape, lengths, strides)
+    if not all(np.isfinite(g).all() for g in weights):
+        raise ValueError('window weights must be finite')
+    c1, c2, cov_norm = float(c1), float(c2), float(cov_norm)
+    if not (0.0 < c1 < float('inf') and 0.0 < c2 < float('inf') and 0.0 < cov_norm < float('inf')):
+        raise ValueError('c1, c2 and cov_norm must be positive and finite, got %r, %r, %r' % (c1, c2, cov_norm))
+    _require_hip(a, b)
+    a, b = _f32c(a.detach()), _f32c(b.detach())
+    n = [int(v) for v in a.shape]
+    lib = _lib.load()
+    w_arr = (ctypes.c_int * 3)(*lengths)
+    s_arr = (ctypes.c_int * 3)(*[int(v) for v in strides])
+    flat = np.concatenate(weights)
+    nbytes = int(lib.lfgc_ssim_workspace_bytes(n[0], n[1], n[2], w_arr, s_arr))
+    if nbytes <= 0:
+        raise _lib.LfgcError('lfgc_ssim_planes_f32 refuses an array of %s with windows %s and strides %s: too many windows '
+                             'for one call' % (tuple(n), tuple(lengths), tuple(int(v) for v in strides)))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+    sums = torch.empty(m[0], dtype=torch.float64, device=a.device)
+    smap = torch.empty(m, dtype=torch.float64, device=a.device) if want_map else None
+    check(lib.lfgc_ssim_planes_f32(a.data_ptr(), b.data_ptr(), n[0], n[1], n[2], flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                   w_arr, s_arr, c1, c2, cov_norm, sums.data_ptr(), _ptr(smap), ws.data_ptr(), nbytes, _stream(a)),
+          'lfgc_ssim_planes_f32')
+    return sums, smap

@@ -613,6 +613,9 @@ def image_psnr(a: torch.Tensor, b: torch.Tensor, peak: float = 1.0) -> float:
     return float('inf') if mse == 0.0 else 10.0 * math.log10(peak * peak / mse)
 
 
+from .Similarity import image_ssim  # noqa: E402,F401 -- the structural measure of the same pair
+
+
 # ---- joint histograms of value and gradient magnitude: what a 2-D transfer function is designed on -------------------------
 
 def _joint_histogram(chunks: Callable, bins, v_range, g_max: Optional[float], device) -> Tuple[torch.Tensor, float]:
